@@ -2,7 +2,7 @@
 """bench.py -- forward+grad lens simulations per second on BASELINE.json's configs[1]:
 EPL+shear lens, Sersic source, 128x128 px, batch 1024, fp32, per MI355X (weak scaling over GPUs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C5|...] [--mode auto|fwdgrad|svi]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C5|...] [--mode auto|fwdgrad|svi] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch.
   * mode fwdgrad (N = 1 default): ``ForwardProbModel.log_prob_and_grad(simulator, z)`` -- ``log_prob`` forward AND its
@@ -21,6 +21,10 @@ One "step" = one pass of the hot path over one batch.
 
 Defaults: 1000 timed steps after 100 warm-up steps.  The chip needs a few tens of milliseconds of sustained load to settle
 at its working clock, so an untimed pre-roll of 0.15 s of steps precedes the W warm-up steps whatever W and K are.
+
+``--dump-outputs DIR`` writes what the last timed step returned, on rank 0, as DIR/<name>.npy (float32, 64 MB at most): mode
+fwdgrad ``log_prob``, ``red_chi2``, ``grad_z`` of every sample of the batch; mode svi the all-reduced ``svi_step_buffer``.  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Refuses to run (exit 3) with any GIGALENS_HIP_* kernel override in the environment.  EVERY rank checks four samples of the shard
 it is about to time against the float64 oracle and its last timed step for finite outputs; the flags are MIN-all-reduced and
@@ -446,6 +450,25 @@ def outputs_finite(last):
     return all(bool(torch.isfinite(t).all()) for t in outs if torch.is_tensor(t))
 
 
+DUMP_MAX_BYTES = 63 * 10 ** 6  # array bytes: with the .npy headers the dump stays under 64 MB
+
+
+def dump_outputs(out_dir, outputs, batch):
+    """``outputs``: (name, tensor, per_sample) -> out_dir/<name>.npy, float64 kept, anything else as float32.  Should the set
+    exceed DUMP_MAX_BYTES, the per-sample arrays keep the same leading rows (the first samples of the seeded batch)."""
+    import numpy as np
+    arrays = []
+    for name, t, per_sample in outputs:
+        a = t.detach().cpu().numpy()
+        arrays.append((name, a if a.dtype in (np.float32, np.float64) else a.astype(np.float32), per_sample))
+    fixed = sum(a.nbytes for _, a, per_sample in arrays if not per_sample)
+    per_row = sum(a.nbytes // batch for _, a, per_sample in arrays if per_sample)
+    rows = batch if per_row == 0 else max(0, min(batch, (DUMP_MAX_BYTES - fixed) // per_row))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a, per_sample in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), a[:rows] if per_sample else a)
+
+
 def measure_c5_sharded(dev, rank, world, steps, warmup, events, stride):
     """BASELINE.json configs[4] on the line of an N > 1 run: the 2048-particle cluster-model SVI, 2048 / N particles per rank --
     forward+gradient on the shard (no collective) and the real SVI iteration with its 8 911-float all-reduce, each for `steps`
@@ -623,9 +646,13 @@ def main():
                     help="untimed sustained load before the warm-up steps (clock settling); 0 disables")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--cpu-samples", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     refuse_tuning_environment()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)  # does not return
@@ -722,6 +749,10 @@ def main():
         sys.stderr.write(f"bench.py: rank {rank}: a timed loop returned non-finite values or the C5 shard failed its check on some rank "
                          f"(this rank: finite {finite_after}, C5 ok {c5_ok})\n")
         sys.exit(4)
+    if args.dump_outputs and rank == 0:
+        outputs = ((("log_prob", last[0], True), ("red_chi2", last[1], True), ("grad_z", last[2], True)) if mode == "fwdgrad"
+                   else (("svi_step_buffer", last, False),))
+        dump_outputs(args.dump_outputs, outputs, B)
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
