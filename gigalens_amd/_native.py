@@ -82,6 +82,9 @@ SYMBOLS = {
     "gl_series_hessian_eval": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "gl_model_set_series_hessian": (c_int, [c_void_p, c_int, c_void_p]),
     "gl_lens_maps": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "gl_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
+                                   c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_model_num_linear": (c_int, [c_void_p]),
     "gl_model_linear_column": (c_int, [c_void_p, c_int]),
     "gl_lstsq_workspace_bytes": (c_size_t, [c_void_p, c_int]),
@@ -576,6 +579,29 @@ class Model:
         out = torch.empty((6,) + tuple(xb.shape), dtype=torch.float32, device=self.device)
         _check(lib().gl_lens_maps(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), xb.shape[0], 1, _ptr(out), _stream()))
         return out.reshape((6,) + tuple(shape))
+
+    def image_positions(self, params, src_x, src_y, window, n_cells, max_images, tol, max_iter):
+        """gl_image_positions: ``src_x, src_y`` [B, S] on the device, ``window`` = (x_lo, x_hi, y_lo, y_hi).  Returns
+        ``out`` [B, S, max_images, 3] (x, y, mu; NaN-padded), ``n_images`` and ``n_dropped`` [B, S] (int32)."""
+        params = self._params(params)
+        B = params.shape[0]
+        src_x = src_x.to(device=self.device, dtype=torch.float32).contiguous()
+        src_y = src_y.to(device=self.device, dtype=torch.float32).contiguous()
+        if src_x.shape != src_y.shape or src_x.dim() != 2 or src_x.shape[0] != B:
+            raise NativeLibraryError(f"source positions must be [B={B}, S], got {tuple(src_x.shape)} / {tuple(src_y.shape)}")
+        S = src_x.shape[1]
+        nbytes = lib().gl_image_positions_workspace_bytes(self._h, B, S, int(n_cells), int(max_images))
+        ws = self._img_ws if getattr(self, "_img_ws", None) is not None and self._img_ws.numel() >= nbytes else None
+        if ws is None:
+            ws = self._img_ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        out = torch.empty((B, S, max(int(max_images), 1), 3), dtype=torch.float32, device=self.device)
+        n_images = torch.empty((B, S), dtype=torch.int32, device=self.device)
+        n_dropped = torch.empty_like(n_images)
+        x_lo, x_hi, y_lo, y_hi = (float(v) for v in window)
+        _check(lib().gl_image_positions(self._h, _ptr(params), B, _ptr(src_x), _ptr(src_y), S, x_lo, x_hi, y_lo, y_hi,
+                                        int(n_cells), int(max_images), float(tol), int(max_iter), _ptr(out), _ptr(n_images),
+                                        _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
+        return out, n_images, n_dropped
 
     def num_linear(self):
         return lib().gl_model_num_linear(self._h)

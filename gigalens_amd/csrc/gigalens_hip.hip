@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +20,7 @@
 #include "gl_static.hip.h"
 #include "gl_post.hip.h"
 #include "gl_positions.hip.h"
+#include "gl_images.hip.h"
 #include "gl_lstsq.hip.h"
 #include "gl_shp.hip.h"
 
@@ -1649,6 +1651,94 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
   }
   hipLaunchKernelGGL(gl_lens_maps_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, a,
                      x, y, (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- lens-equation solver (gl_images.hip.h) -----------------------------------------------------------------
+namespace {
+struct ImgLayout { size_t map, cand, n_cand, n_over, bytes; };
+ImgLayout img_layout(int B, int n_src, int n_cells) {
+  ImgLayout l{};
+  const size_t V = (size_t)(n_cells + 1) * (size_t)(n_cells + 1), BS = (size_t)B * (size_t)n_src;
+  l.map = 0;
+  l.cand = l.map + align_up((size_t)B * V * sizeof(float2), 256);
+  l.n_cand = l.cand + align_up(BS * IMG_MAXC * sizeof(float2), 256);
+  l.n_over = l.n_cand + align_up(BS * sizeof(int), 256);
+  l.bytes = l.n_over + align_up(BS * sizeof(int), 256);
+  return l;
+}
+constexpr int IMG_MAX_CELLS = 8192;
+}  // namespace
+
+size_t gl_image_positions_workspace_bytes(const gl_model* m, int B, int n_src, int n_cells, int max_images) {
+  if (!m || B <= 0 || n_src <= 0 || n_cells <= 0 || n_cells > IMG_MAX_CELLS || max_images < 1) return 0;
+  return img_layout(B, n_src, n_cells).bytes;
+}
+
+int gl_image_positions(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                       float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images, float tol, int max_iter,
+                       float* out, int* n_images, int* n_dropped, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !src_x || !src_y || !out || !n_images || !n_dropped) return fail(GL_EINVAL, "null argument");
+  if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  if (max_images < 1 || max_images > IMG_MAXC) return fail(GL_EINVAL, "max_images %d outside [1, %d]", max_images, IMG_MAXC);
+  if (!(x_hi > x_lo) || !(y_hi > y_lo) || !std::isfinite(x_hi - x_lo) || !std::isfinite(y_hi - y_lo))
+    return fail(GL_EINVAL, "empty or non-finite search window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi);
+  if (!(tol > 0.f) || max_iter < 1) return fail(GL_EINVAL, "tol must be > 0 and max_iter >= 1 (got %g, %d)", tol, max_iter);
+  if (m->n_series)
+    return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image finder");
+  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  const ImgLayout lay = img_layout(B, n_src, n_cells);
+  if (!workspace) return fail(GL_EINVAL, "workspace is null");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  const long long V = (long long)(n_cells + 1) * (n_cells + 1);
+  const long long map_blocks = (V * B + 255) / 256, pairs = (long long)B * n_src;
+  if (map_blocks > 0x7fffffffLL || pairs > 0x7fffffffLL) return fail(GL_EINVAL, "too many samples / vertices / sources for one call");
+  if (m->has_user)  // map and Newton kernels compiled at run time with the user's bodies (the scan does not touch the lens)
+    if (int rc = compile_user_points(m)) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  PosArgs a{};
+  a.comps = m->d_comps;
+  a.n_lens = m->n_lens;
+  a.P = m->P;
+  a.B = B;
+  a.params = params;
+  a.cats = m->d_cats;
+  a.gal_table = m->d_gal_table;
+  a.gal_static = m->d_gal_static;
+  ImgArgs g{};
+  g.src_x = src_x;
+  g.src_y = src_y;
+  g.S = n_src;
+  g.n = n_cells;
+  g.x_lo = x_lo; g.x_hi = x_hi; g.y_lo = y_lo; g.y_hi = y_hi;
+  g.hx = (x_hi - x_lo) / (float)n_cells;
+  g.hy = (y_hi - y_lo) / (float)n_cells;
+  g.max_images = max_images;
+  g.max_iter = max_iter;
+  g.tol = tol;
+  char* base = (char*)workspace;
+  g.map = (float2*)(base + lay.map);
+  g.cand = (float2*)(base + lay.cand);
+  g.n_cand = (int*)(base + lay.n_cand);
+  g.n_over = (int*)(base + lay.n_over);
+  g.out = out;
+  g.n_images = n_images;
+  g.n_dropped = n_dropped;
+  if (m->has_user) {
+    void* args[] = {&a, &g};
+    GL_HIP(hipModuleLaunchKernel(m->user_point_fn[5], (unsigned)map_blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr));
+  } else {
+    hipLaunchKernelGGL(gl_img_map_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
+  }
+  hipLaunchKernelGGL(gl_img_scan_kernel, dim3((unsigned)pairs), dim3(IMG_SCAN_WG), 0, stream, g);
+  if (m->has_user) {
+    void* args[] = {&a, &g};
+    GL_HIP(hipModuleLaunchKernel(m->user_point_fn[6], (unsigned)pairs, 1, 1, 64, 1, 1, 0, stream, args, nullptr));
+  } else {
+    hipLaunchKernelGGL(gl_img_newton_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, a, g);
+  }
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

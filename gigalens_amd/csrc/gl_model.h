@@ -61,11 +61,12 @@ struct gl_model {
   // ... and, for the compositions the pair kernel serves (EPL / SIE / Shear / SIS / user lenses | Sersic / user lights), that kernel
   // specialised on the model's component list with the user bodies inside (gl_pair_kernel<MODE, v2f, 2, KindList<...>, ...>)
   hipFunction_t user_pair_fn[4] = {nullptr, nullptr, nullptr, nullptr};
-  // ... and the point kernels (gl_positions.hip.h: image-position likelihood P1-P4, lens maps) with the bodies on nested duals,
-  // compiled from user_point_src when first asked for (gl_user.hip compile_user_points)
+  // ... and the point kernels (gl_positions.hip.h: image-position likelihood P1-P4, lens maps; gl_images.hip.h: map and Newton
+  // kernels of the lens-equation solver) with the bodies on nested duals, compiled from user_point_src when first asked for
+  // (gl_user.hip compile_user_points)
   std::string user_point_src;
   hipModule_t user_point_module = nullptr;
-  hipFunction_t user_point_fn[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipFunction_t user_point_fn[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int height = 0, width = 0, supersample = 1, N = 0;
   float conversion_factor = 1.f;
   // device-resident, immutable

@@ -326,11 +326,13 @@ static std::string point_program(const std::string& body_text, const std::vector
                    "template <class R> __device__ inline void mass_point(int which, const R* p, R x, R y, R& ax, R& ay) {\n  ax = R(0.f);  ay = R(0.f);\n  switch (which) {\n";
   for (size_t w = 0; w < npar.size(); ++w)
     if (npar[w] >= 0 && light[w] == 0) ps += "    case " + std::to_string(w) + ": glu_body" + std::to_string(w) + "::deriv<R>(x, y, p, ax, ay); break;\n";
-  ps += "  }\n}\n}  // namespace glu\n#include \"gl_positions.hip.h\"\n";
+  ps += "  }\n}\n}  // namespace glu\n#include \"gl_images.hip.h\"\n";
   return ps;
 }
-static const char* const kPointKernels[5] = {"glk::gl_pos_p1_kernel", "glk::gl_pos_p2_kernel", "glk::gl_pos_p3_kernel", "glk::gl_pos_p4_kernel",
-                                             "glk::gl_lens_maps_kernel"};
+// (gl_images.hip.h includes gl_positions.hip.h: [5], [6] are the map and Newton kernels of the lens-equation solver)
+static const char* const kPointKernels[7] = {"glk::gl_pos_p1_kernel", "glk::gl_pos_p2_kernel", "glk::gl_pos_p3_kernel", "glk::gl_pos_p4_kernel",
+                                             "glk::gl_lens_maps_kernel", "glk::gl_img_map_kernel", "glk::gl_img_newton_kernel"};
+constexpr int kNumPointKernels = sizeof(kPointKernels) / sizeof(kPointKernels[0]);
 
 // a mass body through the point kernels' compile, no device needed (gl_user_points_check)
 int check_user_points(const char* body, int n_params) {
@@ -338,7 +340,7 @@ int check_user_points(const char* body, int n_params) {
   if (n_params < 0 || n_params > 16) return fail(GL_EINVAL, "n_params %d outside [0, 16]", n_params);
   const std::string text = std::string("namespace glu_body0 {\n#line 1 \"user_profile_0\"\n") + body + "\n}\n";
   std::shared_ptr<const UserCode> uc;
-  return rtc_compile_cached(point_program(text, {n_params}, {0}), std::vector<std::string>(kPointKernels, kPointKernels + 5), uc);
+  return rtc_compile_cached(point_program(text, {n_params}, {0}), std::vector<std::string>(kPointKernels, kPointKernels + kNumPointKernels), uc);
 }
 
 int compile_user_model(gl_model* m, const char* const* bodies, int n_bodies) {
@@ -457,12 +459,12 @@ int compile_user_points(const gl_model* cm) {
   if (m->user_point_fn[0]) return GL_OK;
   if (m->user_point_src.empty()) return fail(GL_EINVAL, "model without user-written profiles");
   std::shared_ptr<const UserCode> uc;
-  if (int rc = rtc_compile_cached(m->user_point_src, std::vector<std::string>(kPointKernels, kPointKernels + 5), uc)) return rc;
-  hipFunction_t fn[5] = {};
+  if (int rc = rtc_compile_cached(m->user_point_src, std::vector<std::string>(kPointKernels, kPointKernels + kNumPointKernels), uc)) return rc;
+  hipFunction_t fn[kNumPointKernels] = {};
   hipError_t e = hipModuleLoadData(&m->user_point_module, uc->code.data());
-  for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipModuleGetFunction(&fn[k], m->user_point_module, uc->lowered[k].c_str());
+  for (int k = 0; k < kNumPointKernels && e == hipSuccess; ++k) e = hipModuleGetFunction(&fn[k], m->user_point_module, uc->lowered[k].c_str());
   if (e != hipSuccess) return fail(GL_ELAUNCH, "loading the compiled point kernels failed: %s", hipGetErrorString(e));
-  for (int k = 4; k >= 0; --k) m->user_point_fn[k] = fn[k];  // [0] last: it is the "compiled" flag
+  for (int k = kNumPointKernels - 1; k >= 0; --k) m->user_point_fn[k] = fn[k];  // [0] last: it is the "compiled" flag
   return GL_OK;
 }
 

@@ -295,6 +295,47 @@ class ForwardProbModel(ProbabilisticModel):
         ll, chi2 = _PositionsFn.apply(packed, self._bind_positions(simulator))
         return ll, chi2 / self.n_position
 
+    def predicted_positions(self, simulator, params, **solver_kwargs):
+        """Images the model predicts for every family of ``centroids_x/y`` (beyond the reference).  The source of a family is
+        the barycentre of its back-traced observed images, the same mean beta ``stats_positions`` compares against.  Returns
+        one ``(x, y, mu, n)`` tuple per family with ``[B, max_images]`` / ``[B]`` tensors (``LensSimulator.image_positions``,
+        which ``solver_kwargs`` go to)."""
+        if self.centroids_x is None:
+            raise ValueError("predicted_positions needs a model built with centroids_x/centroids_y")
+        packed = params if torch.is_tensor(params) else simulator.pack(params)
+        sx, sy = [], []
+        for cx, cy in zip(self.centroids_x, self.centroids_y):
+            maps = simulator._model.lens_maps(packed, cx.reshape(-1, 1), cy.reshape(-1, 1))  # (6, J_f, B)
+            sx.append(maps[0].mean(dim=0))
+            sy.append(maps[1].mean(dim=0))
+        x, y, mu, n = simulator.image_positions(packed, torch.stack(sx, dim=1), torch.stack(sy, dim=1), **solver_kwargs)
+        return [(x[:, f], y[:, f], mu[:, f], n[:, f]) for f in range(len(self.centroids_x))]
+
+    def image_plane_rms(self, simulator, params, **solver_kwargs):
+        """Image-plane rms of every family (beyond the reference; the Delta theta cluster papers report): each observed image,
+        in the order given, is paired with the nearest predicted image not yet paired.  Returns a dict of ``[B, F]`` tensors:
+        ``rms`` (inf where fewer images are predicted than observed), ``n_predicted``, ``n_observed`` and ``counts_match``;
+        samples whose counts differ are reported there, not left out."""
+        fams = self.predicted_positions(simulator, params, **solver_kwargs)
+        rms, n_pred, n_obs = [], [], []
+        for (px, py, _, n), cx, cy in zip(fams, self.centroids_x, self.centroids_y):
+            ox = torch.as_tensor(cx, device=px.device)
+            oy = torch.as_tensor(cy, device=px.device)
+            d = torch.hypot(px[:, None, :] - ox[None, :, None], py[:, None, :] - oy[None, :, None])  # [B, J, M]
+            d = torch.nan_to_num(d, nan=float("inf"))
+            used = torch.zeros_like(d[:, 0, :], dtype=torch.bool)
+            ss = torch.zeros_like(d[:, 0, 0])
+            for j in range(d.shape[1]):
+                dj = d[:, j, :].masked_fill(used, float("inf"))
+                k = dj.argmin(dim=1, keepdim=True)
+                ss = ss + dj.gather(1, k)[:, 0] ** 2
+                used = used.scatter(1, k, True)
+            rms.append(torch.sqrt(ss / d.shape[1]))
+            n_pred.append(n)
+            n_obs.append(torch.full_like(n, int(cx.size)))
+        n_pred, n_obs = torch.stack(n_pred, dim=1), torch.stack(n_obs, dim=1)
+        return {"rms": torch.stack(rms, dim=1), "n_predicted": n_pred, "n_observed": n_obs, "counts_match": n_pred == n_obs}
+
     def _packed_from_x(self, simulator, x):
         cols, consts = self._perm(simulator)
         if consts.numel():

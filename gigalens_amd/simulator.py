@@ -6,6 +6,7 @@ Differences in HOW (not WHAT): the pixel grid is stored once as two ``(N,)`` dev
 ray-shooting, rendering, NaN->0 and the det(T) scale are one fused kernel; gradients come from
 hand-written VJP kernels wrapped in a ``torch.autograd.Function``.
 """
+import warnings
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
@@ -216,6 +217,64 @@ class LensSimulator(LensSimulatorInterface):
         """tf/simulator.py:100-107: ``(gamma1, gamma2) = ((f_xx - f_yy)/2, f_xy)`` (tf/profile.py:36-42)."""
         _, _, fxx, fxy, _, fyy = self._lens_maps(x, y, lens_params)
         return 0.5 * (fxx - fyy), fxy
+
+    # default Newton tolerance |beta(theta) - beta_s| of image_positions, in units of the float32 spacing at the window's largest
+    # coordinate: beta = theta - alpha is a float32 difference of numbers of that size, so its rounding alone is a few ulp of it
+    # (plus the rounding of alpha itself); 8 eps |theta|_max (8 to 16 ulp) is reached by every converging candidate, and is
+    # still ~1e-6 arcsec on a 10-arcsec window.  A polishing step after convergence takes the point to the noise floor.
+    IMAGE_TOL_EPS = 8.0
+
+    def image_positions(self, lens_params, source_x, source_y, *, window=None, num_cells=None, max_images=8, tol=None,
+                        max_iter=30, strict=False):
+        """Solve the lens equation beta(theta) = beta_s for every sample (beyond the reference: it only maps theta -> beta).
+
+        ``lens_params``: the ``lens_mass`` list of dicts, a nested dict with a ``lens_mass`` entry, or packed ``[B, P]`` rows.
+        ``source_x`` / ``source_y``: ``[B]`` or ``[B, S]``.  ``window`` = ``(x_lo, x_hi, y_lo, y_hi)`` (default: the bounding box
+        of the simulator's grid), searched on ``num_cells`` x ``num_cells`` cells (default ``2 * num_pix``).
+        Returns ``x, y, mu`` ``[B, S, max_images]`` (images sorted by x then y, NaN-padded; ``mu`` is the signed
+        magnification, the quantity ``magnification`` returns) and ``n`` ``[B, S]``.  Images that were found but could not be
+        stored or refined (``max_images`` exceeded, Newton not converged, converged outside the window) warn, or raise
+        ``RuntimeError`` with ``strict=True``.  Forward only (no gradient)."""
+        if torch.is_tensor(lens_params):
+            packed = lens_params
+        elif isinstance(lens_params, dict):
+            packed = self._pack_partial(lens_params)
+        else:
+            packed = self._pack_partial({"lens_mass": lens_params})
+        if packed.requires_grad:
+            raise NotImplementedError("image_positions is a forward-only diagnostic (no gradient)")
+        B = packed.shape[0]
+        sx = torch.as_tensor(source_x, dtype=torch.float32, device=self.device)
+        sy = torch.as_tensor(source_y, dtype=torch.float32, device=self.device)
+        if sx.dim() == 0:
+            sx = sx.expand(B)
+        if sy.dim() == 0:
+            sy = sy.expand(B)
+        if sx.dim() == 1:
+            sx = sx.reshape(-1, 1)
+        if sy.dim() == 1:
+            sy = sy.reshape(-1, 1)
+        sx, sy = torch.broadcast_tensors(sx, sy)
+        if sx.dim() != 2 or sx.shape[0] != B:
+            raise ValueError(f"source_x / source_y must have shape [B] or [B, S] with B = {B}, got {tuple(sx.shape)}")
+        if window is None:
+            window = (float(self.img_X.min()), float(self.img_X.max()), float(self.img_Y.min()), float(self.img_Y.max()))
+        window = tuple(float(v) for v in window)
+        if num_cells is None:
+            num_cells = 2 * int(self.numPix)
+        if tol is None:
+            tol = self.IMAGE_TOL_EPS * float(np.finfo(np.float32).eps) * max(abs(v) for v in window)
+        out, n, dropped = self._model.image_positions(packed, sx, sy, window, int(num_cells), int(max_images), float(tol),
+                                                      int(max_iter))
+        n_drop = int(dropped.sum())
+        if n_drop:
+            msg = (f"image_positions: {n_drop} image(s) found but not returned over {int((dropped > 0).sum())} "
+                   f"(sample, source) pair(s) (max_images={max_images} exceeded, Newton not converged, or converged outside "
+                   f"the window)")
+            if strict:
+                raise RuntimeError(msg)
+            warnings.warn(msg, RuntimeWarning, stacklevel=2)
+        return out[..., 0], out[..., 1], out[..., 2], n
 
     def simulate(self, params, no_deflection=False):
         """tf/simulator.py:109-156.  Returns ``(bs, H, W)`` squeezed like ``tf.squeeze``."""

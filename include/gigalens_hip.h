@@ -260,6 +260,32 @@ int gl_scaled_eval(int base_kind, int n_galaxies, const int32_t scale_col[3], co
 int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
                  int xy_batched, float* out, void* hip_stream);
 
+/* Lens-equation solver (beyond the reference, which maps image plane -> source plane only): the images theta of source
+ * positions beta_s, beta(theta) = beta_s, for every sample.  params [B,P] (DEVICE); src_x, src_y [B][n_src] (DEVICE).
+ * The window [x_lo, x_hi] x [y_lo, y_hi] is cut into n_cells x n_cells cells, two triangles each; beta is mapped at the vertices
+ * (vertices where it is not finite are flagged and their triangles skipped); every triangle whose image in the source plane
+ * contains beta_s (edge-function sign test, a point on a shared edge counted once) seeds Newton at the preimage of beta_s under
+ * the triangle's affine map: theta <- theta + (I - H)^-1 (beta_s - beta(theta)), |step| <= one cell diagonal, until
+ * |beta(theta) - beta_s| <= tol (then one polishing step) or max_iter steps.  Converged candidates closer than 0.05 of a cell
+ * side are one image.  Outputs (DEVICE):
+ *   out [B][n_src][max_images][3] = x, y, signed mu = 1 / det(I - H) (the Hessian as gl_lens_maps has it), images sorted by x
+ *       then y, NaN-padded;
+ *   n_images [B][n_src] images written;
+ *   n_dropped [B][n_src] candidates that did not converge or converged outside the window + triangles that hit beyond the
+ *       64 candidates one (sample, source) holds + images beyond max_images (nothing is truncated silently).  A candidate
+ *       whose seed misses beta_s by more than a cell side (its triangle straddles a singular lens centre: SIS, SIE, EPL with
+ *       gamma >= 2) and does not converge is no image and is not counted.
+ * Guaranteed: every image inside the window whose neighbourhood is not folded more finely than one cell.  Not guaranteed: images
+ * outside the window, two images closer than about one cell at a fold.  Deterministic (two calls give identical bits; a row does
+ * not depend on the other rows).  No host synchronisation, no allocation: workspace of gl_image_positions_workspace_bytes
+ * (0 for invalid sizes).  GL_EINVAL: sizes <= 0, n_cells > 8192, max_images outside [1, 64], an empty window, tol <= 0,
+ * max_iter < 1; GL_EUNSUPPORTED: GL_SERIES lenses (their field exists on the model grid only).  Models with user-written lenses:
+ * the map and Newton kernels are compiled with the point kernels (gl_lens_maps) when first asked for. */
+size_t gl_image_positions_workspace_bytes(const gl_model* m, int B, int n_src, int n_cells, int max_images);
+int gl_image_positions(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                       float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images, float tol, int max_iter,
+                       float* out, int* n_images, int* n_dropped, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Plugin-level point evaluation, the reference's MassProfile.deriv / LightProfile.light called on
  * arbitrary coordinates (tests/test_profiles.py calls exactly these):
  *   x, y [n_pts, B] when xy_batched, else [n_pts] shared by every sample (pixel-major, batch-minor

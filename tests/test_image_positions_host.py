@@ -1,0 +1,24 @@
+"""Lens-equation solver: the C ABI's argument checks, no device needed."""
+import ctypes
+
+import pytest
+
+
+@pytest.fixture(scope="module")
+def native():
+    from gigalens_amd import _native
+    try:
+        _native.lib()
+    except _native.NativeLibraryError as e:
+        pytest.skip(str(e))
+    return _native
+
+
+def test_image_positions_refuses_bad_arguments(native):
+    lib = native.lib()
+    assert lib.gl_image_positions_workspace_bytes(None, 4, 2, 64, 8) == 0
+    null = ctypes.c_void_p(0)
+    rc = lib.gl_image_positions(None, null, 4, null, null, 2, -1.0, 1.0, -1.0, 1.0, 64, 8, 1e-6, 30, null, null, null, null, 0,
+                                null)
+    assert rc == -1  # GL_EINVAL
+    assert b"null" in lib.gl_last_error()
