@@ -2,7 +2,7 @@
 """bench.py -- forward+grad lens simulations per second on BASELINE.json's configs[1]:
 EPL+shear lens, Sersic source, 128x128 px, batch 1024, fp32, per MI355X (weak scaling over GPUs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C5|...] [--mode auto|fwdgrad|svi] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C5|...] [--mode auto|fwdgrad|svi] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch.
   * mode fwdgrad (N = 1 default): ``ForwardProbModel.log_prob_and_grad(simulator, z)`` -- ``log_prob`` forward AND its
@@ -26,16 +26,24 @@ at its working clock, so an untimed pre-roll of 0.15 s of steps precedes the W w
 fwdgrad ``log_prob``, ``red_chi2``, ``grad_z`` of every sample of the batch; mode svi the all-reduced ``svi_step_buffer``.  The
 inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
-Refuses to run (exit 3) with any GIGALENS_HIP_* kernel override in the environment.  EVERY rank checks four samples of the shard
-it is about to time against the float64 oracle and its last timed step for finite outputs; the flags are MIN-all-reduced and
-all ranks exit 4 together on a failure anywhere.  At N = 1 the line carries a `configs` array: the other BASELINE.json configs
-(C1 at batch 1 and 1024, C3 table and direct, C4, C5's per-rank shard) and the SURVEY 8f workloads C6 (catalogue members) and
-C3L (linear solve), each timed for a fraction of a second with the same event ring and priced with the same two fractions (B1
-bytes against HBM peak, ISA-counted flops of the dispatched kernel against the fp32 vector peak).  At N > 1 `configs` holds
-BASELINE.json configs[4] itself: the 2048-particle cluster-model SVI with 2048 / N particles per rank -- forward+gradient on
-the shard and the real SVI step with its 8 911-float all-reduce, timed with the same barrier / max-over-ranks protocol.
+Refuses to run (exit 3) with any GIGALENS_HIP_* kernel override in the environment.  EVERY rank checks its last timed step for
+finite outputs; the flags are MIN-all-reduced and all ranks exit 4 together on a failure anywhere.
 
-Prints ONE JSON line on rank 0 (contract in the round prompt) with two extra objects:
+A plain run does only what the headline figure needs: set-up, pre-roll, the W warm-up and K timed steps, the dump if asked for,
+and the line (`roofline` null, no `configs`, `cpu_baseline` or `oracle_spot_check`).  ``--full`` adds everything else
+(--no-kernel-events, --no-configs and --no-cpu-baseline still leave out their part of it):
+  * before anything is timed, EVERY rank checks four samples of the shard it is about to time against the float64 oracle
+    (MIN-all-reduced like the finite check; exit 4 on a mismatch anywhere), reported as `oracle_spot_check`;
+  * the kernel pass after the timed region and the `roofline` object below;
+  * at N = 1 a `configs` array: the other BASELINE.json configs (C1 at batch 1 and 1024, C3 table and direct, C4, C5's per-rank
+    shard) and the SURVEY 8f workloads C6 (catalogue members) and C3L (linear solve), each timed for a fraction of a second with
+    the same event ring and priced with the same two fractions (B1 bytes against HBM peak, ISA-counted flops of the dispatched
+    kernel against the fp32 vector peak).  At N > 1 `configs` holds BASELINE.json configs[4] itself: the 2048-particle
+    cluster-model SVI with 2048 / N particles per rank -- forward+gradient on the shard and the real SVI step with its 8 911-float
+    all-reduce, timed with the same barrier / max-over-ranks protocol;
+  * at N = 1 the `cpu_baseline` object below.
+
+Prints ONE JSON line on rank 0; with --full it carries two extra objects:
   roofline     -- the dominant kernel, timed by HIP-event pairs that ride on its own dispatch packets (hipExtLaunchKernel, on
                   the launch stream, no host sync) in a pass of >= 20 further steps of the same loop right after the timed
                   region -- not inside it: a timed launch costs ~5 us of its step (12.5 -> 11.8 M sims/s with every launch
@@ -648,6 +656,9 @@ def main():
     ap.add_argument("--cpu-samples", type=int, default=None)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle spot check, the kernel pass with its roofline, the other configs and the CPU baseline "
+                         "(the --no-* options leave parts of it out); a plain run measures the headline figure only")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -697,11 +708,13 @@ def main():
     n_coll = 1 + d + d * (d + 1) // 2
     # the batch the loop will run, checked against the float64 oracle BEFORE anything is timed -- on EVERY rank, each on its own
     # shard (4 samples; 2 at the 256 x 256 configs); the flags are reduced with a MIN all-reduce and a wrong or non-finite
-    # result on any rank ends the run on all of them: a line is never printed for numbers nobody looked at
-    check = oracle_spot_check(wl, pm, sim, z, obs, err, n=2 if N > 16384 else 4)
-    if not all_ranks_ok(check["ok"], dev):
-        sys.stderr.write(f"bench.py: rank {rank}: the timed batch does not match the oracle on some rank (this rank: {check})\n")
-        sys.exit(4)
+    # result on any rank ends the run on all of them.  --full only: the check feeds no figure of the line
+    check = None
+    if args.full:
+        check = oracle_spot_check(wl, pm, sim, z, obs, err, n=2 if N > 16384 else 4)
+        if not all_ranks_ok(check["ok"], dev):
+            sys.stderr.write(f"bench.py: rank {rank}: the timed batch does not match the oracle on some rank (this rank: {check})\n")
+            sys.exit(4)
 
     if mode == "svi":
         step, series_svi = make_svi_step(wl, pm, sim, B, dev, rank)
@@ -722,7 +735,7 @@ def main():
             pm.log_prob_and_grad(sim, z)
         torch.cuda.synchronize()
         n_pre += 50
-    events = not args.no_kernel_events
+    events = args.full and not args.no_kernel_events
     # the kernel pass after the timed region times every main launch (event pairs on the dispatch packets, csrc/gl_launch.hip.h);
     # --kernel-event-stride thins it out if asked to
     stride = max(1, min(args.kernel_event_stride, args.steps))
@@ -743,7 +756,7 @@ def main():
     # BASELINE.json configs[4] rides on the N > 1 line: the 2048-particle cluster-model SVI sharded over the ranks
     c5 = None
     c5_ok = True
-    if world > 1 and args.mode == "auto" and args.workload.upper() == "C2" and not args.no_configs:
+    if world > 1 and args.mode == "auto" and args.workload.upper() == "C2" and args.full and not args.no_configs:
         c5, c5_ok = measure_c5_sharded(dev, rank, world, min(args.steps, 200), min(max(args.warmup, 5), 20), events, stride)
     if not all_ranks_ok(finite_after and c5_ok, dev):
         sys.stderr.write(f"bench.py: rank {rank}: a timed loop returned non-finite values or the C5 shard failed its check on some rank "
@@ -817,9 +830,9 @@ def main():
                                 "ForwardProbModel.log_prob_and_grad: log_prob forward + gradient w.r.t. z (bijector, "
                                 "kernels, prior) in one native launch sequence")},
             "roofline": roofline,
-            "oracle_spot_check": check,
         }
-        out["oracle_spot_check"] = dict(check, ranks_checked=world, all_ranks_ok=True)
+        if check is not None:
+            out["oracle_spot_check"] = dict(check, ranks_checked=world, all_ranks_ok=True)
         if svi_side is not None:
             out["svi_step"] = svi_side
         elif sharded is not None:
@@ -830,12 +843,12 @@ def main():
             out["multi_gpu_note"] = (f"backend {torch.distributed.get_backend()}: until a SCALE_rNN.json of the driver exists, no N > 1 line "
                                      "of this repository has been measured over RCCL / xGMI (the builder's boxes have one GPU; rehearsals "
                                      "run two gloo ranks on it, profiles/*_2rank_gloo_rehearsal.json)")
-        if world == 1 and not args.no_configs and args.workload.upper() == "C2":
+        if world == 1 and args.full and not args.no_configs and args.workload.upper() == "C2":
             del pm, sim, z
             torch.cuda.empty_cache()
             out["configs"] = measure_extra_configs(dev)  # the other BASELINE configs, each with both fractions
             out["configs"].append(measure_c3l(dev))
-        if not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N=1 only
             n_cpu = args.cpu_samples or (256 if N <= 16384 else 32)
             out["cpu_baseline"] = cpu_baseline(wl, obs, seconds=args.cpu_seconds, sample_batch=min(n_cpu, B))
         print(json.dumps(out), flush=True)

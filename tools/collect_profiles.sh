@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -- python3 $R/bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
 for W in C2 C3 C4 C5 C6; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kernel_stats_$W -- python3 $R/tools/prof_kernel.py --workload $W --iters 20 > $OUT/kernel_stats_$W.log 2>&1
 done
@@ -47,12 +47,12 @@ python3 -m pytest $R/tests/test_gpu_dist.py -m gpu -q > $OUT/two_rank_test.log 2
 python3 $R/tools/map_step_time.py > $OUT/map_step_time.log 2>&1
 python3 $R/tools/svi_hmc_step_time.py > $OUT/svi_hmc_step_time.log 2>&1
 python3 $R/tools/bench_configs.py > $OUT/bench_configs.jsonl 2> $OUT/bench_configs.err
-python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
-python3 $R/bench.py --no-cpu-baseline --mode svi > $OUT/bench_svi.json 2> $OUT/bench_svi.err
-python3 $R/bench.py --no-cpu-baseline --workload C5 --steps 200 --warmup 20 > $OUT/bench_C5.json 2> $OUT/bench_C5.err
-python3 $R/bench.py --no-cpu-baseline --workload C5 --mode svi --steps 200 --warmup 20 > $OUT/bench_C5_svi.json 2> $OUT/bench_C5_svi.err
+python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full --no-cpu-baseline --mode svi > $OUT/bench_svi.json 2> $OUT/bench_svi.err
+python3 $R/bench.py --full --no-cpu-baseline --workload C5 --steps 200 --warmup 20 > $OUT/bench_C5.json 2> $OUT/bench_C5.err
+python3 $R/bench.py --full --no-cpu-baseline --workload C5 --mode svi --steps 200 --warmup 20 > $OUT/bench_C5_svi.json 2> $OUT/bench_C5_svi.err
 # round 4: the N > 1 line (C2 value, svi_step, BASELINE configs[4] in `configs`) rehearsed with two gloo ranks sharing this GPU
-GIGALENS_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 2 --steps 20 --warmup 5 > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err
+GIGALENS_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 2 --steps 20 --warmup 5 --full > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err
 # the cluster kernel's issue / wait / LDS counters (tools/pmc_kernel.sh: four passes)
 bash $R/tools/pmc_kernel.sh ${TAG}_C4 C4 > $OUT/pmc_kernel_C4.log 2>&1
 tail -1 $OUT/bench.json
