@@ -128,9 +128,11 @@ int launch_main(const gl_model* m, const MainArgs& a, int B, int n_chunks, hipSt
   constexpr bool GRADM = (MODE == IMG_BWD || MODE == LL_GRAD);
   const bool generic_first = m->has_user || m->shp_big || (GRADM && m->cluster && a.parts == 7u) || MODE == IMG_BASIS;
   m->last_main_user = -1;
-  if (!generic_first && m->static_id && a.parts == 7u && launch_static<MODE>(m, a, grid, block, shmem, stream, ev0, ev1)) {
-    // specialised kernel launched
-  } else {
+  bool launched = false;  // a specialised kernel went out
+  // (the basis stack is always generic_first: launch_static<IMG_BASIS> is never instantiated, so no dead mode-4 kernels ship)
+  if constexpr (MODE != IMG_BASIS)
+    launched = !generic_first && m->static_id && a.parts == 7u && launch_static<MODE>(m, a, grid, block, shmem, stream, ev0, ev1);
+  if (!launched) {
     const int rc = launch_generic<MODE>(m, a, grid, block, shmem, stream, ev0, ev1);
     if (rc) {
       // no kernel went out: the claimed ring slot must still hold a complete pair, or a drain would wait on (or read) events
