@@ -66,10 +66,11 @@ def _vjp_conditioning_bound(wl, packed64, cot, g_o, S, seed=0):
     return out
 
 
-def check_case_vs_oracle(gl, case, kernel_name):
-    """Run the four modes of `case` (environment already set), check the launched kernels and compare each mode with the oracle.
-    Returns the measured errors."""
-    wl = DC.workload(case)
+def check_case_vs_oracle(gl, case, kernel_name, wl=None):
+    """Run the four modes of `case` (environment already set) on its workload (default: DC.workload(case)), check the launched
+    kernels and compare each mode with the oracle.  Returns the measured errors and the number of gradient elements that needed
+    the conditioning allowance."""
+    wl = DC.workload(case) if wl is None else wl
     obs, err, _ = gl.workloads.synthetic_observation(wl, gl.LensSimulator)
     sim = gl.LensSimulator(wl.phys_model, wl.sim_config, bs=wl.batch)
     packed = H.sample_packed(wl, sim, seed=11)
@@ -122,6 +123,7 @@ def check_case_vs_oracle(gl, case, kernel_name):
     # tile kernels give those elements the same errors)
     ok, rep = H.grad_gate(g_vjp, g_vjp_o, GRAD_RTOL_COL, lambda S: _vjp_conditioning_bound(wl, p64, cot, g_vjp_o, S))
     assert ok, ("IMG_BWD", rep, res)
+    res["vjp_conditioned"] = rep["conditioned"]
     # LL_FWD and LL_GRAD: value and reduced chi^2 against the oracle, and against each other
     for ll, red in ((ll_f, red_f), (ll_g, red_g)):
         assert np.allclose(ll, ll_o, rtol=LL_RTOL), res
@@ -130,7 +132,45 @@ def check_case_vs_oracle(gl, case, kernel_name):
     ok, rep = H.grad_gate(g, g_o, GRAD_RTOL_COL,
                           lambda S: H.float32_conditioning_bound(wl, p64, obs_np, err_np, wl.batch, g_o, S))
     assert ok, ("LL_GRAD", rep, res)
+    res["grad_conditioned"] = rep["conditioned"]
+    print(f"{case.id}: conditioned elements: vjp {res['vjp_conditioned']} grad {res['grad_conditioned']}")
     return res
+
+
+def check_basis_vs_oracle(gl, case, kernel_name, wl=None):
+    """The basis stack of lstsq (IMG_BASIS) of `case` against the oracle's, under the gate of
+    test_gpu_lstsq.py::test_lstsq_simulate_vs_oracle; outside a pixel region the stack is exactly 0.  The stack is asked for with
+    an observation and an error map, so the fused shapelet normal-matrix path (no stack) cannot take over.  Before the checked call
+    every 32-bit word of the workspace the stack is rendered into is set to 1 (float 1.4e-45; harmless as any index or count the
+    workspace holds): a stack pixel the call does not write -- outside the region, the zeroing gl_lstsq_fwd owes it -- is not 0."""
+    from oracle import ref_torch as ref
+    wl = DC.workload(case) if wl is None else wl
+    sim = gl.LensSimulator(wl.phys_model, wl.sim_config, bs=wl.batch)
+    packed = H.sample_packed(wl, sim, seed=11)
+    m = sim._model
+    n = wl.sim_config.num_pix
+    obs = torch.zeros((n, n), dtype=torch.float32, device=packed.device)
+    err = torch.ones_like(obs)
+    m.lstsq(packed, obs, err, 7, "stacked")  # sizes the workspace
+    ws = m._lstsq_ws
+    ws[:ws.numel() // 4 * 4].view(torch.int32).fill_(1)
+    (st,) = m.lstsq(packed, obs, err, 7, "stacked")
+    seen = kernel_name(m.last_main_kernel())
+    assert [seen] == list(case.kernels), f"{DC.BASIS_MODE}: launched {seen}\n  declared {case.kernels[0]}"
+    rs = ref.RefSimulator(wl.phys_model, wl.sim_config, wl.batch, dtype=torch.float64)
+    st_o = ref.lstsq_simulate(rs, H.struct_from_packed(wl.phys_model, packed.cpu().double()), None, None, return_stacked=True)
+    st_o = st_o.permute(0, 3, 1, 2)  # (bs, depth, H, W), the native layout
+    st = st.cpu().double()
+    assert st.shape == st_o.shape, (st.shape, st_o.shape)
+    assert torch.isfinite(st_o).all()
+    sc = st_o.abs().amax(dim=(2, 3), keepdim=True)
+    err_st = float(((st - st_o).abs() / (5e-5 * sc + 1e-7)).max())
+    print(f"{case.id}: stack error {err_st:.2f} x the gate")
+    assert torch.all((st - st_o).abs() <= 5e-5 * sc + 1e-7), err_st
+    if case.pix_region:
+        outside = sim.img_region.cpu() == 0
+        assert torch.all(st[:, :, outside] == 0)
+    return dict(stack=err_st)
 
 
 @pytest.mark.parametrize("case", DC.CASES, ids=[c.id for c in DC.CASES])
@@ -140,3 +180,17 @@ def test_dispatch_case_vs_oracle(gl, case, kernel_name, monkeypatch):
     for k, v in case.env.items():
         monkeypatch.setenv(k, v)
     check_case_vs_oracle(gl, case, kernel_name)
+
+
+@pytest.mark.parametrize("case", DC.GENERIC_CASES, ids=[c.id for c in DC.GENERIC_CASES])
+def test_generic_dispatch_case_vs_oracle(gl, case, kernel_name, monkeypatch):
+    """The interpreter, the cluster kernels and the basis stack (launch_generic) against the float64 oracle, one case per
+    instantiation and edge (tests/dispatch_cases.py::GENERIC_CASES)."""
+    for k in DC.ENV_KNOBS + DC.GENERIC_ENV_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in case.env.items():
+        monkeypatch.setenv(k, v)
+    if case.basis:
+        check_basis_vs_oracle(gl, case, kernel_name)
+    else:
+        check_case_vs_oracle(gl, case, kernel_name)
