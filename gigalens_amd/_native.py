@@ -22,6 +22,11 @@ class NativeLibraryError(RuntimeError):
     pass
 
 
+class UnsupportedLensError(NativeLibraryError):
+    """A lens the call cannot serve (GL_EUNSUPPORTED from the lensing-potential calls): series expansions, user-written bodies and
+    the run-time compiled ScalingRelation member loops define a deflection only, no potential."""
+
+
 class gl_component(ctypes.Structure):
     _fields_ = [("kind", c_int32), ("iparam", c_int32), ("flags", c_uint32), ("reserved", c_int32)]
 
@@ -82,6 +87,7 @@ SYMBOLS = {
     "gl_series_hessian_eval": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "gl_model_set_series_hessian": (c_int, [c_void_p, c_int, c_void_p]),
     "gl_lens_maps": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "gl_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
                                    c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -107,6 +113,8 @@ SYMBOLS = {
     "gl_user_profile_destroy": (None, [c_void_p]),
     "gl_profile_hessian": (c_int, [POINTER(gl_component), c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p]),
+    "gl_profile_potential": (c_int, [POINTER(gl_component), c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p]),
     "gl_kind_num_params": (c_int, [POINTER(gl_component)]),
     "gl_model_set_timing": (c_int, [c_void_p, c_int]),
     "gl_model_last_main_ms": (c_int, [c_void_p, POINTER(c_float)]),
@@ -146,6 +154,16 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise NativeLibraryError(f"gigalens_hip error {rc}: {lib().gl_last_error().decode()}")
+
+
+GL_EUNSUPPORTED = -2
+
+
+def _check_potential(rc):
+    """_check for the lensing-potential calls: GL_EUNSUPPORTED becomes UnsupportedLensError."""
+    if rc == GL_EUNSUPPORTED:
+        raise UnsupportedLensError(f"gigalens_hip error {rc}: {lib().gl_last_error().decode()}")
+    _check(rc)
 
 
 def _require_cuda(t, what):
@@ -405,6 +423,21 @@ def profile_hessian(profile, x, y, kwargs):
     return tuple(out[k].reshape(out_shape) for k in range(4))
 
 
+def profile_potential(profile, x, y, kwargs):
+    """MassProfile.potential (beyond the reference): psi on points, free-standing built-in mass kinds only (gl_profile_potential)."""
+    if any(torch.is_tensor(v) and v.requires_grad for v in (x, y, *kwargs.values())):
+        raise NotImplementedError("potential is forward-only (no gradient)")
+    if not profile._component()[0]:
+        raise UnsupportedLensError(f"profile {profile.name!r}: a user-written body defines a deflection only, no potential")
+    dev = device()
+    comp = component_of(profile)
+    xb, yb, P, B, out_shape = _broadcast_points(profile, x, y, kwargs, list(profile.params), dev)
+    out = torch.empty_like(xb)
+    _check_potential(lib().gl_profile_potential(ctypes.byref(comp), _ptr(xb), _ptr(yb), xb.shape[0], B, 1, _ptr(P), _ptr(out),
+                                                _stream()))
+    return out.reshape(out_shape)
+
+
 def profile_eval(profile, x, y, kwargs):
     up = user_profile_of(profile) if not profile._component()[0] else None
     if up is not None:
@@ -579,6 +612,23 @@ class Model:
         out = torch.empty((6,) + tuple(xb.shape), dtype=torch.float32, device=self.device)
         _check(lib().gl_lens_maps(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), xb.shape[0], 1, _ptr(out), _stream()))
         return out.reshape((6,) + tuple(shape))
+
+    def lens_potential(self, params, x, y):
+        """gl_lens_potential: ``x, y`` broadcastable to ``(..., B)`` (or both None: the model's own grid, ``(N, B)``); returns psi."""
+        params = self._params(params)
+        B = params.shape[0]
+        if x is None and y is None:
+            out = torch.empty((self.N, B), dtype=torch.float32, device=self.device)
+            _check_potential(lib().gl_lens_potential(self._h, _ptr(params), B, None, None, self.N, 0, _ptr(out), _stream()))
+            return out
+        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+        y = torch.as_tensor(y, dtype=torch.float32, device=self.device)
+        shape = torch.broadcast_shapes(x.shape, y.shape, (B,))
+        xb = x.expand(shape).reshape(-1, B).contiguous()
+        yb = y.expand(shape).reshape(-1, B).contiguous()
+        out = torch.empty(tuple(xb.shape), dtype=torch.float32, device=self.device)
+        _check_potential(lib().gl_lens_potential(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), xb.shape[0], 1, _ptr(out), _stream()))
+        return out.reshape(tuple(shape))
 
     def image_positions(self, params, src_x, src_y, window, n_cells, max_images, tol, max_iter):
         """gl_image_positions: ``src_x, src_y`` [B, S] on the device, ``window`` = (x_lo, x_hi, y_lo, y_hi).  Returns

@@ -21,6 +21,7 @@
 #include "gl_post.hip.h"
 #include "gl_positions.hip.h"
 #include "gl_images.hip.h"
+#include "gl_potential.hip.h"
 #include "gl_lstsq.hip.h"
 #include "gl_shp.hip.h"
 
@@ -1651,6 +1652,72 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
   }
   hipLaunchKernelGGL(gl_lens_maps_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, a,
                      x, y, (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- lensing potential (gl_potential.hip.h) --------------------------------------------------------------------
+namespace {
+bool potential_kind(int kind) {
+  return (kind >= GL_EPL && kind <= GL_DPIEP) || kind == GL_NFW_ELLIPSE || kind == GL_TNFW;
+}
+}  // namespace
+
+int gl_lens_potential(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
+                      int xy_batched, float* out, void* hip_stream) {
+  if (!m || !params || !out) return fail(GL_EINVAL, "null argument");
+  if ((x == nullptr) != (y == nullptr)) return fail(GL_EINVAL, "x and y must both be given or both be null");
+  if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
+  for (int l = 0; l < m->n_lens; ++l) {
+    const int kind = m->comps[l].kind;
+    if (kind == GL_SERIES)
+      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its precomputed field holds the deflection, no potential", l);
+    if (kind == GL_USER_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
+                                   "a body defines the deflection only, no potential", l);
+    if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
+  }
+  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  if (!x) {
+    if (n_pts != m->N || xy_batched) return fail(GL_EINVAL, "the model grid has %d points and is not batched", m->N);
+    x = m->d_gx;
+    y = m->d_gy;
+  }
+  const long long total = (long long)n_pts * B, blocks = (total + POT_WG - 1) / POT_WG;
+  if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
+  PosArgs a{};
+  a.comps = m->d_comps;
+  a.n_lens = m->n_lens;
+  a.P = m->P;
+  a.B = B;
+  a.params = params;
+  a.cats = m->d_cats;
+  a.gal_table = m->d_gal_table;
+  a.gal_static = m->d_gal_static;
+  hipLaunchKernelGGL(gl_lens_potential_kernel, dim3((unsigned)blocks), dim3(POT_WG), 0, (hipStream_t)hip_stream, a, x, y,
+                     (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+int gl_profile_potential(const gl_component* comp, const float* x, const float* y, int64_t n_pts, int B, int xy_batched,
+                         const float* params, float* out, void* hip_stream) {
+  if (!comp || !x || !y || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (n_pts <= 0 || B <= 0) return fail(GL_EINVAL, "n_pts and B must be positive");
+  if (comp->kind == GL_SCALED || comp->kind == GL_SERIES || comp->kind == GL_USER_MASS)
+    return fail(GL_EUNSUPPORTED, "kind %d has no plugin-level potential (free-standing built-in mass kinds only; catalogues: "
+                                 "gl_lens_potential on a model)", comp->kind);
+  if (!potential_kind(comp->kind)) return fail(GL_EINVAL, "kind %d is not a free-standing mass profile", comp->kind);
+  const long long total = (long long)n_pts * B, blocks = (total + POT_WG - 1) / POT_WG;
+  if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
+  CompDesc cd{};
+  cd.kind = comp->kind;
+  cd.iparam = comp->iparam;
+  cd.flags = comp->flags;
+  cd.n_par = kind_num_params(comp->kind, comp->iparam);
+  if (cd.kind == GL_EPL && cd.iparam <= 0) cd.iparam = 50;
+  hipLaunchKernelGGL(gl_profile_potential_kernel, dim3((unsigned)blocks), dim3(POT_WG), 0, (hipStream_t)hip_stream, cd, x, y,
+                     (long long)n_pts, B, xy_batched, params, out);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

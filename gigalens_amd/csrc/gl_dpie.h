@@ -170,6 +170,24 @@ template <class R, bool FULL> GL_HD void piep_vjp(const R* ds, const R* dd, R x,
   }
 }
 
+// potential of piep_fwd: alpha = grad of S [F(rc) - F(rt)] at the stretched r2, F(a) = W_a - a ln(a + W_a), W_a = sqrt(a^2 + r2)
+// (dF/d r2 = 1 / (2 (W_a + a)); on the stretched coordinates the same holds for DPIEP, an elliptical potential).  Constant:
+// psi(centre) = 0, i.e.  psi = S [(W_c - rc) - (W_t - rt) - rc ln((rc + W_c) / (2 rc)) + rt ln((rt + W_t) / (2 rt))],  with
+// (W_c - rc) - (W_t - rt) = (rt - rc) (u_c + u_t) / (W_c + W_t),  u_a = W_a - a = r2 / (W_a + a),  and the logarithms as
+// log1p(u_a / (2a)): nothing cancels.  Where the dPIS Hessian override adds its convergence excess (dpis_kappa_excess), psi
+// follows the deflection, not the override.
+template <class R> GL_HD R piep_pot(const R* ds, const R* dd, R x, R y) {
+  R dx = x - ds[DPS_CX], dy = y - ds[DPS_CY];
+  R c = ds[DPS_CPHI], s = ds[DPS_SPHI];
+  R rc = dd[DPD_RC], rt = dd[DPD_RT];
+  R xr = dx * c + dy * s, yr = dy * c - dx * s;
+  R r2 = xr * xr * ds[DPS_M1] + yr * yr * ds[DPS_P1];
+  R Wc = sqrt_(r2 + rc * rc), Wt = sqrt_(r2 + rt * rt);
+  R uc = r2 / (Wc + rc), ut = r2 / (Wt + rt);
+  R lin = dd[DPD_DR] * (uc + ut) / (Wc + Wt);
+  return dd[DPD_S] * (lin - rc * log1p_(uc / ((R)2 * rc)) + rt * log1p_(ut / ((R)2 * rt)));
+}
+
 // =============================================================================================
 // DPIE per pixel  (piemd.py:201-255)
 //   znum_w = q x + i (2 sqrt(e) sqrt(w^2 + rem^2) - y/q),  zden_w = x + i (2 sqrt(e) w - y)
@@ -216,6 +234,28 @@ template <class R> GL_HD void piemd_fwd(const R* ds, const R* dd, R x, R y, R& a
   R arx = -SZ * o.arg, ary = SZ * o.L;
   ax = arx * c - ary * s;
   ay = arx * s + ary * c;
+}
+// potential of piemd_fwd.  One Kassiola-Kovner term of core w is, in the lens frame, the cored isothermal ellipsoid of Keeton
+// (2001) with axis ratio q and core s = w (1 + e) (its psi-tilde is (1 - e) W_w, W_w = sqrt(w^2 + rem^2)), whose potential is
+//   x' alpha_x + y' alpha_y - A sqrt(1 - q^2) s ln sqrt((psi-tilde + s)^2 + (1 - q^2) x'^2),   A sqrt(1 - q^2) s = (1 - e^2) w.
+// Differenced over w = rc, rt and scaled by S, with (1 - e^2) = -2 sqrt(e) Z and the arguments divided by (1 + e)^2:
+//   psi = x' alpha_x + y' alpha_y + S Z 2 sqrt(e) (rc l_c - rt l_t),  l_w = ln sqrt((q W_w + w)^2 + (2 sqrt(e) x' / (1 + e)^2)^2)
+// with the total deflection of piemd_fwd in the first term.  Constant: l_w - ln(w (1 + q)) is taken, so psi(centre) = 0; as
+// log1p of ((q W + w)^2 - (q w + w)^2 + ...) / (w (1 + q))^2 with (q W + w)^2 - (q w + w)^2 = q u (q (W + w) + 2w), u = rem^2 / (W + w).
+template <class R> GL_HD R piemd_pot_log(R q, R opq, R rem2, R ex2, R w, R W) {
+  R u = rem2 / (W + w);
+  R d0 = w * opq;
+  return (R)0.5 * log1p_((q * u * (q * (W + w) + (R)2 * w) + ex2) / (d0 * d0));
+}
+template <class R> GL_HD R piemd_pot(const R* ds, const R* dd, R x, R y) {
+  PiemdPix<R> o;
+  piemd_pix(ds, dd, x, y, o);
+  R SZ = dd[DPD_S] * ds[DPS_Z], q = ds[DPS_Q], s2 = ds[DPS_S2], rc = dd[DPD_RC], rt = dd[DPD_RT];
+  R arx = -SZ * o.arg, ary = SZ * o.L;  // deflection in the lens frame
+  R rem2 = o.xr * o.xr * ds[DPS_IX] + o.yr * o.yr * ds[DPS_IY];
+  R ex = s2 * ds[DPS_IX] * o.xr, opq = (R)1 + q;
+  R lc = piemd_pot_log(q, opq, rem2, ex * ex, rc, o.Wc), lt = piemd_pot_log(q, opq, rem2, ex * ex, rt, o.Wt);
+  return o.xr * arx + o.yr * ary + SZ * s2 * (rc * lc - rt * lt);
 }
 template <class R, bool FULL>
 GL_HD void piemd_vjp(const R* ds, const R* dd, const R* de, R x, R y, R gx, R gy, R* acc) {
@@ -272,6 +312,9 @@ template <class R> GL_HD void dpie_prep(int kind, const R* p, R* d) {
 template <class R> GL_HD void dpie_fwd(int kind, const R* d, R x, R y, R& ax, R& ay) {
   if (kind == K_DPIE) piemd_fwd<R>(d, d + DP_NS, x, y, ax, ay);
   else piep_fwd<R>(d, d + DP_NS, x, y, ax, ay);
+}
+template <class R> GL_HD R dpie_pot(int kind, const R* d, R x, R y) {
+  return kind == K_DPIE ? piemd_pot<R>(d, d + DP_NS, x, y) : piep_pot<R>(d, d + DP_NS, x, y);
 }
 template <class R> GL_HD void dpie_vjp(int kind, const R* d, R x, R y, R gx, R gy, R* acc) {
   if (kind == K_DPIE) piemd_vjp<R, true>(d, d + DP_NS, d + DPX_DE, x, y, gx, gy, acc);

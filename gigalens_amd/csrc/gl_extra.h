@@ -43,6 +43,15 @@ template <class R> GL_HD void nfw_ell_fwd(const R* d, R x, R y, R& ax, R& ay) {
   ax = fx * c - fy * s;
   ay = fx * s + fy * c;
 }
+// potential: the spherical NFW psi (nfw_pot) on the stretched coordinates -- an elliptical potential, whose gradient is the
+// deflection above.  Constant: psi(centre) = 0.
+template <class R> GL_HD R nfw_ell_pot(const R* d, R x, R y) {
+  R dx = x - d[NFE_CX], dy = y - d[NFE_CY];
+  R c = d[NFE_C], s = d[NFE_S];
+  R xr = dx * c + dy * s, yr = dy * c - dx * s;
+  const R dl[NFW_ND] = {(R)0, (R)0, d[NFE_INVRS], d[NFE_K0]};
+  return nfw_pot<R>(dl, xr * d[NFE_SM], yr * d[NFE_SP]);
+}
 template <class R> GL_HD void nfw_ell_vjp(const R* d, R x, R y, R gx, R gy, R* acc) {
   R dx = x - d[NFE_CX], dy = y - d[NFE_CY];
   R c = d[NFE_C], s = d[NFE_S], sm = d[NFE_SM], sp = d[NFE_SP];
@@ -161,6 +170,36 @@ template <class R> GL_HD void tnfw_fwd(const R* d, R x, R y, R& ax, R& ay) {
   R a = d[TNF_K] * g / (X * X);
   ax = a * dx;
   ay = a * dy;
+}
+// potential of tnfw_fwd: |alpha| = K Rs g(X) / X, so with u = ln X  psi = K Rs^2 [g(X_b) / 2 + integral_{ln X_b}^{ln X} g(e^u) du],
+// X_b = 0.001 the reference's clamp (inside it the deflection is linear in (dx, dy): psi = K Rs^2 g(X_b) (X / X_b)^2 / 2).  The integral
+// is Gauss-Legendre, 8 nodes on each of n = floor(ln(X / X_b)) + 1 (<= 64) equal panels of width < 1: g(e^u) is analytic in a
+// strip of half-width pi/2 about the real axis (its nearest singularities are the branch points of sqrt(tau^2 + X^2) at
+// u = ln tau +- i pi/2), so a panel's error is ~ 1e-13 of its value and float32 rounding of g dominates.  psi(centre) = 0.
+template <class R> GL_HD R tnfw_pot(const R* d, R x, R y) {
+  constexpr double kT[4] = {0.1834346424956498, 0.5255324099163290, 0.7966664774136267, 0.9602898564975362};
+  constexpr double kW[4] = {0.3626837833783618, 0.3137066458778870, 0.2223810344533743, 0.1012285362903767};
+  R dx = x - d[TNF_CX], dy = y - d[TNF_CY];
+  R X0 = sqrt_(dx * dx + dy * dy) * d[TNF_INVRS];
+  R Rs = (R)1 / d[TNF_INVRS], tau = d[TNF_TAU], K2 = d[TNF_K] * Rs * Rs;
+  const R Xb = (R)0.001;
+  R g, gX, gT;
+  tnfw_g(Xb, tau, g, gX, gT);
+  if (!(X0 > Xb)) return (R)0.5 * K2 * g * (X0 / Xb) * (X0 / Xb);
+  R Lu = log_(X0 / Xb);
+  int n = Lu < (R)63 ? (int)floor_(Lu) + 1 : 64;
+  R h = Lu / (R)n, acc = (R)0.5 * g;
+  for (int i = 0; i < n; ++i) {
+    R mid = ((R)i + (R)0.5) * h, part = (R)0;
+    for (int k = 0; k < 4; ++k) {
+      R off = (R)0.5 * h * (R)kT[k], g1, g2;
+      tnfw_g(Xb * exp_(mid - off), tau, g1, gX, gT);
+      tnfw_g(Xb * exp_(mid + off), tau, g2, gX, gT);
+      part += (R)kW[k] * (g1 + g2);
+    }
+    acc += (R)0.5 * h * part;
+  }
+  return K2 * acc;
 }
 template <class R> GL_HD void tnfw_vjp(const R* d, R x, R y, R gx, R gy, R* acc) {
   R dx = x - d[TNF_CX], dy = y - d[TNF_CY];

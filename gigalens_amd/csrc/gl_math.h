@@ -78,6 +78,8 @@ GL_HD float floor_(float x) { return ::floorf(x); }
 GL_HD bool isnan_(float x) { return x != x; }
 
 template <class R> GL_HD R clamp_(R x, R lo, R hi) { return fmin_(fmax_(x, lo), hi); }
+// log(1 + z) without the cancellation of 1 + z for small |z|: 2 atanh(z / (2 + z)) there (|z / (2 + z)| < 1/3)
+template <class R> GL_HD R log1p_(R z) { return fabs_(z) < (R)0.5 ? (R)2 * atanh_(z / ((R)2 + z)) : log_((R)1 + z); }
 
 // the wider twin of a real type, for the few expressions whose cancellation exceeds fp32 (float -> double; a type that
 // is already wide maps to itself; gl_dual.h extends this to dual numbers component-wise)

@@ -469,6 +469,14 @@ template <class R> GL_HD void epl_point(const R* p, int cap, R x, R y, R& ax, R&
   ax = arx * c - ary * s;
   ay = arx * s + ary * c;
 }
+// lensing potential psi (grad psi = epl_point's deflection).  The EPL potential is homogeneous of degree 2 - t about the
+// centre, so Euler's relation gives psi = (x' alpha_x + y' alpha_y) / (2 - t), (x', y') = (x - cx, y - cy) (Tessore & Metcalf
+// 2015); it holds for the truncated series as well, to the series' own tolerance.  Constant: psi(centre) = 0.
+template <class R> GL_HD R epl_pot(const R* p, int cap, R x, R y) {
+  R ax, ay;
+  epl_point<R>(p, cap, x, y, ax, ay);
+  return ((x - p[4]) * ax + (y - p[5]) * ay) / ((R)3 - p[1]);
+}
 
 // =============================================================================================
 // SIE  (tf/profiles/mass/sie.py:13-42; core s == 0 because s_scale is shadowed by a local, :15)
@@ -540,6 +548,13 @@ template <class R> GL_HD void sie_finalize(const R* p, const R* acc, R* g) {
   g[2] = g_e2;
   g[3] = acc[SIEA_CX];
   g[4] = acc[SIEA_CY];
+}
+// psi of sie_fwd: the singular isothermal ellipsoid (s = 0) is homogeneous of degree 1, psi = x' alpha_x + y' alpha_y.
+// Constant: psi(centre) = 0.
+template <class R> GL_HD R sie_pot(const R* d, R x, R y) {
+  R ax, ay;
+  sie_fwd<R>(d, x, y, ax, ay);
+  return (x - d[SIE_CX]) * ax + (y - d[SIE_CY]) * ay;
 }
 
 // =============================================================================================
@@ -647,6 +662,39 @@ template <class R> GL_HD void nfw_finalize(const R* p, const R* acc, R* g) {
   g[2] = acc[NFWA_CX];
   g[3] = acc[NFWA_CY];
 }
+// NFW potential: |alpha| = K0 Rs g(X) / X at X = r / Rs, so psi = (K0 Rs^2 / 2) h(X) with dh/dX = 2 g(X) / X:
+//   h = ln^2(X/2) - artanh^2 sqrt(1 - X^2)  (X < 1),   ln^2(X/2) + arctan^2 sqrt(X^2 - 1)  (X >= 1).
+// For X < 1 the two squares cancel as X -> 0 (h = O(X^2 ln X)); with a = ln(X/2) and d = ln((1+s)/2), s = sqrt(1 - X^2),
+// artanh s = d - a and h = d (2a - d), d = log1p(-X^2 / (2 (1 + s))): nothing cancels.  h(0) = 0.
+template <class R> GL_HD R nfw_h(R X) {
+  const R D = ((R)1 - X) * ((R)1 + X);
+  const R a = log_((R)0.5 * X);
+  if (D > (R)0) {
+    const R dl = log1p_(-X * X / ((R)2 * ((R)1 + sqrt_(D))));
+    return dl * ((R)2 * a - dl);
+  }
+  const R t = atan_(sqrt_(-D));
+  return a * a + t * t;
+}
+// psi of nfw_fwd (grad psi = its deflection, the clamps R >= 1e-7 and X >= 1e-6 included: below X_b = max(1e-6, 1e-7 / Rs)
+// X is frozen and the deflection is linear in (dx, dy), psi = psi(X_b) + K0 g(X_b) / (2 X_b^2) (r^2 - r_b^2)).  The
+// reference's g(1) = 1 (nfw_gw) differs from the continuous g on a set of measure zero; psi is the continuous one's.
+// Constant: psi(centre) = 0 up to that O(r_b^2) core.
+template <class R> GL_HD R nfw_pot(const R* d, R x, R y) {
+  R dx = x - d[NFW_CX], dy = y - d[NFW_CY];
+  R r2 = dx * dx + dy * dy;
+  R iRs = d[NFW_INVRS], Rs = (R)1 / iRs;
+  R Xb = fmax_((R)1e-6, (R)1e-7 * iRs);
+  R X0 = sqrt_(r2) * iRs;
+  R X = fmax_(X0, Xb);
+  R psi = (R)0.5 * d[NFW_K0] * Rs * Rs * nfw_h(X);
+  if (X0 < Xb) {
+    R g, gp, rb = Xb * Rs;
+    nfw_gw(Xb, g, gp);
+    psi += (R)0.5 * d[NFW_K0] * g / (Xb * Xb) * (r2 - rb * rb);
+  }
+  return psi;
+}
 
 // =============================================================================================
 // SHEAR (tf/profiles/mass/shear.py:14-16; evaluated at the UN-shifted coordinates) and
@@ -686,6 +734,14 @@ template <class R> GL_HD void sis_vjp(const R* d, R x, R y, R gx, R gy, R* acc) 
   acc[2] += ga * iR;
 }
 template <class R> GL_HD void sis_finalize(const R* p, const R* acc, R* g) { (void)p; g[0] = acc[2]; g[1] = acc[0]; g[2] = acc[1]; }
+// potentials: psi = gamma1 (x^2 - y^2) / 2 + gamma2 x y at the un-shifted coordinates (psi(0, 0) = 0), psi = theta_E r (SIS)
+template <class R> GL_HD R shear_pot(const R* d, R x, R y) {
+  return (R)0.5 * d[SHR_G1] * (x * x - y * y) + d[SHR_G2] * x * y;
+}
+template <class R> GL_HD R sis_pot(const R* d, R x, R y) {
+  R dx = x - d[SIS_CX], dy = y - d[SIS_CY];
+  return d[SIS_TE] * sqrt_(dx * dx + dy * dy);
+}
 
 // =============================================================================================
 // SERSIC / SERSIC_ELLIPSE  (tf/profiles/light/sersic.py:29-80)

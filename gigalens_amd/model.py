@@ -303,13 +303,32 @@ class ForwardProbModel(ProbabilisticModel):
         if self.centroids_x is None:
             raise ValueError("predicted_positions needs a model built with centroids_x/centroids_y")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
+        sx, sy = self._family_sources(simulator, packed)
+        x, y, mu, n = simulator.image_positions(packed, sx, sy, **solver_kwargs)
+        return [(x[:, f], y[:, f], mu[:, f], n[:, f]) for f in range(len(self.centroids_x))]
+
+    def _family_sources(self, simulator, packed):
+        """Source of every family: the barycentre of its back-traced observed images, ``[B, F]`` x and y."""
         sx, sy = [], []
         for cx, cy in zip(self.centroids_x, self.centroids_y):
             maps = simulator._model.lens_maps(packed, cx.reshape(-1, 1), cy.reshape(-1, 1))  # (6, J_f, B)
             sx.append(maps[0].mean(dim=0))
             sy.append(maps[1].mean(dim=0))
-        x, y, mu, n = simulator.image_positions(packed, torch.stack(sx, dim=1), torch.stack(sy, dim=1), **solver_kwargs)
-        return [(x[:, f], y[:, f], mu[:, f], n[:, f]) for f in range(len(self.centroids_x))]
+        return torch.stack(sx, dim=1), torch.stack(sy, dim=1)
+
+    def predicted_time_delays(self, simulator, params, time_delay_distance=None, **solver_kwargs):
+        """Images and arrival-time delays the model predicts for every family (beyond the reference), for the same barycentre
+        source as ``predicted_positions``.  Returns one ``(x, y, mu, n, dt)`` tuple per family, ``dt`` ``[B, max_images]`` relative
+        to the family's first-arriving image, in arcsec^2 of Fermat potential or, with ``time_delay_distance`` (D_dt in Mpc, a
+        scalar or ``[B]``), in days (``LensSimulator.time_delays``, which ``solver_kwargs`` go to).  Forward only."""
+        if self.centroids_x is None:
+            raise ValueError("predicted_time_delays needs a model built with centroids_x/centroids_y")
+        packed = params if torch.is_tensor(params) else simulator.pack(params)
+        if packed.requires_grad:
+            raise NotImplementedError("predicted_time_delays is a forward-only diagnostic (no gradient)")
+        sx, sy = self._family_sources(simulator, packed)
+        x, y, mu, n, dt = simulator.time_delays(packed, sx, sy, time_delay_distance=time_delay_distance, **solver_kwargs)
+        return [(x[:, f], y[:, f], mu[:, f], n[:, f], dt[:, f]) for f in range(len(self.centroids_x))]
 
     def image_plane_rms(self, simulator, params, **solver_kwargs):
         """Image-plane rms of every family (beyond the reference; the Delta theta cluster papers report): each observed image,

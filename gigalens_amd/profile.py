@@ -83,6 +83,12 @@ class MassProfile(Parameterized, ABC):
         written (piemd.py:62-83).  Evaluated natively with forward-mode duals -- exact, no finite differences."""
         return _native.profile_hessian(self, x, y, kwargs)
 
+    def potential(self, x, y, **kwargs):
+        """Lensing potential ``psi`` at ``(x, y)`` (beyond the reference), the potential whose gradient is ``deriv``; its additive
+        constant is fixed per kind (include/gigalens_hip.h gl_lens_potential), only differences are physical.  Built-in kinds
+        only: a user-written body, a catalogue or a series expansion raises ``_native.UnsupportedLensError``.  Forward only."""
+        return _native.profile_potential(self, x, y, kwargs)
+
     def convergence(self, x, y, **kwargs):
         """tf/profile.py:29-34."""
         f_xx, _, _, f_yy = self.hessian(x, y, **kwargs)

@@ -224,6 +224,23 @@ class LensSimulator(LensSimulatorInterface):
     # still ~1e-6 arcsec on a 10-arcsec window.  A polishing step after convergence takes the point to the noise floor.
     IMAGE_TOL_EPS = 8.0
 
+    def _source_rows(self, source_x, source_y, B):
+        """Source positions as ``[B, S]`` float32 device tensors (scalars and ``[B]`` broadcast)."""
+        sx = torch.as_tensor(source_x, dtype=torch.float32, device=self.device)
+        sy = torch.as_tensor(source_y, dtype=torch.float32, device=self.device)
+        if sx.dim() == 0:
+            sx = sx.expand(B)
+        if sy.dim() == 0:
+            sy = sy.expand(B)
+        if sx.dim() == 1:
+            sx = sx.reshape(-1, 1)
+        if sy.dim() == 1:
+            sy = sy.reshape(-1, 1)
+        sx, sy = torch.broadcast_tensors(sx, sy)
+        if sx.dim() != 2 or sx.shape[0] != B:
+            raise ValueError(f"source_x / source_y must have shape [B] or [B, S] with B = {B}, got {tuple(sx.shape)}")
+        return sx, sy
+
     def image_positions(self, lens_params, source_x, source_y, *, window=None, num_cells=None, max_images=8, tol=None,
                         max_iter=30, strict=False):
         """Solve the lens equation beta(theta) = beta_s for every sample (beyond the reference: it only maps theta -> beta).
@@ -244,19 +261,7 @@ class LensSimulator(LensSimulatorInterface):
         if packed.requires_grad:
             raise NotImplementedError("image_positions is a forward-only diagnostic (no gradient)")
         B = packed.shape[0]
-        sx = torch.as_tensor(source_x, dtype=torch.float32, device=self.device)
-        sy = torch.as_tensor(source_y, dtype=torch.float32, device=self.device)
-        if sx.dim() == 0:
-            sx = sx.expand(B)
-        if sy.dim() == 0:
-            sy = sy.expand(B)
-        if sx.dim() == 1:
-            sx = sx.reshape(-1, 1)
-        if sy.dim() == 1:
-            sy = sy.reshape(-1, 1)
-        sx, sy = torch.broadcast_tensors(sx, sy)
-        if sx.dim() != 2 or sx.shape[0] != B:
-            raise ValueError(f"source_x / source_y must have shape [B] or [B, S] with B = {B}, got {tuple(sx.shape)}")
+        sx, sy = self._source_rows(source_x, source_y, B)
         if window is None:
             window = (float(self.img_X.min()), float(self.img_X.max()), float(self.img_Y.min()), float(self.img_Y.max()))
         window = tuple(float(v) for v in window)
@@ -275,6 +280,83 @@ class LensSimulator(LensSimulatorInterface):
                 raise RuntimeError(msg)
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
         return out[..., 0], out[..., 1], out[..., 2], n
+
+    def _potential_lenses(self):
+        """The lensing-potential calls serve built-in kinds and fused catalogues; refuse the rest with a typed error up front."""
+        for i, lens in enumerate(self.phys_model.lenses):
+            kind = getattr(lens, "_kind", 0)
+            if kind == 10:
+                raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): a series expansion stores its deflection on the pixel "
+                                                   "grid only, no potential")
+            if not kind and getattr(lens, "profile", None) is not None and getattr(lens, "scaling_params", None) is not None:
+                raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): a ScalingRelation compiled at run time as a member loop "
+                                                   "(base profile outside the dPIE family) defines a deflection only, no potential")
+            if not kind:
+                raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): a user-written body defines a deflection only, "
+                                                   "no potential")
+
+    def _forward_only(self, what, *tensors):
+        if any(torch.is_tensor(t) and t.requires_grad for t in tensors):
+            raise NotImplementedError(f"{what} is a forward-only diagnostic (no gradient)")
+
+    def _lens_rows(self, lens_params):
+        if torch.is_tensor(lens_params):
+            return lens_params
+        if isinstance(lens_params, dict):
+            return self._pack_partial(lens_params)
+        return self._pack_partial({"lens_mass": lens_params})
+
+    def potential(self, x, y, lens_params):
+        """Lensing potential ``psi`` summed over the lenses at ``(x, y)`` (beyond the reference; trailing axis = batch, as
+        ``convergence``): the potential whose gradient is the deflection ``beta`` subtracts.  Each kind's additive constant is
+        fixed (zero at its centre), so only differences are physical.  Built-in kinds and dPIE-family catalogues; series
+        expansions, user-written bodies and run-time compiled ScalingRelation member loops raise
+        ``_native.UnsupportedLensError``.  Forward only."""
+        packed = self._lens_rows(lens_params)
+        self._forward_only("potential", packed, x, y)
+        self._potential_lenses()
+        return self._model.lens_potential(packed, x, y)
+
+    def fermat_potential(self, x, y, source_x, source_y, lens_params):
+        """Fermat potential ``phi = |theta - beta_s|^2 / 2 - psi(theta)`` at ``theta = (x, y)`` for the source ``beta_s`` (beyond the
+        reference; arcsec^2).  ``source_x`` / ``source_y`` broadcast against ``x``, ``y`` (trailing axis = batch).  Forward only."""
+        self._forward_only("fermat_potential", source_x, source_y)
+        psi = self.potential(x, y, lens_params)
+        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+        y = torch.as_tensor(y, dtype=torch.float32, device=self.device)
+        sx = torch.as_tensor(source_x, dtype=torch.float32, device=self.device)
+        sy = torch.as_tensor(source_y, dtype=torch.float32, device=self.device)
+        return 0.5 * ((x - sx) ** 2 + (y - sy) ** 2) - psi
+
+    # D_dt / c * (1 arcsec)^2 in days per Mpc: the time-delay distance turns a Fermat-potential difference in arcsec^2 into a delay
+    # (IAU 2012 astronomical unit -> parsec -> Mpc, c exact, 1 day = 86400 s)
+    MPC_M = 648000.0 / np.pi * 149597870700.0 * 1e6
+    DAYS_PER_MPC_ARCSEC2 = MPC_M / 299792458.0 * (np.pi / 648000.0) ** 2 / 86400.0
+
+    def time_delays(self, lens_params, source_x, source_y, *, time_delay_distance=None, **solver_kwargs):
+        """Images of the sources and their arrival times for every sample (beyond the reference).
+
+        Calls ``image_positions`` (``solver_kwargs`` go there) and returns its ``x, y, mu, n`` plus ``dt`` ``[B, S, max_images]``:
+        the arrival time of every image relative to the first-arriving image of its (sample, source), i.e. its Fermat-potential
+        excess ``phi - min phi`` (``dt >= 0``; NaN where ``x`` is NaN).  Units: arcsec^2, or days when ``time_delay_distance``
+        (D_dt in Mpc, a scalar or ``[B]``) is given: ``dt * D_dt * DAYS_PER_MPC_ARCSEC2``.  Forward only."""
+        packed = self._lens_rows(lens_params)
+        self._forward_only("time_delays", packed, source_x, source_y)
+        self._potential_lenses()
+        B = packed.shape[0]
+        x, y, mu, n = self.image_positions(packed, source_x, source_y, **solver_kwargs)
+        sx, sy = self._source_rows(source_x, source_y, B)                   # [B, S]
+        ok = ~torch.isnan(x)
+        xs, ys = torch.where(ok, x, torch.zeros_like(x)), torch.where(ok, y, torch.zeros_like(y))
+        psi = self._model.lens_potential(packed, xs.permute(1, 2, 0), ys.permute(1, 2, 0)).permute(2, 0, 1)  # [B, S, M]
+        phi = 0.5 * ((xs.double() - sx[..., None].double()) ** 2 + (ys.double() - sy[..., None].double()) ** 2) - psi.double()
+        phi = torch.where(ok, phi, torch.full_like(phi, float("inf")))
+        dt = phi - phi.amin(dim=2, keepdim=True)
+        if time_delay_distance is not None:
+            dd = torch.as_tensor(time_delay_distance, dtype=torch.float64, device=self.device).reshape(-1, 1, 1)
+            dt = dt * dd * self.DAYS_PER_MPC_ARCSEC2
+        dt = torch.where(ok, dt, torch.full_like(dt, float("nan"))).to(torch.float32)
+        return x, y, mu, n, dt
 
     def simulate(self, params, no_deflection=False):
         """tf/simulator.py:109-156.  Returns ``(bs, H, W)`` squeezed like ``tf.squeeze``."""

@@ -260,6 +260,16 @@ int gl_scaled_eval(int base_kind, int n_galaxies, const int32_t scale_col[3], co
 int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
                  int xy_batched, float* out, void* hip_stream);
 
+/* Lensing potential psi summed over the model's lenses (beyond the reference, which has none): out [n_pts][B].  Arguments and
+ * conventions exactly those of gl_lens_maps, x = y = NULL for the model's own grid included.  psi is the potential whose gradient
+ * is this library's deflection (gl_lens_maps' beta = theta - grad psi), reference quirks included; its additive constant is
+ * chosen per kind (zero at the lens centre; Shear: zero at the origin) and only differences are physical.  Served: the built-in
+ * mass kinds and GL_SCALED catalogues.  GL_EUNSUPPORTED: GL_SERIES lenses (the series stores the deflection only) and
+ * GL_USER_MASS lenses (user-written bodies, the run-time compiled ScalingRelation member loops among them: a body defines a
+ * deflection only).  No host synchronisation, no allocation. */
+int gl_lens_potential(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
+                      int xy_batched, float* out, void* hip_stream);
+
 /* Lens-equation solver (beyond the reference, which maps image plane -> source plane only): the images theta of source
  * positions beta_s, beta(theta) = beta_s, for every sample.  params [B,P] (DEVICE); src_x, src_y [B][n_src] (DEVICE).
  * The window [x_lo, x_hi] x [y_lo, y_hi] is cut into n_cells x n_cells cells, two triangles each; beta is mapped at the vertices
@@ -341,6 +351,11 @@ int gl_profile_basis(const gl_component* comp, const float* x, const float* y, i
  * Free-standing mass kinds only (catalogues and series: gl_lens_maps on a model). */
 int gl_profile_hessian(const gl_component* comp, const float* x, const float* y, int64_t n_pts, int B, int xy_batched,
                        const float* params, float* out, void* hip_stream);
+
+/* MassProfile.potential at plugin level, the twin of gl_profile_hessian: out [n_pts][B] = psi (gl_lens_potential's, one lens).
+ * Free-standing built-in mass kinds only; GL_EUNSUPPORTED for GL_SCALED, GL_SERIES and GL_USER_MASS. */
+int gl_profile_potential(const gl_component* comp, const float* x, const float* y, int64_t n_pts, int B, int xy_batched,
+                         const float* params, float* out, void* hip_stream);
 
 int gl_kind_num_params(const gl_component* comp); /* length of the reference's params list for this profile */
 
