@@ -23,8 +23,9 @@ class NativeLibraryError(RuntimeError):
 
 
 class UnsupportedLensError(NativeLibraryError):
-    """A lens the call cannot serve (GL_EUNSUPPORTED from the lensing-potential calls): series expansions, user-written bodies and
-    the run-time compiled ScalingRelation member loops define a deflection only, no potential."""
+    """A lens the call cannot serve (GL_EUNSUPPORTED from the lensing-potential and critical-curve calls): series expansions,
+    user-written bodies and the run-time compiled ScalingRelation member loops define a deflection only, no potential, and are
+    not part of the critical-curve kernels."""
 
 
 class gl_component(ctypes.Structure):
@@ -89,6 +90,9 @@ SYMBOLS = {
     "gl_lens_maps": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "gl_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "gl_critical_curves": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
                                    c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_model_num_linear": (c_int, [c_void_p]),
@@ -160,7 +164,7 @@ GL_EUNSUPPORTED = -2
 
 
 def _check_potential(rc):
-    """_check for the lensing-potential calls: GL_EUNSUPPORTED becomes UnsupportedLensError."""
+    """_check for the lensing-potential and critical-curve calls: GL_EUNSUPPORTED becomes UnsupportedLensError."""
     if rc == GL_EUNSUPPORTED:
         raise UnsupportedLensError(f"gigalens_hip error {rc}: {lib().gl_last_error().decode()}")
     _check(rc)
@@ -652,6 +656,27 @@ class Model:
                                         int(n_cells), int(max_images), float(tol), int(max_iter), _ptr(out), _ptr(n_images),
                                         _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
         return out, n_images, n_dropped
+
+    def critical_curves(self, params, window, n_cells, max_segments):
+        """gl_critical_curves: ``window`` = (x_lo, x_hi, y_lo, y_hi).  Returns ``seg``, ``cau`` [B, max_segments, 2, 2] (NaN-padded),
+        ``kind`` [B, max_segments] (int32; -1 padding), ``n_seg``, ``n_dropped``, ``n_flagged``, ``open`` [B] (int32) and the signed
+        ``area`` [B, 4].  Series-expansion and user-written lenses raise ``UnsupportedLensError``."""
+        params = self._params(params)
+        B, M = params.shape[0], int(max_segments)
+        nbytes = lib().gl_critical_curves_workspace_bytes(self._h, B, int(n_cells), M)
+        ws = self._crit_ws if getattr(self, "_crit_ws", None) is not None and self._crit_ws.numel() >= nbytes else None
+        if ws is None:
+            ws = self._crit_ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        seg = torch.empty((B, max(M, 1), 2, 2), dtype=torch.float32, device=self.device)
+        cau = torch.empty_like(seg)
+        kind = torch.empty((B, max(M, 1)), dtype=torch.int32, device=self.device)
+        n_seg, n_dropped, n_flagged, opened = (torch.empty((B,), dtype=torch.int32, device=self.device) for _ in range(4))
+        area = torch.empty((B, 4), dtype=torch.float32, device=self.device)
+        x_lo, x_hi, y_lo, y_hi = (float(v) for v in window)
+        _check_potential(lib().gl_critical_curves(self._h, _ptr(params), B, x_lo, x_hi, y_lo, y_hi, int(n_cells), M, _ptr(seg),
+                                                  _ptr(cau), _ptr(kind), _ptr(n_seg), _ptr(n_dropped), _ptr(n_flagged),
+                                                  _ptr(opened), _ptr(area), _ptr(ws), ws.numel(), _stream()))
+        return seg, cau, kind, n_seg, n_dropped, n_flagged, opened, area
 
     def num_linear(self):
         return lib().gl_model_num_linear(self._h)

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +22,7 @@
 #include "gl_post.hip.h"
 #include "gl_positions.hip.h"
 #include "gl_images.hip.h"
+#include "gl_critical.hip.h"
 #include "gl_potential.hip.h"
 #include "gl_lstsq.hip.h"
 #include "gl_shp.hip.h"
@@ -1806,6 +1808,95 @@ int gl_image_positions(const gl_model* m, const float* params, int B, const floa
   } else {
     hipLaunchKernelGGL(gl_img_newton_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, a, g);
   }
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- critical curves and caustics (gl_critical.hip.h) ----------------------------------------------------------
+namespace {
+struct CritLayout { size_t dmap, edge_id, edge_pt, edge_omk, n_edges, n_edge_over, bytes; };
+CritLayout crit_layout(int B, int n_cells, int max_segments) {
+  CritLayout l{};
+  const size_t V = (size_t)(n_cells + 1) * (size_t)(n_cells + 1), BE = (size_t)B * 2 * (size_t)max_segments;
+  l.dmap = 0;
+  l.edge_id = l.dmap + align_up((size_t)B * V * sizeof(float), 256);
+  l.edge_pt = l.edge_id + align_up(BE * sizeof(int), 256);
+  l.edge_omk = l.edge_pt + align_up(BE * sizeof(float4), 256);
+  l.n_edges = l.edge_omk + align_up(BE * sizeof(float), 256);
+  l.n_edge_over = l.n_edges + align_up((size_t)B * sizeof(int), 256);
+  l.bytes = l.n_edge_over + align_up((size_t)B * sizeof(int), 256);
+  return l;
+}
+constexpr int CRIT_MAX_SEGMENTS = 1 << 20;
+}  // namespace
+
+size_t gl_critical_curves_workspace_bytes(const gl_model* m, int B, int n_cells, int max_segments) {
+  if (!m || B <= 0 || n_cells <= 0 || n_cells > IMG_MAX_CELLS || max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS) return 0;
+  return crit_layout(B, n_cells, max_segments).bytes;
+}
+
+int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
+                       int max_segments, float* seg, float* cau, int* kind, int* n_seg, int* n_dropped, int* n_flagged, int* open,
+                       float* area, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !seg || !cau || !kind || !n_seg || !n_dropped || !n_flagged || !open || !area)
+    return fail(GL_EINVAL, "null argument");
+  if (B <= 0) return fail(GL_EINVAL, "B (%d) must be positive", B);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  if (max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS)
+    return fail(GL_EINVAL, "max_segments %d outside [1, %d]", max_segments, CRIT_MAX_SEGMENTS);
+  if (!(x_hi > x_lo) || !(y_hi > y_lo) || !std::isfinite(x_hi - x_lo) || !std::isfinite(y_hi - y_lo))
+    return fail(GL_EINVAL, "empty or non-finite window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi);
+  if (m->n_series)
+    return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no critical curves");
+  if (m->has_user)
+    return fail(GL_EUNSUPPORTED, "user-written bodies (and the run-time compiled ScalingRelation member loops) are not served by the "
+                                 "critical-curve kernels");
+  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  const CritLayout lay = crit_layout(B, n_cells, max_segments);
+  if (!workspace) return fail(GL_EINVAL, "workspace is null");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  const long long V = (long long)(n_cells + 1) * (n_cells + 1);
+  const long long map_blocks = (V * B + 255) / 256;
+  const int max_edges = 2 * max_segments;
+  const long long refine_blocks = (long long)B * ((max_edges + 63) / 64);
+  if (map_blocks > 0x7fffffffLL || refine_blocks > 0x7fffffffLL)
+    return fail(GL_EINVAL, "too many samples x vertices (or x max_segments) for one call");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  PosArgs a{};
+  a.comps = m->d_comps;
+  a.n_lens = m->n_lens;
+  a.P = m->P;
+  a.B = B;
+  a.params = params;
+  a.cats = m->d_cats;
+  a.gal_table = m->d_gal_table;
+  a.gal_static = m->d_gal_static;
+  CritArgs g{};
+  g.n = n_cells;
+  g.max_segments = max_segments;
+  g.max_edges = max_edges;
+  g.x_lo = x_lo; g.x_hi = x_hi; g.y_lo = y_lo; g.y_hi = y_hi;
+  g.hx = (x_hi - x_lo) / (float)n_cells;
+  g.hy = (y_hi - y_lo) / (float)n_cells;
+  g.bracket = CRIT_BRACKET_ULP * std::numeric_limits<float>::epsilon() *
+              std::max(std::max(std::fabs(x_lo), std::fabs(x_hi)), std::max(std::fabs(y_lo), std::fabs(y_hi)));
+  char* base = (char*)workspace;
+  g.dmap = (float*)(base + lay.dmap);
+  g.edge_id = (int*)(base + lay.edge_id);
+  g.edge_pt = (float4*)(base + lay.edge_pt);
+  g.edge_omk = (float*)(base + lay.edge_omk);
+  g.n_edges = (int*)(base + lay.n_edges);
+  g.n_edge_over = (int*)(base + lay.n_edge_over);
+  g.seg = seg; g.cau = cau; g.kind = kind;
+  g.n_seg = n_seg; g.n_dropped = n_dropped; g.n_flagged = n_flagged; g.open = open;
+  g.area = area;
+  const bool cat = m->n_scaled > 0;  // catalogues take the build whose evaluation is a function call (gl_critical.hip.h, crit_eval)
+  if (cat) hipLaunchKernelGGL(gl_crit_map_kernel<true>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
+  else hipLaunchKernelGGL(gl_crit_map_kernel<false>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
+  hipLaunchKernelGGL(gl_crit_scan_kernel, dim3((unsigned)B), dim3(CRIT_WG), 0, stream, g);
+  if (cat) hipLaunchKernelGGL(gl_crit_refine_kernel<true>, dim3((unsigned)refine_blocks), dim3(64), 0, stream, a, g);
+  else hipLaunchKernelGGL(gl_crit_refine_kernel<false>, dim3((unsigned)refine_blocks), dim3(64), 0, stream, a, g);
+  hipLaunchKernelGGL(gl_crit_cells_kernel, dim3((unsigned)B), dim3(CRIT_WG), 0, stream, g);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

@@ -6,6 +6,7 @@ Differences in HOW (not WHAT): the pixel grid is stored once as two ``(N,)`` dev
 ray-shooting, rendering, NaN->0 and the det(T) scale are one fused kernel; gradients come from
 hand-written VJP kernels wrapped in a ``torch.autograd.Function``.
 """
+import math
 import warnings
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
@@ -280,6 +281,106 @@ class LensSimulator(LensSimulatorInterface):
                 raise RuntimeError(msg)
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
         return out[..., 0], out[..., 1], out[..., 2], n
+
+    def critical_curves(self, lens_params, *, window=None, num_cells=None, max_segments=None, strict=False):
+        """Critical curves (``det(I - H) = 0``) and caustics of every sample (beyond the reference), as line segments.
+
+        ``lens_params`` as ``image_positions`` takes them.  ``window`` = ``(x_lo, x_hi, y_lo, y_hi)`` (default: the bounding box of
+        the simulator's grid) is contoured on ``num_cells`` x ``num_cells`` cells (default ``2 * num_pix``) by marching squares;
+        every endpoint is refined on its grid edge to float32 accuracy, the curve between two endpoints is a chord of a cell.
+        Returns a dict: ``critical``, ``caustic`` ``[B, M, 2, 2]`` (segment, endpoint, x / y; the caustic holds ``beta`` at the same
+        endpoints; NaN-padded; ``M = max_segments``, default ``8 * num_cells``), ``kind`` ``[B, M]`` (0 tangential, 1 radial,
+        -1 padding), ``n`` ``[B]``, ``closed`` ``[B]`` (no curve reaches the window boundary, nothing dropped or flagged), and the
+        enclosed areas ``area_tangential``, ``area_radial``, ``caustic_area_tangential``, ``caustic_area_radial`` ``[B]`` (NaN
+        where not ``closed``; each the absolute value of the signed sum over all loops of its kind, i.e. the enclosed area when there
+        is one loop of that kind; per-loop areas: ``chain_curves``).  Segments are oriented with ``det < 0`` on their left; ``chain_curves`` joins them into polylines.
+        Segments beyond ``max_segments`` and cells skipped because a vertex is singular while its neighbours differ in sign warn,
+        or raise ``RuntimeError`` with ``strict=True``.  Built-in kinds and dPIE-family catalogues; series expansions, user-written
+        bodies and run-time compiled ScalingRelation member loops raise ``_native.UnsupportedLensError``.  Forward only."""
+        packed = self._lens_rows(lens_params)
+        self._forward_only("critical_curves", packed)
+        if window is None:
+            window = (float(self.img_X.min()), float(self.img_X.max()), float(self.img_Y.min()), float(self.img_Y.max()))
+        window = tuple(float(v) for v in window)
+        if num_cells is None:
+            num_cells = 2 * int(self.numPix)
+        if max_segments is None:
+            max_segments = 8 * int(num_cells)
+        seg, cau, kind, n, dropped, flagged, opened, area = self._model.critical_curves(packed, window, int(num_cells),
+                                                                                         int(max_segments))
+        n_drop, n_flag = int(dropped.sum()), int(flagged.sum())
+        if n_drop or n_flag:
+            msg = (f"critical_curves: {n_drop} segment(s) not returned over {int((dropped > 0).sum())} sample(s) "
+                   f"(max_segments={max_segments} exceeded), {n_flag} cell(s) skipped over {int((flagged > 0).sum())} sample(s) "
+                   f"(a singular vertex between vertices of different sign)")
+            if strict:
+                raise RuntimeError(msg)
+            warnings.warn(msg, RuntimeWarning, stacklevel=2)
+        closed = (opened == 0) & (dropped == 0) & (flagged == 0)
+        area = torch.where(closed[:, None], area.abs(), torch.full_like(area, float("nan")))
+        return {"critical": seg, "caustic": cau, "kind": kind, "n": n, "closed": closed,
+                "area_tangential": area[:, 0], "area_radial": area[:, 1],
+                "caustic_area_tangential": area[:, 2], "caustic_area_radial": area[:, 3]}
+
+    def einstein_radius(self, lens_params, **kwargs):
+        """Effective Einstein radius ``sqrt(A / pi)`` ``[B]`` of every sample (beyond the reference), ``A`` the area the tangential
+        critical curve encloses (``critical_curves``, which takes ``kwargs``).  NaN where the tangential curve is not closed inside
+        the window or absent; such samples are counted in a ``RuntimeWarning``."""
+        res = self.critical_curves(lens_params, **kwargs)
+        has_tangential = (res["kind"] == 0).any(dim=1)
+        theta = torch.sqrt(res["area_tangential"] / math.pi)
+        theta = torch.where(has_tangential, theta, torch.full_like(theta, float("nan")))
+        n_bad = int(torch.isnan(theta).sum())
+        if n_bad:
+            warnings.warn(f"einstein_radius: the tangential critical curve is open or absent in {n_bad} of {theta.numel()} sample(s)",
+                          RuntimeWarning, stacklevel=2)
+        return theta
+
+    @staticmethod
+    def chain_curves(result, b):
+        """Join the segments of sample ``b`` of a ``critical_curves`` result into ordered polylines (host side, numpy).  Returns a list
+        of ``(kind, closed, xy[K, 2], beta[K, 2])`` in the order of each chain's first segment: ``xy`` the image-plane points along
+        the curve (the first point is not repeated at the end of a closed one), ``beta`` the caustic at the same points, ``kind``
+        that of the chain's first segment.  Endpoints shared by two segments are bitwise equal, so they are matched exactly."""
+        n = int(result["n"][b])
+        seg = np.asarray(result["critical"][b, :n].cpu() if torch.is_tensor(result["critical"]) else result["critical"][b, :n])
+        cau = np.asarray(result["caustic"][b, :n].cpu() if torch.is_tensor(result["caustic"]) else result["caustic"][b, :n])
+        kind = np.asarray(result["kind"][b, :n].cpu() if torch.is_tensor(result["kind"]) else result["kind"][b, :n])
+        live = [i for i in range(n) if kind[i] >= 0]
+        key = lambda p: (float(p[0]), float(p[1]))
+        at = {}  # point -> [(segment, which end)]
+        for i in live:
+            for e in (0, 1):
+                at.setdefault(key(seg[i, e]), []).append((i, e))
+        used = set()
+
+        def walk(i, e):
+            """Follow the chain out of end ``e`` of segment ``i``; returns the (segment, entered-at end) pairs visited."""
+            out = []
+            while True:
+                nxt = [(j, f) for j, f in at[key(seg[i, e])] if j != i and j not in used]
+                if not nxt:
+                    return out
+                j, f = nxt[0]
+                used.add(j)
+                out.append((j, f))
+                i, e = j, 1 - f
+        chains = []
+        for i in live:
+            if i in used:
+                continue
+            used.add(i)
+            fwd = walk(i, 1)
+            closed = bool(fwd) and key(seg[fwd[-1][0], 1 - fwd[-1][1]]) == key(seg[i, 0])
+            back = [] if closed else walk(i, 0)
+            # points: backwards chain reversed (far ends first), the seed segment, the forward chain's far ends
+            pts = [(j, 1 - f) for j, f in reversed(back)] + [(i, 0), (i, 1)] + [(j, 1 - f) for j, f in fwd]
+            if closed:
+                pts = pts[:-1]
+            xy = np.array([seg[j, e] for j, e in pts], dtype=seg.dtype).reshape(-1, 2)
+            beta = np.array([cau[j, e] for j, e in pts], dtype=cau.dtype).reshape(-1, 2)
+            chains.append((int(kind[i]), closed, xy, beta))
+        return chains
 
     def _potential_lenses(self):
         """The lensing-potential calls serve built-in kinds and fused catalogues; refuse the rest with a typed error up front."""

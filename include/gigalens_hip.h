@@ -296,6 +296,35 @@ int gl_image_positions(const gl_model* m, const float* params, int B, const floa
                        float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images, float tol, int max_iter,
                        float* out, int* n_images, int* n_dropped, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Critical curves and caustics (beyond the reference): the image-plane locus D = det(I - H) = 0 (the Hessian as gl_lens_maps has
+ * it) of every sample, contoured by marching squares on n_cells x n_cells cells over the window [x_lo, x_hi] x [y_lo, y_hi], and
+ * its image in the source plane.  params [B,P] (DEVICE).  D is mapped at the vertices (one float each; a D that is not finite is
+ * flagged); every grid edge whose two finite endpoint values differ in sign (sign = D < 0) carries one crossing point, bisected ON
+ * the edge until the bracket is 4 float32 spacings of the window's largest |coordinate| (at most 32 halvings), so the cells on both
+ * sides of an edge see the same bits and segments join exactly.  Every cell yields 0, 1 or 2 segments; in the ambiguous case
+ * (diagonal signs equal, neighbours different) the D < 0 corners are joined when the mean of the four vertex values is < 0.
+ * Outputs (DEVICE), segments in row-major cell order:
+ *   seg  [B][max_segments][2][2]  endpoints (x, y) of each segment, oriented with D < 0 on its left; NaN-padded;
+ *   cau  [B][max_segments][2][2]  beta at the same endpoints; NaN-padded;
+ *   kind [B][max_segments]        0 tangential (mean of 1 - kappa at the two endpoints > 0), 1 radial, -1 padding;
+ *   n_seg [B] segments written; n_dropped [B] segments beyond max_segments (or whose endpoint fell off the list of
+ *       2 * max_segments crossing edges: such a slot is padding); n_flagged [B] cells skipped because a vertex is flagged AND
+ *       the finite vertices differ in sign (a flagged vertex among equal signs, the centre of an SIS / SIE / EPL, is skipped
+ *       silently); open [B] != 0 when a crossing edge lies on the window boundary;
+ *   area [B][4]  sum over the written segments of (x1 + x2) / 2 * (y2 - y1): tangential, radial (image plane), tangential,
+ *       radial (source plane); the enclosed area when the curves are closed, positive for a loop that encloses D < 0, negative
+ *       for one that encloses D > 0; float64 sums in a fixed order.
+ * Guaranteed: every endpoint lies on D = 0 to float32 accuracy; between endpoints the curve is a chord of a cell.  Not
+ * guaranteed: features narrower than a cell.  Deterministic (two calls give identical bits; a row does not depend on the other
+ * rows).  No host synchronisation, no allocation: workspace of gl_critical_curves_workspace_bytes (0 for invalid sizes).
+ * GL_EINVAL: sizes <= 0, n_cells > 8192, max_segments outside [1, 2^20], an empty window; GL_EUNSUPPORTED: GL_SERIES lenses (their
+ * field exists on the model grid only) and GL_USER_MASS lenses (user-written bodies, the run-time compiled ScalingRelation
+ * member loops among them: these kernels are not part of the run-time compiled point program). */
+size_t gl_critical_curves_workspace_bytes(const gl_model* m, int B, int n_cells, int max_segments);
+int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
+                       int max_segments, float* seg, float* cau, int* kind, int* n_seg, int* n_dropped, int* n_flagged, int* open,
+                       float* area, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Plugin-level point evaluation, the reference's MassProfile.deriv / LightProfile.light called on
  * arbitrary coordinates (tests/test_profiles.py calls exactly these):
  *   x, y [n_pts, B] when xy_batched, else [n_pts] shared by every sample (pixel-major, batch-minor

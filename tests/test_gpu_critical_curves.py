@@ -1,0 +1,283 @@
+"""Critical curves, caustics and the effective Einstein radius per sample (LensSimulator.critical_curves / einstein_radius /
+chain_curves, gl_critical_curves) against the closed form of the SIS and the float64 restatement of the contouring in
+tests/critical_cases.py on the oracle's Hessians."""
+import math
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from tests import critical_cases as CC
+from tests import helpers as H
+from tests.critical_cases import lens_rows as _lens_rows, packed_rows as _rows, simulator as _sim
+
+pytestmark = pytest.mark.gpu
+
+EPS32 = float(np.finfo(np.float32).eps)
+WINDOW, N_CELLS = (-4.0, 4.0, -4.0, 4.0), 256
+CELL = 8.0 / N_CELLS
+# bracket at which the edge bisection stops: 4 float32 spacings of the window's largest |coordinate| (gl_critical.hip.h)
+BRACKET = 4 * EPS32 * 4.0
+# Endpoint accuracy (distance to the true curve, |D64(p)| / |grad D64(p)|).  Yardstick: the float32 error of D assembled from
+# LensSimulator._lens_maps (gl_lens_maps_kernel) at the returned endpoints against the oracle's float64 Hessian, divided by
+# |grad D64|.  Measured on one MI355X on the first five of the 64 EPL + Shear samples below (seed 2024; 2090 endpoints): max
+# 1.39e-6 arcsec; the float32 error of beta from the same call: max 7.2e-7 arcsec.  (The maxima over all 64 samples have not been
+# recorded yet: the test prints them before it asserts.)  Gate = 4 x yardstick + bracket = 7.5e-6 arcsec: the bisection stops on a
+# float32 sign of D, so it sits up to one float32 error of D from the root on either side; 4 x still catches a refinement that
+# does not converge (one cell is 3e-2).
+D_YARDSTICK, BETA_YARDSTICK = 1.39e-6, 7.2e-7
+ENDPOINT_GATE = 4 * D_YARDSTICK + BRACKET
+BETA_GATE = 4 * BETA_YARDSTICK
+
+
+def _curves(sim, packed, **kw):
+    kw = {"window": WINDOW, "num_cells": N_CELLS, **kw}
+    res = sim.critical_curves(packed, **kw)
+    return res, {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def _epl_shear(B=64, seed=2024):
+    from gigalens_amd.profiles.mass.epl import EPL
+    from gigalens_amd.profiles.mass.shear import Shear
+    sim = _sim([EPL(), Shear()], 64, 0.08, B)
+    names = [n for p in sim.phys_model.lenses for n in p._native_params()]
+    assert names == ["theta_E", "gamma", "e1", "e2", "center_x", "center_y", "gamma1", "gamma2"], names
+    g = np.random.default_rng(seed)
+    u = lambda lo, hi: g.uniform(lo, hi, B)
+    cols = [u(1.0, 1.6), u(1.6, 2.4), u(-0.3, 0.3), u(-0.3, 0.3), u(-0.1, 0.1), u(-0.1, 0.1), u(-0.08, 0.08), u(-0.08, 0.08)]
+    return sim, _rows(sim, np.stack(cols, 1))
+
+
+def _lens_maps_error(sim, packed, b, fields, pts):
+    """float32 error of D and of beta from gl_lens_maps_kernel at ``pts`` [K, 2] of sample b against float64; D's divided by |grad D64|."""
+    x = torch.tensor(pts[:, 0], device=sim.device)[:, None]
+    y = torch.tensor(pts[:, 1], device=sim.device)[:, None]
+    bx, by, fxx, fxy, fyx, fyy = (t[:, 0].double().cpu().numpy() for t in sim._lens_maps(x, y, packed[b:b + 1]))
+    d32 = (1 - fxx) * (1 - fyy) - fxy * fyx
+    x64, y64 = pts[:, 0].astype(np.float64), pts[:, 1].astype(np.float64)
+    d64, bx64, by64, _ = fields(x64, y64)
+    return np.abs(d32 - d64) / CC.grad_D(fields, x64, y64), np.hypot(bx - bx64, by - by64)
+
+
+def _compare_with_restatement(sim, packed, res, b, d_tol_rel=1e-4, deferred=None):
+    """Sample b of a critical_curves result against contour64 on the oracle's fields.  Returns (edges compared, edges that differ,
+    max endpoint distance to the true curve, yardstick of D, yardstick of beta, the restatement's result).  ``deferred``: a list that
+    collects the accuracy failures instead of raising at once (the caller prints every figure first, then asserts)."""
+    fields = CC.oracle_fields(sim.phys_model, _lens_rows(sim, packed), b)
+    ref = CC.contour64(fields, WINDOW, N_CELLS)
+    n = int(res["n"][b])
+    seg, cau, kind = res["critical"][b, :n].astype(np.float64), res["caustic"][b, :n].astype(np.float64), res["kind"][b, :n]
+    assert not ref["open"] and ref["n_flagged"] == 0
+    # crossing edges: an endpoint of the kernel lies ON a grid edge, which identifies the edge
+    h = CELL
+    def edge_of(p):
+        fx, fy = (p[0] - WINDOW[0]) / h, (p[1] - WINDOW[2]) / h
+        on_h = abs(fy - round(fy)) < 1e-9  # y exactly a grid line: a horizontal edge
+        if on_h:
+            return int(round(fy)) * N_CELLS + int(math.floor(fx))
+        assert abs(fx - round(fx)) < 1e-9, p
+        return (N_CELLS + 1) * N_CELLS + int(math.floor(fy)) * (N_CELLS + 1) + int(round(fx))
+    got = {}
+    for s in range(n):
+        for e in (0, 1):
+            got[edge_of(res["critical"][b, s, e].astype(np.float64))] = (seg[s, e], cau[s, e])
+    differ = set(got) ^ set(ref["edges"])
+    common = sorted(set(got) & set(ref["edges"]))
+    pts = np.array([got[e][0] for e in common])
+    d64 = fields(pts[:, 0], pts[:, 1])[0]
+    dist = np.abs(d64) / CC.grad_D(fields, pts[:, 0], pts[:, 1])
+    d_yard, b_yard = _lens_maps_error(sim, packed, b, fields, pts.astype(np.float32))
+    print(f"sample {b}: {n} segments, {len(common)} edges, {len(differ)} differ, endpoint distance max {dist.max():.3e}, "
+          f"yardstick D {d_yard.max():.3e}, beta {b_yard.max():.3e}")
+    fails = [] if deferred is None else deferred
+    check = lambda ok, *what: None if ok else fails.append((b,) + what)
+    check(dist.max() <= ENDPOINT_GATE, "endpoint distance", dist.max())
+    # against the restatement's own endpoints: both lie on the same grid edge, so the offset between them is measured ALONG the
+    # edge, where a distance d to the curve shows as d |grad D| / |dD/dt| (t along the edge; the curve may cross the edge obliquely)
+    ref_pts = np.array([ref["edges"][e][:2] for e in common])
+    horizontal = np.array(common) < (N_CELLS + 1) * N_CELLS
+    st = 1e-6
+    ddt = np.where(horizontal, fields(ref_pts[:, 0] + st, ref_pts[:, 1])[0] - fields(ref_pts[:, 0] - st, ref_pts[:, 1])[0],
+                   fields(ref_pts[:, 0], ref_pts[:, 1] + st)[0] - fields(ref_pts[:, 0], ref_pts[:, 1] - st)[0]) / (2 * st)
+    along_gate = ENDPOINT_GATE * CC.grad_D(fields, ref_pts[:, 0], ref_pts[:, 1]) / np.abs(ddt)
+    off = np.hypot(*(pts - ref_pts).T)
+    check(np.all(off <= along_gate), "offset along the edge", np.max(off / along_gate))
+    # caustic: beta error plus the endpoint offset carried through |d beta / d theta| <= 1 + |H|
+    hess = np.stack(fields.hessian(ref_pts[:, 0], ref_pts[:, 1])[2:], 1)
+    scale = 1 + np.sqrt((hess ** 2).sum(1))
+    cau_err = np.hypot(*(np.array([got[e][1] for e in common]) - np.array([ref["edges"][e][2:4] for e in common])).T)
+    check(np.all(cau_err <= BETA_GATE + scale * along_gate), "caustic", np.max(cau_err / (BETA_GATE + scale * along_gate)))
+    if deferred is None:
+        assert not fails, fails
+    if not differ:
+        assert n == len(ref["seg"]) and np.array_equal(kind, ref["kind"])
+    # areas for every sample; where the crossing-edge sets differ (|D64| at a vertex below the float32 error of D) the two polygons
+    # differ by at most the two cells beside each such edge
+    slack = 2 * len(differ) * CELL ** 2
+    for q, name in enumerate(("area_tangential", "area_radial", "caustic_area_tangential", "caustic_area_radial")):
+        want = abs(ref["area"][q])
+        extra = slack * (1 if q < 2 else float(scale.max()) ** 2)
+        assert abs(res[name][b] - want) <= d_tol_rel * max(want, abs(ref["area"][0])) + extra, (b, name, res[name][b], want)
+    return len(common), len(differ), dist.max(), d_yard.max(), b_yard.max(), ref
+
+
+def test_sis_closed_form():
+    from gigalens_amd.profiles.mass.sis import SIS
+    B = 64
+    sim = _sim([SIS()], 64, 0.08, B)
+    g = np.random.default_rng(17)
+    packed = _rows(sim, np.stack([g.uniform(0.8, 1.8, B), g.uniform(-0.3, 0.3, B), g.uniform(-0.3, 0.3, B)], 1))
+    raw, res = _curves(sim, packed, strict=True)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        theta = sim.einstein_radius(packed, window=WINDOW, num_cells=N_CELLS).double().cpu().numpy()
+    te, cx, cy = (packed[:, k].double().cpu().numpy() for k in range(3))
+    assert res["critical"].shape == (B, 8 * N_CELLS, 2, 2)
+    for b in range(B):
+        n = int(res["n"][b])
+        assert res["closed"][b] and n > 0
+        assert np.all(res["kind"][b, :n] == 0) and np.all(res["kind"][b, n:] == -1)
+        r = np.hypot(res["critical"][b, :n, :, 0].astype(np.float64) - cx[b], res["critical"][b, :n, :, 1].astype(np.float64) - cy[b])
+        assert np.max(np.abs(r - te[b])) <= ENDPOINT_GATE, (b, np.max(np.abs(r - te[b])))
+        rel = (te[b] - theta[b]) / te[b]  # from below: an inscribed polygon with chords of at most sqrt(2) h
+        assert -ENDPOINT_GATE / te[b] <= rel <= CELL ** 2 / (6 * te[b] ** 2) + ENDPOINT_GATE / te[b], (b, rel)
+        rc = np.hypot(res["caustic"][b, :n, :, 0].astype(np.float64) - cx[b], res["caustic"][b, :n, :, 1].astype(np.float64) - cy[b])
+        assert np.max(rc) <= ENDPOINT_GATE + BETA_GATE, (b, np.max(rc))
+        chains = sim.chain_curves(raw, b)
+        assert len(chains) == 1 and chains[0][0] == 0 and chains[0][1] and len(chains[0][2]) == n
+
+
+def test_epl_shear_vs_float64_and_endpoint_accuracy():
+    sim, packed = _epl_shear()
+    B = packed.shape[0]
+    raw, res = _curves(sim, packed, strict=True)
+    dropped_or_flagged = sim._model.critical_curves(packed, WINDOW, N_CELLS, 8 * N_CELLS)[4:6]
+    assert int(dropped_or_flagged[0].sum()) == 0 and int(dropped_or_flagged[1].sum()) == 0
+    assert bool(res["closed"].all())
+    theta = sim.einstein_radius(packed, window=WINDOW, num_cells=N_CELLS).cpu().numpy()
+    edges = differ = 0
+    worst = d_yard = b_yard = 0.0
+    fails = []
+    for b in range(B):
+        e, d, dist, dy, by, ref = _compare_with_restatement(sim, packed, res, b, deferred=fails)
+        edges, differ, worst, d_yard, b_yard = edges + e, differ + d, max(worst, dist), max(d_yard, dy), max(b_yard, by)
+        assert 274 <= len(ref["seg"]) <= 552 and ref["n_ambiguous"] == 0, (b, len(ref["seg"]))
+        want = math.sqrt(ref["area"][0] / math.pi)  # (d differing edges move the area by at most 2 d cells)
+        assert abs(theta[b] - want) <= 1e-4 * want + 2 * d * CELL ** 2 / (2 * math.pi * want), (b, theta[b], want)
+    print(f"EPL + Shear: {edges} crossing edges, {differ} differ; endpoint distance max {worst:.3e} (gate {ENDPOINT_GATE:.3e}); "
+          f"yardsticks: D {d_yard:.3e}, beta {b_yard:.3e}")
+    assert not fails, fails
+    assert differ < 0.01 * edges, (differ, edges)
+
+
+def test_sie_astroid():
+    from gigalens_amd.profiles.mass.sie import SIE
+    sim = _sim([SIE()], 64, 0.08, 1)
+    packed = _rows(sim, np.array([[1.2, 0.25, -0.1, 0.05, -0.04]]))  # theta_E, e1, e2, centre: q ~ 0.57
+    raw, res = _curves(sim, packed, strict=True)
+    assert res["closed"][0] and np.all(res["kind"][0, :int(res["n"][0])] == 0)
+    chains = sim.chain_curves(raw, 0)
+    assert len(chains) == 1 and chains[0][1]
+    beta = chains[0][3].astype(np.float64)
+    rad = np.hypot(beta[:, 0] - 0.05, beta[:, 1] + 0.04)
+    # cusps = local maxima of |beta - centre| along the chain: the largest value within a sixteenth of the chain on either side
+    # (beta is stationary at a cusp, so neighbouring points there differ by float32 noise only)
+    K, w = len(rad), len(rad) // 16
+    cusps = [i for i in range(K) if rad[i] == max(rad[(i + j) % K] for j in range(-w, w + 1))]
+    cusps = [i for k, i in enumerate(cusps) if k == 0 or i - cusps[k - 1] > 1]
+    assert len(cusps) == 4, cusps
+    assert res["caustic_area_tangential"][0] > 0
+
+
+def test_nfw_has_a_radial_curve():
+    from gigalens_amd.profiles.mass.nfw import NFW
+    from gigalens_amd.profiles.mass.shear import Shear
+    sim = _sim([NFW(), Shear()], 64, 0.08, 1)
+    packed = _rows(sim, np.array([[3.0, 2.5, 0.03, -0.02, 0.04, -0.03]]))  # Rs, alpha_Rs, centre, gamma1, gamma2
+    raw, res = _curves(sim, packed, strict=True)
+    assert res["closed"][0]
+    chains = sim.chain_curves(raw, 0)
+    assert sorted((k, c) for k, c, _, _ in chains) == [(0, True), (1, True)], [(k, c) for k, c, _, _ in chains]
+    assert 0 < res["area_radial"][0] < res["area_tangential"][0]
+    assert res["caustic_area_radial"][0] > res["caustic_area_tangential"][0]
+    tang, rad = (next(c for c in chains if c[0] == k) for k in (0, 1))
+    centre = tang[3].mean(0)
+    r_rad = np.hypot(*(rad[3] - centre).T)
+    r_tan = np.hypot(*(tang[3] - centre).T)
+    assert r_rad.min() > r_tan.max()  # the radial caustic encloses the tangential one
+    _compare_with_restatement(sim, packed, res, 0)
+
+
+def test_catalogue_beside_an_epl():
+    from gigalens_amd.profiles.mass.dpie_subhalo import DPIESubhalo
+    from gigalens_amd.profiles.mass.epl import EPL
+    f32 = lambda *v: np.array(v, dtype=np.float32)  # four members, each well over 3 cells from the main curve (r ~ 1.2)
+    proto = dict(lum=f32(1.0, 0.6, 0.8, 1.2), center_x=f32(2.6, -2.4, 0.3, -0.2), center_y=f32(0.4, -1.1, 2.7, -2.5),
+                 e1=f32(0.1, -0.05, 0.0, 0.12), e2=f32(-0.08, 0.1, 0.05, 0.0))
+    lenses = [EPL(), DPIESubhalo(lum_star=1.0, galaxy_catalogue=proto)]
+    sim = _sim(lenses, 64, 0.08, 2)
+    names = [n for p in lenses for n in p._native_params()]
+    rows = np.array([[1.2, 2.0, 0.1, -0.05, 0.02, -0.03, 0.05, 0.05, 1.0], [1.0, 2.1, -0.15, 0.1, -0.02, 0.01, 0.04, 0.06, 1.2]])
+    assert len(names) == rows.shape[1], names
+    packed = _rows(sim, rows)
+    raw, res = _curves(sim, packed, strict=True)
+    for b in range(2):
+        ref = _compare_with_restatement(sim, packed, res, b)[-1]
+        loops = sum(1 for c in sim.chain_curves(raw, b) if c[1])
+        assert (loops, 0) == CC.count_loops(ref["seg"])
+
+
+def test_deterministic_and_bookkeeping():
+    sim, packed = _epl_shear(B=8, seed=5)
+    a = sim.critical_curves(packed, window=WINDOW, num_cells=N_CELLS)
+    b = sim.critical_curves(packed, window=WINDOW, num_cells=N_CELLS)
+    for k in a:
+        ta, tb = a[k].contiguous(), b[k].contiguous()
+        if ta.dtype == torch.float32:
+            ta, tb = ta.view(torch.int32), tb.view(torch.int32)
+        assert torch.equal(ta, tb), k
+    n = a["n"].cpu().numpy()
+    for q in range(8):  # padding
+        assert torch.isnan(a["critical"][q, n[q]:]).all() and torch.isnan(a["caustic"][q, n[q]:]).all()
+        assert torch.isfinite(a["critical"][q, :n[q]]).all() and (a["kind"][q, n[q]:] == -1).all()
+    # too few slots: reported, never silent
+    with pytest.warns(RuntimeWarning, match="not returned"):
+        small = sim.critical_curves(packed, window=WINDOW, num_cells=N_CELLS, max_segments=100)
+    assert small["critical"].shape[1] == 100 and not bool(small["closed"].any())
+    assert torch.isnan(small["area_tangential"]).all()
+    assert int(sim._model.critical_curves(packed, WINDOW, N_CELLS, 100)[4].min()) > 0
+    with pytest.raises(RuntimeError, match="not returned"):
+        sim.critical_curves(packed, window=WINDOW, num_cells=N_CELLS, max_segments=100, strict=True)
+    # a window that cuts the curve
+    cut = sim.critical_curves(packed, window=(0.0, 4.0, -4.0, 4.0), num_cells=N_CELLS)
+    assert not bool(cut["closed"].any()) and torch.isnan(cut["area_tangential"]).all()
+    with pytest.warns(RuntimeWarning, match="open or absent"):
+        theta = sim.einstein_radius(packed, window=(0.0, 4.0, -4.0, 4.0), num_cells=N_CELLS)
+    assert torch.isnan(theta).all()
+    assert any(not c[1] for c in sim.chain_curves(cut, 0))
+
+
+def test_refusals():
+    from gigalens_amd import _native, workloads
+    from gigalens_amd.profile import MassProfile
+    from gigalens_amd.simulator import LensSimulator
+    from tests.critical_cases import SIS_BODY
+    wl = workloads.make("C6S", num_pix=32, batch=2, n_galaxies=8, n_sources=1)
+    sim_s = LensSimulator(wl.phys_model, wl.sim_config, bs=2)
+    with pytest.raises(_native.UnsupportedLensError, match="series"):
+        sim_s.critical_curves(H.sample_packed(wl, sim_s, seed=1))
+
+    class UserSIS(MassProfile):
+        _name, _params = "USER_SIS", ["theta_E", "center_x", "center_y"]
+        hip_body = SIS_BODY
+
+    sim_u = _sim([UserSIS()], 48, 0.1, 1)
+    with pytest.raises(_native.UnsupportedLensError, match="user-written"):
+        sim_u.critical_curves(_rows(sim_u, np.array([[1.0, 0.0, 0.0]])))
+    sim, packed = _epl_shear(B=2, seed=1)
+    with pytest.raises(NotImplementedError):
+        sim.critical_curves(packed.clone().requires_grad_(True))
+    for kw in (dict(num_cells=0), dict(max_segments=0), dict(window=(1.0, 1.0, -1.0, 1.0))):
+        with pytest.raises(_native.NativeLibraryError):
+            sim.critical_curves(packed, **kw)
