@@ -125,6 +125,8 @@ SYMBOLS = {
     "gl_model_set_timing_stride": (c_int, [c_void_p, c_int]),
     "gl_model_timing_drain": (c_int, [c_void_p, POINTER(c_float), c_int, POINTER(c_int)]),
     "gl_model_last_main_kernel": (c_int, [c_void_p, ctypes.c_char_p, c_size_t]),
+    "gl_post_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    "gl_model_last_post_kernel": (c_int, [c_void_p, c_int, ctypes.c_char_p, c_size_t]),
     "gl_model_launch_shape": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]),
     "gl_last_error": (c_char_p, []),
     "gl_version": (c_char_p, []),
@@ -584,6 +586,7 @@ class Model:
         self.N = L.gl_model_num_pixels(h)
         self.offsets = [L.gl_model_param_offset(h, i) for i in range(n)]
         self.out_h, self.out_w = height // supersample, width // supersample
+        self.ss_h, self.ss_w = int(height), int(width)
         self._ws = {}
 
     def __del__(self):
@@ -788,6 +791,29 @@ class Model:
         buf = ctypes.create_string_buffer(1024)
         _check(lib().gl_model_last_main_kernel(self._h, buf, len(buf)))
         return buf.value.decode()
+
+    def last_post_kernel(self, transpose=False):
+        """Mangled symbol of the kernel that served the most recent forward / transposed PSF + pooling launch."""
+        buf = ctypes.create_string_buffer(1024)
+        _check(lib().gl_model_last_post_kernel(self._h, int(bool(transpose)), buf, len(buf)))
+        return buf.value.decode()
+
+    def post_apply(self, inp, out=None, transpose=False, scale=1.0):
+        """gl_post_apply: the model's PSF convolution + pooling (x ``scale``) on a stack ``inp`` of supersampled images
+        ``[B, Hs, Ws]``, or its transpose on pooled images ``[B, H, W]``.  ``out``: a contiguous float32 tensor to write into
+        (default: a new one)."""
+        _require_cuda(inp, "inp")
+        shape_in, shape_out = ((self.out_h, self.out_w), (self.ss_h, self.ss_w)) if transpose else ((self.ss_h, self.ss_w), (self.out_h, self.out_w))
+        if inp.dtype != torch.float32 or inp.dim() != 3 or tuple(inp.shape[1:]) != shape_in or not inp.is_contiguous():
+            raise NativeLibraryError(f"post_apply: inp must be contiguous float32 [B,{shape_in[0]},{shape_in[1]}], got {inp.dtype} {tuple(inp.shape)}")
+        B = inp.shape[0]
+        if out is None:
+            out = torch.empty((B,) + shape_out, dtype=torch.float32, device=inp.device)
+        _require_cuda(out, "out")
+        if out.dtype != torch.float32 or tuple(out.shape) != (B,) + shape_out or not out.is_contiguous():
+            raise NativeLibraryError(f"post_apply: out must be contiguous float32 {(B,) + shape_out}, got {out.dtype} {tuple(out.shape)}")
+        _check(lib().gl_post_apply(self._h, B, _ptr(inp), _ptr(out), int(bool(transpose)), float(scale), _stream()))
+        return out
 
     def partial_rows(self, B):
         """The per-(sample, chunk) partial rows ``[B, n_chunks, A]`` the most recent gradient call on ``B`` samples left in the

@@ -382,8 +382,27 @@ PostArgs post_args(const gl_model* m, float scale) {
 }
 // supersampled pre-PSF image S [B,Hs,Ws] -> final image [B,H,W] (x conversion factor)
 // the register-blocked pair kernel on one plan (gl_post.hip.h); false: no instantiation for this kernel width / stride
+// the instantiations launch_corr can reach: the wide stride-2 family (16 outputs per thread) requires KWP <= 28, and the
+// supersample-2 transpose plan (two column classes per thread) has KWP = pad4(width) with width <= ceil(32 / 2) + 1 = 17
+constexpr bool corr_reachable(int kwp, int ncj, int ox) { return !(ox == 16 && kwp > 28) && !(ncj == 2 && kwp > 20); }
+template <int KWP, int ST, int KS, int NCJ, int OX>
+bool corr_launch(dim3 grid, size_t sh, hipStream_t stream, const float* in, float* out, const CorrArgs& a, std::atomic<const void*>* last) {
+  if constexpr (corr_reachable(KWP, NCJ, OX)) {
+    auto* fn = gl_corr_pair_kernel<KWP, ST, KS, NCJ, OX>;
+    if (sh > 64 * 1024) {
+      static const hipError_t big = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+      if (big != hipSuccess) return false;
+    }
+    hipLaunchKernelGGL(fn, grid, dim3(CORR_GT * KS), sh, stream, in, out, a);
+    if (last) last->store(reinterpret_cast<const void*>(fn), std::memory_order_relaxed);
+    return true;
+  } else {
+    return false;
+  }
+}
+// `last`: where the host function of the launched kernel is recorded (gl_model_last_post_kernel)
 bool launch_corr(const gl_model::CorrPlan& pl, int B, const float* in, float* out, float scale, hipStream_t stream, int dbg = 0,
-                 int max_pairs_env = 0, int corr_wide = 1) {
+                 int max_pairs_env = 0, int corr_wide = 1, std::atomic<const void*>* last = nullptr) {
   if (!pl.ok) return false;
   CorrArgs a = pl.args;
   a.B = B;
@@ -405,22 +424,13 @@ bool launch_corr(const gl_model::CorrPlan& pl, int B, const float* in, float* ou
   if ((B + 1) / 2 > max_pairs) {
     for (int b_lo = 0; b_lo < B; b_lo += 2 * max_pairs) {
       const int nb = std::min(B - b_lo, 2 * max_pairs);
-      if (!launch_corr(pl, nb, in + (size_t)b_lo * a.Hi * a.Wi, out + (size_t)b_lo * a.Hout * a.Wout, scale, stream, dbg, max_pairs_env, corr_wide)) return false;
+      if (!launch_corr(pl, nb, in + (size_t)b_lo * a.Hi * a.Wi, out + (size_t)b_lo * a.Hout * a.Wout, scale, stream, dbg, max_pairs_env, corr_wide, last)) return false;
     }
     return true;
   }
   const dim3 grid((pl.max_Wo + CORR_TCG * ox - 1) / (CORR_TCG * ox), (pl.max_Ho + CORR_TR - 1) / CORR_TR,
                   (unsigned)(a.n_class * ((B + 1) / 2)));
-#define GL_CORR(KWP_, ST_, KS_, NCJ_, OX_)                                                                             \
-  {                                                                                                                    \
-    auto* fn = gl_corr_pair_kernel<KWP_, ST_, KS_, NCJ_, OX_>;                                                          \
-    if (sh > 64 * 1024) {                                                                                              \
-      static const hipError_t big = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-      if (big != hipSuccess) return false;                                                                             \
-    }                                                                                                                  \
-    hipLaunchKernelGGL(fn, grid, dim3(CORR_GT * KS_), sh, stream, in, out, a);                                         \
-    return true;                                                                                                       \
-  }
+#define GL_CORR(KWP_, ST_, KS_, NCJ_, OX_) return corr_launch<KWP_, ST_, KS_, NCJ_, OX_>(grid, sh, stream, in, out, a, last);
 #define GL_CORR_W(ST_, KS_, NCJ_, OX_)                                                                                          \
   switch (pl.KWP) {                                                                                                             \
     case 4: GL_CORR(4, ST_, KS_, NCJ_, OX_) case 8: GL_CORR(8, ST_, KS_, NCJ_, OX_) case 12: GL_CORR(12, ST_, KS_, NCJ_, OX_)     \
@@ -437,31 +447,33 @@ bool launch_corr(const gl_model::CorrPlan& pl, int B, const float* in, float* ou
   return false;
 }
 
-int post_fwd(const gl_model* m, int B, const float* S, float* out, hipStream_t stream, float scale = -1.f) {
-  if (launch_corr(m->corr_fwd, B, S, out, scale < 0.f ? m->conversion_factor : scale, stream, m->dbg_flags, m->corr_max_pairs, m->corr_wide)) {
+int post_fwd(const gl_model* m, int B, const float* S, float* out, hipStream_t stream, float scale) {
+  if (launch_corr(m->corr_fwd, B, S, out, scale, stream, m->dbg_flags, m->corr_max_pairs, m->corr_wide, &m->last_post_fn[0])) {
     GL_HIP(hipGetLastError());
     return GL_OK;
   }
-  PostArgs p = post_args(m, scale < 0.f ? m->conversion_factor : scale);
+  PostArgs p = post_args(m, scale);
   const int TR = (PT - 1) * p.ss + p.KH, TC = ((PT - 1) * p.ss + p.KW) | 1;
   size_t shmem = (size_t)TR * TC * sizeof(float);
   if (shmem > 64 * 1024) return fail(GL_EUNSUPPORTED, "PSF too large for the LDS-tiled convolution (%zu B)", shmem);
   dim3 grid((p.W + PT - 1) / PT, (p.H + PT - 1) / PT, B);
   hipLaunchKernelGGL(gl_psf_pool_fwd_kernel, grid, dim3(256), shmem, stream, S, out, p);
+  m->last_post_fn[0].store(reinterpret_cast<const void*>(gl_psf_pool_fwd_kernel), std::memory_order_relaxed);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
 // cotangent of the final image [B,H,W] -> cotangent of S [B,Hs,Ws]
-int post_bwd(const gl_model* m, int B, const float* gP, float* gS, hipStream_t stream) {
-  if (launch_corr(m->corr_bwd, B, gP, gS, m->conversion_factor, stream, m->dbg_flags, m->corr_max_pairs, m->corr_wide)) {
+int post_bwd(const gl_model* m, int B, const float* gP, float* gS, hipStream_t stream, float scale) {
+  if (launch_corr(m->corr_bwd, B, gP, gS, scale, stream, m->dbg_flags, m->corr_max_pairs, m->corr_wide, &m->last_post_fn[1])) {
     GL_HIP(hipGetLastError());
     return GL_OK;
   }
-  PostArgs p = post_args(m, m->conversion_factor);
+  PostArgs p = post_args(m, scale);
   const int TR = (PT - 1 + p.KH) / p.ss + 3, TC = ((PT - 1 + p.KW) / p.ss + 3) | 1;
   size_t shmem = (size_t)TR * TC * sizeof(float);
   dim3 grid((p.Ws + PT - 1) / PT, (p.Hs + PT - 1) / PT, B);
   hipLaunchKernelGGL(gl_psf_pool_bwd_kernel, grid, dim3(256), shmem, stream, gP, gS, p);
+  m->last_post_fn[1].store(reinterpret_cast<const void*>(gl_psf_pool_bwd_kernel), std::memory_order_relaxed);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -495,7 +507,7 @@ int run_likelihood(const gl_model* m, int B, const Workspace& w, int chunk, int 
   }
   if (!m->has_post) return want_grad ? launch_main<LL_GRAD>(m, a, B, n_chunks, stream) : launch_main<LL_FWD>(m, a, B, n_chunks, stream);
   if ((rc = render_ss(m, a, B, n_chunks, w, stream))) return rc;
-  if ((rc = post_fwd(m, B, w.img_ss, w.img_tmp, stream))) return rc;
+  if ((rc = post_fwd(m, B, w.img_ss, w.img_tmp, stream, m->conversion_factor))) return rc;
   const int HW = (m->height / m->supersample) * (m->width / m->supersample);
   hipLaunchKernelGGL(gl_imgstats_kernel, dim3(B), dim3(256), 0, stream, w.img_tmp, obs, err, mask, a.bg2, a.inv_t, HW,
                      w.stats, want_grad ? w.img_tmp : nullptr);
@@ -503,7 +515,7 @@ int run_likelihood(const gl_model* m, int B, const Workspace& w, int chunk, int 
   *extra_stats = w.stats;
   *use_partial = want_grad ? 1 : 0;
   if (!want_grad) return GL_OK;
-  if ((rc = post_bwd(m, B, w.img_tmp, w.img_ss, stream))) return rc;
+  if ((rc = post_bwd(m, B, w.img_tmp, w.img_ss, stream, m->conversion_factor))) return rc;
   a.gimg = w.img_ss;
   a.out_scale = 1.f;
   return launch_main<IMG_BWD>(m, a, B, n_chunks, stream);
@@ -1005,6 +1017,25 @@ int gl_model_last_main_kernel(const gl_model* m, char* buf, size_t cap) {
   return GL_OK;
 }
 
+int gl_model_last_post_kernel(const gl_model* m, int transpose, char* buf, size_t cap) {
+  if (!m || !buf || cap == 0 || (transpose != 0 && transpose != 1)) return fail(GL_EINVAL, "bad argument");
+  const void* fn = m->last_post_fn[transpose].load();
+  if (!fn) return fail(GL_EINVAL, "no %s post-processing kernel has been launched on this model yet", transpose ? "transposed" : "forward");
+  const char* name = hipKernelNameRefByPtr(fn, nullptr);
+  if (!name) return fail(GL_ELAUNCH, "hipKernelNameRefByPtr returned no name");
+  snprintf(buf, cap, "%s", name);
+  return GL_OK;
+}
+
+int gl_post_apply(const gl_model* m, int B, const float* in, float* out, int transpose, float scale, void* hip_stream) {
+  if (!m || !in || !out) return fail(GL_EINVAL, "null argument");
+  if (B <= 0) return fail(GL_EINVAL, "B must be positive");
+  if (transpose != 0 && transpose != 1) return fail(GL_EINVAL, "transpose must be 0 or 1");
+  if (!m->has_post) return fail(GL_EINVAL, "the model has no PSF and no supersampling: there is no post-processing to apply");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  return transpose ? post_bwd(m, B, in, out, stream, scale) : post_fwd(m, B, in, out, stream, scale);
+}
+
 int gl_model_launch_shape(const gl_model* m, int B, int* chunk_px, int* n_chunks, int* row_floats, size_t* partial_offset_bytes) {
   if (!m || B < 1) return fail(GL_EINVAL, "bad argument");
   int chunk = 0, nc = 0;
@@ -1076,7 +1107,7 @@ int gl_simulate_fwd(const gl_model* m, const float* params, int B, float* img, v
   if ((rc = run_order(m, B, w, &a, stream))) return rc;
   if (m->has_post) {
     if ((rc = render_ss(m, a, B, n_chunks, w, stream))) return rc;
-    return post_fwd(m, B, w.img_ss, img, stream);
+    return post_fwd(m, B, w.img_ss, img, stream, m->conversion_factor);
   }
   if (m->d_pix) GL_HIP(hipMemsetAsync(img, 0, sizeof(float) * (size_t)B * m->height * m->width, stream));
   a.img = img;
@@ -1099,7 +1130,7 @@ int gl_simulate_parts_fwd(const gl_model* m, const float* params, int B, unsigne
   if ((rc = run_order(m, B, w, &a, stream))) return rc;
   if (m->has_post) {
     if ((rc = render_ss(m, a, B, n_chunks, w, stream))) return rc;
-    return post_fwd(m, B, w.img_ss, img, stream);
+    return post_fwd(m, B, w.img_ss, img, stream, m->conversion_factor);
   }
   if (m->d_pix) GL_HIP(hipMemsetAsync(img, 0, sizeof(float) * (size_t)B * m->height * m->width, stream));
   a.img = img;
@@ -1119,7 +1150,7 @@ int gl_simulate_bwd(const gl_model* m, const float* params, const float* grad_im
   MainArgs a = base_args(m, w, chunk);
   a.gimg = grad_img;
   if (m->has_post) {
-    if ((rc = post_bwd(m, B, grad_img, w.img_ss, stream))) return rc;
+    if ((rc = post_bwd(m, B, grad_img, w.img_ss, stream, m->conversion_factor))) return rc;
     a.gimg = w.img_ss;
     a.out_scale = 1.f;
   }

@@ -402,6 +402,20 @@ int gl_model_set_timing_stride(gl_model* m, int stride);
 int gl_model_last_main_ms(gl_model* m, float* ms);
 int gl_model_timing_drain(gl_model* m, float* ms, int cap, int* n);
 int gl_model_last_main_kernel(const gl_model* m, char* buf, size_t cap);
+
+/* The model's image post-processing on a caller-supplied stack (csrc/gl_post.hip.h): PSF convolution (SAME, true convolution),
+ * average pooling by `supersample` and a scale, or the transpose (adjoint) of that linear map.
+ *   transpose == 0: in [B][Hs][Ws] (the supersampled grid of gl_grid) -> out [B][H][W], H = Hs / supersample;
+ *   transpose == 1: in [B][H][W] -> out [B][Hs][Ws].
+ * `scale` multiplies every output (the simulate path passes the grid's conversion_factor, the basis stack of gl_lstsq_fwd 1).
+ * These are the launches gl_simulate_fwd / gl_simulate_bwd / gl_loglike_fwd_bwd make after / before their main kernel, so the
+ * call also serves to convolve a caller's own image stack with the model's PSF.  in and out must not overlap.  No workspace, no
+ * allocation, no host synchronisation.  GL_EINVAL: a model without PSF and supersampling, null pointers, B <= 0, transpose not
+ * 0 or 1; GL_EUNSUPPORTED: a PSF too large for the forward tap kernel's LDS tile.
+ * gl_model_last_post_kernel: the (mangled) symbol of the kernel that served the most recent forward (transpose == 0) or
+ * transposed (1) post-processing launch on this model, whichever entry point made it -- the twin of gl_model_last_main_kernel. */
+int gl_post_apply(const gl_model* m, int B, const float* in, float* out, int transpose, float scale, void* hip_stream);
+int gl_model_last_post_kernel(const gl_model* m, int transpose, char* buf, size_t cap);
 /* Measurement aid: the work decomposition of a gradient call on B samples and where, inside a workspace of
  * gl_workspace_bytes(m, B), the per-(sample, chunk) partial rows [B][n_chunks][row_floats] live after the call (n_chunks is the
  * number of rows a sample owns: its pixel chunks, or more where the cheapest samples of a launch run as more, shorter

@@ -903,6 +903,19 @@ def subgrid_kernel(kernel, subgrid_res, odd=False, num_iter=100):
 # --------------------------------------------------------------------------
 # simulator (tf/simulator.py)
 # --------------------------------------------------------------------------
+def psf_pool(ret, flat_kernel, supersample):
+    """tf/simulator.py:145-155 on a (bs, 1, Hs, Ws) stack: conv2d SAME with the flipped kernel ``flat_kernel`` (None: no PSF),
+    then average pooling by ``supersample``.  The three lines ``RefSimulator.simulate`` runs after rendering."""
+    if flat_kernel is not None:  # :145-147 conv2d SAME, stride 1
+        kh, kw = flat_kernel.shape
+        # TF 'SAME' pads (k-1)//2 before and k//2 after (extra goes to the end)
+        ret = torch.nn.functional.pad(ret, ((kw - 1) // 2, kw // 2, (kh - 1) // 2, kh // 2))
+        ret = torch.nn.functional.conv2d(ret, flat_kernel[None, None])
+    if supersample != 1:  # :149-155
+        ret = torch.nn.functional.avg_pool2d(ret, kernel_size=supersample, stride=supersample)
+    return ret
+
+
 class RefSimulator:
     """tf/simulator.py:13-156 (``__init__``, ``beta``, ``simulate``)."""
 
@@ -960,13 +973,7 @@ class RefSimulator:
         img = torch.where(torch.isnan(img), torch.zeros_like(img), img)  # :140
         img = img.permute(2, 0, 1)  # :141
         ret = img[:, None]
-        if self.flat_kernel is not None:  # :145-147 conv2d SAME, stride 1
-            kh, kw = self.flat_kernel.shape
-            # TF 'SAME' pads (k-1)//2 before and k//2 after (extra goes to the end)
-            ret = torch.nn.functional.pad(ret, ((kw - 1) // 2, kw // 2, (kh - 1) // 2, kh // 2))
-            ret = torch.nn.functional.conv2d(ret, self.flat_kernel[None, None])
-        if self.supersample != 1:  # :149-155
-            ret = torch.nn.functional.avg_pool2d(ret, kernel_size=self.supersample, stride=self.supersample)
+        ret = psf_pool(ret, self.flat_kernel, self.supersample)
         return torch.squeeze(ret) * self.conversion_factor  # :156
 
 
