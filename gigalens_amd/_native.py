@@ -279,25 +279,7 @@ class _UserEval(torch.autograd.Function):
 
 
 def _user_eval(up, profile, x, y, kwargs):
-    dev = device()
-    names = list(profile.params)
-    missing = [n for n in names if n not in kwargs]
-    if missing:
-        raise TypeError(f"{profile.name}: missing parameters {missing}")
-    x = torch.as_tensor(x, dtype=torch.float32, device=dev)
-    y = torch.as_tensor(y, dtype=torch.float32, device=dev)
-    vals = [torch.as_tensor(kwargs[n], dtype=torch.float32, device=dev) for n in names]
-    out_shape = torch.broadcast_shapes(x.shape, y.shape, *[v.shape for v in vals])
-    B = out_shape[-1] if len(out_shape) else 1
-    for n, v in zip(names, vals):
-        if v.dim() > 1 and any(s != 1 for s in v.shape[:-1]):
-            raise NativeLibraryError(f"{profile.name}.{n}: parameters may only vary along the last (batch) axis")
-    if vals:
-        P = torch.stack([v.reshape(-1)[-B:].expand(B) if v.numel() > 1 else v.reshape(()).expand(B) for v in vals], dim=1).contiguous()
-    else:
-        P = torch.zeros((B, 0), dtype=torch.float32, device=dev)
-    xb = x.expand(out_shape).reshape(-1, B).contiguous()
-    yb = y.expand(out_shape).reshape(-1, B).contiguous()
+    xb, yb, P, B, out_shape = _broadcast_points(profile, x, y, kwargs, list(profile.params), device())
     return tuple(o.reshape(out_shape) for o in _UserEval.apply(up, xb, yb, P))
 
 
@@ -310,7 +292,10 @@ def device():
 # --------------------------------------------------------------------------------------------------
 # plugin-level point evaluation (MassProfile.deriv / LightProfile.light)
 # --------------------------------------------------------------------------------------------------
-def _broadcast_points(profile, x, y, kwargs, names, dev):
+def _broadcast_points(profile, x, y, kwargs, names, dev, columns=None):
+    """Points and parameters of a plugin-level call on their common shape ``(..., B)``: ``xb, yb`` [n_pts, B], the parameter rows
+    ``P`` [B, len(columns)] (``columns``: the native parameter order, default ``names``; a column not among ``names`` is 1 -- the
+    unit amplitudes of profile_basis), ``B`` and the broadcast shape."""
     missing = [n for n in names if n not in kwargs]
     if missing:
         raise TypeError(f"{profile.name}: missing parameters {missing}")
@@ -322,8 +307,10 @@ def _broadcast_points(profile, x, y, kwargs, names, dev):
     for n, v in zip(names, vals):
         if v.dim() > 1 and any(s != 1 for s in v.shape[:-1]):
             raise NativeLibraryError(f"{profile.name}.{n}: parameters may only vary along the last (batch) axis")
-    P = torch.stack([v.reshape(-1)[-B:].expand(B) if v.numel() > 1 else v.reshape(()).expand(B) for v in vals],
-                    dim=1).contiguous()
+    cols = {n: (v.reshape(-1)[-B:].expand(B) if v.numel() > 1 else v.reshape(()).expand(B)) for n, v in zip(names, vals)}
+    one = torch.ones(B, dtype=torch.float32, device=dev)
+    rows = [cols.get(n, one) for n in (names if columns is None else columns)]
+    P = torch.stack(rows, dim=1).contiguous() if rows else torch.zeros((B, 0), dtype=torch.float32, device=dev)
     xb = x.expand(out_shape).reshape(-1, B).contiguous()
     yb = y.expand(out_shape).reshape(-1, B).contiguous()
     return xb, yb, P, B, out_shape
@@ -450,22 +437,7 @@ def profile_eval(profile, x, y, kwargs):
         return _user_eval(up, profile, x, y, kwargs)
     dev = device()
     comp = component_of(profile)
-    names = list(profile.params)
-    missing = [n for n in names if n not in kwargs]
-    if missing:
-        raise TypeError(f"{profile.name}: missing parameters {missing}")
-    x = torch.as_tensor(x, dtype=torch.float32, device=dev)
-    y = torch.as_tensor(y, dtype=torch.float32, device=dev)
-    vals = [torch.as_tensor(kwargs[n], dtype=torch.float32, device=dev) for n in names]
-    out_shape = torch.broadcast_shapes(x.shape, y.shape, *[v.shape for v in vals])
-    B = out_shape[-1] if len(out_shape) else 1
-    for n, v in zip(names, vals):
-        if v.dim() > 1 and any(s != 1 for s in v.shape[:-1]):
-            raise NativeLibraryError(f"{profile.name}.{n}: parameters may only vary along the last (batch) axis")
-    P = torch.stack([v.reshape(-1)[-B:].expand(B) if v.numel() > 1 else v.reshape(()).expand(B) for v in vals],
-                    dim=1).contiguous()
-    xb = x.expand(out_shape).reshape(-1, B).contiguous()
-    yb = y.expand(out_shape).reshape(-1, B).contiguous()
+    xb, yb, P, B, out_shape = _broadcast_points(profile, x, y, kwargs, list(profile.params), dev)
     n_pts = xb.shape[0]
     out0 = torch.empty_like(xb)
     is_mass = comp.kind <= 12
@@ -525,23 +497,8 @@ def profile_basis(profile, x, y, kwargs):
     """``light`` of a ``use_lstsq`` profile (gl_profile_basis): ``(depth,) + broadcast shape`` unit-amplitude images."""
     dev = device()
     comp = component_of(profile)
-    names = list(profile.params)  # without the amplitudes (profile.py:40-41)
-    missing = [n for n in names if n not in kwargs]
-    if missing:
-        raise TypeError(f"{profile.name}: missing parameters {missing}")
-    x = torch.as_tensor(x, dtype=torch.float32, device=dev)
-    y = torch.as_tensor(y, dtype=torch.float32, device=dev)
-    vals = [torch.as_tensor(kwargs[n], dtype=torch.float32, device=dev) for n in names]
-    out_shape = torch.broadcast_shapes(x.shape, y.shape, *[v.shape for v in vals])
-    B = out_shape[-1] if len(out_shape) else 1
-    for n, v in zip(names, vals):
-        if v.dim() > 1 and any(s != 1 for s in v.shape[:-1]):
-            raise NativeLibraryError(f"{profile.name}.{n}: parameters may only vary along the last (batch) axis")
-    cols = {n: (v.reshape(-1)[-B:].expand(B) if v.numel() > 1 else v.reshape(()).expand(B)) for n, v in zip(names, vals)}
-    one = torch.ones(B, dtype=torch.float32, device=dev)
-    P = torch.stack([cols.get(n, one) for n in profile._native_params()], dim=1).contiguous()
-    xb = x.expand(out_shape).reshape(-1, B).contiguous()
-    yb = y.expand(out_shape).reshape(-1, B).contiguous()
+    # profile.params: without the amplitudes (profile.py:40-41), which the native row holds as unit columns
+    xb, yb, P, B, out_shape = _broadcast_points(profile, x, y, kwargs, list(profile.params), dev, columns=profile._native_params())
     out = torch.empty((int(profile.depth),) + tuple(xb.shape), dtype=torch.float32, device=dev)
     _check(lib().gl_profile_basis(ctypes.byref(comp), _ptr(xb), _ptr(yb), xb.shape[0], B, 1, _ptr(P), _ptr(out),
                                   _stream()))
@@ -603,6 +560,21 @@ class Model:
                                                 t.ctypes.data_as(POINTER(c_float))))
         self._ws = {}  # the workspace grows with the catalogue
 
+    def _points(self, x, y, B):
+        """``x, y`` broadcastable to ``(..., B)`` as contiguous ``[n_pts, B]`` tensors, and that shape."""
+        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+        y = torch.as_tensor(y, dtype=torch.float32, device=self.device)
+        shape = torch.broadcast_shapes(x.shape, y.shape, (B,))
+        return x.expand(shape).reshape(-1, B).contiguous(), y.expand(shape).reshape(-1, B).contiguous(), shape
+
+    def _scratch(self, name, nbytes):
+        """The scratch workspace ``name`` of at least ``nbytes`` bytes, grown on demand."""
+        ws = getattr(self, name, None)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            setattr(self, name, ws)
+        return ws
+
     def lens_maps(self, params, x, y):
         """gl_lens_maps: ``x, y`` broadcastable to ``(..., B)``; returns ``(6, ...)`` = beta_x, beta_y, f_xx, f_xy, f_yx, f_yy."""
         params = self._params(params)
@@ -611,11 +583,7 @@ class Model:
             out = torch.empty((6, self.N, B), dtype=torch.float32, device=self.device)
             _check(lib().gl_lens_maps(self._h, _ptr(params), B, None, None, self.N, 0, _ptr(out), _stream()))
             return out
-        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
-        y = torch.as_tensor(y, dtype=torch.float32, device=self.device)
-        shape = torch.broadcast_shapes(x.shape, y.shape, (B,))
-        xb = x.expand(shape).reshape(-1, B).contiguous()
-        yb = y.expand(shape).reshape(-1, B).contiguous()
+        xb, yb, shape = self._points(x, y, B)
         out = torch.empty((6,) + tuple(xb.shape), dtype=torch.float32, device=self.device)
         _check(lib().gl_lens_maps(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), xb.shape[0], 1, _ptr(out), _stream()))
         return out.reshape((6,) + tuple(shape))
@@ -628,11 +596,7 @@ class Model:
             out = torch.empty((self.N, B), dtype=torch.float32, device=self.device)
             _check_potential(lib().gl_lens_potential(self._h, _ptr(params), B, None, None, self.N, 0, _ptr(out), _stream()))
             return out
-        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
-        y = torch.as_tensor(y, dtype=torch.float32, device=self.device)
-        shape = torch.broadcast_shapes(x.shape, y.shape, (B,))
-        xb = x.expand(shape).reshape(-1, B).contiguous()
-        yb = y.expand(shape).reshape(-1, B).contiguous()
+        xb, yb, shape = self._points(x, y, B)
         out = torch.empty(tuple(xb.shape), dtype=torch.float32, device=self.device)
         _check_potential(lib().gl_lens_potential(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), xb.shape[0], 1, _ptr(out), _stream()))
         return out.reshape(tuple(shape))
@@ -648,9 +612,7 @@ class Model:
             raise NativeLibraryError(f"source positions must be [B={B}, S], got {tuple(src_x.shape)} / {tuple(src_y.shape)}")
         S = src_x.shape[1]
         nbytes = lib().gl_image_positions_workspace_bytes(self._h, B, S, int(n_cells), int(max_images))
-        ws = self._img_ws if getattr(self, "_img_ws", None) is not None and self._img_ws.numel() >= nbytes else None
-        if ws is None:
-            ws = self._img_ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        ws = self._scratch("_img_ws", nbytes)
         out = torch.empty((B, S, max(int(max_images), 1), 3), dtype=torch.float32, device=self.device)
         n_images = torch.empty((B, S), dtype=torch.int32, device=self.device)
         n_dropped = torch.empty_like(n_images)
@@ -667,9 +629,7 @@ class Model:
         params = self._params(params)
         B, M = params.shape[0], int(max_segments)
         nbytes = lib().gl_critical_curves_workspace_bytes(self._h, B, int(n_cells), M)
-        ws = self._crit_ws if getattr(self, "_crit_ws", None) is not None and self._crit_ws.numel() >= nbytes else None
-        if ws is None:
-            ws = self._crit_ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        ws = self._scratch("_crit_ws", nbytes)
         seg = torch.empty((B, max(M, 1), 2, 2), dtype=torch.float32, device=self.device)
         cau = torch.empty_like(seg)
         kind = torch.empty((B, max(M, 1)), dtype=torch.int32, device=self.device)
@@ -689,9 +649,7 @@ class Model:
         params = self._params(params)
         B, D = params.shape[0], self.num_linear()
         nbytes = lib().gl_lstsq_workspace_bytes(self._h, B)
-        ws = self._lstsq_ws if getattr(self, "_lstsq_ws", None) is not None and self._lstsq_ws.numel() >= nbytes else None
-        if ws is None:
-            ws = self._lstsq_ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        ws = self._scratch("_lstsq_ws", nbytes)
         dev = params.device
         coeffs = torch.empty((B, D), dtype=torch.float32, device=dev) if want == "coeffs" else None
         stacked = torch.empty((B, D, self.out_h, self.out_w), dtype=torch.float32, device=dev) if want == "stacked" else None

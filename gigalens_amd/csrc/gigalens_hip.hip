@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <memory>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -108,6 +109,21 @@ int tail_plan(const gl_model* m, int B, int n_chunks, int* tail_from, int* n_row
   return rows;
 }
 
+// The launch shape of one call on B samples.  Computed once per entry point and passed down: the workspace layout (carve), the
+// rank the front end's sort splits at (run_prep) and the main kernel's grid (run_likelihood) all read the same plan.
+struct LaunchPlan {
+  int chunk, n_chunks;  // pixels per workgroup, workgroups per sample (chunking)
+  int tail_rows;        // workgroups per sample of the tapered end, 0 = the shape has none (tail_plan)
+  int tail_from;        // first rank of the tapered end (B without one)
+  int n_rows;           // partial rows a sample owns in the workspace: max(n_chunks, tail_rows)
+};
+LaunchPlan launch_plan(const gl_model* m, int B) {
+  LaunchPlan p{};
+  chunking(m, B, &p.chunk, &p.n_chunks);
+  p.tail_rows = tail_plan(m, B, p.n_chunks, &p.tail_from, &p.n_rows);
+  return p;
+}
+
 struct Workspace {
   float* derived;
   float* partial;
@@ -122,18 +138,15 @@ struct Workspace {
   size_t bytes;
 };
 
-Workspace carve(const gl_model* m, int B, void* base) {
-  int chunk, n_chunks;
-  chunking(m, B, &chunk, &n_chunks);
+// (the partial rows are sized for the tapered end whenever the shape has one, whether or not the call at hand uses it)
+Workspace carve(const gl_model* m, int B, void* base, const LaunchPlan& plan) {
   Workspace w{};
   size_t off = 0;
   char* p = (char*)base;
   w.derived = (float*)(p + off);
   off += align_up((size_t)B * m->D * sizeof(float), 256);
   w.partial = (float*)(p + off);
-  int tail_from, n_rows;
-  tail_plan(m, B, n_chunks, &tail_from, &n_rows);
-  off += align_up((size_t)B * n_rows * m->A * sizeof(float), 256);
+  off += align_up((size_t)B * plan.n_rows * m->A * sizeof(float), 256);
   w.params = (float*)(p + off);
   off += align_up((size_t)B * std::max(m->P, 1) * sizeof(float), 256);
   w.order = (int*)(p + off);
@@ -202,19 +215,29 @@ MainArgs base_args(const gl_model* m, const Workspace& w, int chunk) {
   return a;
 }
 
-int check_call(const gl_model* m, const void* params, int B, void* ws, size_t ws_bytes) {
+// "The model is ready": every GL_SCALED lens has its catalogue and (with_series) every GL_SERIES lens its coefficient field.  The
+// pixel-grid entry points report how many are missing and the call that attaches them (counted = true), the others name the kind.
+int check_ready(const gl_model* m, bool with_series, bool counted) {
+  const int no_cat = m->n_scaled - (int)m->cats.size(), no_field = m->n_series - m->n_series_set;
+  if (no_cat)
+    return counted ? fail(GL_EINVAL, "%d GL_SCALED component(s) without a catalogue (gl_model_set_catalogue)", no_cat)
+                   : fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  if (with_series && no_field)
+    return counted ? fail(GL_EINVAL, "%d GL_SERIES component(s) without a coefficient field (gl_model_set_series)", no_field)
+                   : fail(GL_EINVAL, "GL_SERIES component without a coefficient field");
+  return GL_OK;
+}
+
+// the arguments every pixel-grid call shares; on success the call's launch plan and its workspace, carved
+int check_call(const gl_model* m, const void* params, int B, void* ws, size_t ws_bytes, LaunchPlan* plan, Workspace* w) {
   if (!m) return fail(GL_EINVAL, "model is null");
   if (!params) return fail(GL_EINVAL, "params is null");
   if (B <= 0 || B > 65535) return fail(GL_EINVAL, "batch size %d outside [1, 65535]", B);
-  if ((int)m->cats.size() != m->n_scaled)
-    return fail(GL_EINVAL, "%d GL_SCALED component(s) without a catalogue (gl_model_set_catalogue)",
-                m->n_scaled - (int)m->cats.size());
-  if (m->n_series_set != m->n_series)
-    return fail(GL_EINVAL, "%d GL_SERIES component(s) without a coefficient field (gl_model_set_series)",
-                m->n_series - m->n_series_set);
+  if (int rc = check_ready(m, true, true)) return rc;
   if (!ws) return fail(GL_EINVAL, "workspace is null");
-  size_t need = gl_workspace_bytes(m, B);
-  if (ws_bytes < need) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+  *plan = launch_plan(m, B);
+  *w = carve(m, B, ws, *plan);
+  if (ws_bytes < w->bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", ws_bytes, w->bytes);
   return GL_OK;
 }
 
@@ -234,28 +257,35 @@ size_t prep_row_bytes(const gl_model* m) {
   return (m->prep_lds && bytes <= 48 * 1024) ? bytes : 0;
 }
 
-// the rank the sort must split deterministically (tail_plan): which samples run the tapered end may not depend on the order
-// the atomics of the counting sort leave inside a cost bin
-int prep_tail_from(const gl_model* m, int B) {
-  int chunk, n_chunks, tail_from, n_rows;
-  chunking(m, B, &chunk, &n_chunks);
-  return tail_plan(m, B, n_chunks, &tail_from, &n_rows) ? tail_from : -1;
-}
-
-int run_prep(const gl_model* m, const float* params, int B, const Workspace& w, hipStream_t stream) {
-  int n_comp = (int)m->comps.size();
-  int total = B * n_comp;
+// The front end of a call: derived constants, dispatch cost and (wavefront form) the cost order of every sample, then the catalogue
+// members' constants.  The rows come packed (`params` [B,P], z null) or unconstrained (`z` [B,d_z], params null: the constrained
+// rows are written to w.params through the model's bijectors).
+int run_prep(const gl_model* m, const float* params, const float* z, int B, const LaunchPlan& plan, const Workspace& w,
+             hipStream_t stream) {
+  const int n_comp = (int)m->comps.size(), d_z = z ? m->d_z : 0;
+  const ZCol* zcols = z ? m->d_zcols.get() : nullptr;
+  const int* src = z ? m->d_src.get() : nullptr;
+  const float* const_row = z ? m->d_const.get() : nullptr;
+  float* rows_out = z ? w.params : nullptr;
+  int* cost = m->epl_comp >= 0 ? w.cost : nullptr;
   if (wave_front_end(m)) {  // one wavefront per sample: the EPL coefficient tables are built by a scan over its lanes
     const bool ord = order_in_front_end(m, B);
     const size_t rows = prep_row_bytes(m);
-    hipLaunchKernelGGL(gl_prep_wave_kernel, dim3((B + 3) / 4 + (ord ? 1 : 0)), dim3(256), rows, stream, m->d_comps, n_comp, params, nullptr,
-                       0, (const ZCol*)nullptr, (const int*)nullptr, (const float*)nullptr, m->P, B, (float*)nullptr, w.derived,
-                       m->D, m->epl_comp >= 0 ? w.cost : nullptr, m->epl_comp, ord ? w.order : nullptr, rows ? 1 : 0, prep_tail_from(m, B));
-  } else
-    hipLaunchKernelGGL(gl_prep_kernel, dim3((total + 127) / 128), dim3(128), 0, stream, m->d_comps, n_comp, params,
-                       m->P, B, w.derived, m->D, m->epl_comp >= 0 ? w.cost : nullptr, m->epl_comp);
+    // the rank the sort must split deterministically: which samples run the tapered end may not depend on the order the atomics
+    // of the counting sort leave inside a cost bin
+    const int split_rank = plan.tail_rows ? plan.tail_from : -1;
+    hipLaunchKernelGGL(gl_prep_wave_kernel, dim3((B + 3) / 4 + (ord ? 1 : 0)), dim3(256), rows, stream, m->d_comps.get(), n_comp,
+                       params, z, d_z, zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp,
+                       ord ? w.order : nullptr, rows ? 1 : 0, split_rank);
+  } else if (z) {  // thread per component
+    hipLaunchKernelGGL(gl_zprep_kernel, dim3((B * n_comp + 127) / 128), dim3(128), 0, stream, m->d_comps.get(), n_comp, z, d_z,
+                       zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp);
+  } else {
+    hipLaunchKernelGGL(gl_prep_kernel, dim3((B * n_comp + 127) / 128), dim3(128), 0, stream, m->d_comps.get(), n_comp, params,
+                       m->P, B, w.derived, m->D, cost, m->epl_comp);
+  }
   GL_HIP(hipGetLastError());
-  return run_galprep(m, params, B, w, stream);
+  return run_galprep(m, z ? w.params : params, B, w, stream);
 }
 
 FinArgs fin_args(const gl_model* m, const float* params, const Workspace& w, float* loglike, float* chi2, float* grad,
@@ -318,19 +348,32 @@ int run_order(const gl_model* m, int B, const Workspace& w, MainArgs* a, hipStre
 }
 
 
-// image-position likelihood on the packed parameter rows `params` [B,P] (already on the device)
-int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream) {
-  if (m->n_series) return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image-position likelihood");
-  if (m->has_user)  // the four kernels below, compiled at run time with the user's bodies on the nested duals (once per model text)
-    if (int rc = compile_user_points(m)) return rc;
+// What every point kernel reads of a model (gl_positions.hip.h PosArgs): the lenses, the packed rows, the catalogues, the series
+// fields.  `series` is set for every user; it is non-null only in gl_lens_maps on the model's own grid, the one user that serves
+// series-expansion lenses -- the others (run_positions, gl_lens_potential, gl_image_positions, gl_critical_curves) refuse a model
+// that holds one before they launch, and a model without one has no d_series.
+PosArgs point_args(const gl_model* m, const float* params, int B) {
   PosArgs a{};
   a.comps = m->d_comps;
   a.n_lens = m->n_lens;
   a.P = m->P;
   a.B = B;
+  a.params = params;
+  a.cats = m->d_cats;
+  a.gal_table = m->d_gal_table;
+  a.gal_static = m->d_gal_static;
+  a.series = m->d_series;
+  return a;
+}
+
+// image-position likelihood on the packed parameter rows `params` [B,P] (already on the device)
+int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream) {
+  if (m->n_series) return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image-position likelihood");
+  if (m->has_user)  // the four kernels below, compiled at run time with the user's bodies on the nested duals (once per model text)
+    if (int rc = compile_user_points(m)) return rc;
+  PosArgs a = point_args(m, params, B);  // + the position tables and the likelihood's workspace
   a.J = m->pos_J;
   a.F = m->pos_F;
-  a.params = params;
   a.px = m->d_pos;
   a.py = m->d_pos + m->pos_J;
   a.ex = m->d_pos + 2 * m->pos_J;
@@ -343,9 +386,6 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
   a.ll = w.pos_ll;
   a.chi2 = w.pos_chi2;
   a.grad = want_grad ? w.pos_grad : nullptr;
-  a.cats = m->d_cats;
-  a.gal_table = m->d_gal_table;
-  a.gal_static = m->d_gal_static;
   auto blocks = [](long long n) { return dim3((unsigned)((n + 63) / 64)); };
   if (m->has_user) {
     int lens_params = m->lens_params;
@@ -486,11 +526,13 @@ int render_ss(const gl_model* m, MainArgs a, int B, int n_chunks, const Workspac
 
 // likelihood after prep: fused kernel when the image never has to exist, else render -> PSF/pool -> pixel
 // statistics (-> transposes -> VJP).  Tells finalize where chi2 / normalisation come from.
-int run_likelihood(const gl_model* m, int B, const Workspace& w, int chunk, int n_chunks, const float* obs,
+// `fin_rows`: the partial rows per sample finalize must reduce (the plan's chunks, or its rows when the tapered end ran).
+int run_likelihood(const gl_model* m, int B, const LaunchPlan& plan, const Workspace& w, const float* obs,
                    const float* err, const float* mask, float bg_rms, float exp_time, bool want_grad,
-                   hipStream_t stream, const float** extra_stats, int* use_partial, int* n_rows) {
+                   hipStream_t stream, const float** extra_stats, int* use_partial, int* fin_rows) {
   int rc;
-  MainArgs a = base_args(m, w, chunk);
+  const int n_chunks = plan.n_chunks;
+  MainArgs a = base_args(m, w, plan.chunk);
   a.obs = obs;
   a.err = err;
   a.mask = mask;
@@ -499,11 +541,13 @@ int run_likelihood(const gl_model* m, int B, const Workspace& w, int chunk, int 
   if ((rc = run_order(m, B, w, &a, stream))) return rc;
   *extra_stats = nullptr;
   *use_partial = 1;
-  *n_rows = n_chunks;
+  *fin_rows = n_chunks;
   if (!m->has_post && a.order && want_grad) {  // (the rounds are counted for the gradient kernels' occupancy; forward-only calls keep the plain grid)
-    a.tail_rows = tail_plan(m, B, n_chunks, &a.tail_from, &a.n_rows);
+    a.tail_rows = plan.tail_rows;
+    a.tail_from = plan.tail_from;
+    a.n_rows = plan.n_rows;
     a.n_samples = B;
-    *n_rows = a.n_rows;
+    *fin_rows = plan.n_rows;
   }
   if (!m->has_post) return want_grad ? launch_main<LL_GRAD>(m, a, B, n_chunks, stream) : launch_main<LL_FWD>(m, a, B, n_chunks, stream);
   if ((rc = render_ss(m, a, B, n_chunks, w, stream))) return rc;
@@ -532,8 +576,19 @@ struct LstsqWs {
   int n_chunks_f;  // workgroups per sample of the stack-free kernel (gl_shp_normal_kernel: 512-pixel tiles dealt round-robin)
   size_t bytes;
 };
-LstsqWs carve_lstsq(const gl_model* m, int B, void* base, size_t off) {
+// a kernel that asks for more than 64 KB of dynamic LDS (up to the CU's 160) has to be told once per process
+int raise_lds_limit(const void* kernel, bool* raised) {
+  if (!*raised) {
+    GL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    *raised = true;
+  }
+  return GL_OK;
+}
+
+// (behind the call workspace `cw` of the same base)
+LstsqWs carve_lstsq(const gl_model* m, int B, void* base, const Workspace& cw) {
   LstsqWs w{};
+  size_t off = align_up(cw.bytes, 256);
   const int D = (int)m->lin_cols.size();
   const size_t HWs = (size_t)m->height * m->width, HW = HWs / ((size_t)m->supersample * m->supersample);
   char* p = (char*)base;
@@ -559,6 +614,381 @@ LstsqWs carve_lstsq(const gl_model* m, int B, void* base, size_t off) {
 }
 }  // namespace
 
+// ---- gl_model_create_user, step by step ----------------------------------------------------------------------------------
+namespace {
+struct ModelDeleter {
+  void operator()(gl_model* m) const { gl_model_destroy(m); }
+};
+
+int check_create_args(const gl_component* comps, int n_lens, int n_lens_light, int n_src, const gl_grid* grid) {
+  if (!grid) return fail(GL_EINVAL, "grid is null");
+  if (n_lens < 0 || n_lens_light < 0 || n_src < 0) return fail(GL_EINVAL, "negative component count");
+  if (n_lens + n_lens_light + n_src > 0 && !comps) return fail(GL_EINVAL, "comps is null");
+  if (grid->height <= 0 || grid->width <= 0 || grid->n_region <= 0) return fail(GL_EINVAL, "empty grid");
+  if (!grid->grid_x || !grid->grid_y) return fail(GL_EINVAL, "grid_x / grid_y is null");
+  if (grid->supersample < 1) return fail(GL_EINVAL, "supersample must be >= 1");
+  if (grid->height % grid->supersample || grid->width % grid->supersample)
+    return fail(GL_EINVAL, "grid size not a multiple of supersample");
+  if ((long long)grid->n_region > (long long)grid->height * grid->width)
+    return fail(GL_EINVAL, "n_region exceeds height*width");
+  if (!grid->pix_index && (long long)grid->n_region != (long long)grid->height * grid->width)
+    return fail(GL_EINVAL, "pix_index is required when n_region != height*width");
+  if (grid->psf && (grid->psf_h <= 0 || grid->psf_w <= 0)) return fail(GL_EINVAL, "bad PSF shape");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GL_ENODEVICE, "no HIP device available");
+  return GL_OK;
+}
+
+// the component table (offsets into the parameter, derived and accumulator rows), the linear columns and what the kinds imply
+int build_components(gl_model* m, const gl_component* comps, int n_comp, const char* const* bodies, int n_bodies) {
+  const int n_lens = m->n_lens;
+  int p_off = 0, d_off = 0, a_off = NSTAT;
+  for (int i = 0; i < n_comp; ++i) {
+    const gl_component& c = comps[i];
+    const bool mass = i < n_lens;
+    const bool is_mass_kind = (c.kind >= GL_EPL && c.kind <= GL_TNFW) || c.kind == GL_USER_MASS;
+    const bool is_light_kind = (c.kind >= GL_SERSIC && c.kind <= GL_CORE_SERSIC) || c.kind == GL_USER_LIGHT;
+    if ((mass && !is_mass_kind) || (!mass && !is_light_kind))
+      return fail(GL_EINVAL, "component %d: kind %d is not a %s profile", i, c.kind, mass ? "mass" : "light");
+    int iparam = c.iparam;
+    if (c.kind == GL_USER_MASS || c.kind == GL_USER_LIGHT) {
+      if (iparam < 0 || iparam > USER_MAXP || (int)c.flags >= n_bodies || !bodies[c.flags])
+        return fail(GL_EINVAL, "component %d: a user-written profile takes 0..%d parameters and the index of its body (got %d parameters, "
+                               "body %u of %d)", i, USER_MAXP, iparam, c.flags, n_bodies);
+      m->has_user = true;
+    }
+    if (c.kind == GL_EPL) {
+      if (iparam <= 0) iparam = 50;  // epl.py:15
+      if (iparam > 1000) return fail(GL_EINVAL, "EPL niter %d too large", iparam);
+    }
+    if (c.kind == GL_EPL) { m->epl_comp = m->has_epl ? -2 : i; m->has_epl = true; }
+    if (c.kind >= GL_DPIS && c.kind <= GL_SERIES) m->fam = std::max(m->fam, 1);
+    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC) m->fam = 2;
+    if (c.kind == GL_SERIES && (iparam < 0 || iparam > SERIES_MAX_ORDER))
+      return fail(GL_EINVAL, "component %d: series order %d outside [0, %d]", i, iparam, SERIES_MAX_ORDER);
+    if (c.kind == GL_SCALED) {
+      if (iparam < 1 || iparam > 3) return fail(GL_EINVAL, "component %d: GL_SCALED takes 1..3 scales, got %d", i, iparam);
+      ++m->n_scaled;
+    }
+    if (c.kind == GL_SHAPELETS) {
+      if (iparam < 0 || iparam > GL_SHAPELETS_NMAX_CAP)
+        return fail(GL_EUNSUPPORTED, "shapelets n_max=%d outside [0,%d]", iparam, GL_SHAPELETS_NMAX_CAP);
+      m->has_shapelets = true;
+      if (iparam > SH_CAP) m->shp_big = true;
+      if (c.flags & GL_FLAG_SHAPELETS_INTERPOLATE) m->has_table = true;
+    }
+    CompDesc cd{};
+    cd.kind = c.kind;
+    cd.iparam = iparam;
+    cd.flags = c.flags;
+    cd.p_off = p_off;
+    cd.d_off = d_off;
+    cd.a_off = a_off;
+    cd.n_par = kind_num_params(c.kind, iparam);
+    cd.n_acc = kind_num_acc(c.kind, iparam);
+    if (c.kind == GL_SCALED) cd.iparam = -1;  // catalogue slot, set by gl_model_set_catalogue
+    if (c.kind == GL_SERIES) {
+      cd.flags = (unsigned)m->n_series++;
+      m->series.push_back(SeriesDev{nullptr, nullptr, 0.f, iparam});
+      m->series_buf.emplace_back();
+      m->series_comp.push_back(i);
+    }
+    cd.lin_off = (int)m->lin_cols.size();
+    for (int k = 0; k < kind_num_linear(c.kind, iparam); ++k) m->lin_cols.push_back(p_off + kind_linear_col(c.kind, iparam) + k);
+    // a user-written light whose last parameter is declared the linear amplitude (gl_component::reserved): one basis image
+    if (c.kind == GL_USER_LIGHT && c.reserved == 1 && iparam >= 1) m->lin_cols.push_back(p_off + iparam - 1);
+    p_off += cd.n_par;
+    d_off += (kind_num_derived(c.kind, iparam) + 3) & ~3;
+    a_off += cd.n_acc;
+    m->comps.push_back(cd);
+  }
+  m->P = p_off;
+  for (int i = 0; i < n_lens; ++i) m->lens_params += m->comps[i].n_par;
+  m->D = std::max(d_off, 4);
+  m->A = a_off;
+  m->Apad = a_off | 1;  // odd: the 16 leader lanes of a wave land on 16 different LDS banks
+  for (int i = 0; i < n_lens; ++i) m->has_nfw = m->has_nfw || m->comps[i].kind == K_NFW;
+  m->nfw_lds = m->has_nfw ? sizeof(float) * 2 * glh::kNfwNodes : 0;  // the h(X) table rides in every main kernel's LDS
+  m->ncols = ((size_t)(((m->D + 3) & ~3) + 64 * m->Apad) * sizeof(float) + m->nfw_lds <= 60 * 1024) ? 64 : 16;
+  return GL_OK;
+}
+
+// Every GIGALENS_HIP_* variable, read once at model creation, one line each: what the calls look at later goes into the model,
+// what only the steps of the creation look at into Knobs.
+struct Knobs {
+  int tile, tile_grad, use_static, pair, shp, cluster, corr_pair;
+};
+Knobs read_env_knobs(gl_model* m) {
+  Knobs k{};
+  k.tile = env_int("GIGALENS_HIP_TILE", 0);                 // pixels per thread per tile: 1, 2 or 4 (0: the kernel's own choice)
+  k.tile_grad = env_int("GIGALENS_HIP_TILE_GRAD", k.tile);  // ... of the gradient launches (default: GIGALENS_HIP_TILE)
+  k.use_static = env_int("GIGALENS_HIP_STATIC", 1);         // 0: the interpreter kernel for every composition
+  m->static_variant = env_int("GIGALENS_HIP_STATIC_VARIANT", 0);
+  k.pair = env_int("GIGALENS_HIP_PAIR", 1);                 // 0: no pixel-pair form of the specialised kernels
+  k.shp = env_int("GIGALENS_HIP_SHP", 1);                   // 0: the round-2 kernels for one-shapelet-source models
+  k.cluster = env_int("GIGALENS_HIP_CLUSTER", -1);          // 0: no cluster kernel; 1 / 2: its pixel-split / component-per-wave form for every cluster model
+  m->target_wgs = std::max(1, env_int("GIGALENS_HIP_TARGET_WGS", 2048));
+  m->target_wgs_set = getenv("GIGALENS_HIP_TARGET_WGS") != nullptr;
+  m->use_order = env_int("GIGALENS_HIP_ORDER", 1) != 0;
+  m->order_fused = env_int("GIGALENS_HIP_ORDER_FUSED", 1) != 0;  // tests: 0 = the sort as a launch of its own (gl_order_kernel)
+  m->prep_lds = env_int("GIGALENS_HIP_PREP_LDS", 1) != 0;  // tests: 0 = the front end reads the parameter row back from global memory
+  m->tail_rows = env_int("GIGALENS_HIP_TAIL_ROWS", -1);  // -1: twice the chunks; 0: no tapered end; n: n workgroups per tail sample
+  m->tail_n = env_int("GIGALENS_HIP_TAIL_N", -1);        // -1: the remainder beyond whole rounds; n: the last n samples
+#ifdef GL_EXPERIMENTS
+  // dissection builds only (hipcc -DGL_EXPERIMENTS; never __graft_entry__.build()): work-skipping flags and a raw chunk size
+  m->chunk_px_override = env_int("GIGALENS_HIP_CHUNK_PX", 0);
+  m->dbg_flags = env_int("GIGALENS_HIP_DBGFLAGS", 0);
+#endif
+  m->shp_cull = env_int("GIGALENS_HIP_SHP_CULL", 1);
+  m->shp_blocked = env_int("GIGALENS_HIP_SHP_BLOCKED", 1);
+  m->corr_max_pairs = env_int("GIGALENS_HIP_CORR_MAXPAIRS", 0);  // tests: force the slicing of the PSF launches (read once)
+  m->corr_wide = env_int("GIGALENS_HIP_CORR_WIDE", 1);           // 0: 8 outputs per thread in the stride-2 forward correlation as well
+  k.corr_pair = env_int("GIGALENS_HIP_CORR_PAIR", 1);            // 0: the tap kernels for every PSF (no register-blocked pair kernel)
+  m->wave_prep = env_int("GIGALENS_HIP_WAVE_PREP", 1) != 0;
+  m->lstsq_wgs = std::max(1, env_int("GIGALENS_HIP_LSTSQ_WGS", 2048));
+  m->lstsq_chol = env_int("GIGALENS_HIP_LSTSQ_CHOL", 1) != 0;    // tests: 0 = every system through the eigenvalue solve
+  m->lstsq_fused = env_int("GIGALENS_HIP_LSTSQ_FUSED", 1) != 0;  // tests: 0 = the linear solve through the basis stack (read once)
+  return k;
+}
+
+// the dissection knobs: checked in an experiment build, refused in the shipped one
+int check_experiment_knobs(const gl_model* m) {
+#ifdef GL_EXPERIMENTS
+  if (m->chunk_px_override < 0 || m->chunk_px_override % (WG * 4) != 0)
+    return fail(GL_EINVAL, "GIGALENS_HIP_CHUNK_PX=%d is not a positive multiple of the tile (%d pixels)", m->chunk_px_override, WG * 4);
+  if (m->dbg_flags || m->chunk_px_override)
+    fprintf(stderr, "libgigalens_hip: EXPERIMENT BUILD with GIGALENS_HIP_DBGFLAGS=%d GIGALENS_HIP_CHUNK_PX=%d -- results are not valid\n",
+            m->dbg_flags, m->chunk_px_override);
+#else
+  // the shipped library has no work-skipping paths: a stray dissection variable is an error, not a silently ignored hint
+  (void)m;
+  for (const char* name : {"GIGALENS_HIP_DBGFLAGS", "GIGALENS_HIP_CHUNK_PX"}) {
+    const char* v = getenv(name);
+    if (v && *v && atoi(v) != 0)
+      return fail(GL_EINVAL, "%s is set but this library was built without -DGL_EXPERIMENTS (the dissection knobs do not exist in it)", name);
+  }
+#endif
+  return GL_OK;
+}
+
+// which main kernel serves the model: a specialised composition (and its pair / shapelet forms), the cluster kernels or the
+// interpreter, and the tile each launches with
+int select_kernels(gl_model* m, const Knobs& k) {
+  const int n_comp = (int)m->comps.size(), n_lens = m->n_lens, n_lens_light = m->n_ll, n_src = m->n_src;
+  m->tile = (k.tile == 4 || k.tile == 1) ? k.tile : 2;
+  m->tile_grad = (k.tile_grad == 4 || k.tile_grad == 1 || k.tile_grad == 2) ? k.tile_grad : 0;
+  m->static_id = k.use_static ? match_static(m) : 0;
+  if (m->has_user) {  // the run-time compiled interpreter serves the whole model
+    m->static_id = 0;
+    if (m->shp_big) return fail(GL_EUNSUPPORTED, "user-written profiles beside shapelets with n_max > %d", SH_CAP);
+  }
+  if (m->shp_big) {  // orders above SH_CAP: the runtime-order interpreter variant only (compiled for the basic profile families)
+    m->static_id = 0;
+    if (m->fam)
+      return fail(GL_EUNSUPPORTED, "shapelets with n_max > %d are served together with EPL / SIE / NFW / Shear / SIS lenses and Sersic "
+                                   "lights only (this model also holds dPIE-family, catalogue, series or extended profiles)", SH_CAP);
+  }
+  m->pair = k.pair;
+  // the pair kernels' epilogue addresses the accumulator row in closed form: [NSTAT | components in order, static_nacc each];
+  // gl_shp.hip.h addresses it as [NSTAT | lenses | lens lights | shapelet] and needs a table-mode model's pair table
+  int off = NSTAT;
+  bool ok_row = true;
+  for (int i = 0; i < n_comp; ++i) {
+    ok_row = ok_row && m->comps[i].a_off == off;
+    off += static_nacc(m->comps[i].kind);
+  }
+  if (m->pair && m->static_id && (!ok_row || off != m->A)) m->pair = 0;
+  m->shp_kernel = k.shp && k.pair && m->static_id && ok_row && n_src == 1 && m->comps.back().kind == K_SHAPELETS;
+  m->light_spherical = n_comp > n_lens;
+  for (int i = n_lens; i < n_comp; ++i) m->light_spherical = m->light_spherical && m->comps[i].kind == K_SERSIC;
+  if (!m->tile_grad) m->tile_grad = m->static_id ? 1 : 2;  // measured: T=1 wins once the VJP state lives in registers
+  if (!m->static_id) {  // the interpreter kernel is built for T = 2 and 4
+    if (!k.tile && !m->has_epl && !m->has_shapelets && !m->fam) m->tile = 4;  // cheap profiles, forward modes: amortise the per-tile work
+    if (m->tile == 1) m->tile = 2;
+    if (m->tile_grad == 1) m->tile_grad = 2;
+  }
+  if (k.cluster && !m->static_id && !m->has_user && n_lens_light == 0 && n_lens >= 1 && n_lens <= 8 && n_src >= 1 &&
+      n_src <= 20 && (size_t)64 * m->Apad * sizeof(float) <= 64 * 1024) {
+    bool ok_c = true, ell = false;
+    for (int i = 0; i < n_lens; ++i) ok_c = ok_c && m->comps[i].kind == K_NFW;
+    for (int i = n_lens; i < n_comp; ++i) {
+      ok_c = ok_c && (m->comps[i].kind == K_SERSIC || m->comps[i].kind == K_SERSIC_ELLIPSE);
+      ell = ell || m->comps[i].kind == K_SERSIC_ELLIPSE;
+    }
+    // the kernel addresses the derived / accumulator blocks in closed form: component-major, fixed block sizes
+    constexpr int NFWP = (NFW_ND + 3) & ~3, SERP = (SER_NDX + 3) & ~3;  // the strides gl_cluster_kernel walks the derived row with
+    for (int i = 0; i < n_lens && ok_c; ++i) ok_c = m->comps[i].d_off == NFWP * i && m->comps[i].a_off == NSTAT + NFW_NACC * i;
+    for (int i = 0; i < n_src && ok_c; ++i)
+      ok_c = m->comps[n_lens + i].d_off == NFWP * n_lens + SERP * i && m->comps[n_lens + i].a_off == NSTAT + NFW_NACC * n_lens + SER_NACC * i;
+    ok_c = ok_c && (size_t)64 * m->Apad * sizeof(float) + sizeof(float) * 2 * glh::kNfwNodes <= 64 * 1024;
+    if (ok_c) m->cluster = ell ? 2 : 1;
+    // ... in its component-per-wave form (gl_clusterw.hip.h) when the model fills at least 60 % of the component slots of the
+    // instantiation that holds it (4 waves x (1 + 2), (2 + 3) or (2 + 5) halos + sources): an unused slot is evaluated all the same.
+    // GIGALENS_HIP_CLUSTER: 1 = the pixel-split kernel for every cluster model, 2 = the component-per-wave kernel for every one
+    if (m->cluster) {
+      const int cap = (n_lens <= 4 && n_src <= 8) ? 12 : (n_src <= 12 ? 20 : 28);
+      m->cluster_w = k.cluster == 2 || (k.cluster != 1 && 10 * (n_lens + n_src) >= 6 * cap);
+    }
+  }
+  return GL_OK;
+}
+
+// the uploads of the creation: every failure of one reports the same way
+int create_failed() { return fail(GL_ENOMEM, "device allocation / upload failed in gl_model_create"); }
+template <class T>
+int put(DevBuf<T>& buf, const T* src, size_t n) {
+  return buf.upload(src, n) == hipSuccess ? GL_OK : create_failed();
+}
+
+// component table, pixel grid, linear columns and pixel list on the device
+int upload_grid(gl_model* m, const gl_grid* grid) {
+  int rc;
+  if (m->comps.empty()) {  // (a model without components still hands the kernels a table)
+    if (m->d_comps.alloc(1) != hipSuccess) return create_failed();
+  } else if ((rc = put(m->d_comps, m->comps.data(), m->comps.size()))) {
+    return rc;
+  }
+  if ((rc = put(m->d_gx, grid->grid_x, m->N))) return rc;
+  for (int i = 0; i < m->N; ++i) m->grid_rmax = std::max(m->grid_rmax, std::hypot(grid->grid_x[i], grid->grid_y[i]));
+  if ((rc = put(m->d_gy, grid->grid_y, m->N))) return rc;
+  if (!m->lin_cols.empty() && (rc = put(m->d_lin_cols, m->lin_cols.data(), m->lin_cols.size()))) return rc;
+  if (grid->pix_index) {
+    for (int i = 0; i < m->N; ++i)
+      if (grid->pix_index[i] < 0 || grid->pix_index[i] >= m->height * m->width)
+        return fail(GL_EINVAL, "pix_index[%d]=%d out of range", i, grid->pix_index[i]);
+    if ((rc = put(m->d_pix, grid->pix_index, m->N))) return rc;
+  }
+  return GL_OK;
+}
+
+// the NFW h(X) tables and the shapelet node table of the models that interpolate
+int upload_tables(gl_model* m) {
+  int rc;
+  if (m->has_nfw) {
+    // [h(X) node table | neutral blocks | H(s) cubics]: the layout gl_clusterw_kernel addresses (CW_NEUTRAL_OFF, CW_TABS_OFF)
+    std::vector<float> tab;
+    glh::build_nfw_table([](double X, double& g, double& gp) { glp::nfw_gw<double>(X, g, gp); }, tab);
+    // behind the table: the constant blocks of an unused component slot of gl_clusterw_kernel (zero amplitude, all else finite)
+    const float neutral_nfw[4] = {0.f, 0.f, 1.f, 0.f};  // NFW_CX, NFW_CY, NFW_INVRS, NFW_K0
+    float neutral_ser[16] = {0.f};
+    neutral_ser[glp::SER_C] = neutral_ser[glp::SER_SQ] = neutral_ser[glp::SER_ISQ] = neutral_ser[glp::SER_INVRS] = 1.f;
+    neutral_ser[glp::SER_INVN] = neutral_ser[glp::SER_IRS2] = 1.f;
+    neutral_ser[glp::SER_BN] = 1.6721f;  // n = 1; SER_IE = SER_CG = 0
+    tab.insert(tab.end(), neutral_nfw, neutral_nfw + 4);
+    tab.insert(tab.end(), neutral_ser, neutral_ser + 16);
+    // ... and the table of the same function in s = X^2 (gl_host_tables.h::build_nfw_table_s), [4][kNfwSIntervals]
+    std::vector<float> tab_s;
+    glh::build_nfw_table_s([](double X, double& g, double& gp) { glp::nfw_gw<double>(X, g, gp); }, tab_s);
+    tab.insert(tab.end(), tab_s.begin(), tab_s.end());
+    if ((rc = put(m->d_nfw_tab, tab.data(), tab.size()))) return rc;
+  }
+  if (m->has_table) {
+    // the full n_max = 10 table (stride 12, two rows of a node pair = six aligned float4), or -- for a model with orders above
+    // 10, whose shapelet components all run the runtime-order path -- the n_max = 20 one (stride 24)
+    std::vector<float> tab;
+    glh::build_shapelet_table(m->shp_big ? SH_CAPB : SH_CAP, tab, &m->shp_stride);
+    if ((rc = put(m->d_shp_tab, tab.data(), tab.size()))) return rc;
+  }
+  return GL_OK;
+}
+
+// Plans of the register-blocked pair kernel (gl_post.hip.h gl_corr_pair_kernel): forward = one class (stride ss, Keff), transpose =
+// ss^2 residue classes (stride 1, the class's decimated and flipped sub-kernel); rows padded to a multiple of four taps.  Each
+// appends its padded kernels to kbuf.
+int pad4(int n) { return std::max(4, (n + 3) & ~3); }
+void plan_corr_fwd(gl_model* m, const std::vector<double>& keff, std::vector<float>& kbuf) {
+  const int ss = m->supersample, Hs = m->height, Ws = m->width, H = Hs / ss, W = Ws / ss;
+  gl_model::CorrPlan& f = m->corr_fwd;
+  f.KWP = pad4(m->KW);
+  f.ST = ss;
+  CorrClass c{};
+  c.koff = 0; c.KH = m->KH; c.pt = m->pad_t; c.pl = m->pad_l; c.Ho = H; c.Wo[0] = W; c.oo_r = 0; c.oo_c[0] = 0;
+  kbuf.assign((size_t)m->KH * f.KWP, 0.f);
+  for (int u = 0; u < m->KH; ++u)
+    for (int v = 0; v < m->KW; ++v) kbuf[(size_t)u * f.KWP + v] = (float)keff[(size_t)u * m->KW + v];
+  f.args.n_class = 1; f.args.ncj = 1; f.args.Hi = Hs; f.args.Wi = Ws; f.args.Hout = H; f.args.Wout = W; f.args.os = 1;
+  f.args.cls[0] = c;
+  f.max_Ho = H; f.max_Wo = W; f.max_KH = m->KH; f.ok = true;
+}
+void plan_corr_bwd(gl_model* m, const std::vector<double>& keff, std::vector<float>& kbuf) {
+  // transpose: row class pi = (i + pt) mod ss -> one workgroup family; its ss column classes pj share a thread.  Class
+  // (pi, pj): outputs i = ss n + ri, j = ss q + rj;  gS = sum_{t, s} gP[n + t - padT][q + s - padL] Kf[t][s] with the
+  // flipped decimated kernel Kf[t][s] = Keff[pi + ss (A - 1 - t)][pj + ss (C - 1 - s)].  The column classes' left
+  // paddings differ by at most one: they are levelled to the largest by shifting the kernel right.
+  const int ss = m->supersample, Hs = m->height, Ws = m->width, H = Hs / ss, W = Ws / ss;
+  gl_model::CorrPlan& g = m->corr_bwd;
+  g.ST = 1;
+  g.args.n_class = ss; g.args.ncj = ss; g.args.Hi = H; g.args.Wi = W; g.args.Hout = Hs; g.args.Wout = Ws; g.args.os = ss;
+  int Cn[4], rjn[4], pln[4], max_pl = -(1 << 30), width = 1;
+  for (int pj = 0; pj < ss; ++pj) {
+    Cn[pj] = m->KW > pj ? (m->KW - pj + ss - 1) / ss : 0;
+    rjn[pj] = ((pj - m->pad_l) % ss + ss) % ss;
+    pln[pj] = (Cn[pj] - 1) - (rjn[pj] + m->pad_l - pj) / ss;
+    max_pl = std::max(max_pl, pln[pj]);
+  }
+  for (int pj = 0; pj < ss; ++pj) width = std::max(width, Cn[pj] + (max_pl - pln[pj]));
+  g.KWP = pad4(width);
+  // column classes ordered by their output offset, so Wo[0] is the largest
+  int order[4];
+  for (int pj = 0; pj < ss; ++pj) order[rjn[pj]] = pj;
+  for (int pi = 0; pi < ss; ++pi) {
+    const int A = m->KH > pi ? (m->KH - pi + ss - 1) / ss : 0;
+    const int ri = ((pi - m->pad_t) % ss + ss) % ss;
+    CorrClass c{};
+    c.koff = (int)kbuf.size();
+    c.KH = A;
+    c.pt = (A - 1) - (ri + m->pad_t - pi) / ss;
+    c.pl = max_pl;
+    c.Ho = ri < Hs ? (Hs - ri + ss - 1) / ss : 0;
+    c.oo_r = ri;
+    kbuf.resize(kbuf.size() + (size_t)A * ss * g.KWP, 0.f);
+    for (int jj = 0; jj < ss; ++jj) {
+      const int pj = order[jj], C = Cn[pj], sh = max_pl - pln[pj];
+      c.Wo[jj] = rjn[pj] < Ws ? (Ws - rjn[pj] + ss - 1) / ss : 0;
+      c.oo_c[jj] = rjn[pj];
+      for (int t = 0; t < A; ++t)
+        for (int q = 0; q < C; ++q)
+          kbuf[(size_t)c.koff + ((size_t)t * ss + jj) * g.KWP + sh + q] =
+              (float)keff[(size_t)(pi + ss * (A - 1 - t)) * m->KW + (pj + ss * (C - 1 - q))];
+    }
+    g.args.cls[pi] = c;
+    g.max_Ho = std::max(g.max_Ho, c.Ho); g.max_Wo = std::max(g.max_Wo, c.Wo[0]); g.max_KH = std::max(g.max_KH, c.KH);
+  }
+  g.ok = true;
+}
+
+// PSF and pooling: the effective kernel flip(psf) (*) box(ss)/ss^2 of the tap kernels and, where it serves, the pair kernel's plans
+int build_post(gl_model* m, const gl_grid* grid, const Knobs& k) {
+  m->has_post = grid->psf != nullptr || grid->supersample != 1;
+  if (!m->has_post) return GL_OK;
+  // flat = flip(psf) cross-correlated with SAME padding (tf/simulator.py:62-70,145-147), then box(ss)/ss^2 pooling
+  const int kh = grid->psf ? grid->psf_h : 1, kw = grid->psf ? grid->psf_w : 1, ss = grid->supersample;
+  m->psf_h = kh;
+  m->psf_w = kw;
+  m->KH = kh + ss - 1;
+  m->KW = kw + ss - 1;
+  m->pad_t = (kh - 1) / 2;
+  m->pad_l = (kw - 1) / 2;
+  std::vector<double> keff((size_t)m->KH * m->KW, 0.0);
+  for (int u = 0; u < kh; ++u)
+    for (int v = 0; v < kw; ++v) {
+      double f = grid->psf ? (double)grid->psf[(size_t)(kh - 1 - u) * kw + (kw - 1 - v)] : 1.0;
+      for (int a2 = 0; a2 < ss; ++a2)
+        for (int c2 = 0; c2 < ss; ++c2) keff[(size_t)(u + a2) * m->KW + (v + c2)] += f / (double)(ss * ss);
+    }
+  std::vector<float> kf(keff.begin(), keff.end());
+  if (int rc = put(m->d_psf, kf.data(), kf.size())) return rc;
+  if (k.corr_pair && ss <= 2 && m->KW <= 32 && m->KH <= 64) {
+    std::vector<float> kbuf;
+    plan_corr_fwd(m, keff, kbuf);
+    plan_corr_bwd(m, keff, kbuf);
+    if (int rc = put(m->d_corr_k, kbuf.data(), kbuf.size())) return rc;
+    m->corr_fwd.args.k = m->corr_bwd.args.k = m->d_corr_k;
+  }
+  return GL_OK;
+}
+}  // namespace
+
 extern "C" {
 
 const char* gl_last_error(void) { return g_err; }
@@ -581,367 +1011,34 @@ int gl_model_create_user(const gl_component* comps, int n_lens, int n_lens_light
   if (!out) return fail(GL_EINVAL, "out is null");
   if (n_bodies < 0 || (n_bodies > 0 && !bodies)) return fail(GL_EINVAL, "bad user bodies");
   *out = nullptr;
-  if (!grid) return fail(GL_EINVAL, "grid is null");
-  if (n_lens < 0 || n_lens_light < 0 || n_src < 0) return fail(GL_EINVAL, "negative component count");
-  int n_comp = n_lens + n_lens_light + n_src;
-  if (n_comp > 0 && !comps) return fail(GL_EINVAL, "comps is null");
-  if (grid->height <= 0 || grid->width <= 0 || grid->n_region <= 0) return fail(GL_EINVAL, "empty grid");
-  if (!grid->grid_x || !grid->grid_y) return fail(GL_EINVAL, "grid_x / grid_y is null");
-  if (grid->supersample < 1) return fail(GL_EINVAL, "supersample must be >= 1");
-  if (grid->height % grid->supersample || grid->width % grid->supersample)
-    return fail(GL_EINVAL, "grid size not a multiple of supersample");
-  if ((long long)grid->n_region > (long long)grid->height * grid->width)
-    return fail(GL_EINVAL, "n_region exceeds height*width");
-  if (!grid->pix_index && (long long)grid->n_region != (long long)grid->height * grid->width)
-    return fail(GL_EINVAL, "pix_index is required when n_region != height*width");
-  if (grid->psf && (grid->psf_h <= 0 || grid->psf_w <= 0)) return fail(GL_EINVAL, "bad PSF shape");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GL_ENODEVICE, "no HIP device available");
-
-  gl_model* m = new (std::nothrow) gl_model();
+  int rc;
+  if ((rc = check_create_args(comps, n_lens, n_lens_light, n_src, grid))) return rc;
+  // (the deleter is gl_model_destroy: every early return below leaves nothing behind)
+  std::unique_ptr<gl_model, ModelDeleter> m(new (std::nothrow) gl_model());
   if (!m) return fail(GL_ENOMEM, "host allocation failed");
   m->n_lens = n_lens;
   m->n_ll = n_lens_light;
   m->n_src = n_src;
-  int p_off = 0, d_off = 0, a_off = NSTAT, sh_nmax = -1;
-  for (int i = 0; i < n_comp; ++i) {
-    const gl_component& c = comps[i];
-    const bool mass = i < n_lens;
-    const bool is_mass_kind = (c.kind >= GL_EPL && c.kind <= GL_TNFW) || c.kind == GL_USER_MASS;
-    const bool is_light_kind = (c.kind >= GL_SERSIC && c.kind <= GL_CORE_SERSIC) || c.kind == GL_USER_LIGHT;
-    if ((mass && !is_mass_kind) || (!mass && !is_light_kind)) {
-      delete m;
-      return fail(GL_EINVAL, "component %d: kind %d is not a %s profile", i, c.kind, mass ? "mass" : "light");
-    }
-    int iparam = c.iparam;
-    if (c.kind == GL_USER_MASS || c.kind == GL_USER_LIGHT) {
-      if (iparam < 0 || iparam > USER_MAXP || (int)c.flags >= n_bodies || !bodies[c.flags]) {
-        delete m;
-        return fail(GL_EINVAL, "component %d: a user-written profile takes 0..%d parameters and the index of its body (got %d parameters, "
-                               "body %u of %d)", i, USER_MAXP, iparam, c.flags, n_bodies);
-      }
-      m->has_user = true;
-    }
-    if (c.kind == GL_EPL) {
-      if (iparam <= 0) iparam = 50;  // epl.py:15
-      if (iparam > 1000) { delete m; return fail(GL_EINVAL, "EPL niter %d too large", iparam); }
-    }
-    if (c.kind == GL_EPL) { m->epl_comp = m->has_epl ? -2 : i; m->has_epl = true; }
-    if (c.kind >= GL_DPIS && c.kind <= GL_SERIES) m->fam = std::max(m->fam, 1);
-    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC) m->fam = 2;
-    if (c.kind == GL_SERIES && (iparam < 0 || iparam > SERIES_MAX_ORDER)) {
-      delete m;
-      return fail(GL_EINVAL, "component %d: series order %d outside [0, %d]", i, iparam, SERIES_MAX_ORDER);
-    }
-    if (c.kind == GL_SCALED) {
-      if (iparam < 1 || iparam > 3) { delete m; return fail(GL_EINVAL, "component %d: GL_SCALED takes 1..3 scales, got %d", i, iparam); }
-      ++m->n_scaled;
-    }
-    if (c.kind == GL_SHAPELETS) {
-      if (iparam < 0 || iparam > GL_SHAPELETS_NMAX_CAP) {
-        delete m;
-        return fail(GL_EUNSUPPORTED, "shapelets n_max=%d outside [0,%d]", iparam, GL_SHAPELETS_NMAX_CAP);
-      }
-      m->has_shapelets = true;
-      if (iparam > SH_CAP) m->shp_big = true;
-      if (c.flags & GL_FLAG_SHAPELETS_INTERPOLATE) { m->has_table = true; sh_nmax = std::max(sh_nmax, iparam); }
-    }
-    CompDesc cd{};
-    cd.kind = c.kind;
-    cd.iparam = iparam;
-    cd.flags = c.flags;
-    cd.p_off = p_off;
-    cd.d_off = d_off;
-    cd.a_off = a_off;
-    cd.n_par = kind_num_params(c.kind, iparam);
-    cd.n_acc = kind_num_acc(c.kind, iparam);
-    if (c.kind == GL_SCALED) cd.iparam = -1;  // catalogue slot, set by gl_model_set_catalogue
-    if (c.kind == GL_SERIES) {
-      cd.flags = (unsigned)m->n_series++;
-      m->series.push_back(SeriesDev{nullptr, nullptr, 0.f, iparam});
-      m->series_comp.push_back(i);
-    }
-    cd.lin_off = (int)m->lin_cols.size();
-    for (int k = 0; k < kind_num_linear(c.kind, iparam); ++k) m->lin_cols.push_back(p_off + kind_linear_col(c.kind, iparam) + k);
-    // a user-written light whose last parameter is declared the linear amplitude (gl_component::reserved): one basis image
-    if (c.kind == GL_USER_LIGHT && c.reserved == 1 && iparam >= 1) m->lin_cols.push_back(p_off + iparam - 1);
-    p_off += cd.n_par;
-    d_off += (kind_num_derived(c.kind, iparam) + 3) & ~3;
-    a_off += cd.n_acc;
-    m->comps.push_back(cd);
-  }
-  m->P = p_off;
-  for (int i = 0; i < n_lens; ++i) m->lens_params += m->comps[i].n_par;
-  m->D = std::max(d_off, 4);
-  m->A = a_off;
-  m->Apad = a_off | 1;  // odd: the 16 leader lanes of a wave land on 16 different LDS banks
-  for (int i = 0; i < n_lens; ++i) m->has_nfw = m->has_nfw || m->comps[i].kind == K_NFW;
-  m->nfw_lds = m->has_nfw ? sizeof(float) * 2 * glh::kNfwNodes : 0;  // the h(X) table rides in every main kernel's LDS
-  m->ncols = ((size_t)(((m->D + 3) & ~3) + 64 * m->Apad) * sizeof(float) + m->nfw_lds <= 60 * 1024) ? 64 : 16;
+  if ((rc = build_components(m.get(), comps, n_lens + n_lens_light + n_src, bodies, n_bodies))) return rc;
   m->height = grid->height;
   m->width = grid->width;
   m->supersample = grid->supersample;
   m->N = grid->n_region;
   m->conversion_factor = grid->conversion_factor;
-  {
-    int t = env_int("GIGALENS_HIP_TILE", 0);
-    m->tile = (t == 4 || t == 1) ? t : 2;
-    int tg = env_int("GIGALENS_HIP_TILE_GRAD", t ? t : 0);
-    m->tile_grad = (tg == 4 || tg == 1 || tg == 2) ? tg : 0;
-  }
-  m->static_id = env_int("GIGALENS_HIP_STATIC", 1) ? match_static(m) : 0;
-  if (m->has_user) {  // the run-time compiled interpreter serves the whole model
-    m->static_id = 0;
-    if (m->shp_big) { delete m; return fail(GL_EUNSUPPORTED, "user-written profiles beside shapelets with n_max > %d", SH_CAP); }
-  }
-  if (m->shp_big) {  // orders above SH_CAP: the runtime-order interpreter variant only (compiled for the basic profile families)
-    m->static_id = 0;
-    if (m->fam) {
-      delete m;
-      return fail(GL_EUNSUPPORTED, "shapelets with n_max > %d are served together with EPL / SIE / NFW / Shear / SIS lenses and Sersic "
-                                   "lights only (this model also holds dPIE-family, catalogue, series or extended profiles)", SH_CAP);
-    }
-  }
-  m->static_variant = env_int("GIGALENS_HIP_STATIC_VARIANT", 0);
-  m->pair = env_int("GIGALENS_HIP_PAIR", 1);
-  if (m->pair && m->static_id) {
-    // the pair kernels' epilogue addresses the accumulator row in closed form: [NSTAT | components in order, static_nacc each]
-    int off = NSTAT;
-    bool ok_row = true;
-    for (int i = 0; i < n_comp; ++i) {
-      ok_row = ok_row && m->comps[i].a_off == off;
-      off += static_nacc(m->comps[i].kind);
-    }
-    if (!ok_row || off != m->A) m->pair = 0;
-  }
-  // gl_shp.hip.h addresses the row as [NSTAT | lenses | lens lights | shapelet] in closed form and needs a table-mode model's pair table
-  {
-    int off = NSTAT;
-    bool ok_row = true;
-    for (int i = 0; i < n_comp; ++i) {
-      ok_row = ok_row && m->comps[i].a_off == off;
-      off += static_nacc(m->comps[i].kind);
-    }
-    m->shp_kernel = env_int("GIGALENS_HIP_SHP", 1) && env_int("GIGALENS_HIP_PAIR", 1) && m->static_id && ok_row && n_src == 1 &&
-                    m->comps.back().kind == K_SHAPELETS;
-  }
-  m->light_spherical = n_comp > n_lens;
-  for (int i = n_lens; i < n_comp; ++i) m->light_spherical = m->light_spherical && m->comps[i].kind == K_SERSIC;
-  if (!m->tile_grad) m->tile_grad = m->static_id ? 1 : 2;  // measured: T=1 wins once the VJP state lives in registers
-  if (!m->static_id) {  // the interpreter kernel is built for T = 2 and 4
-    const bool env_tile = env_int("GIGALENS_HIP_TILE", 0) != 0;
-    if (!env_tile && !m->has_epl && !m->has_shapelets && !m->fam) m->tile = 4;  // cheap profiles, forward modes: amortise the per-tile work
-    if (m->tile == 1) m->tile = 2;
-    if (m->tile_grad == 1) m->tile_grad = 2;
-  }
-  if (env_int("GIGALENS_HIP_CLUSTER", 1) && !m->static_id && !m->has_user && n_lens_light == 0 && n_lens >= 1 && n_lens <= 8 && n_src >= 1 &&
-      n_src <= 20 && (size_t)64 * m->Apad * sizeof(float) <= 64 * 1024) {
-    bool ok_c = true, ell = false;
-    for (int i = 0; i < n_lens; ++i) ok_c = ok_c && m->comps[i].kind == K_NFW;
-    for (int i = n_lens; i < n_comp; ++i) {
-      ok_c = ok_c && (m->comps[i].kind == K_SERSIC || m->comps[i].kind == K_SERSIC_ELLIPSE);
-      ell = ell || m->comps[i].kind == K_SERSIC_ELLIPSE;
-    }
-    // the kernel addresses the derived / accumulator blocks in closed form: component-major, fixed block sizes
-    constexpr int NFWP = (NFW_ND + 3) & ~3, SERP = (SER_NDX + 3) & ~3;  // the strides gl_cluster_kernel walks the derived row with
-    for (int i = 0; i < n_lens && ok_c; ++i) ok_c = m->comps[i].d_off == NFWP * i && m->comps[i].a_off == NSTAT + NFW_NACC * i;
-    for (int i = 0; i < n_src && ok_c; ++i)
-      ok_c = m->comps[n_lens + i].d_off == NFWP * n_lens + SERP * i && m->comps[n_lens + i].a_off == NSTAT + NFW_NACC * n_lens + SER_NACC * i;
-    ok_c = ok_c && (size_t)64 * m->Apad * sizeof(float) + sizeof(float) * 2 * glh::kNfwNodes <= 64 * 1024;
-    if (ok_c) m->cluster = ell ? 2 : 1;
-    // ... in its component-per-wave form (gl_clusterw.hip.h) when the model fills at least 60 % of the component slots of the
-    // instantiation that holds it (4 waves x (1 + 2), (2 + 3) or (2 + 5) halos + sources): an unused slot is evaluated all the same.
-    // GIGALENS_HIP_CLUSTER: 1 = the pixel-split kernel for every cluster model, 2 = the component-per-wave kernel for every one
-    if (m->cluster) {
-      const int cap = (n_lens <= 4 && n_src <= 8) ? 12 : (n_src <= 12 ? 20 : 28);
-      const int mode = env_int("GIGALENS_HIP_CLUSTER", -1);
-      m->cluster_w = mode == 2 || (mode != 1 && 10 * (n_lens + n_src) >= 6 * cap);
-    }
-  }
-  m->target_wgs = std::max(1, env_int("GIGALENS_HIP_TARGET_WGS", 2048));
-  m->target_wgs_set = getenv("GIGALENS_HIP_TARGET_WGS") != nullptr;
-  m->use_order = env_int("GIGALENS_HIP_ORDER", 1) != 0;
-  m->order_fused = env_int("GIGALENS_HIP_ORDER_FUSED", 1) != 0;  // tests: 0 = the sort as a launch of its own (gl_order_kernel)
-  m->prep_lds = env_int("GIGALENS_HIP_PREP_LDS", 1) != 0;  // tests: 0 = the front end reads the parameter row back from global memory
-  m->tail_rows = env_int("GIGALENS_HIP_TAIL_ROWS", -1);  // -1: twice the chunks; 0: no tapered end; n: n workgroups per tail sample
-  m->tail_n = env_int("GIGALENS_HIP_TAIL_N", -1);        // -1: the remainder beyond whole rounds; n: the last n samples
-#ifdef GL_EXPERIMENTS
-  // dissection builds only (hipcc -DGL_EXPERIMENTS; never __graft_entry__.build()): work-skipping flags and a raw chunk size
-  m->chunk_px_override = env_int("GIGALENS_HIP_CHUNK_PX", 0);
-  m->dbg_flags = env_int("GIGALENS_HIP_DBGFLAGS", 0);
-  if (m->chunk_px_override < 0 || m->chunk_px_override % (WG * 4) != 0) {
-    const int bad = m->chunk_px_override;
-    delete m;
-    return fail(GL_EINVAL, "GIGALENS_HIP_CHUNK_PX=%d is not a positive multiple of the tile (%d pixels)", bad, WG * 4);
-  }
-  if (m->dbg_flags || m->chunk_px_override)
-    fprintf(stderr, "libgigalens_hip: EXPERIMENT BUILD with GIGALENS_HIP_DBGFLAGS=%d GIGALENS_HIP_CHUNK_PX=%d -- results are not valid\n",
-            m->dbg_flags, m->chunk_px_override);
-#else
-  // the shipped library has no work-skipping paths: a stray dissection variable is an error, not a silently ignored hint
-  for (const char* name : {"GIGALENS_HIP_DBGFLAGS", "GIGALENS_HIP_CHUNK_PX"}) {
-    const char* v = getenv(name);
-    if (v && *v && atoi(v) != 0) {
-      delete m;
-      return fail(GL_EINVAL, "%s is set but this library was built without -DGL_EXPERIMENTS (the dissection knobs do not exist in it)", name);
-    }
-  }
-#endif
-  m->shp_cull = env_int("GIGALENS_HIP_SHP_CULL", 1);
-  m->shp_blocked = env_int("GIGALENS_HIP_SHP_BLOCKED", 1);
-  m->corr_max_pairs = env_int("GIGALENS_HIP_CORR_MAXPAIRS", 0);  // tests: force the slicing of the PSF launches (read once)
-  m->corr_wide = env_int("GIGALENS_HIP_CORR_WIDE", 1);           // 0: 8 outputs per thread in the stride-2 forward correlation as well
-  m->wave_prep = env_int("GIGALENS_HIP_WAVE_PREP", 1) != 0;
-  m->lstsq_wgs = std::max(1, env_int("GIGALENS_HIP_LSTSQ_WGS", 2048));
-  m->lstsq_chol = env_int("GIGALENS_HIP_LSTSQ_CHOL", 1) != 0;    // tests: 0 = every system through the eigenvalue solve
-  m->lstsq_fused = env_int("GIGALENS_HIP_LSTSQ_FUSED", 1) != 0;  // tests: 0 = the linear solve through the basis stack (read once)
+  const Knobs knobs = read_env_knobs(m.get());
+  if ((rc = select_kernels(m.get(), knobs))) return rc;
+  if ((rc = check_experiment_knobs(m.get()))) return rc;
   size_t shmem = (size_t)(((m->D + 3) & ~3) + m->ncols * m->Apad) * sizeof(float) + m->nfw_lds;
-  if (shmem > 64 * 1024) { delete m; return fail(GL_EUNSUPPORTED, "model needs %zu B of LDS per workgroup (> 64 KiB)", shmem); }
-
-  auto up = [&](void** dst, const void* src, size_t bytes) -> bool {
-    if (hipMalloc(dst, bytes) != hipSuccess) return false;
-    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  bool ok = true;
-  if (n_comp) ok = ok && up((void**)&m->d_comps, m->comps.data(), sizeof(CompDesc) * n_comp);
-  else ok = ok && (hipMalloc((void**)&m->d_comps, sizeof(CompDesc)) == hipSuccess);
-  ok = ok && up((void**)&m->d_gx, grid->grid_x, sizeof(float) * m->N);
-  for (int i = 0; i < m->N; ++i) m->grid_rmax = std::max(m->grid_rmax, std::hypot(grid->grid_x[i], grid->grid_y[i]));
-  ok = ok && up((void**)&m->d_gy, grid->grid_y, sizeof(float) * m->N);
-  if (!m->lin_cols.empty()) ok = ok && up((void**)&m->d_lin_cols, m->lin_cols.data(), sizeof(int) * m->lin_cols.size());
-  if (grid->pix_index) {
-    for (int i = 0; i < m->N && ok; ++i)
-      if (grid->pix_index[i] < 0 || grid->pix_index[i] >= m->height * m->width) {
-        gl_model_destroy(m);
-        return fail(GL_EINVAL, "pix_index[%d]=%d out of range", i, grid->pix_index[i]);
-      }
-    ok = ok && up((void**)&m->d_pix, grid->pix_index, sizeof(int) * m->N);
-  }
-  if (m->has_nfw) {
-    // [h(X) node table | neutral blocks | H(s) cubics]: the layout gl_clusterw_kernel addresses (CW_NEUTRAL_OFF, CW_TABS_OFF)
-    std::vector<float> tab;
-    glh::build_nfw_table([](double X, double& g, double& gp) { glp::nfw_gw<double>(X, g, gp); }, tab);
-    // behind the table: the constant blocks of an unused component slot of gl_clusterw_kernel (zero amplitude, all else finite)
-    const float neutral_nfw[4] = {0.f, 0.f, 1.f, 0.f};  // NFW_CX, NFW_CY, NFW_INVRS, NFW_K0
-    float neutral_ser[16] = {0.f};
-    neutral_ser[glp::SER_C] = neutral_ser[glp::SER_SQ] = neutral_ser[glp::SER_ISQ] = neutral_ser[glp::SER_INVRS] = 1.f;
-    neutral_ser[glp::SER_INVN] = neutral_ser[glp::SER_IRS2] = 1.f;
-    neutral_ser[glp::SER_BN] = 1.6721f;  // n = 1; SER_IE = SER_CG = 0
-    tab.insert(tab.end(), neutral_nfw, neutral_nfw + 4);
-    tab.insert(tab.end(), neutral_ser, neutral_ser + 16);
-    // ... and the table of the same function in s = X^2 (gl_host_tables.h::build_nfw_table_s), [4][kNfwSIntervals]
-    std::vector<float> tab_s;
-    glh::build_nfw_table_s([](double X, double& g, double& gp) { glp::nfw_gw<double>(X, g, gp); }, tab_s);
-    tab.insert(tab.end(), tab_s.begin(), tab_s.end());
-    ok = ok && up((void**)&m->d_nfw_tab, tab.data(), tab.size() * sizeof(float));
-  }
-  if (m->has_table) {
-    std::vector<float> tab;
-    (void)sh_nmax;  // the full n_max = 10 table (stride 12, two rows of a node pair = six aligned float4), or -- for a model with
-                    // orders above 10, whose shapelet components all run the runtime-order path -- the n_max = 20 one (stride 24)
-    glh::build_shapelet_table(m->shp_big ? SH_CAPB : SH_CAP, tab, &m->shp_stride);
-    ok = ok && up((void**)&m->d_shp_tab, tab.data(), tab.size() * sizeof(float));
-  }
-  m->has_post = grid->psf != nullptr || grid->supersample != 1;
-  if (m->has_post) {
-    // flat = flip(psf) cross-correlated with SAME padding (tf/simulator.py:62-70,145-147), then box(ss)/ss^2 pooling
-    const int kh = grid->psf ? grid->psf_h : 1, kw = grid->psf ? grid->psf_w : 1, ss = grid->supersample;
-    m->psf_h = kh;
-    m->psf_w = kw;
-    m->KH = kh + ss - 1;
-    m->KW = kw + ss - 1;
-    m->pad_t = (kh - 1) / 2;
-    m->pad_l = (kw - 1) / 2;
-    std::vector<double> keff((size_t)m->KH * m->KW, 0.0);
-    for (int u = 0; u < kh; ++u)
-      for (int v = 0; v < kw; ++v) {
-        double f = grid->psf ? (double)grid->psf[(size_t)(kh - 1 - u) * kw + (kw - 1 - v)] : 1.0;
-        for (int a2 = 0; a2 < ss; ++a2)
-          for (int c2 = 0; c2 < ss; ++c2) keff[(size_t)(u + a2) * m->KW + (v + c2)] += f / (double)(ss * ss);
-      }
-    std::vector<float> kf(keff.begin(), keff.end());
-    ok = ok && up((void**)&m->d_psf, kf.data(), sizeof(float) * kf.size());
-    // plans of the register-blocked pair kernel: forward = one class (stride ss, Keff), transpose = ss^2 residue classes
-    // (stride 1, the class's decimated and flipped sub-kernel); rows padded to a multiple of four taps
-    if (env_int("GIGALENS_HIP_CORR_PAIR", 1) && ss <= 2 && m->KW <= 32 && m->KH <= 64) {
-      const int Hs = m->height, Ws = m->width, H = Hs / ss, W = Ws / ss;
-      std::vector<float> kbuf;
-      auto pad4 = [](int n) { return std::max(4, (n + 3) & ~3); };
-      {
-        gl_model::CorrPlan& f = m->corr_fwd;
-        f.KWP = pad4(m->KW);
-        f.ST = ss;
-        CorrClass c{};
-        c.koff = 0; c.KH = m->KH; c.pt = m->pad_t; c.pl = m->pad_l; c.Ho = H; c.Wo[0] = W; c.oo_r = 0; c.oo_c[0] = 0;
-        kbuf.assign((size_t)m->KH * f.KWP, 0.f);
-        for (int u = 0; u < m->KH; ++u)
-          for (int v = 0; v < m->KW; ++v) kbuf[(size_t)u * f.KWP + v] = (float)keff[(size_t)u * m->KW + v];
-        f.args.n_class = 1; f.args.ncj = 1; f.args.Hi = Hs; f.args.Wi = Ws; f.args.Hout = H; f.args.Wout = W; f.args.os = 1;
-        f.args.cls[0] = c;
-        f.max_Ho = H; f.max_Wo = W; f.max_KH = m->KH; f.ok = true;
-      }
-      {
-        // transpose: row class pi = (i + pt) mod ss -> one workgroup family; its ss column classes pj share a thread.  Class
-        // (pi, pj): outputs i = ss n + ri, j = ss q + rj;  gS = sum_{t, s} gP[n + t - padT][q + s - padL] Kf[t][s] with the
-        // flipped decimated kernel Kf[t][s] = Keff[pi + ss (A - 1 - t)][pj + ss (C - 1 - s)].  The column classes' left
-        // paddings differ by at most one: they are levelled to the largest by shifting the kernel right.
-        gl_model::CorrPlan& g = m->corr_bwd;
-        g.ST = 1;
-        g.args.n_class = ss; g.args.ncj = ss; g.args.Hi = H; g.args.Wi = W; g.args.Hout = Hs; g.args.Wout = Ws; g.args.os = ss;
-        int Cn[4], rjn[4], pln[4], max_pl = -(1 << 30), width = 1;
-        for (int pj = 0; pj < ss; ++pj) {
-          Cn[pj] = m->KW > pj ? (m->KW - pj + ss - 1) / ss : 0;
-          rjn[pj] = ((pj - m->pad_l) % ss + ss) % ss;
-          pln[pj] = (Cn[pj] - 1) - (rjn[pj] + m->pad_l - pj) / ss;
-          max_pl = std::max(max_pl, pln[pj]);
-        }
-        for (int pj = 0; pj < ss; ++pj) width = std::max(width, Cn[pj] + (max_pl - pln[pj]));
-        g.KWP = pad4(width);
-        // column classes ordered by their output offset, so Wo[0] is the largest
-        int order[4];
-        for (int pj = 0; pj < ss; ++pj) order[rjn[pj]] = pj;
-        for (int pi = 0; pi < ss; ++pi) {
-          const int A = m->KH > pi ? (m->KH - pi + ss - 1) / ss : 0;
-          const int ri = ((pi - m->pad_t) % ss + ss) % ss;
-          CorrClass c{};
-          c.koff = (int)kbuf.size();
-          c.KH = A;
-          c.pt = (A - 1) - (ri + m->pad_t - pi) / ss;
-          c.pl = max_pl;
-          c.Ho = ri < Hs ? (Hs - ri + ss - 1) / ss : 0;
-          c.oo_r = ri;
-          kbuf.resize(kbuf.size() + (size_t)A * ss * g.KWP, 0.f);
-          for (int jj = 0; jj < ss; ++jj) {
-            const int pj = order[jj], C = Cn[pj], sh = max_pl - pln[pj];
-            c.Wo[jj] = rjn[pj] < Ws ? (Ws - rjn[pj] + ss - 1) / ss : 0;
-            c.oo_c[jj] = rjn[pj];
-            for (int t = 0; t < A; ++t)
-              for (int q = 0; q < C; ++q)
-                kbuf[(size_t)c.koff + ((size_t)t * ss + jj) * g.KWP + sh + q] =
-                    (float)keff[(size_t)(pi + ss * (A - 1 - t)) * m->KW + (pj + ss * (C - 1 - q))];
-          }
-          g.args.cls[pi] = c;
-          g.max_Ho = std::max(g.max_Ho, c.Ho); g.max_Wo = std::max(g.max_Wo, c.Wo[0]); g.max_KH = std::max(g.max_KH, c.KH);
-        }
-        g.ok = true;
-      }
-      ok = ok && up((void**)&m->d_corr_k, kbuf.data(), sizeof(float) * kbuf.size());
-      m->corr_fwd.args.k = m->corr_bwd.args.k = m->d_corr_k;
-    }
-  }
-  if (!ok) {
-    gl_model_destroy(m);
-    return fail(GL_ENOMEM, "device allocation / upload failed in gl_model_create");
-  }
+  if (shmem > 64 * 1024) return fail(GL_EUNSUPPORTED, "model needs %zu B of LDS per workgroup (> 64 KiB)", shmem);
+  if ((rc = upload_grid(m.get(), grid))) return rc;
+  if ((rc = upload_tables(m.get()))) return rc;
+  if ((rc = build_post(m.get(), grid, knobs))) return rc;
   if (m->has_user) {  // the interpreter kernel with the user's bodies inside, compiled now (a few seconds, once per model)
     m->tile = 2;
     m->tile_grad = 2;
-    if (int rc = compile_user_model(m, bodies, n_bodies)) {
-      gl_model_destroy(m);
-      return rc;
-    }
+    if ((rc = compile_user_model(m.get(), bodies, n_bodies))) return rc;
   }
-  *out = m;
+  *out = m.release();
   return GL_OK;
 }
 
@@ -1038,45 +1135,20 @@ int gl_post_apply(const gl_model* m, int B, const float* in, float* out, int tra
 
 int gl_model_launch_shape(const gl_model* m, int B, int* chunk_px, int* n_chunks, int* row_floats, size_t* partial_offset_bytes) {
   if (!m || B < 1) return fail(GL_EINVAL, "bad argument");
-  int chunk = 0, nc = 0;
-  chunking(m, B, &chunk, &nc);
-  const Workspace w = carve(m, B, nullptr);
-  int tail_from, n_rows;
-  tail_plan(m, B, nc, &tail_from, &n_rows);
-  if (chunk_px) *chunk_px = chunk;
-  if (n_chunks) *n_chunks = n_rows;  // partial rows a sample owns (the chunks, or the workgroups of a tail sample if more: tail_plan)
+  const LaunchPlan plan = launch_plan(m, B);
+  const Workspace w = carve(m, B, nullptr, plan);
+  if (chunk_px) *chunk_px = plan.chunk;
+  if (n_chunks) *n_chunks = plan.n_rows;  // partial rows a sample owns (the chunks, or the workgroups of a tail sample if more: tail_plan)
   if (row_floats) *row_floats = m->A;
   if (partial_offset_bytes) *partial_offset_bytes = (size_t)((const char*)w.partial - (const char*)nullptr);
   return GL_OK;
 }
 
-void gl_model_destroy(gl_model* m) {
+void gl_model_destroy(gl_model* m) {  // (the device buffers go with their owners: glk::DevBuf)
   if (!m) return;
   if (m->user_module) (void)hipModuleUnload(m->user_module);
   if (m->user_point_module) (void)hipModuleUnload(m->user_point_module);
   for (hipEvent_t e : m->evs) (void)hipEventDestroy(e);
-  if (m->d_comps) (void)hipFree(m->d_comps);
-  if (m->d_gx) (void)hipFree(m->d_gx);
-  if (m->d_gy) (void)hipFree(m->d_gy);
-  if (m->d_pix) (void)hipFree(m->d_pix);
-  if (m->d_shp_tab) (void)hipFree(m->d_shp_tab);
-  if (m->d_nfw_tab) (void)hipFree(m->d_nfw_tab);
-  if (m->d_corr_k) (void)hipFree(m->d_corr_k);
-  if (m->d_psf) (void)hipFree(m->d_psf);
-  if (m->d_pos) (void)hipFree(m->d_pos);
-  if (m->d_fam) (void)hipFree(m->d_fam);
-  if (m->d_zcols) (void)hipFree(m->d_zcols);
-  if (m->d_src) (void)hipFree(m->d_src);
-  if (m->d_const) (void)hipFree(m->d_const);
-  if (m->d_lin_cols) (void)hipFree(m->d_lin_cols);
-  for (auto& sv : m->series) {
-    if (sv.coef) (void)hipFree((void*)sv.coef);
-    if (sv.hcoef) (void)hipFree((void*)sv.hcoef);
-  }
-  if (m->d_series) (void)hipFree(m->d_series);
-  if (m->d_cats) (void)hipFree(m->d_cats);
-  if (m->d_gal_table) (void)hipFree(m->d_gal_table);
-  if (m->d_gal_static) (void)hipFree(m->d_gal_static);
   delete m;
 }
 
@@ -1090,64 +1162,46 @@ int64_t gl_model_num_pixels(const gl_model* m) { return m ? m->N : fail(GL_EINVA
 
 size_t gl_workspace_bytes(const gl_model* m, int B) {
   if (!m || B <= 0) return 0;
-  return carve(m, B, nullptr).bytes;
+  return carve(m, B, nullptr, launch_plan(m, B)).bytes;
 }
 
 int gl_simulate_fwd(const gl_model* m, const float* params, int B, float* img, void* workspace,
                     size_t workspace_bytes, void* hip_stream) {
-  int rc = check_call(m, params, B, workspace, workspace_bytes);
-  if (rc) return rc;
-  if (!img) return fail(GL_EINVAL, "img is null");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  Workspace w = carve(m, B, workspace);
-  int chunk, n_chunks;
-  chunking(m, B, &chunk, &n_chunks);
-  if ((rc = run_prep(m, params, B, w, stream))) return rc;
-  MainArgs a = base_args(m, w, chunk);
-  if ((rc = run_order(m, B, w, &a, stream))) return rc;
-  if (m->has_post) {
-    if ((rc = render_ss(m, a, B, n_chunks, w, stream))) return rc;
-    return post_fwd(m, B, w.img_ss, img, stream, m->conversion_factor);
-  }
-  if (m->d_pix) GL_HIP(hipMemsetAsync(img, 0, sizeof(float) * (size_t)B * m->height * m->width, stream));
-  a.img = img;
-  return launch_main<IMG_FWD>(m, a, B, n_chunks, stream);
+  return gl_simulate_parts_fwd(m, params, B, 7u, img, workspace, workspace_bytes, hip_stream);  // every part
 }
 
 int gl_simulate_parts_fwd(const gl_model* m, const float* params, int B, unsigned parts, float* img, void* workspace,
                           size_t workspace_bytes, void* hip_stream) {
-  int rc = check_call(m, params, B, workspace, workspace_bytes);
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
   if (rc) return rc;
   if (!img) return fail(GL_EINVAL, "img is null");
   if (parts == 0 || parts > 7u) return fail(GL_EINVAL, "parts must be a non-empty subset of {1,2,4}");
   hipStream_t stream = (hipStream_t)hip_stream;
-  Workspace w = carve(m, B, workspace);
-  int chunk, n_chunks;
-  chunking(m, B, &chunk, &n_chunks);
-  if ((rc = run_prep(m, params, B, w, stream))) return rc;
-  MainArgs a = base_args(m, w, chunk);
+  if ((rc = run_prep(m, params, nullptr, B, plan, w, stream))) return rc;
+  MainArgs a = base_args(m, w, plan.chunk);
   a.parts = parts;
   if ((rc = run_order(m, B, w, &a, stream))) return rc;
   if (m->has_post) {
-    if ((rc = render_ss(m, a, B, n_chunks, w, stream))) return rc;
+    if ((rc = render_ss(m, a, B, plan.n_chunks, w, stream))) return rc;
     return post_fwd(m, B, w.img_ss, img, stream, m->conversion_factor);
   }
   if (m->d_pix) GL_HIP(hipMemsetAsync(img, 0, sizeof(float) * (size_t)B * m->height * m->width, stream));
   a.img = img;
-  return launch_main<IMG_FWD>(m, a, B, n_chunks, stream);
+  return launch_main<IMG_FWD>(m, a, B, plan.n_chunks, stream);
 }
 
 int gl_simulate_bwd(const gl_model* m, const float* params, const float* grad_img, int B, float* grad_params,
                     void* workspace, size_t workspace_bytes, void* hip_stream) {
-  int rc = check_call(m, params, B, workspace, workspace_bytes);
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
   if (rc) return rc;
   if (!grad_img || !grad_params) return fail(GL_EINVAL, "grad_img / grad_params is null");
   hipStream_t stream = (hipStream_t)hip_stream;
-  Workspace w = carve(m, B, workspace);
-  int chunk, n_chunks;
-  chunking(m, B, &chunk, &n_chunks);
-  if ((rc = run_prep(m, params, B, w, stream))) return rc;
-  MainArgs a = base_args(m, w, chunk);
+  if ((rc = run_prep(m, params, nullptr, B, plan, w, stream))) return rc;
+  MainArgs a = base_args(m, w, plan.chunk);
   a.gimg = grad_img;
   if (m->has_post) {
     if ((rc = post_bwd(m, B, grad_img, w.img_ss, stream, m->conversion_factor))) return rc;
@@ -1155,27 +1209,26 @@ int gl_simulate_bwd(const gl_model* m, const float* params, const float* grad_im
     a.out_scale = 1.f;
   }
   if ((rc = run_order(m, B, w, &a, stream))) return rc;
-  if ((rc = launch_main<IMG_BWD>(m, a, B, n_chunks, stream))) return rc;
-  return run_finalize(m, params, B, n_chunks, w, nullptr, nullptr, grad_params, stream);
+  if ((rc = launch_main<IMG_BWD>(m, a, B, plan.n_chunks, stream))) return rc;
+  return run_finalize(m, params, B, plan.n_chunks, w, nullptr, nullptr, grad_params, stream);
 }
 
 int gl_loglike_fwd_bwd(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
                        const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
                        float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  int rc = check_call(m, params, B, workspace, workspace_bytes);
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
   if (rc) return rc;
   if (!obs || !loglike || !chi2) return fail(GL_EINVAL, "obs / loglike / chi2 is null");
   hipStream_t stream = (hipStream_t)hip_stream;
-  Workspace w = carve(m, B, workspace);
-  int chunk, n_chunks;
-  chunking(m, B, &chunk, &n_chunks);
-  if ((rc = run_prep(m, params, B, w, stream))) return rc;
+  if ((rc = run_prep(m, params, nullptr, B, plan, w, stream))) return rc;
   const float* extra = nullptr;
-  int use_partial = 1;
-  if ((rc = run_likelihood(m, B, w, chunk, n_chunks, obs, err_or_null, mask_or_null, bg_rms, exp_time,
-                           grad_params_or_null != nullptr, stream, &extra, &use_partial, &n_chunks)))
+  int use_partial = 1, fin_rows = plan.n_chunks;
+  if ((rc = run_likelihood(m, B, plan, w, obs, err_or_null, mask_or_null, bg_rms, exp_time,
+                           grad_params_or_null != nullptr, stream, &extra, &use_partial, &fin_rows)))
     return rc;
-  return run_finalize(m, params, B, n_chunks, w, loglike, chi2, grad_params_or_null, stream, nullptr, nullptr, nullptr,
+  return run_finalize(m, params, B, fin_rows, w, loglike, chi2, grad_params_or_null, stream, nullptr, nullptr, nullptr,
                       1.f, extra, use_partial);
 }
 
@@ -1188,14 +1241,14 @@ int gl_model_linear_column(const gl_model* m, int k) {
 
 size_t gl_lstsq_workspace_bytes(const gl_model* m, int B) {
   if (!m || B <= 0) return 0;
-  return carve_lstsq(m, B, nullptr, align_up(carve(m, B, nullptr).bytes, 256)).bytes;
+  return carve_lstsq(m, B, nullptr, carve(m, B, nullptr, launch_plan(m, B))).bytes;
 }
 
 int gl_lstsq_solve_flags(const gl_model* m, int B, size_t* offset_bytes) {
   if (!m || B <= 0 || !offset_bytes) return fail(GL_EINVAL, "bad argument");
   if ((int)m->lin_cols.size() > LS_LDS_MAXN || !m->lstsq_chol)
     return fail(GL_EUNSUPPORTED, "no Cholesky attempt for this model: every system goes through the eigenvalue solve");
-  const LstsqWs lw = carve_lstsq(m, B, nullptr, align_up(carve(m, B, nullptr).bytes, 256));
+  const LstsqWs lw = carve_lstsq(m, B, nullptr, carve(m, B, nullptr, launch_plan(m, B)));
   *offset_bytes = (size_t)((const char*)lw.todo - (const char*)nullptr);
   return GL_OK;
 }
@@ -1209,27 +1262,26 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
   if (D == 0) return fail(GL_EINVAL, "the model has no linear (light amplitude) coefficients");
   if (!params || !workspace) return fail(GL_EINVAL, "params / workspace is null");
   if (B <= 0 || B > 65535) return fail(GL_EINVAL, "batch size %d outside [1, 65535]", B);
-  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
-  if (m->n_series_set != m->n_series) return fail(GL_EINVAL, "GL_SERIES component without a coefficient field");
+  if (int rc = check_ready(m, true, false)) return rc;
   const bool solve = coeffs_or_null || image_or_null;
   if (solve && D > LS_MAXN)  // the basis stack alone (return_stacked) is served at any depth
     return fail(GL_EUNSUPPORTED, "%d linear coefficients exceed the %d the solve serves", D, LS_MAXN);
   if (solve && (!obs || !err)) return fail(GL_EINVAL, "obs / err_map are required to solve for the coefficients");
   if (!solve && !stacked_or_null) return fail(GL_EINVAL, "nothing to compute");
   if (!(parts & (GL_PART_LENS_LIGHT | GL_PART_SOURCE_LIGHT)) || parts > 7u) return fail(GL_EINVAL, "bad parts");
-  const size_t need = gl_lstsq_workspace_bytes(m, B);
-  if (workspace_bytes < need) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  const LaunchPlan plan = launch_plan(m, B);
+  const Workspace w = carve(m, B, workspace, plan);
+  LstsqWs lw = carve_lstsq(m, B, workspace, w);
+  if (workspace_bytes < lw.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lw.bytes);
   hipStream_t stream = (hipStream_t)hip_stream;
-  Workspace w = carve(m, B, workspace);
-  LstsqWs lw = carve_lstsq(m, B, workspace, align_up(w.bytes, 256));
-  int chunk, n_chunks, rc;
-  chunking(m, B, &chunk, &n_chunks);
+  const int chunk = plan.chunk, n_chunks = plan.n_chunks;
+  int rc;
   const int HW = (m->height / m->supersample) * (m->width / m->supersample);
   // unit amplitudes -> derived constants -> basis stack
   hipLaunchKernelGGL(gl_unit_amplitudes_kernel, dim3((unsigned)(((long long)B * m->P + 255) / 256)), dim3(256), 0,
                      stream, params, m->P, B, m->d_lin_cols, D, w.params);
   GL_HIP(hipGetLastError());
-  if ((rc = run_prep(m, w.params, B, w, stream))) return rc;
+  if ((rc = run_prep(m, w.params, nullptr, B, plan, w, stream))) return rc;
   MainArgs a = base_args(m, w, chunk);
   a.parts = parts | GL_PART_LENS_LIGHT | GL_PART_SOURCE_LIGHT;
   a.n_lin = D;
@@ -1327,13 +1379,8 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
   if (D <= LS_LDS_MAXN && m->lstsq_chol) {  // the inverse when the pseudo-inverse's cut is provably idle (gl_chol_solve_kernel)
     const int nb = D + 1 <= 64 ? 4 : D + 1 <= 80 ? 5 : 8;
     const size_t sm = sizeof(float) * ((size_t)(D + 2) * (16 * nb + 1) + 4);
-    if (sm > 64 * 1024) {
-      static bool raised = false;
-      if (!raised) {
-        GL_HIP(hipFuncSetAttribute((const void*)&gl_chol_solve_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-      }
-    }
+    static bool chol_raised = false;
+    if (sm > 64 * 1024 && (rc = raise_lds_limit((const void*)&gl_chol_solve_kernel<8>, &chol_raised))) return rc;
 #define GL_CHOL(NB_) hipLaunchKernelGGL((gl_chol_solve_kernel<NB_>), dim3(B), dim3(256), sm, stream, lw.partial, lw.n_chunks, n_sum, D, \
                                         lw.Dp, 1e-6f, coeffs, lw.todo)
     if (nb == 4) GL_CHOL(4); else if (nb == 5) GL_CHOL(5); else GL_CHOL(8);
@@ -1343,13 +1390,8 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
   }
   if (D <= LS_LDS_MAXN) {  // A and V in LDS: up to 129 KB of the CU's 160 (above 64 KB the kernel has to be told once)
     const size_t sm = sizeof(float) * ((size_t)2 * D * (D | 1) + 8 * D + 8);
-    if (sm > 64 * 1024) {
-      static bool raised = false;
-      if (!raised) {
-        GL_HIP(hipFuncSetAttribute((const void*)&gl_eigh_solve_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-      }
-    }
+    static bool eigh_raised = false;
+    if (sm > 64 * 1024 && (rc = raise_lds_limit((const void*)&gl_eigh_solve_kernel<2, false>, &eigh_raised))) return rc;
     hipLaunchKernelGGL((gl_eigh_solve_kernel<2, false>), dim3(B), dim3(64), sm, stream, lw.partial, lw.n_chunks, n_sum, D, lw.Dp,
                        1e-6f, coeffs, (float*)nullptr, todo);
   } else {  // the two matrices in the workspace (L2), the vectors in LDS; four registers hold the tridiagonal
@@ -1364,7 +1406,7 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
     hipLaunchKernelGGL(gl_set_amplitudes_kernel, dim3((unsigned)(((long long)B * m->P + 255) / 256)), dim3(256), 0, stream,
                        params, m->P, B, m->d_lin_cols, D, coeffs, w.params);
     GL_HIP(hipGetLastError());
-    if ((rc = run_prep(m, w.params, B, w, stream))) return rc;
+    if ((rc = run_prep(m, w.params, nullptr, B, plan, w, stream))) return rc;
     MainArgs ia = base_args(m, w, chunk);
     ia.parts = a.parts;
     ia.order = a.order;
@@ -1378,6 +1420,39 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
   }
   return GL_OK;
 }
+
+namespace {
+// a free-standing component as the point kernels take it (an EPL without a series length gets the default, epl.py:15)
+CompDesc point_comp(const gl_component* comp) {
+  CompDesc cd{};
+  cd.kind = comp->kind;
+  cd.iparam = comp->iparam;
+  cd.flags = comp->flags;
+  cd.n_par = kind_num_params(comp->kind, comp->iparam);
+  if (cd.kind == GL_EPL && cd.iparam <= 0) cd.iparam = 50;
+  return cd;
+}
+
+// The catalogue arguments of the plugin-level calls, in the order they are reported: base kind, sizes (`sizes_ok`: the caller's own
+// counts), the series order (`order`; 0 where there is none), the scale columns.  `series`: the wording of the series calls.
+int check_catalogue_args(bool series, int base_kind, bool sizes_ok, int order, const int32_t scale_col[3], int n_scales) {
+  if (base_kind != GL_DPIS && base_kind != GL_DPIE && base_kind != GL_DPIEP)
+    return series ? fail(GL_EUNSUPPORTED, "series expansion over profile kind %d is not built (dPIS, dPIE, dPIEP are)", base_kind)
+                  : fail(GL_EUNSUPPORTED, "ScalingRelation over profile kind %d is not built (dPIS, dPIE, dPIEP are)", base_kind);
+  if (!sizes_ok || n_scales < 1 || n_scales > 3) return fail(GL_EINVAL, "bad sizes");
+  if (order < 0 || order > SERIES_MAX_ORDER) return fail(GL_EINVAL, "order %d outside [0, %d]", order, SERIES_MAX_ORDER);
+  for (int k = 0; k < 3; ++k)
+    if (scale_col[k] >= n_scales) return fail(GL_EINVAL, "scale_col[%d]=%d outside the %d scales", k, scale_col[k], n_scales);
+  return GL_OK;
+}
+
+// the window of the lens-equation solver (`search` wording) and of the critical curves
+int check_window(bool search, float x_lo, float x_hi, float y_lo, float y_hi) {
+  if ((x_hi > x_lo) && (y_hi > y_lo) && std::isfinite(x_hi - x_lo) && std::isfinite(y_hi - y_lo)) return GL_OK;
+  return search ? fail(GL_EINVAL, "empty or non-finite search window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi)
+                : fail(GL_EINVAL, "empty or non-finite window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi);
+}
+}  // namespace
 
 // process-lifetime table for plugin-level table-mode shapelets (n_max = cap), built on first use
 static int point_shapelet_table(float** tab_out, int* stride_out) {
@@ -1400,12 +1475,7 @@ static int series_precompute(bool hessian, int base_kind, int n_galaxies, const 
                              const float* table_dev, const float* scales, int n_scales, int order, const float* x_dev,
                              const float* y_dev, int64_t n_pts, float* coeffs_dev, void* hip_stream) {
   if (!scale_col || !table_dev || !scales || !x_dev || !y_dev || !coeffs_dev) return fail(GL_EINVAL, "null argument");
-  if (base_kind != GL_DPIS && base_kind != GL_DPIE && base_kind != GL_DPIEP)
-    return fail(GL_EUNSUPPORTED, "series expansion over profile kind %d is not built (dPIS, dPIE, dPIEP are)", base_kind);
-  if (n_galaxies <= 0 || n_pts <= 0 || n_scales < 1 || n_scales > 3) return fail(GL_EINVAL, "bad sizes");
-  if (order < 0 || order > SERIES_MAX_ORDER) return fail(GL_EINVAL, "order %d outside [0, %d]", order, SERIES_MAX_ORDER);
-  for (int k = 0; k < 3; ++k)
-    if (scale_col[k] >= n_scales) return fail(GL_EINVAL, "scale_col[%d]=%d outside the %d scales", k, scale_col[k], n_scales);
+  if (int rc = check_catalogue_args(true, base_kind, n_galaxies > 0 && n_pts > 0, order, scale_col, n_scales)) return rc;
   if (scale_col[2] < 0) return fail(GL_EINVAL, "the series variable r_cut must be a scaled parameter");
   ScaledDesc sd{base_kind, n_galaxies, {scale_col[0], scale_col[1], scale_col[2]}};
   float s[3] = {1.f, 1.f, 1.f};
@@ -1456,16 +1526,15 @@ int gl_model_set_series_hessian(gl_model* m, int component, const float* coeffs_
   if (!m || !coeffs_dev) return fail(GL_EINVAL, "null argument");
   if (component < 0 || component >= m->n_lens || m->comps[component].kind != K_SERIES)
     return fail(GL_EINVAL, "component %d is not a GL_SERIES lens", component);
-  SeriesDev& sv = m->series[(int)m->comps[component].flags];
+  const int slot = (int)m->comps[component].flags;
+  SeriesDev& sv = m->series[slot];
   if (!sv.coef) return fail(GL_EINVAL, "gl_model_set_series must be called on component %d first", component);
-  const size_t bytes = sizeof(float) * 3 * (size_t)(sv.order + 1) * m->N;
-  if (!sv.hcoef) {
-    float* p = nullptr;
-    GL_HIP(hipMalloc((void**)&p, bytes));
-    sv.hcoef = p;
-  }
-  GL_HIP(hipMemcpy((void*)sv.hcoef, coeffs_dev, bytes, hipMemcpyDeviceToDevice));
-  GL_HIP(hipMemcpy(m->d_series, m->series.data(), sizeof(SeriesDev) * m->series.size(), hipMemcpyHostToDevice));
+  const size_t n = 3 * (size_t)(sv.order + 1) * m->N;
+  glk::DevBuf<float>& buf = m->series_buf[slot].hcoef;
+  if (!buf) GL_HIP(buf.alloc(n));  // (allocated once: the field of a slot keeps its size)
+  sv.hcoef = buf;
+  GL_HIP(buf.write(coeffs_dev, n, hipMemcpyDeviceToDevice));
+  GL_HIP(m->d_series.write(m->series.data(), m->series.size()));
   return GL_OK;
 }
 
@@ -1475,17 +1544,17 @@ int gl_model_set_series(gl_model* m, int component, float r0, const float* coeff
     return fail(GL_EINVAL, "component %d is not a GL_SERIES lens", component);
   const int slot = (int)m->comps[component].flags;
   SeriesDev& sv = m->series[slot];
-  const size_t bytes = sizeof(float) * 2 * (size_t)(sv.order + 1) * m->N;
-  if (!sv.coef) {
-    float* p = nullptr;
-    GL_HIP(hipMalloc((void**)&p, bytes));
-    sv.coef = p;
+  const size_t n = 2 * (size_t)(sv.order + 1) * m->N;
+  glk::DevBuf<float>& buf = m->series_buf[slot].coef;
+  if (!buf) {  // (allocated once: the field of a slot keeps its size)
+    GL_HIP(buf.alloc(n));
+    sv.coef = buf;
     ++m->n_series_set;
   }
-  GL_HIP(hipMemcpy((void*)sv.coef, coeffs_dev, bytes, hipMemcpyDeviceToDevice));
+  GL_HIP(buf.write(coeffs_dev, n, hipMemcpyDeviceToDevice));
   sv.r0 = r0;
-  if (!m->d_series) GL_HIP(hipMalloc((void**)&m->d_series, sizeof(SeriesDev) * m->series.size()));
-  GL_HIP(hipMemcpy(m->d_series, m->series.data(), sizeof(SeriesDev) * m->series.size(), hipMemcpyHostToDevice));
+  if (!m->d_series) GL_HIP(m->d_series.alloc(m->series.size()));
+  GL_HIP(m->d_series.write(m->series.data(), m->series.size()));
   return GL_OK;
 }
 
@@ -1542,16 +1611,10 @@ int gl_model_set_catalogue(gl_model* m, int component, int base_kind, int n_gala
     }
   }
   m->G = G;
-  if (m->d_cats) { (void)hipFree(m->d_cats); m->d_cats = nullptr; }
-  if (m->d_gal_table) { (void)hipFree(m->d_gal_table); m->d_gal_table = nullptr; }
-  if (m->d_gal_static) { (void)hipFree(m->d_gal_static); m->d_gal_static = nullptr; }
-  GL_HIP(hipMalloc((void**)&m->d_cats, sizeof(CatDev) * devs.size()));
-  GL_HIP(hipMalloc((void**)&m->d_gal_table, sizeof(float) * tab.size()));
-  GL_HIP(hipMalloc((void**)&m->d_gal_static, sizeof(float) * stat.size()));
-  GL_HIP(hipMemcpy(m->d_cats, devs.data(), sizeof(CatDev) * devs.size(), hipMemcpyHostToDevice));
-  GL_HIP(hipMemcpy(m->d_gal_table, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-  GL_HIP(hipMemcpy(m->d_gal_static, stat.data(), sizeof(float) * stat.size(), hipMemcpyHostToDevice));
-  GL_HIP(hipMemcpy(m->d_comps, m->comps.data(), sizeof(CompDesc) * m->comps.size(), hipMemcpyHostToDevice));
+  GL_HIP(m->d_cats.upload(devs.data(), devs.size()));
+  GL_HIP(m->d_gal_table.upload(tab.data(), tab.size()));
+  GL_HIP(m->d_gal_static.upload(stat.data(), stat.size()));
+  GL_HIP(m->d_comps.write(m->comps.data(), m->comps.size()));
   return GL_OK;
 }
 
@@ -1559,11 +1622,7 @@ int gl_scaled_eval(int base_kind, int n_galaxies, const int32_t scale_col[3], co
                    const float* y, int64_t n_pts, int B, int xy_batched, const float* scales, int n_scales,
                    float* out0, float* out1, void* hip_stream) {
   if (!scale_col || !table_dev || !x || !y || !scales || !out0 || !out1) return fail(GL_EINVAL, "null argument");
-  if (base_kind != GL_DPIS && base_kind != GL_DPIE && base_kind != GL_DPIEP)
-    return fail(GL_EUNSUPPORTED, "ScalingRelation over profile kind %d is not built (dPIS, dPIE, dPIEP are)", base_kind);
-  if (n_galaxies <= 0 || n_pts <= 0 || B <= 0 || n_scales < 1 || n_scales > 3) return fail(GL_EINVAL, "bad sizes");
-  for (int k = 0; k < 3; ++k)
-    if (scale_col[k] >= n_scales) return fail(GL_EINVAL, "scale_col[%d]=%d outside the %d scales", k, scale_col[k], n_scales);
+  if (int rc = check_catalogue_args(false, base_kind, n_galaxies > 0 && n_pts > 0 && B > 0, 0, scale_col, n_scales)) return rc;
   ScaledDesc sd{base_kind, n_galaxies, {scale_col[0], scale_col[1], scale_col[2]}};
   long long total = (long long)n_pts * B;
   hipLaunchKernelGGL(gl_scaled_point_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
@@ -1577,11 +1636,7 @@ int gl_scaled_hessian(int base_kind, int n_galaxies, const int32_t scale_col[3],
                       const float* y, int64_t n_pts, int B, int xy_batched, const float* scales, int n_scales,
                       float* out, void* hip_stream) {
   if (!scale_col || !table_dev || !x || !y || !scales || !out) return fail(GL_EINVAL, "null argument");
-  if (base_kind != GL_DPIS && base_kind != GL_DPIE && base_kind != GL_DPIEP)
-    return fail(GL_EUNSUPPORTED, "ScalingRelation over profile kind %d is not built (dPIS, dPIE, dPIEP are)", base_kind);
-  if (n_galaxies <= 0 || n_pts <= 0 || B <= 0 || n_scales < 1 || n_scales > 3) return fail(GL_EINVAL, "bad sizes");
-  for (int k = 0; k < 3; ++k)
-    if (scale_col[k] >= n_scales) return fail(GL_EINVAL, "scale_col[%d]=%d outside the %d scales", k, scale_col[k], n_scales);
+  if (int rc = check_catalogue_args(false, base_kind, n_galaxies > 0 && n_pts > 0 && B > 0, 0, scale_col, n_scales)) return rc;
   ScaledDesc sd{base_kind, n_galaxies, {scale_col[0], scale_col[1], scale_col[2]}};
   long long total = (long long)n_pts * B;
   hipLaunchKernelGGL(gl_scaled_hessian_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream,
@@ -1602,12 +1657,8 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
   const int J = off[n_families];
   std::vector<float> tab((size_t)4 * J);
   for (int j = 0; j < J; ++j) { tab[j] = x[j]; tab[J + j] = y[j]; tab[2 * J + j] = err_x[j]; tab[3 * J + j] = err_y[j]; }
-  if (m->d_pos) { (void)hipFree(m->d_pos); m->d_pos = nullptr; }
-  if (m->d_fam) { (void)hipFree(m->d_fam); m->d_fam = nullptr; }
-  GL_HIP(hipMalloc((void**)&m->d_pos, tab.size() * sizeof(float)));
-  GL_HIP(hipMalloc((void**)&m->d_fam, off.size() * sizeof(int)));
-  GL_HIP(hipMemcpy(m->d_pos, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-  GL_HIP(hipMemcpy(m->d_fam, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
+  GL_HIP(m->d_pos.upload(tab.data(), tab.size()));
+  GL_HIP(m->d_fam.upload(off.data(), off.size()));
   m->pos_J = J;
   m->pos_F = n_families;
   return GL_OK;
@@ -1615,12 +1666,13 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
 
 int gl_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
                          float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  int rc = check_call(m, params, B, workspace, workspace_bytes);
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
   if (rc) return rc;
   if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
   if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
   hipStream_t stream = (hipStream_t)hip_stream;
-  Workspace w = carve(m, B, workspace);
   if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream))) return rc;
   GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
   GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
@@ -1635,12 +1687,7 @@ int gl_profile_hessian(const gl_component* comp, const float* x, const float* y,
   if (n_pts <= 0 || B <= 0) return fail(GL_EINVAL, "n_pts and B must be positive");
   if (!((comp->kind >= GL_EPL && comp->kind <= GL_DPIEP) || comp->kind == GL_NFW_ELLIPSE || comp->kind == GL_TNFW))
     return fail(GL_EINVAL, "kind %d is not a free-standing mass profile", comp->kind);
-  CompDesc cd{};
-  cd.kind = comp->kind;
-  cd.iparam = comp->iparam;
-  cd.flags = comp->flags;
-  cd.n_par = kind_num_params(comp->kind, comp->iparam);
-  if (cd.kind == GL_EPL && cd.iparam <= 0) cd.iparam = 50;
+  const CompDesc cd = point_comp(comp);
   const long long total = (long long)n_pts * B;
   hipLaunchKernelGGL(gl_profile_hessian_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream,
                      cd, x, y, (long long)n_pts, B, xy_batched, params, out);
@@ -1655,7 +1702,7 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
     if (int rc = compile_user_points(m)) return rc;
   if ((x == nullptr) != (y == nullptr)) return fail(GL_EINVAL, "x and y must both be given or both be null");
   if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
-  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  if (int rc = check_ready(m, false, false)) return rc;
   if (!x) {
     if (n_pts != m->N || xy_batched) return fail(GL_EINVAL, "the model grid has %d points and is not batched", m->N);
     x = m->d_gx;
@@ -1666,16 +1713,7 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
   } else if (m->n_series) {
     return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the model grid only (series_profile.py:76-89): pass x = y = NULL");
   }
-  PosArgs a{};
-  a.comps = m->d_comps;
-  a.n_lens = m->n_lens;
-  a.P = m->P;
-  a.B = B;
-  a.params = params;
-  a.cats = m->d_cats;
-  a.gal_table = m->d_gal_table;
-  a.gal_static = m->d_gal_static;
-  a.series = m->d_series;
+  PosArgs a = point_args(m, params, B);
   const long long total = (long long)n_pts * B;
   if (m->has_user) {
     long long n_pts_ll = (long long)n_pts;
@@ -1710,7 +1748,7 @@ int gl_lens_potential(const gl_model* m, const float* params, int B, const float
                                    "a body defines the deflection only, no potential", l);
     if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
   }
-  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  if (int rc = check_ready(m, false, false)) return rc;
   if (!x) {
     if (n_pts != m->N || xy_batched) return fail(GL_EINVAL, "the model grid has %d points and is not batched", m->N);
     x = m->d_gx;
@@ -1718,15 +1756,7 @@ int gl_lens_potential(const gl_model* m, const float* params, int B, const float
   }
   const long long total = (long long)n_pts * B, blocks = (total + POT_WG - 1) / POT_WG;
   if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
-  PosArgs a{};
-  a.comps = m->d_comps;
-  a.n_lens = m->n_lens;
-  a.P = m->P;
-  a.B = B;
-  a.params = params;
-  a.cats = m->d_cats;
-  a.gal_table = m->d_gal_table;
-  a.gal_static = m->d_gal_static;
+  PosArgs a = point_args(m, params, B);
   hipLaunchKernelGGL(gl_lens_potential_kernel, dim3((unsigned)blocks), dim3(POT_WG), 0, (hipStream_t)hip_stream, a, x, y,
                      (long long)n_pts, xy_batched, out);
   GL_HIP(hipGetLastError());
@@ -1743,12 +1773,7 @@ int gl_profile_potential(const gl_component* comp, const float* x, const float* 
   if (!potential_kind(comp->kind)) return fail(GL_EINVAL, "kind %d is not a free-standing mass profile", comp->kind);
   const long long total = (long long)n_pts * B, blocks = (total + POT_WG - 1) / POT_WG;
   if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
-  CompDesc cd{};
-  cd.kind = comp->kind;
-  cd.iparam = comp->iparam;
-  cd.flags = comp->flags;
-  cd.n_par = kind_num_params(comp->kind, comp->iparam);
-  if (cd.kind == GL_EPL && cd.iparam <= 0) cd.iparam = 50;
+  const CompDesc cd = point_comp(comp);
   hipLaunchKernelGGL(gl_profile_potential_kernel, dim3((unsigned)blocks), dim3(POT_WG), 0, (hipStream_t)hip_stream, cd, x, y,
                      (long long)n_pts, B, xy_batched, params, out);
   GL_HIP(hipGetLastError());
@@ -1783,12 +1808,11 @@ int gl_image_positions(const gl_model* m, const float* params, int B, const floa
   if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
   if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
   if (max_images < 1 || max_images > IMG_MAXC) return fail(GL_EINVAL, "max_images %d outside [1, %d]", max_images, IMG_MAXC);
-  if (!(x_hi > x_lo) || !(y_hi > y_lo) || !std::isfinite(x_hi - x_lo) || !std::isfinite(y_hi - y_lo))
-    return fail(GL_EINVAL, "empty or non-finite search window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi);
+  if (int rc = check_window(true, x_lo, x_hi, y_lo, y_hi)) return rc;
   if (!(tol > 0.f) || max_iter < 1) return fail(GL_EINVAL, "tol must be > 0 and max_iter >= 1 (got %g, %d)", tol, max_iter);
   if (m->n_series)
     return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image finder");
-  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  if (int rc = check_ready(m, false, false)) return rc;
   const ImgLayout lay = img_layout(B, n_src, n_cells);
   if (!workspace) return fail(GL_EINVAL, "workspace is null");
   if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
@@ -1798,15 +1822,7 @@ int gl_image_positions(const gl_model* m, const float* params, int B, const floa
   if (m->has_user)  // map and Newton kernels compiled at run time with the user's bodies (the scan does not touch the lens)
     if (int rc = compile_user_points(m)) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
-  PosArgs a{};
-  a.comps = m->d_comps;
-  a.n_lens = m->n_lens;
-  a.P = m->P;
-  a.B = B;
-  a.params = params;
-  a.cats = m->d_cats;
-  a.gal_table = m->d_gal_table;
-  a.gal_static = m->d_gal_static;
+  PosArgs a = point_args(m, params, B);
   ImgArgs g{};
   g.src_x = src_x;
   g.src_y = src_y;
@@ -1875,14 +1891,13 @@ int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo
   if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
   if (max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS)
     return fail(GL_EINVAL, "max_segments %d outside [1, %d]", max_segments, CRIT_MAX_SEGMENTS);
-  if (!(x_hi > x_lo) || !(y_hi > y_lo) || !std::isfinite(x_hi - x_lo) || !std::isfinite(y_hi - y_lo))
-    return fail(GL_EINVAL, "empty or non-finite window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi);
+  if (int rc = check_window(false, x_lo, x_hi, y_lo, y_hi)) return rc;
   if (m->n_series)
     return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no critical curves");
   if (m->has_user)
     return fail(GL_EUNSUPPORTED, "user-written bodies (and the run-time compiled ScalingRelation member loops) are not served by the "
                                  "critical-curve kernels");
-  if ((int)m->cats.size() != m->n_scaled) return fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  if (int rc = check_ready(m, false, false)) return rc;
   const CritLayout lay = crit_layout(B, n_cells, max_segments);
   if (!workspace) return fail(GL_EINVAL, "workspace is null");
   if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
@@ -1893,15 +1908,7 @@ int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo
   if (map_blocks > 0x7fffffffLL || refine_blocks > 0x7fffffffLL)
     return fail(GL_EINVAL, "too many samples x vertices (or x max_segments) for one call");
   hipStream_t stream = (hipStream_t)hip_stream;
-  PosArgs a{};
-  a.comps = m->d_comps;
-  a.n_lens = m->n_lens;
-  a.P = m->P;
-  a.B = B;
-  a.params = params;
-  a.cats = m->d_cats;
-  a.gal_table = m->d_gal_table;
-  a.gal_static = m->d_gal_static;
+  PosArgs a = point_args(m, params, B);
   CritArgs g{};
   g.n = n_cells;
   g.max_segments = max_segments;
@@ -1952,15 +1959,9 @@ int gl_model_set_prior(gl_model* m, const gl_zcolumn* cols, int d, const float* 
       cr[p] = const_row[p];
     }
   }
-  if (m->d_zcols) { (void)hipFree(m->d_zcols); m->d_zcols = nullptr; }
-  if (m->d_src) { (void)hipFree(m->d_src); m->d_src = nullptr; }
-  if (m->d_const) { (void)hipFree(m->d_const); m->d_const = nullptr; }
-  GL_HIP(hipMalloc((void**)&m->d_zcols, sizeof(ZCol) * zc.size()));
-  GL_HIP(hipMalloc((void**)&m->d_src, sizeof(int) * src.size()));
-  GL_HIP(hipMalloc((void**)&m->d_const, sizeof(float) * cr.size()));
-  GL_HIP(hipMemcpy(m->d_zcols, zc.data(), sizeof(ZCol) * zc.size(), hipMemcpyHostToDevice));
-  GL_HIP(hipMemcpy(m->d_src, src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice));
-  GL_HIP(hipMemcpy(m->d_const, cr.data(), sizeof(float) * cr.size(), hipMemcpyHostToDevice));
+  GL_HIP(m->d_zcols.upload(zc.data(), zc.size()));
+  GL_HIP(m->d_src.upload(src.data(), src.size()));
+  GL_HIP(m->d_const.upload(cr.data(), cr.size()));
   m->d_z = d;
   return GL_OK;
 }
@@ -1969,7 +1970,9 @@ int gl_logprob_fwd_bwd(const gl_model* m, const float* z, const float* obs, cons
                        const float* mask_or_null, float bg_rms, float exp_time, int B, float* logprob, float* loglike,
                        float* chi2, float* grad_z_or_null, float chi2_divisor, unsigned terms, void* workspace,
                        size_t workspace_bytes, void* hip_stream) {
-  int rc = check_call(m, z, B, workspace, workspace_bytes);
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, z, B, workspace, workspace_bytes, &plan, &w);
   if (rc) return rc;
   const bool pix = terms & GL_TERM_PIXELS, pos = terms & GL_TERM_POSITIONS;
   if (!pix && !pos) return fail(GL_EINVAL, "terms selects no likelihood term");
@@ -1978,32 +1981,16 @@ int gl_logprob_fwd_bwd(const gl_model* m, const float* z, const float* obs, cons
   if (pos && !m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
   if ((pix && !obs) || !logprob || !loglike || !chi2) return fail(GL_EINVAL, "obs / logprob / loglike / chi2 is null");
   hipStream_t stream = (hipStream_t)hip_stream;
-  Workspace w = carve(m, B, workspace);
-  int chunk, n_chunks;
-  chunking(m, B, &chunk, &n_chunks);
-  int n_comp = (int)m->comps.size();
-  if (wave_front_end(m)) {
-    const bool ord = order_in_front_end(m, B);
-    const size_t rows = prep_row_bytes(m);
-    hipLaunchKernelGGL(gl_prep_wave_kernel, dim3((B + 3) / 4 + (ord ? 1 : 0)), dim3(256), rows, stream, m->d_comps, n_comp,
-                       (const float*)nullptr, z, m->d_z, (const ZCol*)m->d_zcols, (const int*)m->d_src, (const float*)m->d_const, m->P,
-                       B, w.params, w.derived, m->D, m->epl_comp >= 0 ? w.cost : nullptr, m->epl_comp, ord ? w.order : nullptr,
-                       rows ? 1 : 0, prep_tail_from(m, B));
-  } else
-    hipLaunchKernelGGL(gl_zprep_kernel, dim3((B * n_comp + 127) / 128), dim3(128), 0, stream, m->d_comps, n_comp, z,
-                       m->d_z, m->d_zcols, m->d_src, m->d_const, m->P, B, w.params, w.derived, m->D,
-                       m->epl_comp >= 0 ? w.cost : nullptr, m->epl_comp);
-  GL_HIP(hipGetLastError());
-  if ((rc = run_galprep(m, w.params, B, w, stream))) return rc;
+  if ((rc = run_prep(m, nullptr, z, B, plan, w, stream))) return rc;
   const float* extra = nullptr;
-  int use_partial = 0;
+  int use_partial = 0, fin_rows = plan.n_chunks;
   // red_chi2 = (red_pix + red_pos) / n_chi  (tf/model.py:150-162)
   const float n_chi = (pix ? 1.f : 0.f) + (pos ? 1.f : 0.f);
-  if (pix && (rc = run_likelihood(m, B, w, chunk, n_chunks, obs, err_or_null, mask_or_null, bg_rms, exp_time,
-                                  grad_z_or_null != nullptr, stream, &extra, &use_partial, &n_chunks)))
+  if (pix && (rc = run_likelihood(m, B, plan, w, obs, err_or_null, mask_or_null, bg_rms, exp_time,
+                                  grad_z_or_null != nullptr, stream, &extra, &use_partial, &fin_rows)))
     return rc;
   if (pos && (rc = run_positions(m, w.params, B, w, grad_z_or_null != nullptr, stream))) return rc;
-  return run_finalize(m, w.params, B, n_chunks, w, loglike, chi2, nullptr, stream, z, logprob, grad_z_or_null,
+  return run_finalize(m, w.params, B, fin_rows, w, loglike, chi2, nullptr, stream, z, logprob, grad_z_or_null,
                       pix ? 1.0f / (chi2_divisor * n_chi) : 0.f, extra, use_partial, pos,
                       pos ? 1.0f / (2.0f * (float)m->pos_J * n_chi) : 0.f);
 }
@@ -2018,12 +2005,7 @@ int gl_profile_eval(const gl_component* comp, const float* x, const float* y, in
   if (comp->kind == GL_SERIES) return fail(GL_EINVAL, "GL_SERIES needs its coefficient field: use gl_series_eval");
   const bool mass = comp->kind <= GL_DPIEP || comp->kind == GL_NFW_ELLIPSE || comp->kind == GL_TNFW;
   if (mass && !out1) return fail(GL_EINVAL, "out1 is required for mass profiles");
-  CompDesc cd{};
-  cd.kind = comp->kind;
-  cd.iparam = comp->iparam;
-  cd.flags = comp->flags;
-  cd.n_par = npar;
-  if (cd.kind == GL_EPL && cd.iparam <= 0) cd.iparam = 50;
+  const CompDesc cd = point_comp(comp);
   hipStream_t stream = (hipStream_t)hip_stream;
   float* s_tab = nullptr;
   int s_stride = 0, rc_tab = 0;
@@ -2111,11 +2093,7 @@ int gl_profile_basis(const gl_component* comp, const float* x, const float* y, i
   int npar = kind_num_params(comp->kind, comp->iparam);
   if (npar < 0) return fail(GL_EINVAL, "unknown profile kind %d", comp->kind);
   if (kind_num_linear(comp->kind, comp->iparam) <= 0) return fail(GL_EINVAL, "kind %d has no linear amplitudes", comp->kind);
-  CompDesc cd{};
-  cd.kind = comp->kind;
-  cd.iparam = comp->iparam;
-  cd.flags = comp->flags;
-  cd.n_par = npar;
+  const CompDesc cd = point_comp(comp);
   float* s_tab = nullptr;
   int s_stride = 0, rc_tab = 0;
   if (cd.kind == GL_SHAPELETS) {

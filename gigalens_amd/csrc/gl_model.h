@@ -1,13 +1,14 @@
-// gl_model.h -- the library-internal model descriptor and error helper shared by the translation units of
-// libgigalens_hip.so (gigalens_hip.hip: C ABI + host logic; gl_launch_mode*.hip: one instantiation of the main-kernel
-// launcher per mode, compiled in parallel).
+// gl_model.h -- the library-internal model descriptor, the owner type of its device buffers (DevBuf) and the error helper shared
+// by the translation units of libgigalens_hip.so (gigalens_hip.hip: C ABI + host logic; gl_launch_mode*.hip /
+// gl_generic_noslp_mode*.hip: one instantiation of a main-kernel launcher per mode, compiled in parallel; gl_user.hip: the run-time
+// compiler of user-written profiles).  The model owns every device allocation it holds: destroying it frees them.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <string>
-#include <vector>
-
 #include <atomic>
+#include <string>
+#include <utility>
+#include <vector>
 
 #include "../../include/gigalens_hip.h"
 #include "gl_kernels.hip.h"
@@ -29,6 +30,45 @@ using glk::SeriesDev;
 using glk::ZCol;
 
 namespace glk {
+// One device allocation with an owner: freed with it, replaced as a whole by alloc() / upload().  Reads as the raw pointer, so
+// kernel arguments and argument structs take it as they would a T*.
+template <class T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p_, o.p_);
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+  // a fresh allocation of n elements (the old one is freed first)
+  hipError_t alloc(size_t n) {
+    reset();
+    return hipMalloc((void**)&p_, sizeof(T) * n);
+  }
+  // overwrites the first n elements of the allocation in place
+  hipError_t write(const T* src, size_t n, hipMemcpyKind kind = hipMemcpyHostToDevice) {
+    return hipMemcpy(p_, src, sizeof(T) * n, kind);
+  }
+  // replaces the contents: a fresh allocation holding src[0..n)
+  hipError_t upload(const T* src, size_t n) {
+    const hipError_t e = alloc(n);
+    return e != hipSuccess ? e : write(src, n);
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
+
 // plans of gl_corr_pair_kernel (gl_post.hip.h)
 struct CorrClass {  // one ROW class; its column classes (ncj of them) are computed by the same thread
   int koff;        // offset of this class's [KH][ncj][KWP] kernel block in the kernel buffer
@@ -69,13 +109,13 @@ struct gl_model {
   hipFunction_t user_point_fn[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int height = 0, width = 0, supersample = 1, N = 0;
   float conversion_factor = 1.f;
-  // device-resident, immutable
-  CompDesc* d_comps = nullptr;
-  float* d_gx = nullptr;
-  float* d_gy = nullptr;
-  int* d_pix = nullptr;
-  float* d_shp_tab = nullptr;
-  float* d_nfw_tab = nullptr;  // models with NFW lenses: h(X) = g(X) / X^2 on the float format's own grid (gl_host_tables.h)
+  // device-resident, immutable (every glk::DevBuf below: owned by the model)
+  glk::DevBuf<CompDesc> d_comps;
+  glk::DevBuf<float> d_gx;
+  glk::DevBuf<float> d_gy;
+  glk::DevBuf<int> d_pix;
+  glk::DevBuf<float> d_shp_tab;
+  glk::DevBuf<float> d_nfw_tab;  // models with NFW lenses: h(X) = g(X) / X^2 on the float format's own grid (gl_host_tables.h)
   int chunk_px_override = 0;  // -DGL_EXPERIMENTS builds only
   int dbg_flags = 0;          // -DGL_EXPERIMENTS builds only
   float grid_rmax = 0.f;      // max |(x, y)| over the pixel grid
@@ -86,19 +126,19 @@ struct gl_model {
   bool has_nfw = false;
   size_t nfw_lds = 0;          // bytes of that table in a main kernel's LDS
   int shp_stride = 0;
-  float* d_psf = nullptr;  // effective kernel flip(psf) (*) box(ss)/ss^2, see gl_post.hip.h
+  glk::DevBuf<float> d_psf;  // effective kernel flip(psf) (*) box(ss)/ss^2, see gl_post.hip.h
   // the register-blocked pair kernel's plans (gl_post.hip.h gl_corr_pair_kernel): class tables, padded kernels on the device
   struct CorrPlan { glk::CorrArgs args{}; int KWP = 0, ST = 0, max_Ho = 0, max_Wo = 0, max_KH = 0; bool ok = false; };
   CorrPlan corr_fwd, corr_bwd;
-  float* d_corr_k = nullptr;
+  glk::DevBuf<float> d_corr_k;
   int psf_h = 0, psf_w = 0;
   int KH = 1, KW = 1, pad_t = 0, pad_l = 0;
   bool has_post = false;
   // unconstrained-space front end (gl_model_set_prior)
   int d_z = 0;
-  ZCol* d_zcols = nullptr;
-  int* d_src = nullptr;
-  float* d_const = nullptr;
+  glk::DevBuf<ZCol> d_zcols;
+  glk::DevBuf<int> d_src;
+  glk::DevBuf<float> d_const;
   int static_id = 0;   // 0 = generic interpreter kernel, >0 = compile-time-specialised composition
   int static_variant = 0;
   int pair = 1;        // pixel-pair (packed fp32) form of the specialised kernels
@@ -107,8 +147,8 @@ struct gl_model {
   int cluster = 0;     // gl_cluster_kernel serves the gradient modes: 1 = halos + spherical Sersic sources, 2 = elliptical sources
   // image-position likelihood (gl_model_set_positions)
   int pos_J = 0, pos_F = 0, lens_params = 0;
-  float* d_pos = nullptr;  // [4][J]: x, y, err_x, err_y
-  int* d_fam = nullptr;    // [F+1]
+  glk::DevBuf<float> d_pos;  // [4][J]: x, y, err_x, err_y
+  glk::DevBuf<int> d_fam;    // [F+1]
   bool has_epl = false;
   int epl_comp = -1;     // the model's only EPL component, or -1 (none / several)
   int fam = 0;  // family level of the interpreter variant (gl_main_kernel FAM): 1 dPIE family / catalogues / series, 2 gl_extra.h
@@ -134,17 +174,19 @@ struct gl_model {
   std::vector<Cat> cats;
   int G = 0;           // galaxies over all catalogues
   int n_scaled = 0;    // GL_SCALED components
-  CatDev* d_cats = nullptr;
-  float* d_gal_table = nullptr;   // [G][7]
-  float* d_gal_static = nullptr;  // [G][DP_NS]
+  glk::DevBuf<CatDev> d_cats;
+  glk::DevBuf<float> d_gal_table;   // [G][7]
+  glk::DevBuf<float> d_gal_static;  // [G][DP_NS]
   // series-expansion lenses (gl_model_set_series): one coefficient field per GL_SERIES component
-  std::vector<SeriesDev> series;      // device pointers owned by the model
+  std::vector<SeriesDev> series;      // what the kernels read (d_series is its copy on the device): pointers into series_buf
+  struct SeriesBuf { glk::DevBuf<float> coef, hcoef; };
+  std::vector<SeriesBuf> series_buf;  // the owners of each slot's two fields
   std::vector<int> series_comp;       // component of each slot
   int n_series = 0, n_series_set = 0;
-  SeriesDev* d_series = nullptr;
+  glk::DevBuf<SeriesDev> d_series;
   // linear amplitudes (lstsq_simulate): channel k of the basis stack <-> packed parameter column
   std::vector<int> lin_cols;
-  int* d_lin_cols = nullptr;
+  glk::DevBuf<int> d_lin_cols;
   int shp_kernel = 0;    // lenses | [Sersic lens lights] | one shapelet source: served by gl_shp.hip.h (GIGALENS_HIP_SHP=0: the round-2 kernels)
   int tile = 2;          // pixels per thread per tile (template T) for forward-only launches
   int tile_grad = 2;     // ... and for launches that also produce gradients
