@@ -66,6 +66,14 @@ SYMBOLS = {
                                    c_void_p]),
     "gl_model_set_positions": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_float), POINTER(c_float),
                                        POINTER(c_float), POINTER(c_float)]),
+    "gl_model_set_source_scales": (c_int, [c_void_p, POINTER(c_float), c_int]),
+    "gl_model_set_position_scales": (c_int, [c_void_p, POINTER(c_float), c_int]),
+    "gl_image_positions_scaled": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_float), c_float, c_float,
+                                          c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]),
+    "gl_critical_curves_scaled": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_float,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]),
     "gl_positions_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
     "gl_series_precompute": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, POINTER(c_float), c_int, c_int, c_void_p,
@@ -170,6 +178,19 @@ def _check_potential(rc):
     if rc == GL_EUNSUPPORTED:
         raise UnsupportedLensError(f"gigalens_hip error {rc}: {lib().gl_last_error().decode()}")
     _check(rc)
+
+
+def deflection_scales(values, n, what):
+    """``n`` deflection scales (``gigalens_amd.cosmology.deflection_scale``) as a float32 array; None = all 1.  ``ValueError`` on a
+    length mismatch or a value that is not finite or not > 0."""
+    if values is None:
+        return np.ones(n, dtype=np.float32)
+    arr = np.atleast_1d(np.asarray(values, dtype=np.float32))
+    if arr.ndim != 1 or arr.size != n:
+        raise ValueError(f"{what}: expected {n} scale(s), got {arr.size if arr.ndim == 1 else tuple(arr.shape)}")
+    if not (np.all(np.isfinite(arr)) and np.all(arr > 0)):
+        raise ValueError(f"{what}: every scale must be finite and > 0, got {arr.tolist()}")
+    return arr
 
 
 def _require_cuda(t, what):
@@ -601,8 +622,23 @@ class Model:
         _check_potential(lib().gl_lens_potential(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), xb.shape[0], 1, _ptr(out), _stream()))
         return out.reshape(tuple(shape))
 
-    def image_positions(self, params, src_x, src_y, window, n_cells, max_images, tol, max_iter):
-        """gl_image_positions: ``src_x, src_y`` [B, S] on the device, ``window`` = (x_lo, x_hi, y_lo, y_hi).  Returns
+    def set_source_scales(self, scales):
+        """One deflection scale per source light (gl_model_set_source_scales); a model with user-written profiles refuses
+        scales != 1 with ``UnsupportedLensError``."""
+        s = np.ascontiguousarray(scales, dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _check_potential(lib().gl_model_set_source_scales(self._h, s.ctypes.data_as(POINTER(c_float)), int(s.size)))
+        self._ws = {}  # the launch plan, and with it the workspace layout, follows the kernels that serve a scaled model
+
+    def set_position_scales(self, scales):
+        """One deflection scale per image family (gl_model_set_position_scales; after ``set_positions``, which resets them)."""
+        s = np.ascontiguousarray(scales, dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _check(lib().gl_model_set_position_scales(self._h, s.ctypes.data_as(POINTER(c_float)), int(s.size)))
+
+    def image_positions(self, params, src_x, src_y, window, n_cells, max_images, tol, max_iter, scales=None):
+        """gl_image_positions[_scaled]: ``src_x, src_y`` [B, S] on the device, ``window`` = (x_lo, x_hi, y_lo, y_hi), ``scales``
+        [S] on the host or None.  Returns
         ``out`` [B, S, max_images, 3] (x, y, mu; NaN-padded), ``n_images`` and ``n_dropped`` [B, S] (int32)."""
         params = self._params(params)
         B = params.shape[0]
@@ -617,13 +653,20 @@ class Model:
         n_images = torch.empty((B, S), dtype=torch.int32, device=self.device)
         n_dropped = torch.empty_like(n_images)
         x_lo, x_hi, y_lo, y_hi = (float(v) for v in window)
-        _check(lib().gl_image_positions(self._h, _ptr(params), B, _ptr(src_x), _ptr(src_y), S, x_lo, x_hi, y_lo, y_hi,
-                                        int(n_cells), int(max_images), float(tol), int(max_iter), _ptr(out), _ptr(n_images),
-                                        _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
+        if scales is None:
+            _check(lib().gl_image_positions(self._h, _ptr(params), B, _ptr(src_x), _ptr(src_y), S, x_lo, x_hi, y_lo, y_hi,
+                                            int(n_cells), int(max_images), float(tol), int(max_iter), _ptr(out), _ptr(n_images),
+                                            _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
+        else:
+            sc = np.ascontiguousarray(scales, dtype=np.float32)
+            _check(lib().gl_image_positions_scaled(self._h, _ptr(params), B, _ptr(src_x), _ptr(src_y), S,
+                                                   sc.ctypes.data_as(POINTER(c_float)), x_lo, x_hi, y_lo, y_hi, int(n_cells),
+                                                   int(max_images), float(tol), int(max_iter), _ptr(out), _ptr(n_images),
+                                                   _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
         return out, n_images, n_dropped
 
-    def critical_curves(self, params, window, n_cells, max_segments):
-        """gl_critical_curves: ``window`` = (x_lo, x_hi, y_lo, y_hi).  Returns ``seg``, ``cau`` [B, max_segments, 2, 2] (NaN-padded),
+    def critical_curves(self, params, window, n_cells, max_segments, scale=None):
+        """gl_critical_curves[_scaled]: ``scale`` the deflection scale of the source plane or None; ``window`` = (x_lo, x_hi, y_lo, y_hi).  Returns ``seg``, ``cau`` [B, max_segments, 2, 2] (NaN-padded),
         ``kind`` [B, max_segments] (int32; -1 padding), ``n_seg``, ``n_dropped``, ``n_flagged``, ``open`` [B] (int32) and the signed
         ``area`` [B, 4].  Series-expansion and user-written lenses raise ``UnsupportedLensError``."""
         params = self._params(params)
@@ -636,9 +679,15 @@ class Model:
         n_seg, n_dropped, n_flagged, opened = (torch.empty((B,), dtype=torch.int32, device=self.device) for _ in range(4))
         area = torch.empty((B, 4), dtype=torch.float32, device=self.device)
         x_lo, x_hi, y_lo, y_hi = (float(v) for v in window)
-        _check_potential(lib().gl_critical_curves(self._h, _ptr(params), B, x_lo, x_hi, y_lo, y_hi, int(n_cells), M, _ptr(seg),
-                                                  _ptr(cau), _ptr(kind), _ptr(n_seg), _ptr(n_dropped), _ptr(n_flagged),
-                                                  _ptr(opened), _ptr(area), _ptr(ws), ws.numel(), _stream()))
+        if scale is None:
+            _check_potential(lib().gl_critical_curves(self._h, _ptr(params), B, x_lo, x_hi, y_lo, y_hi, int(n_cells), M, _ptr(seg),
+                                                      _ptr(cau), _ptr(kind), _ptr(n_seg), _ptr(n_dropped), _ptr(n_flagged),
+                                                      _ptr(opened), _ptr(area), _ptr(ws), ws.numel(), _stream()))
+        else:
+            _check_potential(lib().gl_critical_curves_scaled(self._h, _ptr(params), B, x_lo, x_hi, y_lo, y_hi, int(n_cells), M,
+                                                             float(scale), _ptr(seg), _ptr(cau), _ptr(kind), _ptr(n_seg),
+                                                             _ptr(n_dropped), _ptr(n_flagged), _ptr(opened), _ptr(area), _ptr(ws),
+                                                             ws.numel(), _stream()))
         return seg, cau, kind, n_seg, n_dropped, n_flagged, opened, area
 
     def num_linear(self):

@@ -212,6 +212,7 @@ MainArgs base_args(const gl_model* m, const Workspace& w, int chunk) {
   a.G = m->G;
   a.scaled_first = m->cats.empty() ? -1 : m->cats[0].dev.comp;
   a.series = m->d_series;
+  a.src_scale = m->src_scaled ? m->d_src_scale.get() : nullptr;
   return a;
 }
 
@@ -379,6 +380,7 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
   a.ex = m->d_pos + 2 * m->pos_J;
   a.ey = m->d_pos + 3 * m->pos_J;
   a.fam_off = m->d_fam;
+  a.fam_scale = m->pos_scaled ? m->d_pos_scale.get() : nullptr;
   a.w_pos = w.pos_w;
   a.w_adj = w.pos_adj;
   a.w_g = w.pos_g;
@@ -801,6 +803,7 @@ int select_kernels(gl_model* m, const Knobs& k) {
   m->shp_kernel = k.shp && k.pair && m->static_id && ok_row && n_src == 1 && m->comps.back().kind == K_SHAPELETS;
   m->light_spherical = n_comp > n_lens;
   for (int i = n_lens; i < n_comp; ++i) m->light_spherical = m->light_spherical && m->comps[i].kind == K_SERSIC;
+  m->static_matched = m->static_id;
   if (!m->tile_grad) m->tile_grad = m->static_id ? 1 : 2;  // measured: T=1 wins once the VJP state lives in registers
   if (!m->static_id) {  // the interpreter kernel is built for T = 2 and 4
     if (!k.tile && !m->has_epl && !m->has_shapelets && !m->fam) m->tile = 4;  // cheap profiles, forward modes: amortise the per-tile work
@@ -1291,7 +1294,7 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
   const bool fused = solve && !stacked_or_null && !m->has_post && !m->d_pix && m->shp_kernel && m->static_id == ST_EPLSHEAR_SHAPELETS &&
                      m->n_ll == 0 && m->comps.back().iparam <= SH_CAP && D == sh_layers(m->comps.back().iparam) &&
                      (a.parts & (GL_PART_DEFLECT | GL_PART_SOURCE_LIGHT)) == (GL_PART_DEFLECT | GL_PART_SOURCE_LIGHT) &&
-                     m->lstsq_fused;
+                     m->lstsq_fused;  // (a scaled source has static_id 0: the stack path, whose bases the interpreter renders at beta_s)
   if (fused) {
     lw.n_chunks = lw.n_chunks_f;
     const bool interp = (m->comps.back().flags & GL_FLAG_SHAPELETS_INTERPOLATE) != 0;
@@ -1661,6 +1664,57 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
   GL_HIP(m->d_fam.upload(off.data(), off.size()));
   m->pos_J = J;
   m->pos_F = n_families;
+  m->pos_fam_off = off;
+  m->pos_scaled = false;  // new tables: every family back on the reference plane
+  m->d_pos_scale.reset();
+  return GL_OK;
+}
+
+namespace {
+// n deflection scales: finite and > 0; *any = some scale differs from 1
+int check_scales(const float* scales, int n, int expect, const char* what, bool* any) {
+  if (!scales) return fail(GL_EINVAL, "scales is null");
+  if (n != expect) return fail(GL_EINVAL, "%d scales for %d %s", n, expect, what);
+  *any = false;
+  for (int i = 0; i < n; ++i) {
+    if (!(std::isfinite(scales[i]) && scales[i] > 0.f)) return fail(GL_EINVAL, "scale %d (%g) is not finite and > 0", i, scales[i]);
+    *any = *any || scales[i] != 1.f;
+  }
+  return GL_OK;
+}
+}  // namespace
+
+int gl_model_set_source_scales(gl_model* m, const float* scales, int n_src) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  bool any;
+  if (int rc = check_scales(scales, n_src, m->n_src, "source light component(s)", &any)) return rc;
+  if (any && m->has_user)
+    return fail(GL_EUNSUPPORTED, "per-source deflection scales are not served on the pixel grid for models with user-written profiles");
+  if (any) GL_HIP(m->d_src_scale.upload(scales, (size_t)n_src));
+  else m->d_src_scale.reset();
+  m->src_scaled = any;
+  // A scaled model is the interpreter's (and the scaled cluster kernel's) in EVERY respect, not only at the launch: the chunking
+  // rule, the tapered end of the cost-ordered dispatch (only the pair kernels decode that grid) and the stack-free linear solve all
+  // key on static_id, exactly as for a model created with GIGALENS_HIP_STATIC=0.  The workspace layout follows the launch plan:
+  // callers size it again after this call (gl_workspace_bytes).
+  m->static_id = any ? 0 : m->static_matched;
+  return GL_OK;
+}
+
+int gl_model_set_position_scales(gl_model* m, const float* scales, int n_families) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  bool any;
+  if (int rc = check_scales(scales, n_families, m->pos_F, "image famil(ies)", &any)) return rc;
+  if (any) {
+    std::vector<float> per_image((size_t)m->pos_J);
+    for (int f = 0; f < m->pos_F; ++f)
+      for (int j = m->pos_fam_off[f]; j < m->pos_fam_off[f + 1]; ++j) per_image[j] = scales[f];
+    GL_HIP(m->d_pos_scale.upload(per_image.data(), per_image.size()));
+  } else {
+    m->d_pos_scale.reset();
+  }
+  m->pos_scaled = any;
   return GL_OK;
 }
 
@@ -1782,7 +1836,7 @@ int gl_profile_potential(const gl_component* comp, const float* x, const float* 
 
 // ---- lens-equation solver (gl_images.hip.h) -----------------------------------------------------------------
 namespace {
-struct ImgLayout { size_t map, cand, n_cand, n_over, bytes; };
+struct ImgLayout { size_t map, cand, n_cand, n_over, scale, bytes; };
 ImgLayout img_layout(int B, int n_src, int n_cells) {
   ImgLayout l{};
   const size_t V = (size_t)(n_cells + 1) * (size_t)(n_cells + 1), BS = (size_t)B * (size_t)n_src;
@@ -1790,7 +1844,8 @@ ImgLayout img_layout(int B, int n_src, int n_cells) {
   l.cand = l.map + align_up((size_t)B * V * sizeof(float2), 256);
   l.n_cand = l.cand + align_up(BS * IMG_MAXC * sizeof(float2), 256);
   l.n_over = l.n_cand + align_up(BS * sizeof(int), 256);
-  l.bytes = l.n_over + align_up(BS * sizeof(int), 256);
+  l.scale = l.n_over + align_up(BS * sizeof(int), 256);  // [n_src] deflection scales of gl_image_positions_scaled
+  l.bytes = l.scale + align_up((size_t)n_src * sizeof(float), 256);
   return l;
 }
 constexpr int IMG_MAX_CELLS = 8192;
@@ -1804,6 +1859,14 @@ size_t gl_image_positions_workspace_bytes(const gl_model* m, int B, int n_src, i
 int gl_image_positions(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
                        float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images, float tol, int max_iter,
                        float* out, int* n_images, int* n_dropped, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  return gl_image_positions_scaled(m, params, B, src_x, src_y, n_src, nullptr, x_lo, x_hi, y_lo, y_hi, n_cells, max_images, tol,
+                                   max_iter, out, n_images, n_dropped, workspace, workspace_bytes, hip_stream);
+}
+
+int gl_image_positions_scaled(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                              const float* src_scale, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images,
+                              float tol, int max_iter, float* out, int* n_images, int* n_dropped, void* workspace,
+                              size_t workspace_bytes, void* hip_stream) {
   if (!m || !params || !src_x || !src_y || !out || !n_images || !n_dropped) return fail(GL_EINVAL, "null argument");
   if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
   if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
@@ -1824,6 +1887,15 @@ int gl_image_positions(const gl_model* m, const float* params, int B, const floa
   hipStream_t stream = (hipStream_t)hip_stream;
   PosArgs a = point_args(m, params, B);
   ImgArgs g{};
+  if (src_scale) {  // one scale per source, host -> the call's own workspace on the caller's stream (all 1: the unscaled path)
+    bool any;
+    if (int rc = check_scales(src_scale, n_src, n_src, "source(s)", &any)) return rc;
+    if (any) {
+      float* d_scale = (float*)((char*)workspace + lay.scale);
+      GL_HIP(hipMemcpyAsync(d_scale, src_scale, sizeof(float) * (size_t)n_src, hipMemcpyHostToDevice, stream));
+      g.src_scale = d_scale;
+    }
+  }
   g.src_x = src_x;
   g.src_y = src_y;
   g.S = n_src;
@@ -1885,8 +1957,17 @@ size_t gl_critical_curves_workspace_bytes(const gl_model* m, int B, int n_cells,
 int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
                        int max_segments, float* seg, float* cau, int* kind, int* n_seg, int* n_dropped, int* n_flagged, int* open,
                        float* area, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  return gl_critical_curves_scaled(m, params, B, x_lo, x_hi, y_lo, y_hi, n_cells, max_segments, 1.f, seg, cau, kind, n_seg, n_dropped,
+                                   n_flagged, open, area, workspace, workspace_bytes, hip_stream);
+}
+
+int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi,
+                              int n_cells, int max_segments, float scale, float* seg, float* cau, int* kind, int* n_seg,
+                              int* n_dropped, int* n_flagged, int* open, float* area, void* workspace, size_t workspace_bytes,
+                              void* hip_stream) {
   if (!m || !params || !seg || !cau || !kind || !n_seg || !n_dropped || !n_flagged || !open || !area)
     return fail(GL_EINVAL, "null argument");
+  if (!(std::isfinite(scale) && scale > 0.f)) return fail(GL_EINVAL, "scale (%g) is not finite and > 0", scale);
   if (B <= 0) return fail(GL_EINVAL, "B (%d) must be positive", B);
   if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
   if (max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS)
@@ -1911,6 +1992,7 @@ int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo
   PosArgs a = point_args(m, params, B);
   CritArgs g{};
   g.n = n_cells;
+  g.scale = scale;
   g.max_segments = max_segments;
   g.max_edges = max_edges;
   g.x_lo = x_lo; g.x_hi = x_hi; g.y_lo = y_lo; g.y_hi = y_hi;

@@ -179,8 +179,15 @@ template <int HPW> struct CwLensNfw {
 // interpreter's 16 100 instructions per pixel, so serving the 20 sources efficiently can save 6 % at most, and the interpreter
 // runs that loop at four waves per SIMD (120 VGPRs, VALU busy 0.90) where this kernel's per-wave accumulators leave two.)
 
-template <int MODE, class LENS, int SPW, bool ELL, int WAVES>
-__global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int n_lens, int n_s) {
+// The body of gl_clusterw_kernel and of gl_clusterw_scaled_kernel (below).  SCALED: every source has its own deflection scale c_j
+// (MainArgs::src_scale; sources at different redshifts behind one lens plane) and is rendered at beta_j = x - c_j sum alpha.  What the
+// first exchange leaves in every wave is then the sum -sum alpha itself (added in wave order from zero), beta_j = fma(c_j, -sum alpha, x)
+// in packed form per source of the wave, and a source's (dg_x, dg_y) joins the wave's cotangent partial as c_j dg: what crosses LDS in
+// the third exchange is the cotangent of alpha.  c_j is wave-uniform (scalar loads); a neutral slot has c = 1.  Between the second and
+// the third barrier no wave writes the first exchange's partials (the next step's writes come after the third barrier), so the
+// source VJPs read them again instead of holding -sum alpha and the grid coordinates in registers through the statistics.
+template <int MODE, class LENS, int SPW, bool ELL, bool SCALED>
+__device__ __forceinline__ void clusterw_body(const MainArgs& a, int n_lens, int n_s) {
   static_assert(MODE == IMG_BWD || MODE == LL_GRAD, "gradient modes only (forward modes: gl_main_kernel)");
   using V = v2f;
   constexpr int NFWP = (NFW_ND + 3) & ~3;
@@ -220,6 +227,11 @@ __global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int 
     pS[j] = (cw_gptr)(on ? gder + cd.d_off : neutral + NFWP);
     aS[j] = on ? cd.a_off : -1;
   }
+  float cS[SCALED ? SPW : 1];
+  if constexpr (SCALED) {
+#pragma unroll
+    for (int j = 0; j < SPW; ++j) cS[j] = wave + 4 * j < n_s ? a.src_scale[wave + 4 * j] : 1.f;
+  }
   V accS[SPW][NSA];
 #pragma unroll
   for (int j = 0; j < SPW; ++j)
@@ -248,15 +260,15 @@ __global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int 
     V vmask = V(1.f);
     if (CHECK) vmask = V{valid[0] ? 1.f : 0.f, valid[1] ? 1.f : 0.f};
     using PS = cw_gptr;
-    cw_gptr cS[SPW];
+    cw_gptr cP[SPW];
 #pragma unroll
-    for (int j = 0; j < SPW; ++j) cS[j] = cw_launder(pS[j]);
+    for (int j = 0; j < SPW; ++j) cP[j] = cw_launder(pS[j]);
     // ---- ray-shoot: this wave's lenses (tf/simulator.py:72-78) ----
     V pax = V(0.f), pay = V(0.f);  // -(sum of this wave's alpha)
     lens.fwd(x, y, pax, pay);
     s_xa[my] = float4{pax.x, pax.y, pay.x, pay.y};
     __syncthreads();
-    V bx = x, by = y;
+    V bx = SCALED ? V(0.f) : x, by = SCALED ? V(0.f) : y;  // SCALED: -(sum alpha) alone
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
       const float4 t = s_xa[w * 64 + lane];
@@ -269,8 +281,12 @@ __global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int 
     V pm = V(0.f);
 #pragma unroll
     for (int j = 0; j < SPW; ++j) {
-      const PS d = cS[j];
-      pm += sersic_fwd_c<V, ELL, PS>(d, bx, by, sst[j], ELL ? nullptr : &sL2[ELL ? 0 : j]);
+      const PS d = cP[j];
+      if constexpr (SCALED)
+        pm += sersic_fwd_c<V, ELL, PS>(d, __builtin_elementwise_fma(V(cS[j]), bx, x), __builtin_elementwise_fma(V(cS[j]), by, y), sst[j],
+                                       ELL ? nullptr : &sL2[ELL ? 0 : j]);
+      else
+        pm += sersic_fwd_c<V, ELL, PS>(d, bx, by, sst[j], ELL ? nullptr : &sL2[ELL ? 0 : j]);
       CW_FENCE();
     }
     s_xm[my] = float2{pm.x, pm.y};
@@ -319,19 +335,42 @@ __global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int 
     }
     // ---- source VJPs: parameter gradients and this wave's part of the cotangent of beta ----
     V gbx = V(0.f), gby = V(0.f);
+    // the grid coordinates are read again (L1 hits) instead of holding four registers through the source phases
+    V xh, yh, sax = V(0.f), say = V(0.f);
+    if constexpr (SCALED) {
+      xh = V{ldf(a.gx, jo0), ldf(a.gx, jo1)};
+      yh = V{ldf(a.gy, jo0), ldf(a.gy, jo1)};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {  // the same four partials in the same order: bitwise the sum the render phase used
+        const float4 t = s_xa[w * 64 + lane];
+        sax += V{t.x, t.y};
+        say += V{t.z, t.w};
+      }
+    }
 #pragma unroll
     for (int j = 0; j < SPW; ++j) {
-      const PS d = cS[j];
+      const PS d = cP[j];
+      V pbx = bx, pby = by, dgx = V(0.f), dgy = V(0.f);
+      if constexpr (SCALED) {
+        pbx = __builtin_elementwise_fma(V(cS[j]), sax, xh);
+        pby = __builtin_elementwise_fma(V(cS[j]), say, yh);
+      }
+      V& ogx = SCALED ? dgx : gbx;
+      V& ogy = SCALED ? dgy : gby;
       if constexpr (ELL) {
         V va[SER_NACC];
-        sersic_vjp_c<V, true, PS>(d, bx, by, sst[j], gm, va, gbx, gby);
+        sersic_vjp_c<V, true, PS>(d, pbx, pby, sst[j], gm, va, ogx, ogy);
 #pragma unroll
         for (int k = 0; k < SER_NACC; ++k) accS[j][k] += va[k];
       } else {
         V va[S5_N];
-        sersic_vjp5_keep_c<V, PS>(d, bx, by, sst[j], sL2[ELL ? 0 : j], gm, va, gbx, gby);
+        sersic_vjp5_keep_c<V, PS>(d, pbx, pby, sst[j], sL2[ELL ? 0 : j], gm, va, ogx, ogy);
 #pragma unroll
         for (int k = 0; k < S5_N; ++k) accS[j][k] += va[k];
+      }
+      if constexpr (SCALED) {
+        gbx = __builtin_elementwise_fma(V(cS[j]), dgx, gbx);
+        gby = __builtin_elementwise_fma(V(cS[j]), dgy, gby);
       }
       CW_FENCE();
     }
@@ -347,8 +386,10 @@ __global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int 
     // ---- lens VJPs with the cotangent -g_beta (beta = x - sum alpha) ----
     tgx = -tgx;
     tgy = -tgy;
-    // the grid coordinates are read again (L1 hits) instead of holding four registers through the source phases
-    const V xh = V{ldf(a.gx, jo0), ldf(a.gx, jo1)}, yh = V{ldf(a.gy, jo0), ldf(a.gy, jo1)};
+    if constexpr (!SCALED) {
+      xh = V{ldf(a.gx, jo0), ldf(a.gx, jo1)};
+      yh = V{ldf(a.gy, jo0), ldf(a.gy, jo1)};
+    }
     lens.vjp(xh, yh, tgx, tgy);
   };
   {
@@ -396,6 +437,16 @@ __global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int 
   __syncthreads();
   float* out = a.partial + ((size_t)b * gridDim.x + chunk) * a.A;
   for (int k = tid; k < a.A; k += WG) out[k] = s_row[k];
+}
+
+template <int MODE, class LENS, int SPW, bool ELL, int WAVES>
+__global__ void __launch_bounds__(WG, WAVES) gl_clusterw_kernel(MainArgs a, int n_lens, int n_s) {
+  clusterw_body<MODE, LENS, SPW, ELL, false>(a, n_lens, n_s);
+}
+// ... with per-source deflection scales (a.src_scale is not null)
+template <int MODE, class LENS, int SPW, bool ELL, int WAVES>
+__global__ void __launch_bounds__(WG, WAVES) gl_clusterw_scaled_kernel(MainArgs a, int n_lens, int n_s) {
+  clusterw_body<MODE, LENS, SPW, ELL, true>(a, n_lens, n_s);
 }
 
 }  // namespace glk

@@ -54,6 +54,7 @@ struct CritArgs {
   float x_lo, x_hi, y_lo, y_hi;
   float hx, hy;       // cell sides
   float bracket;      // CRIT_BRACKET_ULP * eps * max |window coordinate|
+  float scale;        // deflection scale c of the source plane the curves are drawn for: D = det(I - c H), beta = theta - c sum alpha
   float* dmap;        // [B][(n+1)^2] D at the vertices, row-major (y rows, x columns); NaN = flagged
   int* edge_id;       // [B][max_edges] crossing edges, ascending
   float4* edge_pt;    // [B][max_edges] x, y, beta_x, beta_y of the refined crossing
@@ -78,7 +79,7 @@ __device__ inline float crit_vy(const CritArgs& g, int r) { return g.y_lo + (flo
 // models without a GL_SCALED catalogue: without the member loop in the switch of lens_point the evaluation fits the 256 VGPRs
 // inline; with it (CAT = true) it is a function call, which keeps the kernels free of register spills.
 template <bool CAT>
-__device__ inline float crit_eval_impl(const PosArgs& a, int b, float px, float py, float& bx, float& by, float& omk) {
+__device__ inline float crit_eval_impl(const PosArgs& a, int b, float px, float py, float c, float& bx, float& by, float& omk) {
   using R = gld::Dual<float, 2>;
   R x(px), y(py);
   x.d[0] = 1.f;
@@ -99,17 +100,22 @@ __device__ inline float crit_eval_impl(const PosArgs& a, int b, float px, float 
     by -= ay.v;
     h[0] += ax.d[0] + ex; h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1] + ex;
   }
+  if (c != 1.f) {  // (c == 1: every value as the sum formed it)
+    bx = px + c * (bx - px);
+    by = py + c * (by - py);
+    h[0] *= c; h[1] *= c; h[2] *= c; h[3] *= c;
+  }
   omk = 1.f - 0.5f * (h[0] + h[3]);
   return (1.f - h[0]) * (1.f - h[3]) - h[1] * h[2];
 }
 
-static __device__ __attribute__((noinline)) float crit_eval_cat(const PosArgs& a, int b, float px, float py, float& bx, float& by, float& omk) {
-  return crit_eval_impl<true>(a, b, px, py, bx, by, omk);
+static __device__ __attribute__((noinline)) float crit_eval_cat(const PosArgs& a, int b, float px, float py, float c, float& bx, float& by, float& omk) {
+  return crit_eval_impl<true>(a, b, px, py, c, bx, by, omk);
 }
 template <bool CAT>
-__device__ inline float crit_eval(const PosArgs& a, int b, float px, float py, float& bx, float& by, float& omk) {
-  if constexpr (CAT) return crit_eval_cat(a, b, px, py, bx, by, omk);
-  else return crit_eval_impl<false>(a, b, px, py, bx, by, omk);
+__device__ inline float crit_eval(const PosArgs& a, int b, float px, float py, float c, float& bx, float& by, float& omk) {
+  if constexpr (CAT) return crit_eval_cat(a, b, px, py, c, bx, by, omk);
+  else return crit_eval_impl<false>(a, b, px, py, c, bx, by, omk);
 }
 
 template <bool CAT> __global__ void __launch_bounds__(256) gl_crit_map_kernel(PosArgs a, CritArgs g) {
@@ -120,7 +126,7 @@ template <bool CAT> __global__ void __launch_bounds__(256) gl_crit_map_kernel(Po
   const int b = (int)(i / V), v = (int)(i - (long long)b * V);
   const int r = v / V1, c = v - r * V1;
   float bx, by, omk;
-  float d = crit_eval<CAT>(a, b, crit_vx(g, c), crit_vy(g, r), bx, by, omk);
+  float d = crit_eval<CAT>(a, b, crit_vx(g, c), crit_vy(g, r), g.scale, bx, by, omk);
   if (!isfinite(d)) d = __builtin_nanf("");
   g.dmap[i] = d;
 }
@@ -198,13 +204,13 @@ template <bool CAT> __global__ void __launch_bounds__(64) gl_crit_refine_kernel(
   float t_lo = 0.f, t_hi = 1.f, bx, by, omk;
   for (int it = 0; it < CRIT_MAX_BISECT && (t_hi - t_lo) * len > g.bracket; ++it) {
     const float t = 0.5f * (t_lo + t_hi);
-    const float d = crit_eval<CAT>(a, b, hz ? x0 + t * len : x0, hz ? y0 : y0 + t * len, bx, by, omk);
+    const float d = crit_eval<CAT>(a, b, hz ? x0 + t * len : x0, hz ? y0 : y0 + t * len, g.scale, bx, by, omk);
     if ((d < 0.f) == neg0) t_lo = t;
     else t_hi = t;
   }
   const float t = 0.5f * (t_lo + t_hi);
   const float x = hz ? x0 + t * len : x0, y = hz ? y0 : y0 + t * len;
-  crit_eval<CAT>(a, b, x, y, bx, by, omk);
+  crit_eval<CAT>(a, b, x, y, g.scale, bx, by, omk);
   g.edge_pt[(size_t)b * g.max_edges + k] = float4{x, y, bx, by};
   g.edge_omk[(size_t)b * g.max_edges + k] = omk;
 }

@@ -30,6 +30,7 @@ constexpr float IMG_MERGE = 0.05f;  // converged candidates closer than this fra
 struct ImgArgs {
   const float* src_x;  // [B][S]
   const float* src_y;
+  const float* src_scale;  // [S] deflection scale of every source (its own plane: beta_s = theta - c_s sum alpha), or null: all 1
   int S, n;            // sources per sample, cells per side
   float x_lo, x_hi, y_lo, y_hi;
   float hx, hy;        // cell sides
@@ -80,14 +81,26 @@ __device__ inline float img_edge(float2 p, float2 q, float sx, float sy) {
 // A point is inside when every oriented edge function is > 0; on an edge (== 0) it belongs to the triangle that owns that edge,
 // and of two triangles sharing an edge with the same orientation exactly one owns it: the owner is the one whose oriented
 // direction d along the edge has d.y > 0, or d.y == 0 and d.x > 0.  Triangles with a flagged vertex or zero area are skipped.
-__device__ inline bool img_tri_hit(const ImgArgs& g, const float2* mp, int t, float sx, float sy, float& seed_x, float& seed_y) {
+// the stored map (beta of the reference plane at vertex v) on the plane of a source with scale c: theta + c (beta - theta).  A function
+// of the vertex alone, without contraction: every triangle that touches the vertex sees bitwise the same value, so the tie rule of
+// img_tri_hit still counts a source on a shared edge once
+__device__ inline float2 img_vertex_beta(const ImgArgs& g, const float2* mp, int v, float c) {
+#pragma clang fp contract(off)
+  const float2 b1 = mp[v];
+  if (c == 1.f) return b1;
+  const int V1 = g.n + 1, r = v / V1, col = v - r * V1;
+  const float x = img_vx(g, col), y = img_vy(g, r);
+  return float2{x + c * (b1.x - x), y + c * (b1.y - y)};
+}
+
+__device__ inline bool img_tri_hit(const ImgArgs& g, const float2* mp, int t, float sx, float sy, float c, float& seed_x, float& seed_y) {
   const int n = g.n, V1 = n + 1;
   const int cell = t >> 1, k = t & 1;
   const int cj = cell / n, ci = cell - cj * n;
   const int v00 = cj * V1 + ci;
   int vi[3] = {v00, k ? v00 + V1 + 1 : v00 + 1, k ? v00 + V1 : v00 + V1 + 1};
   float2 bv[3];
-  for (int e = 0; e < 3; ++e) bv[e] = mp[vi[e]];
+  for (int e = 0; e < 3; ++e) bv[e] = img_vertex_beta(g, mp, vi[e], c);
   float w[3], dx[3], dy[3];
   for (int e = 0; e < 3; ++e) {  // edge e runs from vertex e to vertex e+1
     const int p = e, q = e == 2 ? 0 : e + 1;
@@ -122,6 +135,7 @@ __global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
   const int bs = blockIdx.x, b = bs / g.S;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float sx = g.src_x[bs], sy = g.src_y[bs];
+  const float c = g.src_scale ? g.src_scale[bs - b * g.S] : 1.f;
   const long long V1 = g.n + 1;
   const float2* mp = g.map + (size_t)b * (size_t)(V1 * V1);
   // wave w walks the w-th quarter of the triangles, 64 consecutive triangles (32 cells of one row) per round
@@ -131,7 +145,7 @@ __global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
   for (int base = t0; base < t1; base += 64) {
     const int t = base + lane;
     float seed_x = 0.f, seed_y = 0.f;
-    const bool hit = t < t1 && img_tri_hit(g, mp, t, sx, sy, seed_x, seed_y);
+    const bool hit = t < t1 && img_tri_hit(g, mp, t, sx, sy, c, seed_x, seed_y);
     const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
     const int rank = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
     if (hit && rank < IMG_MAXC) list[wave][rank] = float2{seed_x, seed_y};
@@ -154,7 +168,8 @@ __global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
 }
 
 // beta and Hessian (f_xx, f_xy, f_yx, f_yy; the dPIS convergence excess included, as P1 and gl_lens_maps have it) at one point
-__device__ inline void img_lens_eval(const PosArgs& a, int b, float px, float py, float& bx, float& by, float* h) {
+// (c: the deflection scale of the source's plane; 1 leaves every value as the sum formed it)
+__device__ inline void img_lens_eval(const PosArgs& a, int b, float px, float py, float& bx, float& by, float* h, float c = 1.f) {
   using R = gld::Dual<float, 2>;
   R x(px), y(py);
   x.d[0] = 1.f;
@@ -174,6 +189,11 @@ __device__ inline void img_lens_eval(const PosArgs& a, int b, float px, float py
     by -= ay.v;
     h[0] += ax.d[0] + ex; h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1] + ex;
   }
+  if (c != 1.f) {
+    bx = px + c * (bx - px);
+    by = py + c * (by - py);
+    h[0] *= c; h[1] *= c; h[2] *= c; h[3] *= c;
+  }
 }
 
 __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g) {
@@ -183,6 +203,7 @@ __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g)
   const int bs = blockIdx.x, b = bs / g.S, lane = threadIdx.x;
   const int nc = g.n_cand[bs];
   const float sx = g.src_x[bs], sy = g.src_y[bs], tol2 = g.tol * g.tol;
+  const float c = g.src_scale ? g.src_scale[bs - b * g.S] : 1.f;
   const float max_step = sqrtf(g.hx * g.hx + g.hy * g.hy);  // a step is at most one cell diagonal (folds: near-singular I - H)
   bool ok = false;
   float x = 0.f, y = 0.f, mu = 0.f;
@@ -191,7 +212,7 @@ __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g)
     x = s0.x;
     y = s0.y;
     float bx, by, h[4];
-    img_lens_eval(a, b, x, y, bx, by, h);
+    img_lens_eval(a, b, x, y, bx, by, h, c);
     float r_x = sx - bx, r_y = sy - by, r2 = r_x * r_x + r_y * r_y;
     // the affine preimage misses beta_s by more than a cell side: the triangle straddles a singular or discontinuous point of
     // the deflection (the centre of an SIS / SIE / EPL with gamma >= 2), not a smooth neighbourhood of an image; if such a
@@ -214,7 +235,7 @@ __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g)
       }
       const float nx = x + dx, ny = y + dy;
       float nbx, nby, nh[4];
-      img_lens_eval(a, b, nx, ny, nbx, nby, nh);
+      img_lens_eval(a, b, nx, ny, nbx, nby, nh, c);
       const float nr_x = sx - nbx, nr_y = sy - nby, nr2 = nr_x * nr_x + nr_y * nr_y;
       if (conv) {  // the polishing step
         if (nr2 <= r2) { x = nx; y = ny; for (int k = 0; k < 4; ++k) h[k] = nh[k]; }

@@ -104,6 +104,7 @@ struct MainArgs {
   int n_lin;         // IMG_BASIS: channels of the stack  img[B][n_lin][img_stride]
   const SeriesDev* series;
   const float* nfw_tab;  // models with NFW lenses: the shared h(X) table (gl_host_tables.h), [kNfwNodes][2]; else null
+  const float* src_scale;  // per-source deflection scales c_s [n_src] (beta_s = x - c_s sum alpha), or null: one source plane
   const float* neutral;  // gl_clusterw_kernel: constant blocks of an unused component slot, [NFW (4) | Sersic (16)]; else null
   float grid_rmax;       // largest |(x, y)| of the pixel grid (gl_shp.hip.h: the bound on the shear's deflection)
   int blk_w;             // table-mode shapelet kernel: image width when a wave-tile is an 8-row x 16-column BLOCK of the image (0: 128 consecutive pixels)
@@ -783,6 +784,17 @@ template <int T> __device__ __forceinline__ void epl_vjp_T(const float* d, const
 //   FAM 2: + NFW_ELLIPSE, TNFW, CoreSersic (gl_extra.h; the fp64 core of TNFW alone costs ~80 VGPRs)
 //   BIG: some shapelet component has n_max above SH_CAP (up to SH_CAPB = 20): every shapelet component of the model runs the
 //   runtime-order code of gl_profiles.h on the model's wide table, amplitude gradients leave shell by shell into the LDS columns
+// Where a light component is evaluated along one axis: the grid coordinate x for lens light, beta for a source -- on the source's
+// own plane beta_s = x + c_s (beta - x) when the model carries per-source deflection scales (MainArgs::src_scale).  c_s == 1 takes
+// beta as it stands (x + 1 (beta - x) is not beta in float32), so a model without scales computes exactly what it did before them;
+// the cotangent of beta_s enters the lens VJPs as c_s times itself, which is exact at c_s == 1.  cs is wave-uniform.
+__device__ __forceinline__ float light_point(bool src, float cs, float beta, float x) {
+  return src ? (cs == 1.f ? beta : __builtin_fmaf(cs, beta - x, x)) : x;
+}
+// the scale of light component ci (lens lights and models without scales: 1)
+__device__ __forceinline__ float light_scale(const MainArgs& a, int ci) {
+  return (ci >= a.n_ll && a.src_scale) ? a.src_scale[ci - a.n_ll] : 1.f;
+}
 template <int MODE, int T, bool SHP, int FAM, bool BIG = false>
 __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainArgs a) {
   constexpr bool DP = FAM >= 1, XF = FAM >= 2;
@@ -930,6 +942,7 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
         const CompDesc& cd = comps[n_lens + ci];
         const float* d = s_d + cd.d_off;
         const bool src = ci >= n_ll;
+        const float cs = light_scale(a, ci);
         float* row = a.img + ((size_t)b * a.n_lin + cd.lin_off) * a.img_stride;
         if (cd.kind == K_SHAPELETS) {
           if constexpr (SHP) {
@@ -938,14 +951,14 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
               if (!valid[t]) continue;
               const int pi = pidx[t];
               const long long st = a.img_stride;
-              shapelets_basis<float, BIG ? SH_CAPB : SH_CAP>(d, a.shp_tab, a.shp_stride, cd.flags & 1u, src ? bx[t] : x[t],
-                                             src ? by[t] : y[t], [&](int k, float v) { row[(size_t)k * st + pi] = isnan_(v) ? 0.f : v; });
+              shapelets_basis<float, BIG ? SH_CAPB : SH_CAP>(d, a.shp_tab, a.shp_stride, cd.flags & 1u, light_point(src, cs, bx[t], x[t]),
+                                             light_point(src, cs, by[t], y[t]), [&](int k, float v) { row[(size_t)k * st + pi] = isnan_(v) ? 0.f : v; });
             }
           }
         } else {
 #pragma unroll
           for (int t = 0; t < T; ++t) {
-            const float px_ = src ? bx[t] : x[t], py_ = src ? by[t] : y[t];
+            const float px_ = light_point(src, cs, bx[t], x[t]), py_ = light_point(src, cs, by[t], y[t]);
             float v;
             if (XF && cd.kind == K_CORE_SERSIC) v = core_sersic_fwd<float>(d, px_, py_);
 #ifdef GL_HAVE_USER
@@ -963,6 +976,7 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
       const CompDesc& cd = comps[n_lens + ci];
       const float* d = s_d + cd.d_off;
       const bool src = ci >= n_ll;
+      const float cs = light_scale(a, ci);
       if (!(a.parts & (src ? 4u : 2u))) continue;
       if (cd.kind == K_SHAPELETS) {
         if (SHP) {
@@ -971,35 +985,35 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
 #pragma unroll 1
           for (int t = 0; t < T; ++t) {
             if constexpr (BIG) {
-              m[t] += shapelets_fwd<float, SH_CAPB>(d, a.shp_tab, a.shp_stride, interp, src ? bx[t] : x[t], src ? by[t] : y[t]);
+              m[t] += shapelets_fwd<float, SH_CAPB>(d, a.shp_tab, a.shp_stride, interp, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]));
             } else {
               ShpState<SH_CAP> hs;
-              m[t] += shp_fwd_state<SH_CAP>(d, gamp, a.shp_tab, interp, src ? bx[t] : x[t], src ? by[t] : y[t], hs);
+              m[t] += shp_fwd_state<SH_CAP>(d, gamp, a.shp_tab, interp, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]), hs);
             }
           }
         }
       } else if (cd.kind == K_CORE_SERSIC) {
         if constexpr (XF) {
 #pragma unroll
-          for (int t = 0; t < T; ++t) m[t] += core_sersic_fwd<float>(d, src ? bx[t] : x[t], src ? by[t] : y[t]);
+          for (int t = 0; t < T; ++t) m[t] += core_sersic_fwd<float>(d, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]));
         }
 #ifdef GL_HAVE_USER
       } else if (cd.kind == K_USER_LIGHT) {
 #pragma unroll
-        for (int t = 0; t < T; ++t) m[t] += glu::light_fwd(cd.flags, d, src ? bx[t] : x[t], src ? by[t] : y[t]);
+        for (int t = 0; t < T; ++t) m[t] += glu::light_fwd(cd.flags, d, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]));
 #endif
       } else if constexpr (T % 2 == 0) {
 #pragma unroll
         for (int t = 0; t < T; t += 2) {
           SerStateV<v2f> stv;
-          v2f I = sersic_fwd_v<v2f>(d, src ? v2f{bx[t], bx[t + 1]} : v2f{x[t], x[t + 1]},
-                                    src ? v2f{by[t], by[t + 1]} : v2f{y[t], y[t + 1]}, stv);
+          v2f I = sersic_fwd_v<v2f>(d, v2f{light_point(src, cs, bx[t], x[t]), light_point(src, cs, bx[t + 1], x[t + 1])},
+                                    v2f{light_point(src, cs, by[t], y[t]), light_point(src, cs, by[t + 1], y[t + 1])}, stv);
           m[t] += I.x;
           m[t + 1] += I.y;
         }
       } else {
 #pragma unroll
-        for (int t = 0; t < T; ++t) m[t] += sersic_fwd(d, src ? bx[t] : x[t], src ? by[t] : y[t]);
+        for (int t = 0; t < T; ++t) m[t] += sersic_fwd(d, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]));
       }
     }
     bool nanp[T];
@@ -1043,6 +1057,7 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
         const CompDesc& cd = comps[n_lens + ci];
         const float* d = s_d + cd.d_off;
         const bool src = ci >= n_ll;
+        const float cs = light_scale(a, ci);
         if (cd.kind == K_SHAPELETS) {
           if constexpr (SHP && BIG) {
             // runtime-order path: one pixel at a time, every shell n = n1 + n2 of the amplitude gradient reduced over the lane
@@ -1052,14 +1067,14 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
 #pragma unroll 1
             for (int t = 0; t < T; ++t) {
               float dgx = 0.f, dgy = 0.f;
-              (void)shapelets_vjp_shells<float, SH_CAPB>(d, a.shp_tab, a.shp_stride, interp, src ? bx[t] : x[t], src ? by[t] : y[t],
+              (void)shapelets_vjp_shells<float, SH_CAPB>(d, a.shp_tab, a.shp_stride, interp, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]),
                                                          gm[t], acc3, dgx, dgy, [&](int first, int count, float* vals) {
                 float tmp[SH_CAPB + 1];
 #pragma unroll
                 for (int k = 0; k <= SH_CAPB; ++k) tmp[k] = vals[k];
                 wave_acc<SH_CAPB + 1>(tmp, ac, cd.a_off + SHPA_AMP + first, count);
               });
-              if (src) { gbx[t] += dgx; gby[t] += dgy; }
+              if (src) { gbx[t] += cs * dgx; gby[t] += cs * dgy; }
             }
             wave_acc<SHPA_AMP>(acc3, ac, cd.a_off, SHPA_AMP);
           } else if (SHP) {
@@ -1072,9 +1087,9 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
             for (int t = 0; t < T; ++t) {
               float dgx = 0.f, dgy = 0.f;
               ShpState<SH_CAP> hs;  // bases re-evaluated (the interpreter keeps no per-component state), contractions separable
-              (void)shp_fwd_state<SH_CAP>(d, gamp, a.shp_tab, interp, src ? bx[t] : x[t], src ? by[t] : y[t], hs);
+              (void)shp_fwd_state<SH_CAP>(d, gamp, a.shp_tab, interp, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]), hs);
               shp_vjp_state<SH_CAP>(d, gamp, interp, hs, gm[t], acc, dgx, dgy);
-              if (src) { gbx[t] += dgx; gby[t] += dgy; }
+              if (src) { gbx[t] += cs * dgx; gby[t] += cs * dgy; }
             }
             wave_acc<SHPA_AMP + SH_MAXL>(acc, ac, cd.a_off, cd.n_acc);
           }
@@ -1086,8 +1101,8 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
 #pragma unroll
           for (int t = 0; t < T; ++t) {
             float dgx = 0.f, dgy = 0.f;
-            glu::light_vjp(cd.flags, d, src ? bx[t] : x[t], src ? by[t] : y[t], gm[t], acc, dgx, dgy);
-            if (src) { gbx[t] += dgx; gby[t] += dgy; }
+            glu::light_vjp(cd.flags, d, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]), gm[t], acc, dgx, dgy);
+            if (src) { gbx[t] += cs * dgx; gby[t] += cs * dgy; }
           }
           wave_acc<USER_MAXP>(acc, ac, cd.a_off, cd.n_acc);
 #endif
@@ -1099,8 +1114,8 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
 #pragma unroll
             for (int t = 0; t < T; ++t) {
               float dgx = 0.f, dgy = 0.f;
-              core_sersic_vjp<float>(d, src ? bx[t] : x[t], src ? by[t] : y[t], gm[t], acc, dgx, dgy);
-              if (src) { gbx[t] += dgx; gby[t] += dgy; }
+              core_sersic_vjp<float>(d, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]), gm[t], acc, dgx, dgy);
+              if (src) { gbx[t] += cs * dgx; gby[t] += cs * dgy; }
             }
             wave_acc<CSR_NACC>(acc, ac, cd.a_off);
           }
@@ -1113,11 +1128,11 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
 #pragma unroll
             for (int t = 0; t < T; t += 2) {
               SerStateV<v2f> stv;
-              (void)sersic_fwd_v<v2f>(d, src ? v2f{bx[t], bx[t + 1]} : v2f{x[t], x[t + 1]},
-                                      src ? v2f{by[t], by[t + 1]} : v2f{y[t], y[t + 1]}, stv);
+              (void)sersic_fwd_v<v2f>(d, v2f{light_point(src, cs, bx[t], x[t]), light_point(src, cs, bx[t + 1], x[t + 1])},
+                                      v2f{light_point(src, cs, by[t], y[t]), light_point(src, cs, by[t + 1], y[t + 1])}, stv);
               v2f dgx(0.f), dgy(0.f);
               sersic_vjp_v<v2f, true>(d, stv, v2f{gm[t], gm[t + 1]}, va, dgx, dgy);
-              if (src) { gbx[t] += dgx.x; gbx[t + 1] += dgx.y; gby[t] += dgy.x; gby[t + 1] += dgy.y; }
+              if (src) { gbx[t] += cs * dgx.x; gbx[t + 1] += cs * dgx.y; gby[t] += cs * dgy.x; gby[t + 1] += cs * dgy.y; }
             }
 #pragma unroll
             for (int k = 0; k < SER_NACC; ++k) acc[k] = va[k].x + va[k].y;
@@ -1128,8 +1143,8 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
 #pragma unroll
             for (int t = 0; t < T; ++t) {
               float dgx = 0.f, dgy = 0.f;
-              sersic_vjp(d, src ? bx[t] : x[t], src ? by[t] : y[t], gm[t], acc, dgx, dgy);
-              if (src) { gbx[t] += dgx; gby[t] += dgy; }
+              sersic_vjp(d, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]), gm[t], acc, dgx, dgy);
+              if (src) { gbx[t] += cs * dgx; gby[t] += cs * dgy; }
             }
           }
           wave_acc<SER_NACC>(acc, ac, cd.a_off);

@@ -126,6 +126,7 @@ int launch_main(const gl_model* m, const MainArgs& a, int B, int n_chunks, hipSt
   // models with user-written profiles, shapelets above n_max = 10, the cluster models in the gradient modes and the basis stack
   // go to the generic launcher first; then the specialised compositions; then the interpreter
   constexpr bool GRADM = (MODE == IMG_BWD || MODE == LL_GRAD);
+  // (a model whose sources have deflection scales of their own has static_id 0: gl_model_set_source_scales)
   const bool generic_first = m->has_user || m->shp_big || (GRADM && m->cluster && a.parts == 7u) || MODE == IMG_BASIS;
   m->last_main_user = -1;
   bool launched = false;  // a specialised kernel went out

@@ -51,6 +51,20 @@ int launch_generic(const gl_model* m, const MainArgs& a, dim3 grid, dim3 block, 
     m->last_main_fn = (const void*)&gl_clusterw_kernel<MODE, LENS_, SPW_, E_, W_>;                       \
     hipExtLaunchKernelGGL((gl_clusterw_kernel<MODE, LENS_, SPW_, E_, W_>), grid, block, (std::uint32_t)(sh), stream, ev0, ev1, 0, a, m->n_lens, m->n_src); \
   } while (0)
+#define GL_CLUSTERW_SCALED(LENS_, SPW_, E_, W_)                                                          \
+  do {                                                                                                 \
+    const size_t sh = sizeof(float) * (CW_XCHG_FLOATS + LENS_::kLdsFloats + 16 + m->A);                \
+    m->last_main_fn = (const void*)&gl_clusterw_scaled_kernel<MODE, LENS_, SPW_, E_, W_>;                \
+    hipExtLaunchKernelGGL((gl_clusterw_scaled_kernel<MODE, LENS_, SPW_, E_, W_>), grid, block, (std::uint32_t)(sh), stream, ev0, ev1, 0, a, m->n_lens, m->n_src); \
+  } while (0)
+    // sources with their own deflection scales: the scaled form of that kernel under the same fill rule, else the interpreter
+    if (!done && m->cluster && m->cluster_w && a.parts == 7u && a.src_scale) {
+      const int size = (m->n_lens <= 4 && m->n_src <= 8) ? 0 : (m->n_src <= 12 ? 1 : 2);
+      if (m->cluster == 2) { if (size == 0) GL_CLUSTERW_SCALED(CwLensNfw<1>, 2, true, 4); else if (size == 1) GL_CLUSTERW_SCALED(CwLensNfw<2>, 3, true, 3); else GL_CLUSTERW_SCALED(CwLensNfw<2>, 5, true, 2); }
+      else { if (size == 0) GL_CLUSTERW_SCALED(CwLensNfw<1>, 2, false, 4); else if (size == 1) GL_CLUSTERW_SCALED(CwLensNfw<2>, 3, false, 4); else GL_CLUSTERW_SCALED(CwLensNfw<2>, 5, false, 3); }
+      done = true;
+    }
+#undef GL_CLUSTERW_SCALED
     if (!done && m->cluster && m->cluster_w && a.parts == 7u) {  // ... with the components dealt over the four waves (gl_clusterw.hip.h)
       const int size = (m->n_lens <= 4 && m->n_src <= 8) ? 0 : (m->n_src <= 12 ? 1 : 2);
       if (m->cluster == 2) { if (size == 0) GL_CLUSTERW(CwLensNfw<1>, 2, true, 4); else if (size == 1) GL_CLUSTERW(CwLensNfw<2>, 3, true, 3); else GL_CLUSTERW(CwLensNfw<2>, 5, true, 2); }
@@ -58,7 +72,7 @@ int launch_generic(const gl_model* m, const MainArgs& a, dim3 grid, dim3 block, 
       done = true;
     }
 #undef GL_CLUSTERW
-    if (!done && m->cluster && a.parts == 7u) {  // N x same-kind cluster model: forward state of every component kept in registers
+    if (!done && m->cluster && a.parts == 7u && !a.src_scale) {  // N x same-kind cluster model: forward state of every component kept in registers
       const size_t sh = (size_t)64 * m->Apad * sizeof(float) + sizeof(float) * 2 * NFW_TAB_NODES;  // gradient columns + the h(X) table
 #define GL_CLUSTER(NH_, NS_, E_, W_)                                                                     \
   do {                                                                                                 \

@@ -140,6 +140,7 @@ struct gl_model {
   glk::DevBuf<int> d_src;
   glk::DevBuf<float> d_const;
   int static_id = 0;   // 0 = generic interpreter kernel, >0 = compile-time-specialised composition
+  int static_matched = 0;  // ... as matched at creation: static_id is 0 while the sources carry deflection scales (src_scaled)
   int static_variant = 0;
   int pair = 1;        // pixel-pair (packed fp32) form of the specialised kernels
   bool light_spherical = false;  // every light profile is the spherical Sersic: the pair kernels take their fast path
@@ -149,6 +150,14 @@ struct gl_model {
   int pos_J = 0, pos_F = 0, lens_params = 0;
   glk::DevBuf<float> d_pos;  // [4][J]: x, y, err_x, err_y
   glk::DevBuf<int> d_fam;    // [F+1]
+  std::vector<int> pos_fam_off;  // ... on the host
+  // per-source / per-family deflection scales c = [D_LS/D_S](z_source) / [D_LS/D_S](z_ref): sources and image families at their own
+  // redshifts behind one lens plane (gl_model_set_source_scales, gl_model_set_position_scales).  Empty buffers: every scale is 1 and
+  // every kernel runs as it did before the scales existed.
+  bool src_scaled = false;             // some source light has a scale != 1
+  glk::DevBuf<float> d_src_scale;      // [n_src], allocated only while src_scaled
+  bool pos_scaled = false;             // some image family has a scale != 1
+  glk::DevBuf<float> d_pos_scale;      // [J]: the scale of every image's family, allocated only while pos_scaled
   bool has_epl = false;
   int epl_comp = -1;     // the model's only EPL component, or -1 (none / several)
   int fam = 0;  // family level of the interpreter variant (gl_main_kernel FAM): 1 dPIE family / catalogues / series, 2 gl_extra.h

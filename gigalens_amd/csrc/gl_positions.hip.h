@@ -27,6 +27,9 @@ struct PosArgs {
   const float* ex;      // [J] position errors
   const float* ey;
   const int* fam_off;   // [F+1]
+  // [J] deflection scale c of every image's family (families at their own redshifts: beta = x - c sum alpha, A = I - c H), or
+  // null: one source plane, and the kernels compute exactly what they did without it
+  const float* fam_scale;
   float* w_pos;         // [B][J][6]  beta_x, beta_y, f_xx, f_xy, f_yx, f_yy
   float* w_adj;         // [B][J][3]  d ll/d beta_x, d ll/d beta_y, d ll/d det
   float* w_g;           // [B][J][P]
@@ -130,6 +133,11 @@ __global__ void __launch_bounds__(64) gl_pos_p1_kernel(PosArgs a) {
     const float ex = lens_kappa_excess<float>(a, cd, pf, a.px[j], a.py[j]);
     bx -= ax.v; by -= ay.v;
     fxx += ax.d[0] + ex; fxy += ax.d[1]; fyx += ay.d[0]; fyy += ay.d[1] + ex;
+  }
+  if (a.fam_scale) {  // deflection, Hessian and the dPIS excess times the family's scale before P2 forms mean beta and det A
+    const float c = a.fam_scale[j];
+    bx = a.px[j] + c * (bx - a.px[j]); by = a.py[j] + c * (by - a.py[j]);
+    fxx *= c; fxy *= c; fyx *= c; fyy *= c;
   }
   float* o = a.w_pos + (size_t)i * 6;
   o[0] = bx; o[1] = by; o[2] = fxx; o[3] = fxy; o[4] = fyx; o[5] = fyy;
@@ -321,7 +329,9 @@ __global__ void __launch_bounds__(64) gl_pos_p3_kernel(PosArgs a, int lens_param
   const float dbx = -ax.v.d[0], dby = -ay.v.d[0];
   const float ddet = -(1.f - q[5]) * (ax.d[0].d[0] + ex.d[0]) - (1.f - q[2]) * (ay.d[1].d[0] + ex.d[0]) -
                      q[4] * ax.d[1].d[0] - q[3] * ay.d[0].d[0];
-  a.w_g[((size_t)b * a.J + j) * a.P + col] = adj[0] * dbx + adj[1] * dby + adj[2] * ddet;
+  // (q holds the scaled Hessian; the derivatives of c alpha and c H are c times those of alpha and H)
+  const float g = adj[0] * dbx + adj[1] * dby + adj[2] * ddet;
+  a.w_g[((size_t)b * a.J + j) * a.P + col] = a.fam_scale ? a.fam_scale[j] * g : g;
 }
 
 __global__ void __launch_bounds__(64) gl_pos_p4_kernel(PosArgs a, int lens_params) {

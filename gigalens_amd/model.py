@@ -77,9 +77,15 @@ class PhysicalModel(PhysicalModelBase):
     """src/gigalens/tf/model.py:276-306: constants are cast to float32."""
 
     def __init__(self, lenses, lens_light, source_light, lenses_constants: List[Dict] = None,
-                 lens_light_constants: List[Dict] = None, source_light_constants: List[Dict] = None):
+                 lens_light_constants: List[Dict] = None, source_light_constants: List[Dict] = None,
+                 source_light_scales=None):
+        """``source_light_scales`` (beyond the reference): one deflection scale per ``source_light`` entry, for sources at different
+        redshifts behind the one lens plane -- source s is rendered at ``beta_s = theta - c_s sum alpha``
+        (``gigalens_amd.cosmology.deflection_scale`` gives c from the redshifts).  Default: all 1, the reference's single plane."""
         super().__init__(lenses, lens_light, source_light, lenses_constants, lens_light_constants,
                          source_light_constants)
+        self.source_light_scales = _native.deflection_scales(source_light_scales, len(source_light), "source_light_scales")
+        self._source_scales_given = source_light_scales is not None
         cast = lambda ds: [{k: np.asarray(v, dtype=np.float32) for k, v in d.items()} for d in ds]
         self.lenses_constants = cast(self.lenses_constants)
         self.lens_light_constants = cast(self.lens_light_constants)
@@ -192,7 +198,10 @@ class ForwardProbModel(ProbabilisticModel):
 
     def __init__(self, prior, observed_image=None, background_rms=None, exp_time=None, error_map=None,
                  centroids_x=None, centroids_y=None, centroids_errors_x=None, centroids_errors_y=None,
-                 include_pixels=True, include_positions=True):
+                 include_pixels=True, include_positions=True, centroids_scales=None):
+        """``centroids_scales`` (beyond the reference): one deflection scale per image family of ``centroids_x`` -- a family at its
+        own redshift is traced with ``beta = theta - c_f alpha`` and ``A = I - c_f H`` in the position likelihood, the predicted
+        positions and the image-plane rms.  Default: all 1."""
         super().__init__(prior)
         self.include_pixels = include_pixels
         self.include_positions = include_positions
@@ -220,6 +229,11 @@ class ForwardProbModel(ProbabilisticModel):
             self.centroids_errors_x = [np.broadcast_to(e, x.shape).copy() for e, x in zip(f32(centroids_errors_x), self.centroids_x)]
             self.centroids_errors_y = [np.broadcast_to(e, x.shape).copy() for e, x in zip(f32(centroids_errors_y), self.centroids_y)]
             self.n_position = 2.0 * float(sum(x.size for x in self.centroids_x))  # tf/model.py:74
+        if centroids_scales is not None and self.centroids_x is None:
+            raise ValueError("centroids_scales needs centroids_x/centroids_y (include_positions=True)")
+        n_fam = len(self.centroids_x) if self.centroids_x is not None else 0
+        self.centroids_scales = _native.deflection_scales(centroids_scales, n_fam, "centroids_scales")
+        self._centroids_scales_given = centroids_scales is not None
         self._flat = prior.flat(self.device)
         example = prior.sample(seed=0)
         self.pack_bij = _PackBijector(example)
@@ -283,6 +297,8 @@ class ForwardProbModel(ProbabilisticModel):
         model = simulator._model
         if getattr(model, "_positions_owner", None) is not self:
             model.set_positions(self.centroids_x, self.centroids_y, self.centroids_errors_x, self.centroids_errors_y)
+            if self._centroids_scales_given:
+                model.set_position_scales(self.centroids_scales)
             model._positions_owner = self
         return model
 
@@ -304,16 +320,23 @@ class ForwardProbModel(ProbabilisticModel):
             raise ValueError("predicted_positions needs a model built with centroids_x/centroids_y")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         sx, sy = self._family_sources(simulator, packed)
+        if self._centroids_scales_given:  # every family on its own plane
+            solver_kwargs = dict(solver_kwargs, deflection_scale=self.centroids_scales)
         x, y, mu, n = simulator.image_positions(packed, sx, sy, **solver_kwargs)
         return [(x[:, f], y[:, f], mu[:, f], n[:, f]) for f in range(len(self.centroids_x))]
 
     def _family_sources(self, simulator, packed):
-        """Source of every family: the barycentre of its back-traced observed images, ``[B, F]`` x and y."""
+        """Source of every family: the barycentre of its back-traced observed images (on the family's own plane), ``[B, F]`` x and y."""
         sx, sy = [], []
-        for cx, cy in zip(self.centroids_x, self.centroids_y):
+        for cx, cy, c in zip(self.centroids_x, self.centroids_y, self.centroids_scales):
             maps = simulator._model.lens_maps(packed, cx.reshape(-1, 1), cy.reshape(-1, 1))  # (6, J_f, B)
-            sx.append(maps[0].mean(dim=0))
-            sy.append(maps[1].mean(dim=0))
+            bx, by = maps[0], maps[1]
+            if c != 1.0:  # beta = theta + c (beta_1 - theta)
+                tx = torch.as_tensor(cx.reshape(-1, 1), device=bx.device)
+                ty = torch.as_tensor(cy.reshape(-1, 1), device=bx.device)
+                bx, by = tx + float(c) * (bx - tx), ty + float(c) * (by - ty)
+            sx.append(bx.mean(dim=0))
+            sy.append(by.mean(dim=0))
         return torch.stack(sx, dim=1), torch.stack(sy, dim=1)
 
     def predicted_time_delays(self, simulator, params, time_delay_distance=None, **solver_kwargs):
@@ -323,6 +346,9 @@ class ForwardProbModel(ProbabilisticModel):
         scalar or ``[B]``), in days (``LensSimulator.time_delays``, which ``solver_kwargs`` go to).  Forward only."""
         if self.centroids_x is None:
             raise ValueError("predicted_time_delays needs a model built with centroids_x/centroids_y")
+        if np.any(self.centroids_scales != 1.0):
+            raise NotImplementedError("predicted_time_delays: the Fermat potential of a scaled source plane (centroids_scales != 1) "
+                                      "is not served; time delays stay single-plane")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         if packed.requires_grad:
             raise NotImplementedError("predicted_time_delays is a forward-only diagnostic (no gradient)")

@@ -168,6 +168,8 @@ class LensSimulator(LensSimulatorInterface):
                 self._model.set_series(i, lens.series_var_0, lens._coefs)
             elif getattr(lens, "_kind", 0) == 9:  # galaxy catalogues of ScalingRelation lenses (fused dPIE-family kernels)
                 self._model.set_catalogue(i, *lens._catalogue())
+        if getattr(phys_model, "_source_scales_given", False):  # sources on planes of their own (PhysicalModel source_light_scales)
+            self._model.set_source_scales(phys_model.source_light_scales)
         self._layout = phys_model._packing()
         assert self._layout.P == self._model.P
 
@@ -175,12 +177,22 @@ class LensSimulator(LensSimulatorInterface):
     def pack(self, params: Dict[str, List[Dict]]):
         return self._layout.pack(params, self.bs, self.device)
 
-    def beta(self, x, y, lens_params: List[Dict]):
-        """tf/simulator.py:72-78 on arbitrary points (plugin-level kernels, one per lens)."""
+    @staticmethod
+    def _scale(deflection_scale):
+        """A scalar ``deflection_scale`` keyword as a float (``ValueError`` unless finite and > 0)."""
+        return float(_native.deflection_scales(deflection_scale, 1, "deflection_scale")[0])
+
+    def beta(self, x, y, lens_params: List[Dict], deflection_scale=1.0):
+        """tf/simulator.py:72-78 on arbitrary points (plugin-level kernels, one per lens).  ``deflection_scale`` (beyond the
+        reference, as on the methods below): the scale c of a source plane at another redshift than the model's reference plane
+        (``gigalens_amd.cosmology.deflection_scale``): ``beta = theta - c sum alpha``, Hessian ``c H``."""
+        cs = self._scale(deflection_scale)
         beta_x, beta_y = x, y
         for lens, p, c in zip(self.phys_model.lenses, lens_params, self.phys_model.lenses_constants):
             f_xi, f_yi = lens.deriv(x, y, **p, **c)
             beta_x, beta_y = beta_x - f_xi, beta_y - f_yi
+        if cs != 1.0:
+            beta_x, beta_y = x + cs * (beta_x - x), y + cs * (beta_y - y)
         return beta_x, beta_y
 
     def _lens_maps(self, x, y, lens_params):
@@ -204,19 +216,25 @@ class LensSimulator(LensSimulatorInterface):
                 lens._hessian_bound = lens._hcoefs
         return self._model.lens_maps(packed, None, None)
 
-    def magnification(self, x, y, lens_params: List[Dict]):
+    def _hessian(self, x, y, lens_params, deflection_scale):
+        """``f_xx, f_xy, f_yx, f_yy`` of ``_lens_maps`` on the plane of ``deflection_scale`` (linear in it: ``c H``)."""
+        cs = self._scale(deflection_scale)
+        h = self._lens_maps(x, y, lens_params)[2:]
+        return tuple(h) if cs == 1.0 else tuple(cs * f for f in h)
+
+    def magnification(self, x, y, lens_params: List[Dict], deflection_scale=1.0):
         """tf/simulator.py:80-91: ``1 / det(1 - Hessian)`` at ``(x, y)`` (trailing axis = batch)."""
-        _, _, fxx, fxy, fyx, fyy = self._lens_maps(x, y, lens_params)
+        fxx, fxy, fyx, fyy = self._hessian(x, y, lens_params, deflection_scale)
         return 1.0 / ((1 - fxx) * (1 - fyy) - fxy * fyx)
 
-    def convergence(self, x, y, lens_params: List[Dict]):
+    def convergence(self, x, y, lens_params: List[Dict], deflection_scale=1.0):
         """tf/simulator.py:93-98 (sum of the lenses' ``(f_xx + f_yy) / 2``, tf/profile.py:30-34)."""
-        _, _, fxx, _, _, fyy = self._lens_maps(x, y, lens_params)
+        fxx, _, _, fyy = self._hessian(x, y, lens_params, deflection_scale)
         return 0.5 * (fxx + fyy)
 
-    def shear(self, x, y, lens_params: List[Dict]):
+    def shear(self, x, y, lens_params: List[Dict], deflection_scale=1.0):
         """tf/simulator.py:100-107: ``(gamma1, gamma2) = ((f_xx - f_yy)/2, f_xy)`` (tf/profile.py:36-42)."""
-        _, _, fxx, fxy, _, fyy = self._lens_maps(x, y, lens_params)
+        fxx, fxy, _, fyy = self._hessian(x, y, lens_params, deflection_scale)
         return 0.5 * (fxx - fyy), fxy
 
     # default Newton tolerance |beta(theta) - beta_s| of image_positions, in units of the float32 spacing at the window's largest
@@ -243,7 +261,7 @@ class LensSimulator(LensSimulatorInterface):
         return sx, sy
 
     def image_positions(self, lens_params, source_x, source_y, *, window=None, num_cells=None, max_images=8, tol=None,
-                        max_iter=30, strict=False):
+                        max_iter=30, strict=False, deflection_scale=1.0):
         """Solve the lens equation beta(theta) = beta_s for every sample (beyond the reference: it only maps theta -> beta).
 
         ``lens_params``: the ``lens_mass`` list of dicts, a nested dict with a ``lens_mass`` entry, or packed ``[B, P]`` rows.
@@ -252,7 +270,8 @@ class LensSimulator(LensSimulatorInterface):
         Returns ``x, y, mu`` ``[B, S, max_images]`` (images sorted by x then y, NaN-padded; ``mu`` is the signed
         magnification, the quantity ``magnification`` returns) and ``n`` ``[B, S]``.  Images that were found but could not be
         stored or refined (``max_images`` exceeded, Newton not converged, converged outside the window) warn, or raise
-        ``RuntimeError`` with ``strict=True``.  Forward only (no gradient)."""
+        ``RuntimeError`` with ``strict=True``.  ``deflection_scale``: a scalar, or one value per source ``[S]`` -- source s is solved
+        on its own plane ``beta_s(theta) = theta - c_s sum alpha`` (``mu`` is that plane's magnification).  Forward only (no gradient)."""
         if torch.is_tensor(lens_params):
             packed = lens_params
         elif isinstance(lens_params, dict):
@@ -270,8 +289,11 @@ class LensSimulator(LensSimulatorInterface):
             num_cells = 2 * int(self.numPix)
         if tol is None:
             tol = self.IMAGE_TOL_EPS * float(np.finfo(np.float32).eps) * max(abs(v) for v in window)
+        S = sx.shape[1]
+        scales = np.asarray(deflection_scale, dtype=np.float32)
+        scales = _native.deflection_scales(np.broadcast_to(scales, (S,)) if scales.ndim == 0 else scales, S, "deflection_scale")
         out, n, dropped = self._model.image_positions(packed, sx, sy, window, int(num_cells), int(max_images), float(tol),
-                                                      int(max_iter))
+                                                      int(max_iter), scales=scales if np.any(scales != 1.0) else None)
         n_drop = int(dropped.sum())
         if n_drop:
             msg = (f"image_positions: {n_drop} image(s) found but not returned over {int((dropped > 0).sum())} "
@@ -282,7 +304,7 @@ class LensSimulator(LensSimulatorInterface):
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
         return out[..., 0], out[..., 1], out[..., 2], n
 
-    def critical_curves(self, lens_params, *, window=None, num_cells=None, max_segments=None, strict=False):
+    def critical_curves(self, lens_params, *, window=None, num_cells=None, max_segments=None, strict=False, deflection_scale=1.0):
         """Critical curves (``det(I - H) = 0``) and caustics of every sample (beyond the reference), as line segments.
 
         ``lens_params`` as ``image_positions`` takes them.  ``window`` = ``(x_lo, x_hi, y_lo, y_hi)`` (default: the bounding box of
@@ -296,9 +318,11 @@ class LensSimulator(LensSimulatorInterface):
         is one loop of that kind; per-loop areas: ``chain_curves``).  Segments are oriented with ``det < 0`` on their left; ``chain_curves`` joins them into polylines.
         Segments beyond ``max_segments`` and cells skipped because a vertex is singular while its neighbours differ in sign warn,
         or raise ``RuntimeError`` with ``strict=True``.  Built-in kinds and dPIE-family catalogues; series expansions, user-written
-        bodies and run-time compiled ScalingRelation member loops raise ``_native.UnsupportedLensError``.  Forward only."""
+        bodies and run-time compiled ScalingRelation member loops raise ``_native.UnsupportedLensError``.  ``deflection_scale``: the
+        curves of the source plane with that scale, ``det(I - c H) = 0`` and ``beta = theta - c sum alpha``.  Forward only."""
         packed = self._lens_rows(lens_params)
         self._forward_only("critical_curves", packed)
+        cs = self._scale(deflection_scale)
         if window is None:
             window = (float(self.img_X.min()), float(self.img_X.max()), float(self.img_Y.min()), float(self.img_Y.max()))
         window = tuple(float(v) for v in window)
@@ -307,7 +331,8 @@ class LensSimulator(LensSimulatorInterface):
         if max_segments is None:
             max_segments = 8 * int(num_cells)
         seg, cau, kind, n, dropped, flagged, opened, area = self._model.critical_curves(packed, window, int(num_cells),
-                                                                                         int(max_segments))
+                                                                                         int(max_segments),
+                                                                                         scale=None if cs == 1.0 else cs)
         n_drop, n_flag = int(dropped.sum()), int(flagged.sum())
         if n_drop or n_flag:
             msg = (f"critical_curves: {n_drop} segment(s) not returned over {int((dropped > 0).sum())} sample(s) "
@@ -324,7 +349,7 @@ class LensSimulator(LensSimulatorInterface):
 
     def einstein_radius(self, lens_params, **kwargs):
         """Effective Einstein radius ``sqrt(A / pi)`` ``[B]`` of every sample (beyond the reference), ``A`` the area the tangential
-        critical curve encloses (``critical_curves``, which takes ``kwargs``).  NaN where the tangential curve is not closed inside
+        critical curve encloses (``critical_curves``, which takes ``kwargs``, ``deflection_scale`` among them).  NaN where the tangential curve is not closed inside
         the window or absent; such samples are counted in a ``RuntimeWarning``."""
         res = self.critical_curves(lens_params, **kwargs)
         has_tangential = (res["kind"] == 0).any(dim=1)

@@ -177,6 +177,23 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
 int gl_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
                          float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Source planes at different redshifts behind the one lens plane (beyond the reference).  A source light or an image family at
+ * redshift z_s sees the deflection scaled by  c = [D_LS / D_S](z_s) / [D_LS / D_S](z_ref):  beta = theta - c sum alpha,
+ * A = I - c H.  The scales are constants of the model (HOST pointers, copied), each finite and > 0; all 1 (or never set) is the
+ * single source plane, served by exactly the kernels and arithmetic of a model without scales.
+ *   gl_model_set_source_scales    one scale per source light component (n_src = the model's): every pixel-grid call renders
+ *                                 source s at its own beta_s and carries its cotangent into the lens gradients times c_s.  A model
+ *                                 with some scale != 1 runs the interpreter kernel (or gl_clusterw_scaled_kernel for N x NFW |
+ *                                 N x Sersic models in the gradient modes), never a specialised composition.
+ *                                 The launch plan changes with it (chunking as for the interpreter, no tapered dispatch), and
+ *                                 with the plan the workspace: size it again with gl_workspace_bytes after this call.
+ *                                 GL_EUNSUPPORTED: some scale != 1 on a model with user-written profiles.
+ *   gl_model_set_position_scales  one scale per image family of gl_model_set_positions, which must have been called (and which
+ *                                 resets the scales to 1): the image-position likelihood and its gradient use c_f of image j's family.
+ * GL_EINVAL: a count that does not match, a scale that is not finite or not > 0. */
+int gl_model_set_source_scales(gl_model* m, const float* scales, int n_src);
+int gl_model_set_position_scales(gl_model* m, const float* scales, int n_families);
+
 /* ScalingRelation.hessian on arbitrary points (scaling_relation.py:72-83): out [4][n_pts][B] = f_xx, f_xy, f_yx, f_yy
  * summed over the catalogue; other arguments as gl_scaled_eval. */
 int gl_scaled_hessian(int base_kind, int n_galaxies, const int32_t scale_col[3], const float* table_dev, const float* x,
@@ -295,6 +312,14 @@ size_t gl_image_positions_workspace_bytes(const gl_model* m, int B, int n_src, i
 int gl_image_positions(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
                        float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images, float tol, int max_iter,
                        float* out, int* n_images, int* n_dropped, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* ... with one deflection scale per source, src_scale [n_src] (HOST; null = all 1 = gl_image_positions): source s is solved on its
+ * own plane, beta_s(theta) = theta - c_s sum alpha(theta), from the one map of the sample (the scan forms beta_s at the vertices,
+ * Newton scales deflection and Hessian; mu = 1 / det(I - c_s H)).  The scales are copied on hip_stream into the call's workspace
+ * (gl_image_positions_workspace_bytes holds room for them): the call is as re-entrant as gl_image_positions. */
+int gl_image_positions_scaled(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                              const float* src_scale, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images,
+                              float tol, int max_iter, float* out, int* n_images, int* n_dropped, void* workspace,
+                              size_t workspace_bytes, void* hip_stream);
 
 /* Critical curves and caustics (beyond the reference): the image-plane locus D = det(I - H) = 0 (the Hessian as gl_lens_maps has
  * it) of every sample, contoured by marching squares on n_cells x n_cells cells over the window [x_lo, x_hi] x [y_lo, y_hi], and
@@ -324,6 +349,12 @@ size_t gl_critical_curves_workspace_bytes(const gl_model* m, int B, int n_cells,
 int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
                        int max_segments, float* seg, float* cau, int* kind, int* n_seg, int* n_dropped, int* n_flagged, int* open,
                        float* area, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* ... of the source plane with deflection scale `scale` (finite, > 0; 1 = gl_critical_curves): D = det(I - scale H), the caustic is
+ * beta = theta - scale sum alpha, the curve kind comes from 1 - scale kappa. */
+int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi,
+                              int n_cells, int max_segments, float scale, float* seg, float* cau, int* kind, int* n_seg,
+                              int* n_dropped, int* n_flagged, int* open, float* area, void* workspace, size_t workspace_bytes,
+                              void* hip_stream);
 
 /* Plugin-level point evaluation, the reference's MassProfile.deriv / LightProfile.light called on
  * arbitrary coordinates (tests/test_profiles.py calls exactly these):
