@@ -16,6 +16,8 @@ _LIB_PATH = os.environ.get("GIGALENS_HIP_LIB") or os.path.join(os.path.dirname(o
 _lib = None
 
 GL_FLAG_SHAPELETS_INTERPOLATE = 1
+GL_FLAG_INTERPOL_LINEAR = 1
+GL_INTERPOL = 21
 
 
 class NativeLibraryError(RuntimeError):
@@ -110,6 +112,9 @@ SYMBOLS = {
     "gl_lstsq_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_size_t, c_void_p]),
     "gl_model_set_catalogue": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_float)]),
+    "gl_model_set_light_image": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float)]),
+    "gl_interpol_eval": (c_int, [POINTER(gl_component), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                 c_void_p, c_int, c_void_p]),
     "gl_scaled_eval": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gl_scaled_hessian": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
@@ -526,6 +531,22 @@ def profile_basis(profile, x, y, kwargs):
     return out.reshape((int(profile.depth),) + tuple(out_shape))
 
 
+def interpol_eval(profile, x, y, kwargs):
+    """``Interpolated.light`` on points (gl_interpol_eval): the surface brightness, or with ``use_lstsq`` the unit-amplitude basis
+    image with a leading axis of 1.  Forward only."""
+    dev = device()
+    comp = component_of(profile)
+    basis = bool(profile.use_lstsq)
+    xb, yb, P, B, out_shape = _broadcast_points(profile, x, y, kwargs, list(profile.params), dev, columns=profile._native_params())
+    if profile._dev_table is None or profile._dev_table.device != dev:  # the image with its two-pixel zero apron
+        profile._dev_table = torch.nn.functional.pad(torch.from_numpy(profile.image), (2, 2, 2, 2)).to(dev).contiguous()
+    h, w = profile.image.shape
+    out = torch.empty_like(xb)
+    _check(lib().gl_interpol_eval(ctypes.byref(comp), h, w, _ptr(profile._dev_table), _ptr(xb), _ptr(yb), xb.shape[0], B, 1, _ptr(P),
+                                  _ptr(out), int(basis), _stream()))
+    return out.reshape((1,) + tuple(out_shape)) if basis else out.reshape(out_shape)
+
+
 # --------------------------------------------------------------------------------------------------
 # model handle
 # --------------------------------------------------------------------------------------------------
@@ -556,7 +577,8 @@ class Model:
         with torch.cuda.device(self.device):
             if bodies:  # user-written profiles: the interpreter kernel is compiled with them now (seconds, once)
                 barr = (ctypes.c_char_p * len(bodies))(*[b.encode() for b in bodies])
-                _check(L.gl_model_create_user(arr, n_lens, n_lens_light, n_src, ctypes.byref(g), barr, len(bodies), ctypes.byref(h)))
+                # (GL_EUNSUPPORTED -- user-written profiles beside an Interpolated light -- raises UnsupportedLensError)
+                _check_potential(L.gl_model_create_user(arr, n_lens, n_lens_light, n_src, ctypes.byref(g), barr, len(bodies), ctypes.byref(h)))
             else:
                 _check(L.gl_model_create(arr, n_lens, n_lens_light, n_src, ctypes.byref(g), ctypes.byref(h)))
         self._h = h
@@ -580,6 +602,13 @@ class Model:
             _check(lib().gl_model_set_catalogue(self._h, int(component), int(base_kind), int(t.shape[0]), col_arr,
                                                 t.ctypes.data_as(POINTER(c_float))))
         self._ws = {}  # the workspace grows with the catalogue
+
+    def set_light_image(self, component, image):
+        """Attach the image of a GL_INTERPOL light (gl_model_set_light_image): ``image`` a 2-D float32 host array."""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _check(lib().gl_model_set_light_image(self._h, int(component), int(img.shape[0]), int(img.shape[1]),
+                                                  img.ctypes.data_as(POINTER(c_float))))
 
     def _points(self, x, y, B):
         """``x, y`` broadcastable to ``(..., B)`` as contiguous ``[n_pts, B]`` tensors, and that shape."""

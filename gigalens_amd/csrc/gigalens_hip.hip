@@ -212,17 +212,21 @@ MainArgs base_args(const gl_model* m, const Workspace& w, int chunk) {
   a.G = m->G;
   a.scaled_first = m->cats.empty() ? -1 : m->cats[0].dev.comp;
   a.series = m->d_series;
+  a.interp = m->d_interp;
   a.src_scale = m->src_scaled ? m->d_src_scale.get() : nullptr;
   return a;
 }
 
-// "The model is ready": every GL_SCALED lens has its catalogue and (with_series) every GL_SERIES lens its coefficient field.  The
+// "The model is ready": every GL_SCALED lens has its catalogue, every GL_INTERPOL light its image and (with_series) every GL_SERIES
+// lens its coefficient field.  The
 // pixel-grid entry points report how many are missing and the call that attaches them (counted = true), the others name the kind.
 int check_ready(const gl_model* m, bool with_series, bool counted) {
   const int no_cat = m->n_scaled - (int)m->cats.size(), no_field = m->n_series - m->n_series_set;
   if (no_cat)
     return counted ? fail(GL_EINVAL, "%d GL_SCALED component(s) without a catalogue (gl_model_set_catalogue)", no_cat)
                    : fail(GL_EINVAL, "GL_SCALED component without a catalogue");
+  if (m->n_interp != m->n_interp_set)
+    return fail(GL_EINVAL, "%d GL_INTERPOL component(s) without an image (gl_model_set_light_image)", m->n_interp - m->n_interp_set);
   if (with_series && no_field)
     return counted ? fail(GL_EINVAL, "%d GL_SERIES component(s) without a coefficient field (gl_model_set_series)", no_field)
                    : fail(GL_EINVAL, "GL_SERIES component without a coefficient field");
@@ -277,13 +281,13 @@ int run_prep(const gl_model* m, const float* params, const float* z, int B, cons
     const int split_rank = plan.tail_rows ? plan.tail_from : -1;
     hipLaunchKernelGGL(gl_prep_wave_kernel, dim3((B + 3) / 4 + (ord ? 1 : 0)), dim3(256), rows, stream, m->d_comps.get(), n_comp,
                        params, z, d_z, zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp,
-                       ord ? w.order : nullptr, rows ? 1 : 0, split_rank);
+                       ord ? w.order : nullptr, rows ? 1 : 0, split_rank, m->d_interp.get());
   } else if (z) {  // thread per component
     hipLaunchKernelGGL(gl_zprep_kernel, dim3((B * n_comp + 127) / 128), dim3(128), 0, stream, m->d_comps.get(), n_comp, z, d_z,
-                       zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp);
+                       zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp, m->d_interp.get());
   } else {
     hipLaunchKernelGGL(gl_prep_kernel, dim3((B * n_comp + 127) / 128), dim3(128), 0, stream, m->d_comps.get(), n_comp, params,
-                       m->P, B, w.derived, m->D, cost, m->epl_comp);
+                       m->P, B, w.derived, m->D, cost, m->epl_comp, m->d_interp.get());
   }
   GL_HIP(hipGetLastError());
   return run_galprep(m, z ? w.params : params, B, w, stream);
@@ -649,7 +653,7 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
     const gl_component& c = comps[i];
     const bool mass = i < n_lens;
     const bool is_mass_kind = (c.kind >= GL_EPL && c.kind <= GL_TNFW) || c.kind == GL_USER_MASS;
-    const bool is_light_kind = (c.kind >= GL_SERSIC && c.kind <= GL_CORE_SERSIC) || c.kind == GL_USER_LIGHT;
+    const bool is_light_kind = (c.kind >= GL_SERSIC && c.kind <= GL_CORE_SERSIC) || c.kind == GL_USER_LIGHT || c.kind == GL_INTERPOL;
     if ((mass && !is_mass_kind) || (!mass && !is_light_kind))
       return fail(GL_EINVAL, "component %d: kind %d is not a %s profile", i, c.kind, mass ? "mass" : "light");
     int iparam = c.iparam;
@@ -665,7 +669,7 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
     }
     if (c.kind == GL_EPL) { m->epl_comp = m->has_epl ? -2 : i; m->has_epl = true; }
     if (c.kind >= GL_DPIS && c.kind <= GL_SERIES) m->fam = std::max(m->fam, 1);
-    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC) m->fam = 2;
+    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC || c.kind == GL_INTERPOL) m->fam = 2;
     if (c.kind == GL_SERIES && (iparam < 0 || iparam > SERIES_MAX_ORDER))
       return fail(GL_EINVAL, "component %d: series order %d outside [0, %d]", i, iparam, SERIES_MAX_ORDER);
     if (c.kind == GL_SCALED) {
@@ -695,6 +699,12 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
       m->series_buf.emplace_back();
       m->series_comp.push_back(i);
     }
+    if (c.kind == GL_INTERPOL) {  // table slot; the table itself arrives with gl_model_set_light_image
+      cd.iparam = m->n_interp++;
+      cd.flags = c.flags & GL_FLAG_INTERPOL_LINEAR;
+      m->interp.push_back(InterpDev{nullptr, 0, 0});
+      m->interp_buf.emplace_back();
+    }
     cd.lin_off = (int)m->lin_cols.size();
     for (int k = 0; k < kind_num_linear(c.kind, iparam); ++k) m->lin_cols.push_back(p_off + kind_linear_col(c.kind, iparam) + k);
     // a user-written light whose last parameter is declared the linear amplitude (gl_component::reserved): one basis image
@@ -704,6 +714,9 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
     a_off += cd.n_acc;
     m->comps.push_back(cd);
   }
+  if (m->has_user && m->n_interp)
+    return fail(GL_EUNSUPPORTED, "a model that mixes user-written profiles with GL_INTERPOL lights is not served: the run-time "
+                                 "compiled kernels carry no image tables");
   m->P = p_off;
   for (int i = 0; i < n_lens; ++i) m->lens_params += m->comps[i].n_par;
   m->D = std::max(d_off, 4);
@@ -1541,6 +1554,54 @@ int gl_model_set_series_hessian(gl_model* m, int component, const float* coeffs_
   return GL_OK;
 }
 
+int gl_model_set_light_image(gl_model* m, int component, int h, int w, const float* image_host) {
+  if (!m || !image_host) return fail(GL_EINVAL, "null argument");
+  if (component < m->n_lens || component >= (int)m->comps.size() || m->comps[component].kind != K_INTERPOL)
+    return fail(GL_EINVAL, "component %d is not a GL_INTERPOL light", component);
+  if (h < 1 || h > GL_INTERPOL_MAX_SIDE || w < 1 || w > GL_INTERPOL_MAX_SIDE)
+    return fail(GL_EINVAL, "image of %d x %d pixels: height and width must lie in 1..%d", h, w, GL_INTERPOL_MAX_SIDE);
+  for (size_t i = 0; i < (size_t)h * w; ++i)
+    if (!std::isfinite(image_host[i])) return fail(GL_EINVAL, "image pixel %zu is not finite", i);
+  // the two-pixel zero apron is added here, on the host: an in-range lane of the kernels needs no per-tap bounds test
+  const int ws = w + 2 * glp::INT_APRON, hs = h + 2 * glp::INT_APRON;
+  std::vector<float> padded((size_t)hs * ws, 0.f);
+  for (int j = 0; j < h; ++j)
+    std::copy(image_host + (size_t)j * w, image_host + (size_t)(j + 1) * w, padded.begin() + (size_t)(j + glp::INT_APRON) * ws + glp::INT_APRON);
+  const int slot = m->comps[component].iparam;
+  glk::DevBuf<float>& buf = m->interp_buf[slot];
+  const bool first = !buf;
+  GL_HIP(buf.upload(padded.data(), padded.size()));
+  m->interp[slot] = InterpDev{buf.get(), h, w};
+  if (first) ++m->n_interp_set;
+  if (!m->d_interp) GL_HIP(m->d_interp.alloc(m->interp.size()));
+  GL_HIP(m->d_interp.write(m->interp.data(), m->interp.size()));
+  return GL_OK;
+}
+
+int gl_interpol_eval(const gl_component* comp, int h, int w, const float* image_dev, const float* x, const float* y,
+                     int64_t n_pts, int B, int xy_batched, const float* params, float* out, int basis, void* hip_stream) {
+  if (!comp || !image_dev || !x || !y || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (comp->kind != GL_INTERPOL) return fail(GL_EINVAL, "kind %d is not GL_INTERPOL", comp->kind);
+  if (n_pts <= 0 || B <= 0) return fail(GL_EINVAL, "n_pts and B must be positive");
+  if (h < 1 || h > GL_INTERPOL_MAX_SIDE || w < 1 || w > GL_INTERPOL_MAX_SIDE)
+    return fail(GL_EINVAL, "image of %d x %d pixels: height and width must lie in 1..%d", h, w, GL_INTERPOL_MAX_SIDE);
+  CompDesc cd{};
+  cd.kind = comp->kind;
+  cd.flags = comp->flags & GL_FLAG_INTERPOL_LINEAR;
+  cd.n_par = kind_num_params(comp->kind, 0);
+  const InterpDev tb{image_dev, h, w};
+  const long long total = (long long)n_pts * B;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (basis)
+    hipLaunchKernelGGL(gl_basis_point_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, cd, x, y, (long long)n_pts, B,
+                       xy_batched, params, out, (const float*)nullptr, 0, tb);
+  else
+    hipLaunchKernelGGL(gl_point_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, cd, x, y, (long long)n_pts, B, xy_batched,
+                       params, out, (float*)nullptr, (const float*)nullptr, 0, tb);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
 int gl_model_set_series(gl_model* m, int component, float r0, const float* coeffs_dev) {
   if (!m || !coeffs_dev) return fail(GL_EINVAL, "null argument");
   if (component < 0 || component >= m->n_lens || m->comps[component].kind != K_SERIES)
@@ -2085,6 +2146,7 @@ int gl_profile_eval(const gl_component* comp, const float* x, const float* y, in
   if (npar < 0) return fail(GL_EINVAL, "unknown profile kind %d", comp->kind);
   if (comp->kind == GL_SCALED) return fail(GL_EINVAL, "GL_SCALED needs its catalogue: use gl_scaled_eval");
   if (comp->kind == GL_SERIES) return fail(GL_EINVAL, "GL_SERIES needs its coefficient field: use gl_series_eval");
+  if (comp->kind == GL_INTERPOL) return fail(GL_EINVAL, "GL_INTERPOL needs its image: use gl_interpol_eval");
   const bool mass = comp->kind <= GL_DPIEP || comp->kind == GL_NFW_ELLIPSE || comp->kind == GL_TNFW;
   if (mass && !out1) return fail(GL_EINVAL, "out1 is required for mass profiles");
   const CompDesc cd = point_comp(comp);
@@ -2097,7 +2159,7 @@ int gl_profile_eval(const gl_component* comp, const float* x, const float* y, in
     return rc_tab;
   long long total = (long long)n_pts * B;
   hipLaunchKernelGGL(gl_point_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, cd, x, y,
-                     (long long)n_pts, B, xy_batched, params, out0, mass ? out1 : nullptr, s_tab, s_stride);
+                     (long long)n_pts, B, xy_batched, params, out0, mass ? out1 : nullptr, s_tab, s_stride, InterpDev{nullptr, 0, 0});
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -2175,6 +2237,7 @@ int gl_profile_basis(const gl_component* comp, const float* x, const float* y, i
   int npar = kind_num_params(comp->kind, comp->iparam);
   if (npar < 0) return fail(GL_EINVAL, "unknown profile kind %d", comp->kind);
   if (kind_num_linear(comp->kind, comp->iparam) <= 0) return fail(GL_EINVAL, "kind %d has no linear amplitudes", comp->kind);
+  if (comp->kind == GL_INTERPOL) return fail(GL_EINVAL, "GL_INTERPOL needs its image: use gl_interpol_eval");
   const CompDesc cd = point_comp(comp);
   float* s_tab = nullptr;
   int s_stride = 0, rc_tab = 0;
@@ -2185,7 +2248,7 @@ int gl_profile_basis(const gl_component* comp, const float* x, const float* y, i
   }
   long long total = (long long)n_pts * B;
   hipLaunchKernelGGL(gl_basis_point_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
-                     cd, x, y, (long long)n_pts, B, xy_batched, params, out, s_tab, s_stride);
+                     cd, x, y, (long long)n_pts, B, xy_batched, params, out, s_tab, s_stride, InterpDev{nullptr, 0, 0});
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

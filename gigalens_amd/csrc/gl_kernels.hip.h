@@ -14,6 +14,7 @@
 #include "gl_profiles.h"
 #include "gl_dpie.h"
 #include "gl_extra.h"
+#include "gl_interp.h"
 #include "gl_vec.hip.h"
 #include "gl_members.hip.h"
 #include "gl_series.h"
@@ -49,6 +50,9 @@ struct SeriesDev {
   float r0;
   int order;
 };
+
+// image table of one K_INTERPOL light (gl_model_set_light_image): tab[(h + 4)][(w + 4)] with its zero apron; CompDesc::iparam indexes it
+using InterpDev = InterpTab<float>;
 
 struct ZCol;
 struct FinArgs {
@@ -105,6 +109,7 @@ struct MainArgs {
   const SeriesDev* series;
   const float* nfw_tab;  // models with NFW lenses: the shared h(X) table (gl_host_tables.h), [kNfwNodes][2]; else null
   const float* src_scale;  // per-source deflection scales c_s [n_src] (beta_s = x - c_s sum alpha), or null: one source plane
+  const InterpDev* interp;  // image tables of the K_INTERPOL lights, or null: the model has none
   const float* neutral;  // gl_clusterw_kernel: constant blocks of an unused component slot, [NFW (4) | Sersic (16)]; else null
   float grid_rmax;       // largest |(x, y)| of the pixel grid (gl_shp.hip.h: the bound on the shear's deflection)
   int blk_w;             // table-mode shapelet kernel: image width when a wave-tile is an 8-row x 16-column BLOCK of the image (0: 128 consecutive pixels)
@@ -215,7 +220,7 @@ template <int G> __device__ __forceinline__ void wave_acc(float (&acc)[G], const
 __global__ void __launch_bounds__(128) gl_prep_kernel(const CompDesc* __restrict__ comps, int n_comp,
                                                       const float* __restrict__ params, int P, int B,
                                                       float* __restrict__ derived, int D, int* __restrict__ cost,
-                                                      int cost_comp) {
+                                                      int cost_comp, const InterpDev* __restrict__ interp) {
   int i = blockIdx.x * 128 + threadIdx.x;
   if (i >= B * n_comp) return;
   int b = i / n_comp, c = i - b * n_comp;
@@ -234,6 +239,7 @@ __global__ void __launch_bounds__(128) gl_prep_kernel(const CompDesc* __restrict
     case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, d); break;
     case K_TNFW: tnfw_prep<float>(p, d); break;
     case K_CORE_SERSIC: core_sersic_prep<float>(p, d); break;
+    case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, d); break;
     case K_SERSIC: sersic_prep<float>(p, false, d); break;
     case K_SERSIC_ELLIPSE: sersic_prep<float>(p, true, d); break;
     case K_SHAPELETS: shapelets_prep<float>(p, cd.iparam, d); break;
@@ -307,7 +313,7 @@ __global__ void __launch_bounds__(128) gl_zprep_kernel(const CompDesc* __restric
                                                        const ZCol* __restrict__ zcols, const int* __restrict__ src,
                                                        const float* __restrict__ const_row, int P, int B,
                                                        float* __restrict__ params, float* __restrict__ derived, int D,
-                                                       int* __restrict__ cost, int cost_comp) {
+                                                       int* __restrict__ cost, int cost_comp, const InterpDev* __restrict__ interp) {
   int i = blockIdx.x * 128 + threadIdx.x;
   if (i >= B * n_comp) return;
   int b = i / n_comp, c = i - b * n_comp;
@@ -331,6 +337,7 @@ __global__ void __launch_bounds__(128) gl_zprep_kernel(const CompDesc* __restric
     case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, dd); break;
     case K_TNFW: tnfw_prep<float>(p, dd); break;
     case K_CORE_SERSIC: core_sersic_prep<float>(p, dd); break;
+    case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, dd); break;
     case K_SERSIC: sersic_prep<float>(p, false, dd); break;
     case K_SERSIC_ELLIPSE: sersic_prep<float>(p, true, dd); break;
     case K_SHAPELETS: shapelets_prep<float>(p, cd.iparam, dd); break;
@@ -461,7 +468,8 @@ __global__ void __launch_bounds__(256) gl_prep_wave_kernel(const CompDesc* __res
                                                            const int* __restrict__ src, const float* __restrict__ const_row,
                                                            int P, int B, float* __restrict__ params_out,
                                                            float* __restrict__ derived, int D, int* __restrict__ cost,
-                                                           int cost_comp, int* __restrict__ order, int row_lds, int split_rank) {
+                                                           int cost_comp, int* __restrict__ order, int row_lds, int split_rank,
+                                                           const InterpDev* __restrict__ interp) {
   // Cost-ordered dispatch without a launch of its own: with `order` the grid carries ONE extra workgroup that sorts the samples
   // by the trip count of their EPL series while the others build the samples' constants.  It needs no result of theirs: the count
   // depends on (e1, e2) alone (epl_cost), which it takes from the parameter rows -- or, on the z path, through the two columns'
@@ -542,6 +550,7 @@ __global__ void __launch_bounds__(256) gl_prep_wave_kernel(const CompDesc* __res
       case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, d); break;
       case K_TNFW: tnfw_prep<float>(p, d); break;
       case K_CORE_SERSIC: core_sersic_prep<float>(p, d); break;
+      case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, d); break;
       case K_SERSIC: sersic_prep<float>(p, false, d); break;
       case K_SERSIC_ELLIPSE: sersic_prep<float>(p, true, d); break;
       case K_USER_MASS: case K_USER_LIGHT: for (int k = 0; k < cd.iparam; ++k) d[k] = p[k]; break;
@@ -961,6 +970,7 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
             const float px_ = light_point(src, cs, bx[t], x[t]), py_ = light_point(src, cs, by[t], y[t]);
             float v;
             if (XF && cd.kind == K_CORE_SERSIC) v = core_sersic_fwd<float>(d, px_, py_);
+            else if (XF && cd.kind == K_INTERPOL) v = interp_fwd_unit<float>(d, a.interp[cd.iparam], cd.flags & 1u, px_, py_);  // amplitude 1
 #ifdef GL_HAVE_USER
             else if (cd.kind == K_USER_LIGHT) v = glu::light_fwd(cd.flags, d, px_, py_);  // (its amplitude column holds 1, like a Sersic's)
 #endif
@@ -996,6 +1006,13 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
         if constexpr (XF) {
 #pragma unroll
           for (int t = 0; t < T; ++t) m[t] += core_sersic_fwd<float>(d, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]));
+        }
+      } else if (cd.kind == K_INTERPOL) {
+        if constexpr (XF) {
+          const InterpDev tb = a.interp[cd.iparam];
+          const bool linear = cd.flags & 1u;
+#pragma unroll
+          for (int t = 0; t < T; ++t) m[t] += interp_fwd<float>(d, tb, linear, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]));
         }
 #ifdef GL_HAVE_USER
       } else if (cd.kind == K_USER_LIGHT) {
@@ -1118,6 +1135,21 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
               if (src) { gbx[t] += cs * dgx; gby[t] += cs * dgy; }
             }
             wave_acc<CSR_NACC>(acc, ac, cd.a_off);
+          }
+        } else if (cd.kind == K_INTERPOL) {
+          if constexpr (XF) {
+            const InterpDev tb = a.interp[cd.iparam];
+            const bool linear = cd.flags & 1u;
+            float acc[INT_NACC];
+#pragma unroll
+            for (int k = 0; k < INT_NACC; ++k) acc[k] = 0.f;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+              float dgx = 0.f, dgy = 0.f;
+              interp_vjp<float>(d, tb, linear, light_point(src, cs, bx[t], x[t]), light_point(src, cs, by[t], y[t]), gm[t], acc, dgx, dgy);
+              if (src) { gbx[t] += cs * dgx; gby[t] += cs * dgy; }
+            }
+            wave_acc<INT_NACC>(acc, ac, cd.a_off);
           }
         } else {
           float acc[SER_NACC];
@@ -1377,6 +1409,7 @@ __device__ __forceinline__ void finalize_sample(const CompDesc* __restrict__ com
         case K_NFW_ELLIPSE: if constexpr (!BASIC) nfw_ell_finalize<float>(p, acc, g); break;
         case K_TNFW: if constexpr (!BASIC) tnfw_finalize<float>(p, acc, g); break;
         case K_CORE_SERSIC: if constexpr (!BASIC) core_sersic_finalize<float>(p, acc, g); break;
+        case K_INTERPOL: if constexpr (!BASIC) interp_finalize<float>(p, acc, g); break;
         case K_SERSIC: sersic_finalize<float>(p, false, acc, g); break;
         case K_SERSIC_ELLIPSE: sersic_finalize<float>(p, true, acc, g); break;
         case K_SHAPELETS: if constexpr (!BASIC) shapelets_finalize<float>(p, cd.iparam, acc, g); break;
@@ -1631,7 +1664,7 @@ __global__ void __launch_bounds__(256) gl_point_kernel(CompDesc cd, const float*
                                                        const float* __restrict__ y, long long n_pts, int B,
                                                        int xy_batched, const float* __restrict__ params,
                                                        float* __restrict__ out0, float* __restrict__ out1,
-                                                       const float* __restrict__ shp_tab, int shp_stride) {
+                                                       const float* __restrict__ shp_tab, int shp_stride, InterpDev itab) {
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_pts * B) return;
   long long pt = i / B;
@@ -1649,6 +1682,7 @@ __global__ void __launch_bounds__(256) gl_point_kernel(CompDesc cd, const float*
     case K_NFW_ELLIPSE: { float d[NFE_ND]; nfw_ell_prep<float>(p, d); nfw_ell_fwd<float>(d, px, py, o0, o1); } break;
     case K_TNFW: { float d[TNF_ND]; tnfw_prep<float>(p, d); tnfw_fwd<float>(d, px, py, o0, o1); } break;
     case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(p, d); o0 = core_sersic_fwd<float>(d, px, py); } break;
+    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(p, itab.h, itab.w, d); o0 = interp_fwd<float>(d, itab, cd.flags & 1u, px, py); } break;
     case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(p, false, d); o0 = sersic_fwd(d, px, py); } break;
     case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(p, true, d); o0 = sersic_fwd(d, px, py); } break;
     case K_SHAPELETS: {
@@ -1673,7 +1707,7 @@ __global__ void __launch_bounds__(256) gl_basis_point_kernel(CompDesc cd, const 
                                                              const float* __restrict__ y, long long n_pts, int B,
                                                              int xy_batched, const float* __restrict__ params,
                                                              float* __restrict__ out,
-                                                             const float* __restrict__ shp_tab, int shp_stride) {
+                                                             const float* __restrict__ shp_tab, int shp_stride, InterpDev itab) {
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = n_pts * B;
   if (i >= total) return;
@@ -1701,6 +1735,7 @@ __global__ void __launch_bounds__(256) gl_basis_point_kernel(CompDesc cd, const 
   float v = 0.f;
   switch (cd.kind) {
     case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(q, d); v = core_sersic_fwd<float>(d, px, py); } break;
+    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(q, itab.h, itab.w, d); v = interp_fwd_unit<float>(d, itab, cd.flags & 1u, px, py); } break;
     case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(q, false, d); v = sersic_fwd(d, px, py); } break;
     case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(q, true, d); v = sersic_fwd(d, px, py); } break;
   }

@@ -27,6 +27,7 @@ __attribute__((visibility("hidden"))) int fail(int code, const char* fmt, ...);
 using glk::CompDesc;
 using glk::CatDev;
 using glk::SeriesDev;
+using glk::InterpDev;
 using glk::ZCol;
 
 namespace glk {
@@ -193,6 +194,11 @@ struct gl_model {
   std::vector<int> series_comp;       // component of each slot
   int n_series = 0, n_series_set = 0;
   glk::DevBuf<SeriesDev> d_series;
+  // interpolated light components (gl_model_set_light_image): one image table per GL_INTERPOL component, CompDesc::iparam = its slot
+  std::vector<InterpDev> interp;               // what the kernels read (d_interp is its copy on the device): pointers into interp_buf
+  std::vector<glk::DevBuf<float>> interp_buf;  // the owner of each slot's table, [(h + 4)][(w + 4)] with its zero apron
+  int n_interp = 0, n_interp_set = 0;
+  glk::DevBuf<InterpDev> d_interp;
   // linear amplitudes (lstsq_simulate): channel k of the basis stack <-> packed parameter column
   std::vector<int> lin_cols;
   glk::DevBuf<int> d_lin_cols;

@@ -30,7 +30,8 @@ enum Kind : int {
   K_USER_MASS = 13,                     // a body the user wrote (gl_user.hip): iparam = its parameter count, flags = body slot of the model
   K_SERSIC = 16, K_SERSIC_ELLIPSE = 17, K_SHAPELETS = 18,
   K_CORE_SERSIC = 19,                   // gl_extra.h
-  K_USER_LIGHT = 20                     // same for a light profile (amplitude: whatever the body makes of its parameters)
+  K_USER_LIGHT = 20,                    // same for a light profile (amplitude: whatever the body makes of its parameters)
+  K_INTERPOL = 21                       // a pixelated source image (gl_interp.h): iparam = table slot of the model, flags bit 0 = bilinear
 };
 constexpr int USER_MAXP = 16;  // parameters of a user-written profile inside a model (its gradient sums are register arrays)
 
@@ -94,6 +95,7 @@ GL_HD int kind_num_params(int kind, int iparam) {
     case K_NFW_ELLIPSE: return 6;
     case K_TNFW: return 5;
     case K_CORE_SERSIC: return 10;
+    case K_INTERPOL: return 5;
     case K_SERSIC: return 5;
     case K_SERSIC_ELLIPSE: return 7;
     case K_SHAPELETS: return 3 + sh_layers(iparam);
@@ -117,6 +119,7 @@ GL_HD int kind_num_derived(int kind, int iparam) {
     case K_NFW_ELLIPSE:
     case K_TNFW: return 8;
     case K_CORE_SERSIC: return 16;
+    case K_INTERPOL: return 8;  // INT_ND
     case K_SERSIC:
     case K_SERSIC_ELLIPSE: return SER_NDX;
     case K_SHAPELETS:  // n_max <= 10: amplitude triangle zero-padded to n_max = 10, then the square matrix; above: the triangle only
@@ -131,7 +134,8 @@ GL_HD int kind_num_linear(int kind, int iparam) {
   switch (kind) {
     case K_SERSIC:
     case K_SERSIC_ELLIPSE:
-    case K_CORE_SERSIC: return 1;
+    case K_CORE_SERSIC:
+    case K_INTERPOL: return 1;
     case K_SHAPELETS: return sh_layers(iparam);
   }
   return 0;
@@ -142,6 +146,7 @@ GL_HD int kind_linear_col(int kind, int iparam) {  // first amplitude column ins
     case K_SERSIC_ELLIPSE: return 6;
     case K_SHAPELETS: return 3;
     case K_CORE_SERSIC: return 9;
+    case K_INTERPOL: return 4;
   }
   (void)iparam;
   return -1;
@@ -161,6 +166,7 @@ GL_HD int kind_num_acc(int kind, int iparam) {
     case K_NFW_ELLIPSE: return 6;
     case K_TNFW: return 5;
     case K_CORE_SERSIC: return 10;
+    case K_INTERPOL: return 5;  // INT_NACC
     case K_SERSIC:
     case K_SERSIC_ELLIPSE: return SER_NACC;
     case K_SHAPELETS: return SHPA_AMP + sh_layers(iparam);

@@ -1,1 +1,2 @@
-from gigalens_amd.profiles.light import sersic, shapelets  # noqa: F401
+from gigalens_amd.profiles.light import interpol, sersic, shapelets  # noqa: F401
+from gigalens_amd.profiles.light.interpol import Interpolated  # noqa: F401

@@ -168,6 +168,9 @@ class LensSimulator(LensSimulatorInterface):
                 self._model.set_series(i, lens.series_var_0, lens._coefs)
             elif getattr(lens, "_kind", 0) == 9:  # galaxy catalogues of ScalingRelation lenses (fused dPIE-family kernels)
                 self._model.set_catalogue(i, *lens._catalogue())
+        for i, light in enumerate(list(phys_model.lens_light) + list(phys_model.source_light)):
+            if getattr(light, "_kind", 0) == _native.GL_INTERPOL:  # the image of an Interpolated light, a constant of the model
+                self._model.set_light_image(len(phys_model.lenses) + i, light.image)
         if getattr(phys_model, "_source_scales_given", False):  # sources on planes of their own (PhysicalModel source_light_scales)
             self._model.set_source_scales(phys_model.source_light_scales)
         self._layout = phys_model._packing()

@@ -66,12 +66,17 @@ typedef enum gl_kind {
   GL_SERSIC_ELLIPSE = 17, /* sersic.py:68-69 [R_sersic,n_sersic,e1,e2,center_x,center_y,Ie] */
   GL_SHAPELETS = 18,      /* tf/profiles/light/shapelets.py:18,34-36 [beta,center_x,center_y,amp0..amp{L-1}] */
   GL_CORE_SERSIC = 19,    /* sersic.py:85-96 [R_sersic,n_sersic,Rb,alpha,gamma,e1,e2,center_x,center_y,Ie] */
-  GL_USER_LIGHT = 20      /* profile.py:24-60 as an extension point: a user-written light body (gl_model_create_user) */
+  GL_USER_LIGHT = 20,     /* profile.py:24-60 as an extension point: a user-written light body (gl_model_create_user) */
+  GL_INTERPOL = 21        /* beyond the reference: a pixelated source image, interpolated (lenstronomy's INTERPOL by name)
+                             [center_x,center_y,phi,scale,amp]; flags: GL_FLAG_INTERPOL_LINEAR; image attached with
+                             gl_model_set_light_image */
 } gl_kind;
 
 #define GL_SHAPELETS_NMAX_CAP 20 /* largest n_max served (231 amplitudes); above 10 the runtime-order path of the interpreter kernel runs */
 #define GL_SHAPELETS_TABLE_NODES 6000
 #define GL_FLAG_SHAPELETS_INTERPOLATE 1u /* shapelets.py:20 interpolate=True (table mode) */
+#define GL_FLAG_INTERPOL_LINEAR 1u /* GL_INTERPOL: bilinear interpolation (order 1) instead of Keys' cubic convolution (order 3) */
+#define GL_INTERPOL_MAX_SIDE 2048 /* largest height / width of an interpolated image */
 
 typedef struct gl_component {
   int32_t kind;   /* gl_kind */
@@ -260,6 +265,28 @@ int gl_lstsq_solve_flags(const gl_model* m, int B, size_t* offset_bytes);
  *              the quantity is a catalogue constant */
 int gl_model_set_catalogue(gl_model* m, int component, int base_kind, int n_galaxies, const int32_t scale_col[3],
                            const float* table);
+
+/* Image of a GL_INTERPOL light component (beyond the reference: every light profile there is parametric).  With
+ *   dx = px - center_x, dy = py - center_y,
+ *   u = ( dx cos phi + dy sin phi) / scale + (w - 1) / 2      (column coordinate; scale = arcsec per image pixel, > 0)
+ *   v = (-dx sin phi + dy cos phi) / scale + (h - 1) / 2      (row coordinate)
+ * the component's surface brightness at (px, py) is  amp * sum_j sum_i k(v - j) k(u - i) image[j][i],  the image zero-extended
+ * over all integers and k the hat function (GL_FLAG_INTERPOL_LINEAR) or Keys' cubic convolution kernel with a = -1/2: continuous
+ * everywhere (C1 for the cubic), zero once u < -2, u > w + 1, v < -2 or v > h + 1 -- a coordinate that is not finite included --
+ * with zero gradient there.  No division by scale^2: `amp` scales surface brightness.  The gradient calls differentiate with
+ * respect to the five parameters and the evaluation point (so the lens parameters see it), not the pixels.
+ *   image  HOST [h][w], copied with a two-pixel zero apron into a device buffer the model owns; one image per component, shared
+ *          by the whole batch.  A set-up call like gl_model_set_series: the model is immutable once compute calls have begun.
+ * Every GL_INTERPOL component needs its image before gl_workspace_bytes / any compute call (GL_EINVAL otherwise).  A model that
+ * holds one runs the interpreter kernel in every mode.  GL_EINVAL: `component` is not a GL_INTERPOL light, h or w outside
+ * 1..GL_INTERPOL_MAX_SIDE, a pixel that is not finite.  gl_model_create_user answers GL_EUNSUPPORTED for a model that mixes
+ * user-written profiles with GL_INTERPOL (the run-time compiled kernels carry no image tables). */
+int gl_model_set_light_image(gl_model* m, int component, int h, int w, const float* image_host);
+/* LightProfile.light of a free-standing GL_INTERPOL component on arbitrary points: arguments as gl_profile_eval (basis == 0;
+ * params [B,5]) or gl_profile_basis (basis != 0: amplitude 1, out [1][n_pts][B]); image_dev: DEVICE [(h+4)][(w+4)], the image
+ * with its two-pixel zero apron. */
+int gl_interpol_eval(const gl_component* comp, int h, int w, const float* image_dev, const float* x, const float* y,
+                     int64_t n_pts, int B, int xy_batched, const float* params, float* out, int basis, void* hip_stream);
 
 /* ScalingRelation.deriv on arbitrary points (scaling_relation.py:61-70); arguments as gl_profile_eval, with
  * table a DEVICE pointer [n_galaxies][7] and scales [B][n_scales]. */
