@@ -103,6 +103,10 @@ SYMBOLS = {
     "gl_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "gl_critical_curves": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gl_pixsrc_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "gl_pixsrc_reconstruct": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "gl_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
                                    c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_model_num_linear": (c_int, [c_void_p]),
@@ -718,6 +722,38 @@ class Model:
                                                              _ptr(n_dropped), _ptr(n_flagged), _ptr(opened), _ptr(area), _ptr(ws),
                                                              ws.numel(), _stream()))
         return seg, cau, kind, n_seg, n_dropped, n_flagged, opened, area
+
+    def pixsrc_reconstruct(self, beta_x, beta_y, obs, sigma, lens_light, pix, n_src, pose, regularization, strength):
+        """gl_pixsrc_reconstruct: ``beta_x, beta_y`` [B, Hs Ws], ``obs, sigma`` [B, n_used], ``lens_light`` [B, H, W] or None, ``pix``
+        [n_used] int32, ``pose`` [B, 3] (pitch, cx, cy), ``strength`` [B, L], all on the device; ``regularization`` 0, 1 or 2.
+        Returns ``source`` [B, L, ny, nx], ``model_image`` [B, L, H, W], ``scalars`` [B, L, 3] (float64: chi2, s^T R s, log det M)
+        and ``ok`` [B, L] (int32)."""
+        ny, nx = (int(v) for v in n_src)
+        B, L, n_used = int(beta_x.shape[0]), int(strength.shape[1]), int(pix.numel())
+        f32 = lambda t, shape, what: self._pix_tensor(t, torch.float32, shape, what)
+        beta_x, beta_y = f32(beta_x, (B, self.ss_h * self.ss_w), "beta_x"), f32(beta_y, (B, self.ss_h * self.ss_w), "beta_y")
+        obs, sigma = f32(obs, (B, n_used), "obs"), f32(sigma, (B, n_used), "sigma")
+        pose, strength = f32(pose, (B, 3), "pose"), f32(strength, (B, L), "strength")
+        pix = self._pix_tensor(pix, torch.int32, (n_used,), "pix")
+        if lens_light is not None:
+            lens_light = f32(lens_light, (B, self.out_h, self.out_w), "lens_light")
+        nbytes = lib().gl_pixsrc_workspace_bytes(self._h, B, L, ny, nx, n_used)
+        ws = self._scratch("_pix_ws", nbytes)
+        source = torch.empty((B, L, ny, nx), dtype=torch.float32, device=self.device)
+        image = torch.empty((B, L, self.out_h, self.out_w), dtype=torch.float32, device=self.device)
+        scalars = torch.empty((B, L, 3), dtype=torch.float64, device=self.device)
+        ok = torch.empty((B, L), dtype=torch.int32, device=self.device)
+        _check(lib().gl_pixsrc_reconstruct(self._h, _ptr(beta_x), _ptr(beta_y), B, _ptr(obs), _ptr(sigma), _ptr(lens_light),
+                                                     _ptr(pix), n_used, ny, nx, _ptr(pose), int(regularization), _ptr(strength), L,
+                                                     _ptr(source), _ptr(image), _ptr(scalars), _ptr(ok), _ptr(ws), ws.numel(),
+                                                     _stream()))
+        return source, image, scalars, ok
+
+    def _pix_tensor(self, t, dtype, shape, what):
+        _require_cuda(t, what)
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+            raise NativeLibraryError(f"pixsrc_reconstruct: {what} must be {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+        return t.contiguous()
 
     def num_linear(self):
         return lib().gl_model_num_linear(self._h)

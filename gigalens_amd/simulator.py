@@ -487,6 +487,129 @@ class LensSimulator(LensSimulatorInterface):
         dt = torch.where(ok, dt, torch.full_like(dt, float("nan"))).to(torch.float32)
         return x, y, mu, n, dt
 
+    REGULARIZATIONS = {"identity": 0, "gradient": 1, "curvature": 2}
+    MAX_SOURCE_NODES = 1024
+
+    @staticmethod
+    def log_det_regularization(regularization, n_src):
+        """``log det R`` of the regularisation of ``reconstruct_source`` on a ``(ny, nx)`` grid, in float64 from the closed-form
+        eigenvalues ``2 - 2 cos(k pi / (n + 1))`` of ``T_n = tridiag(-1, 2, -1)``: ``identity`` 0, ``gradient`` the sum of
+        ``log(e_x + e_y)``, ``curvature`` of ``log(e_x^2 + e_y^2)``."""
+        if regularization not in LensSimulator.REGULARIZATIONS:
+            raise ValueError(f"regularization must be one of {sorted(LensSimulator.REGULARIZATIONS)}, got {regularization!r}")
+        ny, nx = (int(v) for v in n_src)
+        if regularization == "identity":
+            return 0.0
+        ex = 2.0 - 2.0 * np.cos(np.arange(1, nx + 1, dtype=np.float64) * np.pi / (nx + 1))
+        ey = 2.0 - 2.0 * np.cos(np.arange(1, ny + 1, dtype=np.float64) * np.pi / (ny + 1))
+        if regularization == "curvature":
+            ex, ey = ex * ex, ey * ey
+        return float(np.sum(np.log(ey[:, None] + ex[None, :])))
+
+    def _per_sample(self, value, B, what, positive):
+        """A scalar or ``[B]`` keyword as a float32 ``[B]`` host array (``ValueError`` unless finite, and > 0 when ``positive``)."""
+        self._forward_only("reconstruct_source", value)
+        arr = np.asarray(value.detach().cpu() if torch.is_tensor(value) else value, dtype=np.float64)
+        if arr.size == 1:
+            arr = arr.reshape(())
+        if arr.ndim > 1 or (arr.ndim == 1 and arr.size != B):
+            raise ValueError(f"{what}: expected a scalar or [B={B}], got shape {tuple(arr.shape)}")
+        arr = np.broadcast_to(arr, (B,))
+        if not np.all(np.isfinite(arr)) or (positive and not np.all(arr > 0)):
+            raise ValueError(f"{what}: every value must be finite{' and > 0' if positive else ''}, got {arr.tolist()}")
+        return arr.astype(np.float32)
+
+    def reconstruct_source(self, params, observed_image, err_map, *, n_src, pitch, center=(0.0, 0.0), regularization="gradient",
+                           strength=1.0, mask=None, deflection_scale=1.0):
+        """Pixelated source reconstruction with the Bayesian evidence of every sample (beyond the reference): the most probable
+        source on a regular grid given the lens model (semi-linear inversion, Warren & Dye 2003) and the evidence that ranks lens
+        models and regularisation strengths (Suyu et al. 2006, eq. 19).
+
+        ``params``: the nested dict or packed ``[B, P]`` rows; lenses and lens light are used, the model's ``source_light`` is ignored
+        (the grid replaces it).  ``observed_image`` and ``err_map``: ``[H, W]`` (or ``[B, H, W]``, one per sample).  ``n_src = (ny, nx)``,
+        ``pitch`` and ``center = (cx, cy)`` (scalars or ``[B]``) define the source grid: node ``(j, i)`` lies at ``(cx + (i - (nx-1)/2)
+        pitch, cy + (j - (ny-1)/2) pitch)``, the pose of ``Interpolated(order=1)`` with ``phi = 0``, ``scale = pitch``; the source is zero
+        outside the grid.  ``regularization``: ``"identity"``, ``"gradient"`` or ``"curvature"``; ``strength`` (lambda): a scalar, ``[B]``
+        or ``[B, L]`` -- a scan over ``L`` strengths reuses the normal matrix of a sample.  ``mask``: ``[H, W]`` bool, combined with the
+        simulator's ``pix_region``; the fit uses the pixels that remain.  ``deflection_scale``: the source plane, as on ``beta``.
+
+        Returns a dict (an ``L`` axis follows ``B`` where ``strength`` is 2-D): ``source`` ``[B, ny, nx]``; ``model_image`` ``[B, H, W]``
+        (lens light + ``F s`` on the used pixels, the lens light alone elsewhere); ``chi2``, ``reg`` (``s^T R s``), ``log_det``
+        (``log det(A0 + lambda R)``) and ``log_evidence`` ``[B]`` (float64); ``ok`` ``[B]`` bool -- false where a Cholesky pivot is not
+        finite or not positive, and the sample's other outputs are then NaN.  ``ValueError`` for ``ny nx > 1024``, a ``strength`` or
+        ``pitch`` that is not finite or not > 0, an ``err_map`` that is not finite or not > 0 on a used pixel, an unknown
+        ``regularization`` and shapes that do not match; lens kinds ``lens_maps`` refuses stay refused with its error.  Forward only."""
+        if regularization not in self.REGULARIZATIONS:
+            raise ValueError(f"regularization must be one of {sorted(self.REGULARIZATIONS)}, got {regularization!r}")
+        ny, nx = (int(v) for v in n_src)
+        if ny < 1 or nx < 1 or ny * nx > self.MAX_SOURCE_NODES:
+            raise ValueError(f"n_src = ({ny}, {nx}): the source grid must have 1 .. {self.MAX_SOURCE_NODES} nodes")
+        packed = self._pack_partial(params)
+        self._forward_only("reconstruct_source", packed, observed_image, err_map, strength)
+        B = packed.shape[0]
+        H, W = self._model.out_h, self._model.out_w
+        ss, dev = self.supersample, self.device
+        cs = self._scale(deflection_scale)
+        pitch_h = self._per_sample(pitch, B, "pitch", True)
+        if len(center) != 2:
+            raise ValueError("center must be (cx, cy)")
+        cx_h, cy_h = self._per_sample(center[0], B, "center[0]", False), self._per_sample(center[1], B, "center[1]", False)
+        lam = np.asarray(strength.detach().cpu() if torch.is_tensor(strength) else strength, dtype=np.float64)
+        scan = lam.ndim == 2
+        if lam.ndim > 2 or (lam.ndim >= 1 and lam.shape[0] != B) or lam.size == 0:
+            raise ValueError(f"strength: expected a scalar, [B={B}] or [B, L], got shape {tuple(lam.shape)}")
+        lam = np.broadcast_to(lam.reshape(-1, 1) if lam.ndim == 1 else lam, (B, lam.shape[1] if scan else 1)).astype(np.float32)
+        if not (np.all(np.isfinite(lam)) and np.all(lam > 0)):
+            raise ValueError("strength: every value must be finite and > 0 (as float32)")
+        used = np.asarray(self.img_region.cpu()) != 0
+        if mask is not None:
+            mk = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask)
+            if mk.shape != (H, W):
+                raise ValueError(f"mask must be [{H}, {W}], got {tuple(mk.shape)}")
+            used = used & mk.astype(bool)
+        pix = np.flatnonzero(used.reshape(-1)).astype(np.int32)
+        if pix.size == 0:
+            raise ValueError("no pixel is left to fit (mask and pix_region)")
+
+        def per_pixel(a, what):
+            t = torch.as_tensor(a, dtype=torch.float32, device=dev)
+            if tuple(t.shape) not in ((H, W), (B, H, W)):
+                raise ValueError(f"{what} must be [{H}, {W}] or [{B}, {H}, {W}], got {tuple(t.shape)}")
+            return t.reshape(-1, H * W)[:, torch.from_numpy(pix.astype(np.int64)).to(dev)].expand(B, pix.size).contiguous()
+        obs_u, sig_u = per_pixel(observed_image, "observed_image"), per_pixel(err_map, "err_map")
+        if not bool((torch.isfinite(sig_u) & (sig_u > 0)).all()):
+            raise ValueError("err_map must be finite and > 0 on every used pixel")
+        # ray shooting on the whole supersampled frame (gl_lens_maps); pixels outside pix_region are not rendered by the simulator:
+        # a NaN there gives them a row of zeros
+        Hs, Ws = H * ss, W * ss
+        cc, rr = np.meshgrid(np.arange(Ws), np.arange(Hs))
+        gx, gy = self.wcs.pix2angle(cc.reshape(-1), rr.reshape(-1))
+        gx_t, gy_t = torch.from_numpy(gx).to(dev), torch.from_numpy(gy).to(dev)
+        maps = self._lens_maps(gx_t.reshape(-1, 1), gy_t.reshape(-1, 1), packed)
+        bx, by = maps[0].reshape(Hs * Ws, B), maps[1].reshape(Hs * Ws, B)
+        if cs != 1.0:
+            bx, by = gx_t[:, None] + cs * (bx - gx_t[:, None]), gy_t[:, None] + cs * (by - gy_t[:, None])
+        bx, by = bx.t().contiguous(), by.t().contiguous()
+        if self._region_np.shape[0] != Hs * Ws:
+            outside = torch.ones(Hs * Ws, dtype=torch.bool, device=dev)
+            outside[self.region[:, 0] * Ws + self.region[:, 1]] = False
+            bx[:, outside] = float("nan")
+            by[:, outside] = float("nan")
+        lens_light = self._model.simulate_parts(packed, 2) if len(self.phys_model.lens_light) else None
+        pose = torch.from_numpy(np.stack([pitch_h, cx_h, cy_h], axis=1)).to(dev)
+        lam_t = torch.from_numpy(np.ascontiguousarray(lam)).to(dev)
+        source, image, scal, ok = self._model.pixsrc_reconstruct(bx, by, obs_u, sig_u, lens_light, torch.from_numpy(pix).to(dev),
+                                                                 (ny, nx), pose, self.REGULARIZATIONS[regularization], lam_t)
+        S = ny * nx
+        chi2, reg, log_det = scal[..., 0], scal[..., 1], scal[..., 2]
+        lam64 = lam_t.double()
+        noise = torch.log(2.0 * math.pi * sig_u.double() ** 2).sum(dim=1, keepdim=True)
+        log_ev = (-0.5 * chi2 - 0.5 * lam64 * reg - 0.5 * log_det + 0.5 * S * torch.log(lam64)
+                  + 0.5 * self.log_det_regularization(regularization, (ny, nx)) - 0.5 * noise)
+        out = {"source": source, "model_image": image, "chi2": chi2, "reg": reg, "log_det": log_det, "log_evidence": log_ev,
+               "ok": ok != 0}
+        return out if scan else {k: v[:, 0] for k, v in out.items()}
+
     def simulate(self, params, no_deflection=False):
         """tf/simulator.py:109-156.  Returns ``(bs, H, W)`` squeezed like ``tf.squeeze``."""
         packed = params if torch.is_tensor(params) else self.pack(params)

@@ -383,6 +383,37 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
                               int* n_dropped, int* n_flagged, int* open, float* area, void* workspace, size_t workspace_bytes,
                               void* hip_stream);
 
+/* Pixelated source reconstruction (beyond the reference): semi-linear inversion (Warren & Dye 2003) with the Bayesian evidence
+ * terms of Suyu et al. 2006, for every sample and every regularisation strength.  The source lives on a regular grid of
+ * S = ny nx <= 1024 nodes, node (j, i) at (cx + (i - (nx-1)/2) pitch, cy + (j - (ny-1)/2) pitch) -- the pose of a GL_INTERPOL light
+ * with phi = 0, scale = pitch, bilinear -- and is zero outside it.  Inputs (DEVICE):
+ *   beta_x, beta_y [B][Hs Ws]  source-plane position of every supersampled pixel (gl_lens_maps), row-major on the model's
+ *       supersampled frame; a value that is not finite (or is out of the float range test of a GL_INTERPOL light) gives that
+ *       pixel a row of exact zeros;
+ *   pix [n_used]  indices into the H x W image of the pixels that are fitted, ascending, each in [0, H W) (NOT checked: the
+ *       call does not read device memory on the host);  obs, sigma [B][n_used]  data and its rms at those pixels;
+ *   lens_light [B][H W] or null: subtracted from obs, added to model_image;
+ *   pose [B][3] = pitch, cx, cy;  strength [B][n_strength] = lambda.
+ * With L[q, (j,i)] = hat(v_q - j) hat(u_q - i), u = (beta_x - cx) / pitch + (nx-1)/2, v likewise, hat(t) = max(0, 1 - |t|), and
+ * F = conversion_factor Pool PSF L (the operator gl_post_apply applies) restricted to the used pixels:
+ *   A0 = F^T W F, b = F^T W y, W = diag(1 / sigma^2), y = obs - lens_light;  M = A0 + lambda R;  s = M^-1 b by Cholesky -- no
+ *   rcond cut;  R by `regularization`: 0 identity, 1 gradient I (x) T_x + T_y (x) I, 2 curvature I (x) T_x^2 + T_y^2 (x) I with
+ *   T_n = tridiag(-1, 2, -1) (the zero extension makes every form positive definite).
+ * Outputs (DEVICE): source [B][n_strength][S]; model_image [B][n_strength][H W] = lens_light + F s on the used pixels, lens_light
+ * alone elsewhere; scalars [B][n_strength][3] (float64) = chi2 = sum ((y - F s) / sigma)^2, s^T R s, log det M (the sum of the logs
+ * of the Cholesky pivots); ok [B][n_strength] = 0 where a pivot is not finite or not positive -- the other outputs of that
+ * (sample, strength) are then NaN.  A0 and b are built once per sample and reused for every strength.  Accumulation is float32 in
+ * a fixed order (the three scalars: float64): two calls give identical bits, and a (sample, strength) does not depend on the
+ * others.  No host synchronisation, no allocation: everything lives in `workspace` (gl_pixsrc_workspace_bytes; 0 for invalid
+ * sizes), which is bounded by a chunk of samples and a slice of strengths, not by B or n_strength.
+ * GL_EINVAL: null arguments, sizes <= 0, B or n_strength > 65535, n_used > H W, unknown regularization;
+ * GL_EUNSUPPORTED: S > 1024. */
+size_t gl_pixsrc_workspace_bytes(const gl_model* m, int B, int n_strength, int ny, int nx, int n_used);
+int gl_pixsrc_reconstruct(const gl_model* m, const float* beta_x, const float* beta_y, int B, const float* obs, const float* sigma,
+                          const float* lens_light, const int* pix, int n_used, int ny, int nx, const float* pose, int regularization,
+                          const float* strength, int n_strength, float* source, float* model_image, double* scalars, int* ok,
+                          void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Plugin-level point evaluation, the reference's MassProfile.deriv / LightProfile.light called on
  * arbitrary coordinates (tests/test_profiles.py calls exactly these):
  *   x, y [n_pts, B] when xy_batched, else [n_pts] shared by every sample (pixel-major, batch-minor
