@@ -115,6 +115,10 @@ SYMBOLS = {
     "gl_lstsq_solve_flags": (c_int, [c_void_p, c_int, ctypes.POINTER(c_size_t)]),
     "gl_lstsq_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_size_t, c_void_p]),
+    "gl_lstsq_solve_stack_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gl_lstsq_solve_stack": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "gl_lstsq_last_kernels": (c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_size_t]),
     "gl_model_set_catalogue": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_float)]),
     "gl_model_set_light_image": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float)]),
     "gl_interpol_eval": (c_int, [POINTER(gl_component), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
@@ -213,6 +217,38 @@ def _stream():
 
 def _ptr(t):
     return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
+
+
+def lstsq_solve_stack_workspace_bytes(B, D, HW, workgroups=2048):
+    return lib().gl_lstsq_solve_stack_workspace_bytes(int(B), int(D), int(HW), int(workgroups))
+
+
+def lstsq_solve_stack(stack, obs, err, workgroups=2048, cholesky=True, coeffs=None, flags=None, normal=None, workspace=None):
+    """gl_lstsq_solve_stack: the solve of ``lstsq_simulate`` on a caller's basis stack ``[B, D, HW]`` with ``obs`` / ``err``
+    ``[HW]`` (float32, on the GPU; ``obs`` / ``err`` may be views at any float offset).  ``coeffs [B, D]``, ``flags [B]`` int32,
+    ``normal [B, Dp, Dp]`` and ``workspace`` (uint8) are written into when given; returns ``coeffs``."""
+    for t, what in ((stack, "stack"), (obs, "obs"), (err, "err")):
+        _require_cuda(t, what)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise NativeLibraryError(f"lstsq_solve_stack: {what} must be contiguous float32, got {t.dtype} {tuple(t.shape)}")
+    if stack.dim() != 3 or obs.numel() != stack.shape[2] or err.numel() != stack.shape[2]:
+        raise NativeLibraryError(f"lstsq_solve_stack: stack [B,D,HW] with obs, err [HW], got {tuple(stack.shape)}, {tuple(obs.shape)}, {tuple(err.shape)}")
+    B, D, HW = stack.shape
+    if workspace is None:
+        workspace = torch.empty(max(lstsq_solve_stack_workspace_bytes(B, D, HW, workgroups), 1), dtype=torch.uint8, device=stack.device)
+    if coeffs is None:
+        coeffs = torch.empty((B, D), dtype=torch.float32, device=stack.device)
+    with torch.cuda.device(stack.device):
+        _check(lib().gl_lstsq_solve_stack(_ptr(stack), _ptr(obs), _ptr(err), B, D, HW, int(workgroups), int(bool(cholesky)),
+                                          _ptr(coeffs), _ptr(flags), _ptr(normal), _ptr(workspace), workspace.numel(), _stream()))
+    return coeffs
+
+
+def lstsq_last_kernels():
+    """Mangled symbols (normal-matrix, Cholesky, eigenvalue kernel) of the most recent linear solve; '' = the stage did not run."""
+    bufs = [ctypes.create_string_buffer(1024) for _ in range(3)]
+    _check(lib().gl_lstsq_last_kernels(*bufs, 1024))
+    return tuple(b.value.decode() for b in bufs)
 
 
 def component_of(profile, bodies=None):

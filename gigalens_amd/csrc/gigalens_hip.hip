@@ -592,6 +592,15 @@ int raise_lds_limit(const void* kernel, bool* raised) {
   return GL_OK;
 }
 
+// pixel chunks per sample of the normal-matrix kernels: ~`wgs` (2048) workgroups in flight, whole 64-pixel groups per chunk
+void lstsq_chunks(long long HW, int B, int wgs, int* chunk, int* n_chunks) {
+  long long want = std::max<long long>(1, ((long long)wgs + B - 1) / B);
+  long long per = (HW + want - 1) / want;
+  per = std::max<long long>(2 * LS_TPP, (per + 2 * LS_TPP - 1) / (2 * LS_TPP) * (2 * LS_TPP));
+  *chunk = (int)per;
+  *n_chunks = (int)((HW + per - 1) / per);
+}
+
 // (behind the call workspace `cw` of the same base)
 LstsqWs carve_lstsq(const gl_model* m, int B, void* base, const Workspace& cw) {
   LstsqWs w{};
@@ -601,12 +610,7 @@ LstsqWs carve_lstsq(const gl_model* m, int B, void* base, const Workspace& cw) {
   char* p = (char*)base;
   auto take = [&](size_t n) { float* q = (float*)(p + off); off += align_up(n * sizeof(float), 256); return q; };
   w.Dp = (D + 1 + 3) & ~3;
-  // pixel chunks per sample: ~2048 workgroups in flight, whole LDS tiles per chunk
-  long long want = std::max<long long>(1, (m->lstsq_wgs + B - 1) / B);
-  long long per = ((long long)HW + want - 1) / want;
-  per = std::max<long long>(2 * LS_TPP, (per + 2 * LS_TPP - 1) / (2 * LS_TPP) * (2 * LS_TPP));
-  w.chunk = (int)per;
-  w.n_chunks = (int)(((long long)HW + per - 1) / per);
+  lstsq_chunks((long long)HW, B, m->lstsq_wgs, &w.chunk, &w.n_chunks);
   w.stack_ss = m->has_post ? take((size_t)B * D * HWs) : nullptr;
   w.stack = take((size_t)B * D * HW);
   // three workgroups per CU there: 1.5 x the workgroup target = four full rounds of the chip at the default (measured: 2048 ->
@@ -1256,6 +1260,173 @@ int gl_model_linear_column(const gl_model* m, int k) {
   return m->lin_cols[k];
 }
 
+namespace {
+// what the solve half of the linear-amplitude step needs of a workspace
+struct SolveWs {
+  float* partial;  // [B][n_chunks][Dp*Dp]
+  float* mats;     // [B][2][D][D | 1] above LS_LDS_MAXN unknowns, else null
+  int* todo;       // [B]
+  int Dp, chunk, n_chunks;
+};
+// host function pointers of the most recent solve's normal-matrix, Cholesky and eigen kernel (null: the stage did not run)
+std::atomic<const void*> g_lstsq_last_fn[3];
+#define GL_LS_LAUNCH(slot_, kernel_, ...)                      \
+  do {                                                         \
+    g_lstsq_last_fn[slot_] = (const void*)&kernel_;            \
+    hipLaunchKernelGGL((kernel_), __VA_ARGS__);                \
+  } while (0)
+
+// The solve of gl_lstsq_fwd and gl_lstsq_solve_stack: normal matrices of [stack / err | obs / err] per (sample, pixel chunk) --
+// unless the stack-free kernel already left them (`have_partials`) --, their sum, the Cholesky attempt, the eigenvalue solve.
+int lstsq_solve(const float* stack, const float* obs, const float* err, int B, int D, int HW, const SolveWs& sw,
+                bool have_partials, bool chol, float* coeffs, hipStream_t stream) {
+  int rc;
+  NormalArgs na{};
+  na.stack = stack;
+  na.obs = obs;
+  na.err = err;
+  na.D = D;
+  na.Dp = sw.Dp;
+  na.HW = HW;
+  na.chunk = sw.chunk;
+  na.n_chunks = sw.n_chunks;
+  na.partial = sw.partial;
+  if (have_partials) {
+    // the partials are already there
+  } else if (D + 1 <= LS_SMALL)
+    GL_LS_LAUNCH(0, gl_normal_small_kernel<LS_SMALL>, dim3(sw.n_chunks, B), dim3(256), 0, stream, na);
+  else if (D + 1 > LS_MAXD) {  // more than five tile rows: super-block pairs (gl_normal_pair_kernel)
+    const int vec_ok = (HW % 4 == 0) && ((uintptr_t)obs % 16 == 0) && ((uintptr_t)err % 16 == 0) && ((uintptr_t)stack % 16 == 0);
+    const int n_sb = (D + 1 + 16 * LS_SB - 1) / (16 * LS_SB);
+    const dim3 grid(sw.n_chunks, B, n_sb * (n_sb + 1) / 2), block(256);
+    if (vec_ok) GL_LS_LAUNCH(0, gl_normal_pair_kernel<true>, grid, block, 0, stream, na);
+    else GL_LS_LAUNCH(0, gl_normal_pair_kernel<false>, grid, block, 0, stream, na);
+  } else {
+    // 16-byte loads need every channel row, obs and err on a 16-byte pitch
+    const int vec_ok = (HW % 4 == 0) && ((uintptr_t)obs % 16 == 0) && ((uintptr_t)err % 16 == 0) && ((uintptr_t)stack % 16 == 0);
+    const dim3 grid(sw.n_chunks, B), block(256);
+#define GL_NORMAL_MFMA(NT_)                                                                                  \
+  if (vec_ok) GL_LS_LAUNCH(0, (gl_normal_mfma_kernel<NT_, true>), grid, block, 0, stream, na);               \
+  else GL_LS_LAUNCH(0, (gl_normal_mfma_kernel<NT_, false>), grid, block, 0, stream, na)
+    switch ((D + 1 + 15) / 16) {
+      case 1: GL_NORMAL_MFMA(1); break;
+      case 2: GL_NORMAL_MFMA(2); break;
+      case 3: GL_NORMAL_MFMA(3); break;
+      case 4: GL_NORMAL_MFMA(4); break;
+      default: GL_NORMAL_MFMA(5); break;
+    }
+#undef GL_NORMAL_MFMA
+  }
+  GL_HIP(hipGetLastError());
+  int n_sum = sw.n_chunks;
+  if (n_sum > 8) {  // many chunks (small batches): reduce them with the whole chip first
+    hipLaunchKernelGGL(gl_partial_sum_kernel, dim3((sw.Dp * sw.Dp + 255) / 256, B), dim3(256), 0, stream, sw.partial,
+                       sw.n_chunks, sw.Dp * sw.Dp);
+    GL_HIP(hipGetLastError());
+    n_sum = 1;
+  }
+  const int* todo = nullptr;
+  g_lstsq_last_fn[1] = nullptr;
+  if (D <= LS_LDS_MAXN && chol) {  // the inverse when the pseudo-inverse's cut is provably idle (gl_chol_solve_kernel)
+    const int nb = D + 1 <= 64 ? 4 : D + 1 <= 80 ? 5 : 8;
+    const size_t sm = sizeof(float) * ((size_t)(D + 2) * (16 * nb + 1) + 4);
+    static bool chol_raised = false;
+    if (sm > 64 * 1024 && (rc = raise_lds_limit((const void*)&gl_chol_solve_kernel<8>, &chol_raised))) return rc;
+#define GL_CHOL(NB_) GL_LS_LAUNCH(1, gl_chol_solve_kernel<NB_>, dim3(B), dim3(256), sm, stream, sw.partial, sw.n_chunks, n_sum, D, \
+                                  sw.Dp, 1e-6f, coeffs, sw.todo)
+    if (nb == 4) GL_CHOL(4); else if (nb == 5) GL_CHOL(5); else GL_CHOL(8);
+#undef GL_CHOL
+    GL_HIP(hipGetLastError());
+    todo = sw.todo;
+  }
+  if (D <= LS_LDS_MAXN) {  // A and V in LDS: up to 129 KB of the CU's 160 (above 64 KB the kernel has to be told once)
+    const size_t sm = sizeof(float) * ((size_t)2 * D * (D | 1) + 8 * D + 8);
+    static bool eigh_raised = false;
+    if (sm > 64 * 1024 && (rc = raise_lds_limit((const void*)&gl_eigh_solve_kernel<2, false>, &eigh_raised))) return rc;
+    GL_LS_LAUNCH(2, (gl_eigh_solve_kernel<2, false>), dim3(B), dim3(64), sm, stream, sw.partial, sw.n_chunks, n_sum, D, sw.Dp,
+                 1e-6f, coeffs, (float*)nullptr, todo);
+  } else {  // the two matrices in the workspace (L2), the vectors in LDS; four registers hold the tridiagonal
+    const size_t sm = sizeof(float) * ((size_t)8 * D + 8);
+    GL_LS_LAUNCH(2, (gl_eigh_solve_kernel<4, true>), dim3(B), dim3(64), sm, stream, sw.partial, sw.n_chunks, n_sum, D, sw.Dp,
+                 1e-6f, coeffs, sw.mats, todo);
+  }
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// the workspace of gl_lstsq_solve_stack: partials, the eigen solve's matrices above LS_LDS_MAXN unknowns, the flags
+SolveWs carve_solve_stack(int B, int D, int HW, int wgs, void* base, size_t* bytes) {
+  SolveWs w{};
+  size_t off = 0;
+  char* p = (char*)base;
+  auto take = [&](size_t n) { float* q = (float*)(p + off); off += align_up(n * sizeof(float), 256); return q; };
+  w.Dp = (D + 1 + 3) & ~3;
+  lstsq_chunks((long long)HW, B, wgs, &w.chunk, &w.n_chunks);
+  w.partial = take((size_t)B * w.n_chunks * w.Dp * w.Dp);
+  w.mats = D > LS_LDS_MAXN ? take((size_t)B * 2 * D * (D | 1)) : nullptr;
+  w.todo = (int*)take((size_t)B);
+  *bytes = off;
+  return w;
+}
+
+int check_solve_stack_shape(int B, int D, int HW, int workgroups) {
+  if (B <= 0 || B > 65535) return fail(GL_EINVAL, "batch size %d outside [1, 65535]", B);
+  if (D <= 0 || HW <= 0 || workgroups <= 0) return fail(GL_EINVAL, "D, HW and workgroups must be positive");
+  if (D > LS_MAXN) return fail(GL_EUNSUPPORTED, "%d linear coefficients exceed the %d the solve serves", D, LS_MAXN);
+  return GL_OK;
+}
+}  // namespace
+
+size_t gl_lstsq_solve_stack_workspace_bytes(int B, int D, int HW, int workgroups) {
+  if (check_solve_stack_shape(B, D, HW, workgroups)) return 0;
+  size_t bytes = 0;
+  carve_solve_stack(B, D, HW, workgroups, nullptr, &bytes);
+  return bytes;
+}
+
+int gl_lstsq_solve_stack(const float* stack, const float* obs, const float* err, int B, int D, int HW, int workgroups,
+                         int cholesky, float* coeffs, int* flags_or_null, float* normal_or_null, void* workspace,
+                         size_t workspace_bytes, void* hip_stream) {
+  if (!stack || !obs || !err || !coeffs || !workspace) return fail(GL_EINVAL, "null argument");
+  if (int rc = check_solve_stack_shape(B, D, HW, workgroups)) return rc;
+  size_t bytes = 0;
+  const SolveWs sw = carve_solve_stack(B, D, HW, workgroups, workspace, &bytes);
+  if (workspace_bytes < bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, bytes);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (int rc = lstsq_solve(stack, obs, err, B, D, HW, sw, false, cholesky != 0, coeffs, stream)) return rc;
+  if (flags_or_null) {  // no attempt: every system went to the eigenvalue solve
+    if (cholesky && D <= LS_LDS_MAXN)
+      GL_HIP(hipMemcpyAsync(flags_or_null, sw.todo, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, stream));
+    else
+      GL_HIP(hipMemsetD32Async((hipDeviceptr_t)flags_or_null, 1, (size_t)B, stream));
+  }
+  if (normal_or_null) {
+    const int DpDp = sw.Dp * sw.Dp;
+    // 2..8 chunks: the solve kernels summed the partials themselves; this pass repeats their additions in their order, so the
+    // matrix handed out is a re-sum, bitwise equal to the values they consumed, not a copy of them
+    if (sw.n_chunks > 1 && sw.n_chunks <= 8) {
+      hipLaunchKernelGGL(gl_partial_sum_kernel, dim3((DpDp + 255) / 256, B), dim3(256), 0, stream, sw.partial, sw.n_chunks, DpDp);
+      GL_HIP(hipGetLastError());
+    }
+    GL_HIP(hipMemcpy2DAsync(normal_or_null, sizeof(float) * DpDp, sw.partial, sizeof(float) * (size_t)sw.n_chunks * DpDp,
+                            sizeof(float) * DpDp, (size_t)B, hipMemcpyDeviceToDevice, stream));
+  }
+  return GL_OK;
+}
+
+int gl_lstsq_last_kernels(char* normal, char* chol, char* eigen, size_t cap) {
+  if (!normal || !chol || !eigen || cap == 0) return fail(GL_EINVAL, "bad argument");
+  char* out[3] = {normal, chol, eigen};
+  if (!g_lstsq_last_fn[2].load()) return fail(GL_EINVAL, "no linear solve has been launched in this process yet");
+  for (int k = 0; k < 3; ++k) {
+    const void* fn = g_lstsq_last_fn[k].load();
+    const char* name = fn ? hipKernelNameRefByPtr(fn, nullptr) : "";
+    if (!name) return fail(GL_ELAUNCH, "hipKernelNameRefByPtr returned no name");
+    snprintf(out[k], cap, "%s", name);
+  }
+  return GL_OK;
+}
+
 size_t gl_lstsq_workspace_bytes(const gl_model* m, int B) {
   if (!m || B <= 0) return 0;
   return carve_lstsq(m, B, nullptr, carve(m, B, nullptr, launch_plan(m, B))).bytes;
@@ -1327,6 +1498,7 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
     /* (table mode, five tile rows: 17 spilled VGPRs under the 128-register budget of four waves per SIMD since the live-pixel \
        list of round 4 -- three waves there) */                                                                  \
     m->last_main_fn = (const void*)&gl_shp_normal_kernel<NT_, ((I_ && NT_ < 5) ? 4 : 3), L_EplShear, NPS, I_>;              \
+    g_lstsq_last_fn[0] = m->last_main_fn.load();                                                                \
     hipLaunchKernelGGL((gl_shp_normal_kernel<NT_, ((I_ && NT_ < 5) ? 4 : 3), L_EplShear, NPS, I_>), grid, block, sh, stream, fa, sn);  \
   } while (0)
     if (nt == 1) { if (interp) GL_SHPN(1, true); else GL_SHPN(1, false); }
@@ -1347,76 +1519,9 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
     GL_HIP(hipMemcpyAsync(stacked_or_null, lw.stack, sizeof(float) * (size_t)B * D * HW, hipMemcpyDeviceToDevice, stream));
   }  // !fused
   if (!solve) return GL_OK;
-  NormalArgs na{};
-  na.stack = lw.stack;
-  na.obs = obs;
-  na.err = err;
-  na.D = D;
-  na.Dp = lw.Dp;
-  na.HW = HW;
-  na.chunk = lw.chunk;
-  na.n_chunks = lw.n_chunks;
-  na.partial = lw.partial;
-  if (fused) {
-    // the partials are already there
-  } else if (D + 1 <= LS_SMALL)
-    hipLaunchKernelGGL((gl_normal_small_kernel<LS_SMALL>), dim3(lw.n_chunks, B), dim3(256), 0, stream, na);
-  else if (D + 1 > LS_MAXD) {  // more than five tile rows: super-block pairs (gl_normal_pair_kernel)
-    const int vec_ok = (HW % 4 == 0) && ((uintptr_t)obs % 16 == 0) && ((uintptr_t)err % 16 == 0) && ((uintptr_t)lw.stack % 16 == 0);
-    const int n_sb = (D + 1 + 16 * LS_SB - 1) / (16 * LS_SB);
-    const dim3 grid(lw.n_chunks, B, n_sb * (n_sb + 1) / 2), block(256);
-    if (vec_ok) hipLaunchKernelGGL((gl_normal_pair_kernel<true>), grid, block, 0, stream, na);
-    else hipLaunchKernelGGL((gl_normal_pair_kernel<false>), grid, block, 0, stream, na);
-  } else {
-    // 16-byte loads need every channel row, obs and err on a 16-byte pitch
-    const int vec_ok = (HW % 4 == 0) && ((uintptr_t)obs % 16 == 0) && ((uintptr_t)err % 16 == 0) && ((uintptr_t)lw.stack % 16 == 0);
-    const dim3 grid(lw.n_chunks, B), block(256);
-#define GL_NORMAL_MFMA(NT_)                                                                          \
-  if (vec_ok) hipLaunchKernelGGL((gl_normal_mfma_kernel<NT_, true>), grid, block, 0, stream, na);   \
-  else hipLaunchKernelGGL((gl_normal_mfma_kernel<NT_, false>), grid, block, 0, stream, na)
-    switch ((D + 1 + 15) / 16) {
-      case 1: GL_NORMAL_MFMA(1); break;
-      case 2: GL_NORMAL_MFMA(2); break;
-      case 3: GL_NORMAL_MFMA(3); break;
-      case 4: GL_NORMAL_MFMA(4); break;
-      default: GL_NORMAL_MFMA(5); break;
-    }
-#undef GL_NORMAL_MFMA
-  }
-  GL_HIP(hipGetLastError());
   float* coeffs = coeffs_or_null ? coeffs_or_null : lw.coeffs;
-  int n_sum = lw.n_chunks;
-  if (n_sum > 8) {  // many chunks (small batches): reduce them with the whole chip first
-    hipLaunchKernelGGL(gl_partial_sum_kernel, dim3((lw.Dp * lw.Dp + 255) / 256, B), dim3(256), 0, stream, lw.partial,
-                       lw.n_chunks, lw.Dp * lw.Dp);
-    GL_HIP(hipGetLastError());
-    n_sum = 1;
-  }
-  const int* todo = nullptr;
-  if (D <= LS_LDS_MAXN && m->lstsq_chol) {  // the inverse when the pseudo-inverse's cut is provably idle (gl_chol_solve_kernel)
-    const int nb = D + 1 <= 64 ? 4 : D + 1 <= 80 ? 5 : 8;
-    const size_t sm = sizeof(float) * ((size_t)(D + 2) * (16 * nb + 1) + 4);
-    static bool chol_raised = false;
-    if (sm > 64 * 1024 && (rc = raise_lds_limit((const void*)&gl_chol_solve_kernel<8>, &chol_raised))) return rc;
-#define GL_CHOL(NB_) hipLaunchKernelGGL((gl_chol_solve_kernel<NB_>), dim3(B), dim3(256), sm, stream, lw.partial, lw.n_chunks, n_sum, D, \
-                                        lw.Dp, 1e-6f, coeffs, lw.todo)
-    if (nb == 4) GL_CHOL(4); else if (nb == 5) GL_CHOL(5); else GL_CHOL(8);
-#undef GL_CHOL
-    GL_HIP(hipGetLastError());
-    todo = lw.todo;
-  }
-  if (D <= LS_LDS_MAXN) {  // A and V in LDS: up to 129 KB of the CU's 160 (above 64 KB the kernel has to be told once)
-    const size_t sm = sizeof(float) * ((size_t)2 * D * (D | 1) + 8 * D + 8);
-    static bool eigh_raised = false;
-    if (sm > 64 * 1024 && (rc = raise_lds_limit((const void*)&gl_eigh_solve_kernel<2, false>, &eigh_raised))) return rc;
-    hipLaunchKernelGGL((gl_eigh_solve_kernel<2, false>), dim3(B), dim3(64), sm, stream, lw.partial, lw.n_chunks, n_sum, D, lw.Dp,
-                       1e-6f, coeffs, (float*)nullptr, todo);
-  } else {  // the two matrices in the workspace (L2), the vectors in LDS; four registers hold the tridiagonal
-    const size_t sm = sizeof(float) * ((size_t)8 * D + 8);
-    hipLaunchKernelGGL((gl_eigh_solve_kernel<4, true>), dim3(B), dim3(64), sm, stream, lw.partial, lw.n_chunks, n_sum, D, lw.Dp,
-                       1e-6f, coeffs, lw.mats, todo);
-  }
-  GL_HIP(hipGetLastError());
+  const SolveWs sw{lw.partial, lw.mats, lw.todo, lw.Dp, lw.chunk, lw.n_chunks};
+  if ((rc = lstsq_solve(lw.stack, obs, err, B, D, HW, sw, fused, m->lstsq_chol, coeffs, stream))) return rc;
   if (image_or_null && fused) {
     // image = sum_d coeffs_d basis_d = the ordinary render with the solved amplitudes in their parameter columns (no det(T):
     // the stack carries none, tf/simulator.py:226-240)

@@ -253,6 +253,26 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
  * solve live: 0 = the Cholesky attempt proved tf.linalg.pinv's rcond cut idle and solved the system (csrc/gl_lstsq.hip.h
  * gl_chol_solve_kernel), 1 = left to the eigenvalue solve.  GL_EUNSUPPORTED for systems the attempt does not serve (> 127). */
 int gl_lstsq_solve_flags(const gl_model* m, int B, size_t* offset_bytes);
+/* The solve half of gl_lstsq_fwd on a caller's own basis stack -- no gl_model: the normal-matrix kernel, the sum of the chunk
+ * partials, the Cholesky attempt and the eigenvalue solve, launched exactly as gl_lstsq_fwd launches them for a model with D linear
+ * coefficients on HW pixels (gl_lstsq_fwd runs this function after rendering its stack).
+ *   stack [B][D][HW], obs [HW], err [HW]   device pointers; err = +inf masks a pixel (weight 0)
+ *   workgroups   target of workgroups in flight of the normal-matrix kernel (gl_lstsq_fwd: 2048): sets the pixels per chunk
+ *   cholesky     0 = every system through the eigenvalue solve
+ *   coeffs [B][D];  flags_or_null [B] int32 as gl_lstsq_solve_flags (1 everywhere when no attempt ran);
+ *   normal_or_null [B][Dp][Dp], Dp = D + 1 rounded up to a multiple of 4: the summed normal matrix of the augmented system
+ *   [X | Y] the solve kernels consumed (lower triangle; row D = X^T Y, Y^T Y; columns D + 1 .. Dp - 1 are padding), copied from the
+ *   partials after the solve.
+ * GL_EUNSUPPORTED: D > 255.  GL_EINVAL: null pointers, non-positive sizes.  GL_ENOMEM: a workspace under
+ * gl_lstsq_solve_stack_workspace_bytes (0 for arguments the call refuses).
+ * gl_lstsq_last_kernels: the (mangled) symbols of the normal-matrix, Cholesky and eigenvalue kernel of this process's most
+ * recent solve through either entry point, an empty string for a stage that did not run; after a gl_lstsq_fwd on its stack-free
+ * path the first is the gl_shp_normal_kernel that formed the partials. */
+size_t gl_lstsq_solve_stack_workspace_bytes(int B, int D, int HW, int workgroups);
+int gl_lstsq_solve_stack(const float* stack, const float* obs, const float* err, int B, int D, int HW, int workgroups,
+                         int cholesky, float* coeffs, int* flags_or_null, float* normal_or_null, void* workspace,
+                         size_t workspace_bytes, void* hip_stream);
+int gl_lstsq_last_kernels(char* normal, char* chol, char* eigen, size_t cap);
 
 /* Galaxy catalogue of a GL_SCALED component (ScalingRelation.__init__, scaling_relation.py:27-55).  Must be attached
  * to every GL_SCALED component before gl_workspace_bytes / any compute call (the workspace holds one block of

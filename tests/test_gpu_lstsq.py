@@ -194,6 +194,39 @@ def test_lstsq_errors(gl):
     packed = sim2.pack(wl2.prior.sample(2, seed=0))
     with pytest.raises(_native.NativeLibraryError):  # coefficients need obs and err
         sim2._model.lstsq(packed, None, None, 7, want="coeffs")
+    # the direct entry on a caller's stack (gl_lstsq_solve_stack): D = 255 is served, 256 is GL_EUNSUPPORTED (-2); null or
+    # non-positive arguments are GL_EINVAL (-1), a short workspace GL_ENOMEM (-4); a refused shape has no workspace size
+    L, s, p = _native.lib(), _native._stream(), _native._ptr
+    dev = packed.device
+    HW = 320
+    for D, rc in ((255, 0), (256, -2)):
+        st = torch.zeros((1, D, HW), dtype=torch.float32, device=dev)
+        oe = torch.ones(HW, dtype=torch.float32, device=dev)
+        co = torch.full((D,), float("nan"), dtype=torch.float32, device=dev)
+        nb = L.gl_lstsq_solve_stack_workspace_bytes(1, D, HW, 4)
+        assert (nb > 0) == (rc == 0)
+        ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=dev)
+        assert L.gl_lstsq_solve_stack(p(st), p(oe), p(oe), 1, D, HW, 4, 1, p(co), None, None, p(ws), ws.numel(), s) == rc
+        torch.cuda.synchronize()
+        if rc == 0:
+            assert not co.any()  # an empty system: exactly 0
+        else:
+            assert b"exceed the 255" in L.gl_last_error() and torch.isnan(co).all()  # nothing was launched
+    D = 5
+    st = torch.zeros((2, D, HW), dtype=torch.float32, device=dev)
+    co = torch.zeros((2, D), dtype=torch.float32, device=dev)
+    nb = L.gl_lstsq_solve_stack_workspace_bytes(2, D, HW, 4)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    call = lambda stack=st, obs=oe, err=oe, B=2, D=D, HW=HW, wgs=4, out=co, w=ws, n=nb: L.gl_lstsq_solve_stack(
+        p(stack), p(obs), p(err), B, D, HW, wgs, 1, p(out), None, None, p(w), n, s)
+    assert call(stack=None) == -1 and call(obs=None) == -1 and call(err=None) == -1 and call(out=None) == -1 and call(w=None) == -1
+    assert call(B=0) == -1 and call(B=-2) == -1 and call(D=0) == -1 and call(HW=0) == -1 and call(wgs=0) == -1
+    assert call(n=nb - 1) == -4 and b"workspace too small" in L.gl_last_error()
+    for bad in ((0, D, HW, 4), (2, 0, HW, 4), (2, D, -1, 4), (2, D, HW, 0)):
+        assert L.gl_lstsq_solve_stack_workspace_bytes(*bad) == 0
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert L.gl_lstsq_last_kernels(None, None, None, 0) == -1
 
 
 def test_full_size_round_trip(gl):
