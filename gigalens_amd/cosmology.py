@@ -41,3 +41,61 @@ def deflection_scale(z_lens, z_source, z_ref, omega_m=0.3):
         raise ValueError(f"z_ref must be finite and > z_lens = {z_lens}, got {z_ref}")
     c = distance_ratio(z_lens, zs, omega_m) / distance_ratio(z_lens, z_ref, omega_m)
     return float(c) if zs.ndim == 0 else c
+
+
+class MultiPlane:
+    """Couplings of lens planes at several redshifts (multi-plane ray tracing; host only, numpy float64).
+
+    Every lens keeps its parameters as the reduced deflection for the reference plane ``z_ref``.  With the planes sorted by
+    redshift, ``z_1 < ... < z_K``, a ray that leaves the observer at ``theta`` meets plane j at
+
+        theta_j = theta - sum_{i<j} C_ij a_i,   a_i = sum_{lenses l on plane i} alpha_l(theta_i),   theta_1 = theta,
+
+    and a target t behind some of the planes at ``beta_t = theta - sum_{i: z_i < z_t} C_it a_i``, with the coupling
+    ``C_ij = deflection_scale(z_i, z_j, z_ref) = [D_ij / D_j] / [D_i,ref / D_ref]``.  One plane gives ``beta = theta - c sum alpha``.
+
+    ``z_lenses``: one redshift per lens of the model, in the model's order; lenses at equal redshift share a plane.  ``z_sources``: one
+    per source light.  Attributes: ``z_planes`` ``[K]`` ascending; ``plane_of_lens`` (one int per lens); ``lens_scales`` ``[K, K]``,
+    strictly upper triangular; ``source_scales`` ``[K, S]`` (0 for the planes at or behind a source); ``K``, ``S``.
+    ``ValueError``: a redshift that is not finite or not > 0, ``z_ref`` not behind every lens, a source at or in front of the first
+    plane, more than ``MAX_PLANES`` planes."""
+
+    MAX_PLANES = 4
+
+    def __init__(self, z_lenses, z_sources, z_ref, omega_m=0.3):
+        zl = np.atleast_1d(np.asarray(z_lenses, dtype=np.float64))
+        zs = np.atleast_1d(np.asarray(z_sources, dtype=np.float64)) if np.size(z_sources) else np.zeros(0)
+        if zl.ndim != 1 or zl.size == 0:
+            raise ValueError("z_lenses: one redshift per lens, at least one")
+        if zs.ndim != 1:
+            raise ValueError("z_sources: one redshift per source light")
+        for what, z in (("z_lenses", zl), ("z_sources", zs), ("z_ref", np.atleast_1d(np.float64(z_ref)))):
+            if not (np.all(np.isfinite(z)) and np.all(z > 0.0)):
+                raise ValueError(f"{what}: every redshift must be finite and > 0, got {z.tolist()}")
+        self.z_ref, self.omega_m = float(z_ref), float(omega_m)
+        if not self.z_ref > zl.max():
+            raise ValueError(f"z_ref = {self.z_ref} must lie behind every lens plane (largest z_lens = {zl.max()})")
+        self.z_planes, inverse = np.unique(zl, return_inverse=True)
+        self.plane_of_lens = inverse.astype(np.int32).reshape(-1)
+        self.K, self.S = int(self.z_planes.size), int(zs.size)
+        if self.K > self.MAX_PLANES:
+            raise ValueError(f"{self.K} lens planes: at most {self.MAX_PLANES} are served")
+        if np.any(zs <= self.z_planes[0]):
+            raise ValueError(f"every source must lie behind the first lens plane (z = {self.z_planes[0]}), got {zs.tolist()}")
+        self.z_sources = zs
+        self.lens_scales = np.zeros((self.K, self.K))
+        for i in range(self.K - 1):
+            self.lens_scales[i, i + 1:] = deflection_scale(self.z_planes[i], self.z_planes[i + 1:], self.z_ref, omega_m)
+        self.source_scales = (np.stack([self.target_scales(z) for z in zs], axis=1) if self.S else np.zeros((self.K, 0)))
+
+    def target_scales(self, z):
+        """``[K]`` couplings of a target plane at redshift ``z``: ``deflection_scale(z_i, z, z_ref)`` for the planes in front of it, 0
+        for those at or behind it.  ``ValueError`` unless ``z`` is finite and behind the first plane."""
+        z = float(z)
+        if not (np.isfinite(z) and z > self.z_planes[0]):
+            raise ValueError(f"a target must be finite and lie behind the first lens plane (z = {self.z_planes[0]}), got {z}")
+        out = np.zeros(self.K)
+        for i, zi in enumerate(self.z_planes):
+            if zi < z:
+                out[i] = deflection_scale(zi, z, self.z_ref, self.omega_m)
+        return out

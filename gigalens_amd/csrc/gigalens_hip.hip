@@ -25,6 +25,7 @@
 #include "gl_images.hip.h"
 #include "gl_critical.hip.h"
 #include "gl_pixsrc.hip.h"
+#include "gl_multiplane.hip.h"
 #include "gl_potential.hip.h"
 #include "gl_lstsq.hip.h"
 #include "gl_shp.hip.h"
@@ -175,6 +176,11 @@ Workspace carve(const gl_model* m, int B, void* base, const LaunchPlan& plan) {
     off += align_up((size_t)B * (m->height / m->supersample) * (m->width / m->supersample) * sizeof(float), 256);
     w.stats = (float*)(p + off);
     off += align_up((size_t)B * 2 * sizeof(float), 256);
+  } else if (m->mp_K >= 2) {  // lens planes (gl_multiplane_loglike): the image is materialised for the pixel statistics
+    w.img_tmp = (float*)(p + off);
+    off += align_up((size_t)B * m->height * m->width * sizeof(float), 256);
+    w.stats = (float*)(p + off);
+    off += align_up((size_t)B * 2 * sizeof(float), 256);
   }
   w.bytes = off;
   return w;
@@ -231,6 +237,15 @@ int check_ready(const gl_model* m, bool with_series, bool counted) {
   if (with_series && no_field)
     return counted ? fail(GL_EINVAL, "%d GL_SERIES component(s) without a coefficient field (gl_model_set_series)", no_field)
                    : fail(GL_EINVAL, "GL_SERIES component without a coefficient field");
+  return GL_OK;
+}
+
+// A model with lens planes (gl_model_set_lens_planes) is served by the gl_multiplane_* entries alone: every single-plane entry
+// refuses it instead of tracing its lenses as if they shared a plane.
+int refuse_planes(const gl_model* m, const char* what) {
+  if (m && m->mp_K >= 2)
+    return fail(GL_EUNSUPPORTED, "%s does not serve a model with %d lens planes (gl_model_set_lens_planes): forward maps, renders and "
+                                 "pixel statistics only (gl_multiplane_maps, gl_multiplane_simulate, gl_multiplane_loglike)", what, m->mp_K);
   return GL_OK;
 }
 
@@ -1193,6 +1208,7 @@ int gl_simulate_fwd(const gl_model* m, const float* params, int B, float* img, v
 
 int gl_simulate_parts_fwd(const gl_model* m, const float* params, int B, unsigned parts, float* img, void* workspace,
                           size_t workspace_bytes, void* hip_stream) {
+  if (int rp = refuse_planes(m, "gl_simulate_parts_fwd")) return rp;
   LaunchPlan plan;
   Workspace w;
   int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
@@ -1215,6 +1231,7 @@ int gl_simulate_parts_fwd(const gl_model* m, const float* params, int B, unsigne
 
 int gl_simulate_bwd(const gl_model* m, const float* params, const float* grad_img, int B, float* grad_params,
                     void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rp = refuse_planes(m, "gl_simulate_bwd")) return rp;
   LaunchPlan plan;
   Workspace w;
   int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
@@ -1237,6 +1254,7 @@ int gl_simulate_bwd(const gl_model* m, const float* params, const float* grad_im
 int gl_loglike_fwd_bwd(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
                        const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
                        float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rp = refuse_planes(m, "gl_loglike_fwd_bwd")) return rp;
   LaunchPlan plan;
   Workspace w;
   int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
@@ -1445,6 +1463,7 @@ int gl_lstsq_fwd(const gl_model* m, const float* params, const float* obs, const
                  float* coeffs_or_null, float* stacked_or_null, float* image_or_null, void* workspace,
                  size_t workspace_bytes, void* hip_stream) {
   if (!m) return fail(GL_EINVAL, "model is null");
+  if (int rp = refuse_planes(m, "gl_lstsq_fwd")) return rp;
   if (m->has_user && !m->user_fn[IMG_BASIS]) return fail(GL_EUNSUPPORTED, "the basis-stack kernel of this model with user-written profiles was not built");
   const int D = (int)m->lin_cols.size();
   if (D == 0) return fail(GL_EINVAL, "the model has no linear (light amplitude) coefficients");
@@ -1855,6 +1874,7 @@ int gl_model_set_source_scales(gl_model* m, const float* scales, int n_src) {
   if (!m) return fail(GL_EINVAL, "model is null");
   bool any;
   if (int rc = check_scales(scales, n_src, m->n_src, "source light component(s)", &any)) return rc;
+  if (any && m->mp_K >= 2) return fail(GL_EINVAL, "the model has lens planes (gl_model_set_lens_planes): their source couplings replace per-source scales");
   if (any && m->has_user)
     return fail(GL_EUNSUPPORTED, "per-source deflection scales are not served on the pixel grid for models with user-written profiles");
   if (any) GL_HIP(m->d_src_scale.upload(scales, (size_t)n_src));
@@ -1887,6 +1907,7 @@ int gl_model_set_position_scales(gl_model* m, const float* scales, int n_familie
 
 int gl_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
                          float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rp = refuse_planes(m, "gl_positions_fwd_bwd")) return rp;
   LaunchPlan plan;
   Workspace w;
   int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
@@ -1919,6 +1940,7 @@ int gl_profile_hessian(const gl_component* comp, const float* x, const float* y,
 int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
                  int xy_batched, float* out, void* hip_stream) {
   if (!m || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_lens_maps")) return rp;
   if (m->has_user)  // the kernel below compiled at run time with the user's bodies (Hessians from the duals)
     if (int rc = compile_user_points(m)) return rc;
   if ((x == nullptr) != (y == nullptr)) return fail(GL_EINVAL, "x and y must both be given or both be null");
@@ -1958,6 +1980,7 @@ bool potential_kind(int kind) {
 int gl_lens_potential(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
                       int xy_batched, float* out, void* hip_stream) {
   if (!m || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_lens_potential")) return rp;
   if ((x == nullptr) != (y == nullptr)) return fail(GL_EINVAL, "x and y must both be given or both be null");
   if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
   for (int l = 0; l < m->n_lens; ++l) {
@@ -2035,6 +2058,7 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
                               float tol, int max_iter, float* out, int* n_images, int* n_dropped, void* workspace,
                               size_t workspace_bytes, void* hip_stream) {
   if (!m || !params || !src_x || !src_y || !out || !n_images || !n_dropped) return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_image_positions")) return rp;
   if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
   if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
   if (max_images < 1 || max_images > IMG_MAXC) return fail(GL_EINVAL, "max_images %d outside [1, %d]", max_images, IMG_MAXC);
@@ -2134,6 +2158,7 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
                               void* hip_stream) {
   if (!m || !params || !seg || !cau || !kind || !n_seg || !n_dropped || !n_flagged || !open || !area)
     return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_critical_curves")) return rp;
   if (!(std::isfinite(scale) && scale > 0.f)) return fail(GL_EINVAL, "scale (%g) is not finite and > 0", scale);
   if (B <= 0) return fail(GL_EINVAL, "B (%d) must be positive", B);
   if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
@@ -2235,6 +2260,7 @@ int gl_pixsrc_reconstruct(const gl_model* m, const float* beta_x, const float* b
                           void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!m || !beta_x || !beta_y || !obs || !sigma || !pix || !pose || !strength || !source || !model_image || !scalars || !ok)
     return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_pixsrc_reconstruct")) return rp;
   if (ny <= 0 || nx <= 0) return fail(GL_EINVAL, "source grid %d x %d: both sides must be positive", ny, nx);
   if ((long long)ny * nx > PIX_MAX_S) return fail(GL_EUNSUPPORTED, "source grid %d x %d has more than %d nodes", ny, nx, PIX_MAX_S);
   if (regularization < PIX_REG_IDENTITY || regularization > PIX_REG_CURVATURE) return fail(GL_EINVAL, "unknown regularization %d", regularization);
@@ -2300,6 +2326,150 @@ int gl_pixsrc_reconstruct(const gl_model* m, const float* beta_x, const float* b
   return GL_OK;
 }
 
+// ---- lens planes at redshifts of their own (gl_multiplane.hip.h) ---------------------------------------------------
+namespace {
+MpArgs mp_args(const gl_model* m) {
+  MpArgs a{};
+  a.order = m->d_mp_lens;
+  a.plane = m->d_mp_lens + m->n_lens;
+  a.scale = m->d_mp_scale;
+  return a;
+}
+
+// the model's image of `parts` on its planes: into `img` [B][H][W] (x conversion factor), through the PSF + pooling launch of the
+// single-plane render where the model has one
+int mp_render(const gl_model* m, const float* params, int B, unsigned parts, float* img, const Workspace& w, hipStream_t stream) {
+  MpRender r{};
+  r.gx = m->d_gx;
+  r.gy = m->d_gy;
+  r.pix = m->d_pix;
+  r.N = m->N;
+  r.n_ll = m->n_ll;
+  r.n_src = m->n_src;
+  r.parts = parts;
+  r.img_stride = (long long)m->height * m->width;
+  r.img = m->has_post ? w.img_ss : img;
+  r.out_scale = m->has_post ? 1.f : m->conversion_factor;  // (with a PSF the det(T) scale is applied after pooling, as in render_ss)
+  if (m->d_pix) GL_HIP(hipMemsetAsync(r.img, 0, sizeof(float) * (size_t)B * m->height * m->width, stream));
+  hipLaunchKernelGGL(gl_mp_render_kernel, dim3((unsigned)((m->N + MP_WG - 1) / MP_WG), (unsigned)B), dim3(MP_WG), 0, stream,
+                     point_args(m, params, B), mp_args(m), r);
+  GL_HIP(hipGetLastError());
+  return m->has_post ? post_fwd(m, B, w.img_ss, img, stream, m->conversion_factor) : GL_OK;
+}
+
+int check_planes_set(const gl_model* m) {
+  return m->mp_K >= 2 ? GL_OK : fail(GL_EINVAL, "gl_model_set_lens_planes has not been called on this model");
+}
+}  // namespace
+
+int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, int n_planes, const float* lens_scales,
+                             const float* source_scales, int n_src) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  if (n_planes > MP_MAXK) return fail(GL_EUNSUPPORTED, "%d lens planes: at most %d are served", n_planes, MP_MAXK);
+  if (n_planes < 2) return fail(GL_EINVAL, "%d lens plane(s): two or more (one plane: gl_model_set_source_scales)", n_planes);
+  if (!plane_of_lens || !lens_scales || (!source_scales && n_src > 0)) return fail(GL_EINVAL, "null argument");
+  if (n_lens != m->n_lens) return fail(GL_EINVAL, "%d plane indices for %d lens(es)", n_lens, m->n_lens);
+  if (n_src != m->n_src) return fail(GL_EINVAL, "source couplings of %d source(s) for %d source light component(s)", n_src, m->n_src);
+  const int K = n_planes;
+  if (m->has_user) return fail(GL_EUNSUPPORTED, "lens planes are not served for models with user-written profiles");
+  if (m->n_series)
+    return fail(GL_EUNSUPPORTED, "a series-expansion lens stores its field on the image-plane grid theta, not on the ray's position "
+                                 "theta_j on its own plane: not served on lens planes");
+  if (m->src_scaled) return fail(GL_EINVAL, "the model carries per-source deflection scales (gl_model_set_source_scales): the source couplings of the planes replace them");
+  for (int l = 0; l < m->n_lens; ++l)
+    if (m->comps[l].kind == K_SCALED)
+      return fail(GL_EUNSUPPORTED, "lens %d: galaxy catalogues (GL_SCALED) are not served on lens planes", l);
+  for (int c = m->n_lens; c < (int)m->comps.size(); ++c) {
+    const int kind = m->comps[c].kind;
+    if (kind != K_SERSIC && kind != K_SERSIC_ELLIPSE && kind != K_CORE_SERSIC)
+      return fail(GL_EUNSUPPORTED, "light component %d (kind %d): lens planes serve Sersic, SersicEllipse and CoreSersic lights", c, kind);
+  }
+  std::vector<int> count(K, 0);
+  for (int l = 0; l < n_lens; ++l) {
+    if (plane_of_lens[l] < 0 || plane_of_lens[l] >= K) return fail(GL_EINVAL, "plane_of_lens[%d] = %d outside [0, %d)", l, plane_of_lens[l], K);
+    ++count[plane_of_lens[l]];
+  }
+  for (int i = 0; i < K; ++i)
+    if (!count[i]) return fail(GL_EINVAL, "lens plane %d holds no lens", i);
+  std::vector<float> scale((size_t)MP_MAXK * MP_MAXK + (size_t)MP_MAXK * std::max(n_src, 0), 0.f);
+  for (int i = 0; i < K; ++i)
+    for (int j = 0; j < K; ++j) {
+      const float c = lens_scales[i * K + j];
+      if (i >= j ? c != 0.f : !(std::isfinite(c) && c > 0.f))
+        return fail(GL_EINVAL, "lens_scales[%d][%d] = %g: strictly upper triangular, finite and > 0 above the diagonal", i, j, c);
+      scale[(size_t)i * MP_MAXK + j] = c;
+    }
+  for (int s = 0; s < n_src; ++s)
+    for (int i = 0; i < K; ++i) {
+      const float c = source_scales[(size_t)i * n_src + s];
+      // a plane at or behind a source does not deflect it: zero from that plane on; the first plane lies in front of every source
+      const bool ok = std::isfinite(c) && c >= 0.f && (i == 0 ? c > 0.f : (c == 0.f || source_scales[(size_t)(i - 1) * n_src + s] > 0.f));
+      if (!ok) return fail(GL_EINVAL, "source_scales[%d][%d] = %g: finite, > 0 on the first plane, 0 from the first plane behind the source on", i, s, c);
+      scale[(size_t)MP_MAXK * MP_MAXK + (size_t)i * n_src + s] = c;
+    }
+  std::vector<int> lens((size_t)2 * std::max(n_lens, 1));
+  int t = 0;
+  for (int i = 0; i < K; ++i)
+    for (int l = 0; l < n_lens; ++l)
+      if (plane_of_lens[l] == i) lens[t++] = l;
+  for (int l = 0; l < n_lens; ++l) lens[(size_t)n_lens + l] = plane_of_lens[l];
+  GL_HIP(m->d_mp_lens.upload(lens.data(), lens.size()));
+  GL_HIP(m->d_mp_scale.upload(scale.data(), scale.size()));
+  m->mp_K = K;
+  return GL_OK;
+}
+
+int gl_multiplane_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
+                       const float* target_scales, int n_planes, float* out, void* hip_stream) {
+  if (!m || !params || !x || !y || !target_scales || !out) return fail(GL_EINVAL, "null argument");
+  if (int rc = check_planes_set(m)) return rc;
+  if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
+  if (n_planes != m->mp_K) return fail(GL_EINVAL, "%d target couplings for %d lens planes", n_planes, m->mp_K);
+  if (int rc = check_ready(m, false, false)) return rc;
+  MpTarget tg{};
+  for (int i = 0; i < n_planes; ++i) {
+    const float c = target_scales[i];
+    if (!(std::isfinite(c) && c >= 0.f) || (i > 0 && c != 0.f && target_scales[i - 1] == 0.f))
+      return fail(GL_EINVAL, "target_scales[%d] = %g: finite and >= 0, 0 from the first plane at or behind the target on", i, c);
+    tg.c[i] = c;
+  }
+  const long long total = (long long)n_pts * B, blocks = (total + MP_MAPS_WG - 1) / MP_MAPS_WG;
+  if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
+  hipLaunchKernelGGL(gl_mp_maps_kernel, dim3((unsigned)blocks), dim3(MP_MAPS_WG), 0, (hipStream_t)hip_stream, point_args(m, params, B),
+                     mp_args(m), tg, x, y, (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+int gl_multiplane_simulate(const gl_model* m, const float* params, int B, unsigned parts, float* img, void* workspace,
+                           size_t workspace_bytes, void* hip_stream) {
+  LaunchPlan plan;
+  Workspace w;
+  if (int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w)) return rc;
+  if (int rc = check_planes_set(m)) return rc;
+  if (!img) return fail(GL_EINVAL, "img is null");
+  if (parts == 0 || parts > 7u) return fail(GL_EINVAL, "parts must be a non-empty subset of {1,2,4}");
+  return mp_render(m, params, B, parts, img, w, (hipStream_t)hip_stream);
+}
+
+int gl_multiplane_loglike(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
+                          const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
+                          void* workspace, size_t workspace_bytes, void* hip_stream) {
+  LaunchPlan plan;
+  Workspace w;
+  if (int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w)) return rc;
+  if (int rc = check_planes_set(m)) return rc;
+  if (!obs || !loglike || !chi2) return fail(GL_EINVAL, "obs / loglike / chi2 is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (int rc = mp_render(m, params, B, 7u, w.img_tmp, w, stream)) return rc;
+  const int HW = (m->height / m->supersample) * (m->width / m->supersample);
+  hipLaunchKernelGGL(gl_imgstats_kernel, dim3(B), dim3(256), 0, stream, w.img_tmp, obs, err_or_null, mask_or_null, bg_rms * bg_rms,
+                     1.0f / exp_time, HW, w.stats, (float*)nullptr);
+  GL_HIP(hipGetLastError());
+  // chi2 and normalisation of the materialised image -> loglike, chi2: the finalize launch of the PSF path, forward only
+  return run_finalize(m, params, B, plan.n_chunks, w, loglike, chi2, nullptr, stream, nullptr, nullptr, nullptr, 1.f, w.stats, 0);
+}
+
 int gl_model_set_prior(gl_model* m, const gl_zcolumn* cols, int d, const float* const_row) {
   if (!m) return fail(GL_EINVAL, "model is null");
   if (d < 0 || (d > 0 && !cols)) return fail(GL_EINVAL, "bad prior column table");
@@ -2331,6 +2501,7 @@ int gl_logprob_fwd_bwd(const gl_model* m, const float* z, const float* obs, cons
                        const float* mask_or_null, float bg_rms, float exp_time, int B, float* logprob, float* loglike,
                        float* chi2, float* grad_z_or_null, float chi2_divisor, unsigned terms, void* workspace,
                        size_t workspace_bytes, void* hip_stream) {
+  if (int rp = refuse_planes(m, "gl_logprob_fwd_bwd")) return rp;
   LaunchPlan plan;
   Workspace w;
   int rc = check_call(m, z, B, workspace, workspace_bytes, &plan, &w);

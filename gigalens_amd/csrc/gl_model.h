@@ -159,6 +159,11 @@ struct gl_model {
   glk::DevBuf<float> d_src_scale;      // [n_src], allocated only while src_scaled
   bool pos_scaled = false;             // some image family has a scale != 1
   glk::DevBuf<float> d_pos_scale;      // [J]: the scale of every image's family, allocated only while pos_scaled
+  // lens planes at redshifts of their own (gl_model_set_lens_planes, gl_multiplane.hip.h).  mp_K = 0: one plane, and every entry
+  // point runs as it did before the planes existed; mp_K >= 2: the multi-plane entries serve the model, the single-plane ones refuse
+  int mp_K = 0;
+  glk::DevBuf<int> d_mp_lens;     // [2][n_lens]: the lenses sorted by plane, the plane of every lens
+  glk::DevBuf<float> d_mp_scale;  // [4][4] plane couplings, then [4][n_src] source couplings (zero-padded rows)
   bool has_epl = false;
   int epl_comp = -1;     // the model's only EPL component, or -1 (none / several)
   int fam = 0;  // family level of the interpreter variant (gl_main_kernel FAM): 1 dPIE family / catalogues / series, 2 gl_extra.h

@@ -78,12 +78,28 @@ class PhysicalModel(PhysicalModelBase):
 
     def __init__(self, lenses, lens_light, source_light, lenses_constants: List[Dict] = None,
                  lens_light_constants: List[Dict] = None, source_light_constants: List[Dict] = None,
-                 source_light_scales=None):
+                 source_light_scales=None, multiplane=None):
         """``source_light_scales`` (beyond the reference): one deflection scale per ``source_light`` entry, for sources at different
         redshifts behind the one lens plane -- source s is rendered at ``beta_s = theta - c_s sum alpha``
-        (``gigalens_amd.cosmology.deflection_scale`` gives c from the redshifts).  Default: all 1, the reference's single plane."""
+        (``gigalens_amd.cosmology.deflection_scale`` gives c from the redshifts).  Default: all 1, the reference's single plane.
+
+        ``multiplane`` (beyond the reference): a ``gigalens_amd.cosmology.MultiPlane`` -- the lenses sit at redshifts of their own.
+        With one plane it is rewritten here into ``source_light_scales`` (the existing kernels, the existing bits).  With two to four
+        planes ``LensSimulator`` traces every ray through them in redshift order (``self.multiplane``; forward only: lens maps,
+        renders and ``ForwardProbModel.stats_pixels`` -- everything else raises ``_native.UnsupportedLensError``)."""
         super().__init__(lenses, lens_light, source_light, lenses_constants, lens_light_constants,
                          source_light_constants)
+        self.multiplane = None
+        if multiplane is not None:
+            if source_light_scales is not None:
+                raise ValueError("multiplane and source_light_scales are two ways to place the sources: give one")
+            if len(multiplane.plane_of_lens) != len(lenses) or multiplane.S != len(source_light):
+                raise ValueError(f"multiplane describes {len(multiplane.plane_of_lens)} lens(es) and {multiplane.S} source(s), the model "
+                                 f"has {len(lenses)} and {len(source_light)}")
+            if multiplane.K == 1:
+                source_light_scales = multiplane.source_scales[0]
+            else:
+                self.multiplane = multiplane
         self.source_light_scales = _native.deflection_scales(source_light_scales, len(source_light), "source_light_scales")
         self._source_scales_given = source_light_scales is not None
         cast = lambda ds: [{k: np.asarray(v, dtype=np.float32) for k, v in d.items()} for d in ds]
@@ -388,6 +404,12 @@ class ForwardProbModel(ProbabilisticModel):
         return x.index_select(1, cols)
 
     def _pixel_stats_packed(self, simulator, packed):
+        if getattr(simulator, "_mp", None) is not None:  # lens planes: the forward image through the image-statistics launch
+            if packed.requires_grad:
+                raise NotImplementedError("the pixel statistics of a model with several lens planes are forward only (no gradient)")
+            ll, chi2 = simulator._model.multiplane_loglike(packed, self.observed_image, self.error_map, self._mask(simulator),
+                                                           self.background_rms or 0.0, self.exp_time or 1.0)
+            return ll, chi2 / self._n_eff(simulator)
         ll, chi2 = _LogLikeFn.apply(packed, simulator._model, self.observed_image, self.error_map,
                                     simulator.img_region if simulator.sim_config.pix_region is not None else None,
                                     self.background_rms or 0.0, self.exp_time or 1.0)

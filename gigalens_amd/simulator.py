@@ -153,6 +153,9 @@ class LensSimulator(LensSimulatorInterface):
             from gigalens_amd.kernel_util import subgrid_kernel
             psf = np.asarray(subgrid_kernel(np.asarray(sim_config.kernel), ss, odd=True), dtype=np.float32)
         self.kernel = psf
+        self._mp = getattr(phys_model, "multiplane", None)  # lenses on planes of their own (PhysicalModel multiplane, K >= 2)
+        if self._mp is not None:
+            self._refuse_on_planes_profiles()
         bodies = []  # user-written profile bodies (profile.py `hip_body`): compiled into this model's kernels
         comps = ([_native.component_of(p, bodies) for p in phys_model.lenses]
                  + [_native.component_of(p, bodies) for p in phys_model.lens_light]
@@ -171,10 +174,52 @@ class LensSimulator(LensSimulatorInterface):
         for i, light in enumerate(list(phys_model.lens_light) + list(phys_model.source_light)):
             if getattr(light, "_kind", 0) == _native.GL_INTERPOL:  # the image of an Interpolated light, a constant of the model
                 self._model.set_light_image(len(phys_model.lenses) + i, light.image)
+        if self._mp is not None:
+            self._model.set_lens_planes(self._mp.plane_of_lens, self._mp.lens_scales, self._mp.source_scales)
         if getattr(phys_model, "_source_scales_given", False):  # sources on planes of their own (PhysicalModel source_light_scales)
             self._model.set_source_scales(phys_model.source_light_scales)
         self._layout = phys_model._packing()
         assert self._layout.P == self._model.P
+
+    # -- lenses on planes of their own (PhysicalModel multiplane with K >= 2) ------------------------
+    def _refuse_on_planes_profiles(self):
+        pm = self.phys_model
+        for i, lens in enumerate(pm.lenses):
+            if getattr(lens, "_kind", 0) == 10:
+                raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): a series expansion stores its field on the image-plane "
+                                                   "grid, not at the ray's position on the lens's own plane: not served on lens planes")
+        for p in list(pm.lenses) + list(pm.lens_light) + list(pm.source_light):
+            if not getattr(p, "_kind", 0):
+                raise _native.UnsupportedLensError(f"profile {p.name!r}: user-written bodies (hip_body) and run-time compiled member "
+                                                   "loops are not served on lens planes")
+
+    def _single_plane(self, what):
+        if self._mp is not None:
+            raise _native.UnsupportedLensError(f"{what} does not serve a model with {self._mp.K} lens planes: multi-plane ray tracing "
+                                               "is forward only (beta, magnification, convergence, shear, rotation, simulate*, "
+                                               "stats_pixels)")
+
+    def _target_scales(self, deflection_scale):
+        """The ``deflection_scale`` keyword of the lens maps on a multi-plane model: a source index, or the ``[K]`` couplings of the
+        target plane (``MultiPlane.target_scales(z)``)."""
+        mp = self._mp
+        if isinstance(deflection_scale, (int, np.integer)) and not isinstance(deflection_scale, bool):
+            if not 0 <= int(deflection_scale) < mp.S:
+                raise ValueError(f"deflection_scale: source index {deflection_scale} outside [0, {mp.S})")
+            return np.asarray(mp.source_scales[:, int(deflection_scale)], dtype=np.float32)
+        t = np.asarray(deflection_scale, dtype=np.float64)
+        if t.shape != (mp.K,):
+            raise ValueError(f"deflection_scale: a model with {mp.K} lens planes takes a source index or the [{mp.K}] couplings of "
+                             f"the target plane (MultiPlane.target_scales(z)), got {deflection_scale!r}")
+        if not (np.all(np.isfinite(t)) and np.all(t >= 0)):
+            raise ValueError(f"deflection_scale: every coupling must be finite and >= 0, got {t.tolist()}")
+        return t.astype(np.float32)
+
+    def _mp_maps(self, what, x, y, lens_params, deflection_scale):
+        t = self._target_scales(deflection_scale)
+        packed = self._lens_rows(lens_params)
+        self._forward_only(what, packed, x, y)
+        return self._model.multiplane_maps(packed, x, y, t)
 
     # -- packing between the reference's nested parameter dicts and the native [B, P] rows ---------
     def pack(self, params: Dict[str, List[Dict]]):
@@ -189,6 +234,9 @@ class LensSimulator(LensSimulatorInterface):
         """tf/simulator.py:72-78 on arbitrary points (plugin-level kernels, one per lens).  ``deflection_scale`` (beyond the
         reference, as on the methods below): the scale c of a source plane at another redshift than the model's reference plane
         (``gigalens_amd.cosmology.deflection_scale``): ``beta = theta - c sum alpha``, Hessian ``c H``."""
+        if self._mp is not None:  # lens planes: ``deflection_scale`` a source index or MultiPlane.target_scales(z)
+            maps = self._mp_maps("beta", x, y, lens_params, deflection_scale)
+            return maps[0], maps[1]
         cs = self._scale(deflection_scale)
         beta_x, beta_y = x, y
         for lens, p, c in zip(self.phys_model.lenses, lens_params, self.phys_model.lenses_constants):
@@ -220,7 +268,10 @@ class LensSimulator(LensSimulatorInterface):
         return self._model.lens_maps(packed, None, None)
 
     def _hessian(self, x, y, lens_params, deflection_scale):
-        """``f_xx, f_xy, f_yx, f_yy`` of ``_lens_maps`` on the plane of ``deflection_scale`` (linear in it: ``c H``)."""
+        """``f_xx, f_xy, f_yx, f_yy`` of ``_lens_maps`` on the plane of ``deflection_scale`` (linear in it: ``c H``).  With lens
+        planes: ``I - A_t`` of the target plane, which is not symmetric."""
+        if self._mp is not None:
+            return tuple(self._mp_maps("the lens maps", x, y, lens_params, deflection_scale)[2:])
         cs = self._scale(deflection_scale)
         h = self._lens_maps(x, y, lens_params)[2:]
         return tuple(h) if cs == 1.0 else tuple(cs * f for f in h)
@@ -239,6 +290,12 @@ class LensSimulator(LensSimulatorInterface):
         """tf/simulator.py:100-107: ``(gamma1, gamma2) = ((f_xx - f_yy)/2, f_xy)`` (tf/profile.py:36-42)."""
         fxx, fxy, _, fyy = self._hessian(x, y, lens_params, deflection_scale)
         return 0.5 * (fxx - fyy), fxy
+
+    def rotation(self, x, y, lens_params: List[Dict], deflection_scale=1.0):
+        """Rotation ``(A_xy - A_yx) / 2`` of the lensing Jacobian ``A = I - Hessian`` (beyond the reference): zero to rounding for one
+        lens plane, where A is symmetric, and the signature of lens-lens coupling between several."""
+        _, fxy, fyx, _ = self._hessian(x, y, lens_params, deflection_scale)
+        return 0.5 * (fyx - fxy)
 
     # default Newton tolerance |beta(theta) - beta_s| of image_positions, in units of the float32 spacing at the window's largest
     # coordinate: beta = theta - alpha is a float32 difference of numbers of that size, so its rounding alone is a few ulp of it
@@ -275,6 +332,7 @@ class LensSimulator(LensSimulatorInterface):
         stored or refined (``max_images`` exceeded, Newton not converged, converged outside the window) warn, or raise
         ``RuntimeError`` with ``strict=True``.  ``deflection_scale``: a scalar, or one value per source ``[S]`` -- source s is solved
         on its own plane ``beta_s(theta) = theta - c_s sum alpha`` (``mu`` is that plane's magnification).  Forward only (no gradient)."""
+        self._single_plane("image_positions")
         if torch.is_tensor(lens_params):
             packed = lens_params
         elif isinstance(lens_params, dict):
@@ -323,6 +381,7 @@ class LensSimulator(LensSimulatorInterface):
         or raise ``RuntimeError`` with ``strict=True``.  Built-in kinds and dPIE-family catalogues; series expansions, user-written
         bodies and run-time compiled ScalingRelation member loops raise ``_native.UnsupportedLensError``.  ``deflection_scale``: the
         curves of the source plane with that scale, ``det(I - c H) = 0`` and ``beta = theta - c sum alpha``.  Forward only."""
+        self._single_plane("critical_curves")
         packed = self._lens_rows(lens_params)
         self._forward_only("critical_curves", packed)
         cs = self._scale(deflection_scale)
@@ -441,6 +500,7 @@ class LensSimulator(LensSimulatorInterface):
         fixed (zero at its centre), so only differences are physical.  Built-in kinds and dPIE-family catalogues; series
         expansions, user-written bodies and run-time compiled ScalingRelation member loops raise
         ``_native.UnsupportedLensError``.  Forward only."""
+        self._single_plane("potential")
         packed = self._lens_rows(lens_params)
         self._forward_only("potential", packed, x, y)
         self._potential_lenses()
@@ -469,6 +529,7 @@ class LensSimulator(LensSimulatorInterface):
         the arrival time of every image relative to the first-arriving image of its (sample, source), i.e. its Fermat-potential
         excess ``phi - min phi`` (``dt >= 0``; NaN where ``x`` is NaN).  Units: arcsec^2, or days when ``time_delay_distance``
         (D_dt in Mpc, a scalar or ``[B]``) is given: ``dt * D_dt * DAYS_PER_MPC_ARCSEC2``.  Forward only."""
+        self._single_plane("time_delays")
         packed = self._lens_rows(lens_params)
         self._forward_only("time_delays", packed, source_x, source_y)
         self._potential_lenses()
@@ -539,6 +600,7 @@ class LensSimulator(LensSimulatorInterface):
         finite or not positive, and the sample's other outputs are then NaN.  ``ValueError`` for ``ny nx > 1024``, a ``strength`` or
         ``pitch`` that is not finite or not > 0, an ``err_map`` that is not finite or not > 0 on a used pixel, an unknown
         ``regularization`` and shapes that do not match; lens kinds ``lens_maps`` refuses stay refused with its error.  Forward only."""
+        self._single_plane("reconstruct_source")
         if regularization not in self.REGULARIZATIONS:
             raise ValueError(f"regularization must be one of {sorted(self.REGULARIZATIONS)}, got {regularization!r}")
         ny, nx = (int(v) for v in n_src)
@@ -615,10 +677,16 @@ class LensSimulator(LensSimulatorInterface):
         packed = params if torch.is_tensor(params) else self.pack(params)
         if no_deflection:  # tf/simulator.py:125-126: sources are rendered on the un-deflected grid
             return self._parts(packed, 2 | 4)
+        if self._mp is not None:  # lens planes: forward only
+            return self._parts(packed, 1 | 2 | 4)
         img = _SimulateFn.apply(packed, self._model)
         return torch.squeeze(img)
 
     def _parts(self, packed, parts):
+        if self._mp is not None:
+            if packed.requires_grad:
+                raise NotImplementedError("renders of a model with several lens planes are forward only (no gradient)")
+            return torch.squeeze(self._model.multiplane_simulate(packed, parts))
         if packed.requires_grad:
             raise NotImplementedError("partial renders are forward-only helpers (no gradient)")
         return torch.squeeze(self._model.simulate_parts(packed, parts))
@@ -654,6 +722,7 @@ class LensSimulator(LensSimulatorInterface):
         ``coeffs = pinv(X^T X, rcond=1e-6) X^T Y`` per sample and return the best-fit image (default), the stack
         ``(bs, H, W, depth)`` or the coefficients ``(bs, depth)``.  All light profiles of the model must have been
         built with ``use_lstsq=True`` (the reference stacks every component, :183-201)."""
+        self._single_plane("lstsq_simulate")
         if len(self._layout.linear) != self._model.num_linear():
             raise ValueError("lstsq_simulate needs every light profile built with use_lstsq=True")
         packed = params if torch.is_tensor(params) else self.pack(params)

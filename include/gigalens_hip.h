@@ -324,6 +324,41 @@ int gl_scaled_eval(int base_kind, int n_galaxies, const int32_t scale_col[3], co
 int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
                  int xy_batched, float* out, void* hip_stream);
 
+/* Lens planes at redshifts of their own: multi-plane ray tracing (beyond the reference, which bends every ray at one plane).
+ * Planes are numbered 0 .. n_planes - 1 by ascending redshift; every lens keeps its parameters as the reduced deflection for the
+ * model's reference plane.  With theta_0 = theta the ray meets plane j at
+ *   theta_j = theta - sum_{i<j} C_ij a_i,   a_i = sum_{lenses l on plane i} alpha_l(theta_i),
+ * and a target t (a source light, an arbitrary plane) at beta_t = theta - sum_i T_i a_i, with A_t = d beta_t / d theta (not
+ * symmetric once two planes are offset).  C_ij = [D_ij / D_j] / [D_i,ref / D_ref]; T_i likewise for the target, 0 for the planes
+ * at or behind it.
+ *   gl_model_set_lens_planes  HOST arrays, copied to the device: plane_of_lens [n_lens]; lens_scales [n_planes][n_planes] = C,
+ *       strictly upper triangular; source_scales [n_planes][n_src], the couplings of every source light component (> 0 on plane 0,
+ *       0 from the first plane at or behind the source on).  n_planes in 2 .. 4, every plane holds a lens.  A model just created has
+ *       no planes.  From this call on the single-plane entry points (gl_simulate_*, gl_loglike_fwd_bwd, gl_logprob_fwd_bwd,
+ *       gl_lstsq_fwd, gl_positions_fwd_bwd, gl_lens_maps, gl_lens_potential, gl_image_positions*, gl_critical_curves*,
+ *       gl_pixsrc_reconstruct) answer GL_EUNSUPPORTED for the model -- none of them falls back to one plane -- and the workspace
+ *       changes: size it again with gl_workspace_bytes.  GL_EUNSUPPORTED: n_planes > 4, GL_SERIES lenses (their field lives on the
+ *       grid theta, not on theta_j), GL_SCALED catalogues, user-written profiles, lights other than Sersic, SersicEllipse and
+ *       CoreSersic.  GL_EINVAL: counts that do not match the
+ *       model, a plane index out of range, an empty plane, couplings that are not finite or break the rules above.
+ *   gl_multiplane_maps        the twin of gl_lens_maps on arbitrary points: x, y [n_pts] or [n_pts][B] (DEVICE), target_scales
+ *       [n_planes] (HOST) = T; out [6][n_pts][B] = beta_x, beta_y, f_xx, f_xy, f_yx, f_yy with f = I - A_t.  No workspace.
+ *   gl_multiplane_simulate    the twin of gl_simulate_parts_fwd: lens lights at theta, source s at beta_s of its own couplings
+ *       (at theta without GL_PART_DEFLECT), NaN -> 0, the model's PSF + pooling launch, x conversion factor; img [B][H][W].
+ *   gl_multiplane_loglike     the forward half of gl_loglike_fwd_bwd on that image (materialised in the workspace, then the
+ *       image-statistics and finalize launches of the PSF path): loglike, chi2 [B].
+ * Forward only.  All three enqueue on the caller's stream, without allocation or host synchronisation; the last two take a
+ * workspace of gl_workspace_bytes(m, B).  Deterministic: two calls give identical bits.  GL_EINVAL before gl_model_set_lens_planes. */
+int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, int n_planes, const float* lens_scales,
+                             const float* source_scales, int n_src);
+int gl_multiplane_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
+                       const float* target_scales, int n_planes, float* out, void* hip_stream);
+int gl_multiplane_simulate(const gl_model* m, const float* params, int B, unsigned parts, float* img, void* workspace,
+                           size_t workspace_bytes, void* hip_stream);
+int gl_multiplane_loglike(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
+                          const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
+                          void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Lensing potential psi summed over the model's lenses (beyond the reference, which has none): out [n_pts][B].  Arguments and
  * conventions exactly those of gl_lens_maps, x = y = NULL for the model's own grid included.  psi is the potential whose gradient
  * is this library's deflection (gl_lens_maps' beta = theta - grad psi), reference quirks included; its additive constant is
