@@ -104,6 +104,11 @@ SYMBOLS = {
     "gl_multiplane_simulate": (c_int, [c_void_p, c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_multiplane_loglike": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
+    "gl_multiplane_simulate_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gl_multiplane_loglike_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gl_multiplane_logprob_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_float, c_uint32, c_void_p, c_size_t, c_void_p]),
     "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "gl_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
@@ -711,7 +716,8 @@ class Model:
     def set_lens_planes(self, plane_of_lens, lens_scales, source_scales):
         """Lens planes at redshifts of their own (gl_model_set_lens_planes): ``plane_of_lens`` one int per lens, ``lens_scales``
         ``[K, K]``, ``source_scales`` ``[K, n_src]`` (``gigalens_amd.cosmology.MultiPlane``).  From here on the model is served by
-        ``multiplane_maps`` / ``multiplane_simulate`` / ``multiplane_loglike``; the single-plane calls raise ``UnsupportedLensError``."""
+        ``multiplane_maps`` / ``multiplane_simulate`` / ``multiplane_loglike`` and the gradients ``multiplane_simulate_bwd`` /
+        ``multiplane_loglike_grad`` / ``multiplane_logprob``; the single-plane calls raise ``UnsupportedLensError``."""
         pl = np.ascontiguousarray(plane_of_lens, dtype=np.int32).reshape(-1)
         C = np.ascontiguousarray(lens_scales, dtype=np.float32)
         S = np.ascontiguousarray(source_scales, dtype=np.float32)
@@ -726,8 +732,8 @@ class Model:
 
     def _single_plane(self, what):
         if self.n_planes >= 2:
-            raise UnsupportedLensError(f"{what} does not serve a model with {self.n_planes} lens planes: multi-plane ray tracing is "
-                                       "forward only (lens maps, renders, pixel statistics)")
+            raise UnsupportedLensError(f"{what} does not serve a model with {self.n_planes} lens planes: they are served by the "
+                                       "multiplane_* calls alone (lens maps, renders, pixel statistics and their gradients)")
 
     def multiplane_maps(self, params, x, y, target_scales, shared_points=False):
         """gl_multiplane_maps: ``lens_maps`` of the target plane with couplings ``target_scales`` ``[K]``; ``(6, ...)`` = beta_x, beta_y
@@ -770,6 +776,47 @@ class Model:
         _check_potential(lib().gl_multiplane_loglike(self._h, _ptr(params), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
                                                      float(exp_time), B, _ptr(ll), _ptr(chi2), _ptr(ws), ws.numel(), _stream()))
         return ll, chi2
+
+    def multiplane_simulate_bwd(self, params, grad_img):
+        """gl_multiplane_simulate_bwd: the VJP of ``multiplane_simulate`` (every part), ``grad_img`` ``[B, H, W]`` -> ``[B, P]``."""
+        params = self._params(params)
+        B = params.shape[0]
+        ws = self._workspace(B)
+        grad_img = grad_img.to(device=params.device, dtype=torch.float32).expand(B, self.out_h, self.out_w).contiguous()
+        grad = torch.empty_like(params)
+        _check_potential(lib().gl_multiplane_simulate_bwd(self._h, _ptr(params), _ptr(grad_img), B, _ptr(grad), _ptr(ws), ws.numel(),
+                                                          _stream()))
+        return grad
+
+    def multiplane_loglike_grad(self, params, obs, err, mask, bg_rms, exp_time):
+        """gl_multiplane_loglike_fwd_bwd: ``(loglike, chi2, d loglike / d params)``; the first two are ``multiplane_loglike``'s bits."""
+        params = self._params(params)
+        B = params.shape[0]
+        ws = self._workspace(B)
+        ll = torch.empty(B, dtype=torch.float32, device=params.device)
+        chi2 = torch.empty_like(ll)
+        grad = torch.empty_like(params)
+        _check_potential(lib().gl_multiplane_loglike_fwd_bwd(self._h, _ptr(params), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
+                                                             float(exp_time), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(ws), ws.numel(),
+                                                             _stream()))
+        return ll, chi2, grad
+
+    def multiplane_logprob(self, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor=1.0):
+        """gl_multiplane_logprob_fwd_bwd (the pixel term): ``(logprob, loglike, red_chi2, d logprob / d z or None)``."""
+        _require_cuda(z, "z")
+        if z.dtype != torch.float32 or z.dim() != 2 or z.shape[1] != self.d_z:
+            raise NativeLibraryError(f"z must be float32 [B,{self.d_z}], got {z.dtype} {tuple(z.shape)}")
+        z = z.contiguous()
+        B = z.shape[0]
+        ws = self._workspace(B)
+        lp = torch.empty(B, dtype=torch.float32, device=z.device)
+        ll = torch.empty_like(lp)
+        chi2 = torch.empty_like(lp)
+        grad = torch.empty_like(z) if want_grad else None
+        _check_potential(lib().gl_multiplane_logprob_fwd_bwd(self._h, _ptr(z), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
+                                                             float(exp_time), B, _ptr(lp), _ptr(ll), _ptr(chi2), _ptr(grad),
+                                                             float(chi2_divisor), 1, _ptr(ws), ws.numel(), _stream()))
+        return lp, ll, chi2, grad
 
     def set_position_scales(self, scales):
         """One deflection scale per image family (gl_model_set_position_scales; after ``set_positions``, which resets them)."""

@@ -26,6 +26,7 @@
 #include "gl_critical.hip.h"
 #include "gl_pixsrc.hip.h"
 #include "gl_multiplane.hip.h"
+#include "gl_multiplane_bwd.hip.h"
 #include "gl_potential.hip.h"
 #include "gl_lstsq.hip.h"
 #include "gl_shp.hip.h"
@@ -244,8 +245,8 @@ int check_ready(const gl_model* m, bool with_series, bool counted) {
 // refuses it instead of tracing its lenses as if they shared a plane.
 int refuse_planes(const gl_model* m, const char* what) {
   if (m && m->mp_K >= 2)
-    return fail(GL_EUNSUPPORTED, "%s does not serve a model with %d lens planes (gl_model_set_lens_planes): forward maps, renders and "
-                                 "pixel statistics only (gl_multiplane_maps, gl_multiplane_simulate, gl_multiplane_loglike)", what, m->mp_K);
+    return fail(GL_EUNSUPPORTED, "%s does not serve a model with %d lens planes (gl_model_set_lens_planes): lens maps, renders, "
+                                 "pixel statistics and their gradients through the gl_multiplane_* entries alone", what, m->mp_K);
   return GL_OK;
 }
 
@@ -2360,6 +2361,55 @@ int mp_render(const gl_model* m, const float* params, int B, unsigned parts, flo
 int check_planes_set(const gl_model* m) {
   return m->mp_K >= 2 ? GL_OK : fail(GL_EINVAL, "gl_model_set_lens_planes has not been called on this model");
 }
+
+// The VJP of mp_render's kernel (gl_multiplane_bwd.hip.h): cotangent `gimg` [B][Hs Ws] of the supersampled frame (x out_scale) ->
+// one row of accumulators per (sample, chunk of the plan) in w.partial, for run_finalize.  Reads w.derived: run_prep comes first.
+int mp_render_bwd(const gl_model* m, int B, const LaunchPlan& plan, const Workspace& w, const float* gimg, float out_scale,
+                  hipStream_t stream) {
+  MpBwd r{};
+  r.comps = m->d_comps;
+  r.n_lens = m->n_lens;
+  r.n_ll = m->n_ll;
+  r.n_src = m->n_src;
+  r.derived = w.derived;
+  r.D = m->D;
+  r.A = m->A;
+  r.Apad = m->Apad;
+  r.ncols = m->ncols;
+  r.gx = m->d_gx;
+  r.gy = m->d_gy;
+  r.pix = m->d_pix;
+  r.N = m->N;
+  r.chunk = plan.chunk;
+  r.gimg = gimg;
+  r.img_stride = (long long)m->height * m->width;
+  r.out_scale = out_scale;
+  r.partial = w.partial;
+  bool xf = false;  // the instantiation that carries the NFW_ELLIPSE / TNFW / CoreSersic VJPs
+  for (const CompDesc& c : m->comps) xf = xf || c.kind == K_NFW_ELLIPSE || c.kind == K_TNFW || c.kind == K_CORE_SERSIC;
+  const size_t shmem = (size_t)(((m->D + 3) & ~3) + m->ncols * m->Apad) * sizeof(float);
+  const dim3 grid((unsigned)plan.n_chunks, (unsigned)B), block(MP_WG);
+  if (xf) hipLaunchKernelGGL(gl_mp_bwd_kernel<true>, grid, block, shmem, stream, mp_args(m), r);
+  else hipLaunchKernelGGL(gl_mp_bwd_kernel<false>, grid, block, shmem, stream, mp_args(m), r);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// pixel likelihood of the multi-plane image of `params` (packed rows; w.derived holds their derived rows when want_grad):
+// render -> [PSF + pooling] -> image statistics [with cotangent -> transposes -> VJP kernel].  w.stats holds chi2 and the
+// normalisation for run_finalize (extra_stats), w.partial the accumulator rows when want_grad.
+int mp_likelihood(const gl_model* m, const float* params, int B, const LaunchPlan& plan, const Workspace& w, const float* obs,
+                  const float* err, const float* mask, float bg_rms, float exp_time, bool want_grad, hipStream_t stream) {
+  if (int rc = mp_render(m, params, B, 7u, w.img_tmp, w, stream)) return rc;
+  const int HW = (m->height / m->supersample) * (m->width / m->supersample);
+  hipLaunchKernelGGL(gl_imgstats_kernel, dim3(B), dim3(256), 0, stream, w.img_tmp, obs, err, mask, bg_rms * bg_rms, 1.0f / exp_time, HW,
+                     w.stats, want_grad ? w.img_tmp : nullptr);
+  GL_HIP(hipGetLastError());
+  if (!want_grad) return GL_OK;
+  if (!m->has_post) return mp_render_bwd(m, B, plan, w, w.img_tmp, m->conversion_factor, stream);
+  if (int rc = post_bwd(m, B, w.img_tmp, w.img_ss, stream, m->conversion_factor)) return rc;
+  return mp_render_bwd(m, B, plan, w, w.img_ss, 1.f, stream);
+}
 }  // namespace
 
 int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, int n_planes, const float* lens_scales,
@@ -2455,19 +2505,66 @@ int gl_multiplane_simulate(const gl_model* m, const float* params, int B, unsign
 int gl_multiplane_loglike(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
                           const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
                           void* workspace, size_t workspace_bytes, void* hip_stream) {
+  return gl_multiplane_loglike_fwd_bwd(m, params, obs, err_or_null, mask_or_null, bg_rms, exp_time, B, loglike, chi2, nullptr, workspace,
+                                       workspace_bytes, hip_stream);  // the forward half: the same launches, no front end, no VJP
+}
+
+int gl_multiplane_simulate_bwd(const gl_model* m, const float* params, const float* grad_img, int B, float* grad_params,
+                               void* workspace, size_t workspace_bytes, void* hip_stream) {
+  LaunchPlan plan;
+  Workspace w;
+  if (int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w)) return rc;
+  if (int rc = check_planes_set(m)) return rc;
+  if (!grad_img || !grad_params) return fail(GL_EINVAL, "grad_img / grad_params is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (int rc = run_prep(m, params, nullptr, B, plan, w, stream)) return rc;
+  const float* gimg = grad_img;
+  float out_scale = m->conversion_factor;
+  if (m->has_post) {
+    if (int rc = post_bwd(m, B, grad_img, w.img_ss, stream, m->conversion_factor)) return rc;
+    gimg = w.img_ss;
+    out_scale = 1.f;
+  }
+  if (int rc = mp_render_bwd(m, B, plan, w, gimg, out_scale, stream)) return rc;
+  return run_finalize(m, params, B, plan.n_chunks, w, nullptr, nullptr, grad_params, stream);
+}
+
+int gl_multiplane_loglike_fwd_bwd(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
+                                  const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
+                                  float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
   LaunchPlan plan;
   Workspace w;
   if (int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w)) return rc;
   if (int rc = check_planes_set(m)) return rc;
   if (!obs || !loglike || !chi2) return fail(GL_EINVAL, "obs / loglike / chi2 is null");
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (int rc = mp_render(m, params, B, 7u, w.img_tmp, w, stream)) return rc;
-  const int HW = (m->height / m->supersample) * (m->width / m->supersample);
-  hipLaunchKernelGGL(gl_imgstats_kernel, dim3(B), dim3(256), 0, stream, w.img_tmp, obs, err_or_null, mask_or_null, bg_rms * bg_rms,
-                     1.0f / exp_time, HW, w.stats, (float*)nullptr);
-  GL_HIP(hipGetLastError());
-  // chi2 and normalisation of the materialised image -> loglike, chi2: the finalize launch of the PSF path, forward only
-  return run_finalize(m, params, B, plan.n_chunks, w, loglike, chi2, nullptr, stream, nullptr, nullptr, nullptr, 1.f, w.stats, 0);
+  const bool want_grad = grad_params_or_null != nullptr;
+  if (want_grad)
+    if (int rc = run_prep(m, params, nullptr, B, plan, w, stream)) return rc;
+  if (int rc = mp_likelihood(m, params, B, plan, w, obs, err_or_null, mask_or_null, bg_rms, exp_time, want_grad, stream)) return rc;
+  return run_finalize(m, params, B, plan.n_chunks, w, loglike, chi2, grad_params_or_null, stream, nullptr, nullptr, nullptr, 1.f,
+                      w.stats, want_grad ? 1 : 0);
+}
+
+int gl_multiplane_logprob_fwd_bwd(const gl_model* m, const float* z, const float* obs, const float* err_or_null,
+                                  const float* mask_or_null, float bg_rms, float exp_time, int B, float* logprob, float* loglike,
+                                  float* red_chi2, float* grad_z_or_null, float chi2_divisor, unsigned terms, void* workspace,
+                                  size_t workspace_bytes, void* hip_stream) {
+  LaunchPlan plan;
+  Workspace w;
+  if (int rc = check_call(m, z, B, workspace, workspace_bytes, &plan, &w)) return rc;
+  if (int rc = check_planes_set(m)) return rc;
+  if (terms != GL_TERM_PIXELS)
+    return fail(GL_EINVAL, "terms = %u: a model with lens planes has the pixel term alone (no multi-plane position likelihood)", terms);
+  if (!(chi2_divisor > 0.f)) return fail(GL_EINVAL, "chi2_divisor must be positive");
+  if (!m->d_zcols) return fail(GL_EINVAL, "gl_model_set_prior has not been called on this model");
+  if (!obs || !logprob || !loglike || !red_chi2) return fail(GL_EINVAL, "obs / logprob / loglike / red_chi2 is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const bool want_grad = grad_z_or_null != nullptr;
+  if (int rc = run_prep(m, nullptr, z, B, plan, w, stream)) return rc;  // constrained rows -> w.params, derived rows
+  if (int rc = mp_likelihood(m, w.params, B, plan, w, obs, err_or_null, mask_or_null, bg_rms, exp_time, want_grad, stream)) return rc;
+  return run_finalize(m, w.params, B, plan.n_chunks, w, loglike, red_chi2, nullptr, stream, z, logprob, grad_z_or_null,
+                      1.0f / chi2_divisor, w.stats, want_grad ? 1 : 0);
 }
 
 int gl_model_set_prior(gl_model* m, const gl_zcolumn* cols, int d, const float* const_row) {

@@ -85,8 +85,11 @@ class PhysicalModel(PhysicalModelBase):
 
         ``multiplane`` (beyond the reference): a ``gigalens_amd.cosmology.MultiPlane`` -- the lenses sit at redshifts of their own.
         With one plane it is rewritten here into ``source_light_scales`` (the existing kernels, the existing bits).  With two to four
-        planes ``LensSimulator`` traces every ray through them in redshift order (``self.multiplane``; forward only: lens maps,
-        renders and ``ForwardProbModel.stats_pixels`` -- everything else raises ``_native.UnsupportedLensError``)."""
+        planes ``LensSimulator`` traces every ray through them in redshift order (``self.multiplane``): lens maps, renders with
+        ``LensSimulator.simulate_vjp``, ``ForwardProbModel.stats_pixels`` and, on a ``ForwardProbModel`` without image positions, the
+        fused ``log_prob`` / ``log_prob_and_grad`` / ``term_log_prob_and_grad(..., "pixels")`` that MAP, SVI and HMC run on.  The
+        image-position likelihood, ``BackwardProbModel`` / ``lstsq_simulate``, the solver, curves, potentials and
+        ``reconstruct_source`` raise ``_native.UnsupportedLensError``."""
         super().__init__(lenses, lens_light, source_light, lenses_constants, lens_light_constants,
                          source_light_constants)
         self.multiplane = None
@@ -158,6 +161,24 @@ class _LogProbFn(torch.autograd.Function):
     def backward(ctx, g_lp, g_ll, g_chi2):
         (grad,) = ctx.saved_tensors
         return g_lp[:, None] * grad, None, None, None, None, None, None, None, None
+
+
+class _MpLogProbFn(torch.autograd.Function):
+    """autograd glue around gl_multiplane_logprob_fwd_bwd (lens planes at redshifts of their own: the pixel term)."""
+
+    @staticmethod
+    def forward(ctx, z, model, obs, err, mask, bg_rms, exp_time, n_eff):
+        want = z.requires_grad
+        lp, ll, chi2, grad = model.multiplane_logprob(z.detach(), obs, err, mask, bg_rms, exp_time, want, n_eff)
+        if want:
+            ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(ll, chi2)
+        return lp, ll, chi2
+
+    @staticmethod
+    def backward(ctx, g_lp, g_ll, g_chi2):
+        (grad,) = ctx.saved_tensors
+        return g_lp[:, None] * grad, None, None, None, None, None, None, None
 
 
 class _PositionsFn(torch.autograd.Function):
@@ -318,6 +339,22 @@ class ForwardProbModel(ProbabilisticModel):
             model._positions_owner = self
         return model
 
+    def _on_planes(self, simulator):
+        """True for a simulator with several lens planes, whose fused log-probability is the pixel term of the multi-plane entries;
+        a model that carries image positions is refused there (no multi-plane position likelihood exists)."""
+        mp = getattr(simulator, "_mp", None)
+        if mp is None:
+            return False
+        if self.include_positions or not self.include_pixels:
+            raise _native.UnsupportedLensError(f"a model with {mp.K} lens planes has the pixel likelihood alone: the image-position "
+                                               "likelihood is not served on lens planes (include_positions=False)")
+        return True
+
+    def _mp_logprob(self, simulator, z, want_grad):
+        model = self._bind_prior(simulator)
+        return model.multiplane_logprob(z.detach(), self.observed_image, self.error_map, self._mask(simulator),
+                                        self.background_rms or 0.0, self.exp_time or 1.0, want_grad, self._n_eff(simulator))
+
     def _terms(self):
         return (1 if self.include_pixels else 0) | (2 if self.include_positions else 0)
 
@@ -406,7 +443,8 @@ class ForwardProbModel(ProbabilisticModel):
     def _pixel_stats_packed(self, simulator, packed):
         if getattr(simulator, "_mp", None) is not None:  # lens planes: the forward image through the image-statistics launch
             if packed.requires_grad:
-                raise NotImplementedError("the pixel statistics of a model with several lens planes are forward only (no gradient)")
+                raise NotImplementedError("the pixel statistics of a model with several lens planes carry no autograd graph: the "
+                                          "gradient entries are log_prob / log_prob_and_grad and _model.multiplane_loglike_grad")
             ll, chi2 = simulator._model.multiplane_loglike(packed, self.observed_image, self.error_map, self._mask(simulator),
                                                            self.background_rms or 0.0, self.exp_time or 1.0)
             return ll, chi2 / self._n_eff(simulator)
@@ -422,6 +460,11 @@ class ForwardProbModel(ProbabilisticModel):
     def log_prob(self, simulator, z):
         """tf/model.py:126-167: ``z`` is ``(bs, d)`` unconstrained; returns ``(log_prob, red_chi2)``."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        if self._on_planes(simulator):
+            lp, _, red_chi2 = _MpLogProbFn.apply(z, self._bind_prior(simulator), self.observed_image, self.error_map,
+                                                 self._mask(simulator), self.background_rms or 0.0, self.exp_time or 1.0,
+                                                 self._n_eff(simulator))
+            return lp, red_chi2
         if self._fused_ok(simulator):
             # bijector -> prep -> fused render/chi2/VJP -> finalize + prior, all inside the native library
             model = self._bind_prior(simulator)
@@ -441,6 +484,11 @@ class ForwardProbModel(ProbabilisticModel):
         (``"pixels"`` or ``"positions"``) -- the pieces the tempered SMC target is assembled from
         (tf/inference.py:213-238,292-303)."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        if self._on_planes(simulator):
+            if term != "pixels":
+                raise _native.UnsupportedLensError("the image-position likelihood is not served on lens planes")
+            lp, ll, _, grad = self._mp_logprob(simulator, z, True)
+            return lp, ll, grad
         model = self._bind_prior(simulator)
         bit = {"pixels": 1, "positions": 2}[term]
         if bit == 2:
@@ -461,8 +509,12 @@ class ForwardProbModel(ProbabilisticModel):
         copied into the graph's static input unless it already IS that tensor (``graph_input(simulator, z)`` hands it out, for loops
         that update ``z`` in place)."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        on_planes = self._on_planes(simulator)
         if graph and z.is_cuda and self._fused_ok(simulator):
             return self._log_prob_and_grad_graph(simulator, z)
+        if on_planes:
+            lp, _, red, grad = self._mp_logprob(simulator, z, True)
+            return lp, red, grad
         if self._fused_ok(simulator):
             model = self._bind_prior(simulator)
             if self.include_positions:

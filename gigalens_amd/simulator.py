@@ -196,8 +196,8 @@ class LensSimulator(LensSimulatorInterface):
     def _single_plane(self, what):
         if self._mp is not None:
             raise _native.UnsupportedLensError(f"{what} does not serve a model with {self._mp.K} lens planes: multi-plane ray tracing "
-                                               "is forward only (beta, magnification, convergence, shear, rotation, simulate*, "
-                                               "stats_pixels)")
+                                               "serves beta, magnification, convergence, shear, rotation, simulate*, simulate_vjp and "
+                                               "the pixel likelihood with its gradient")
 
     def _target_scales(self, deflection_scale):
         """The ``deflection_scale`` keyword of the lens maps on a multi-plane model: a source index, or the ``[K]`` couplings of the
@@ -677,15 +677,23 @@ class LensSimulator(LensSimulatorInterface):
         packed = params if torch.is_tensor(params) else self.pack(params)
         if no_deflection:  # tf/simulator.py:125-126: sources are rendered on the un-deflected grid
             return self._parts(packed, 2 | 4)
-        if self._mp is not None:  # lens planes: forward only
+        if self._mp is not None:  # lens planes: no autograd node (the gradient entry is simulate_vjp)
             return self._parts(packed, 1 | 2 | 4)
         img = _SimulateFn.apply(packed, self._model)
         return torch.squeeze(img)
 
+    def simulate_vjp(self, params, cotangent):
+        """The vector-Jacobian product of ``simulate``: ``cotangent`` ``[B, H, W]`` (or broadcastable to it) -> ``[B, P]`` in packed
+        order.  On a model with several lens planes this is the gradient entry of ``simulate`` (``torch.autograd`` through
+        ``simulate`` is served on one plane only)."""
+        packed = params if torch.is_tensor(params) else self.pack(params)
+        packed, cotangent = packed.detach(), torch.as_tensor(cotangent, device=packed.device)
+        return self._model.multiplane_simulate_bwd(packed, cotangent) if self._mp is not None else self._model.simulate_bwd(packed, cotangent)
+
     def _parts(self, packed, parts):
         if self._mp is not None:
             if packed.requires_grad:
-                raise NotImplementedError("renders of a model with several lens planes are forward only (no gradient)")
+                raise NotImplementedError("renders of a model with several lens planes carry no autograd graph: simulate_vjp is their gradient")
             return torch.squeeze(self._model.multiplane_simulate(packed, parts))
         if packed.requires_grad:
             raise NotImplementedError("partial renders are forward-only helpers (no gradient)")

@@ -347,8 +347,17 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
  *       (at theta without GL_PART_DEFLECT), NaN -> 0, the model's PSF + pooling launch, x conversion factor; img [B][H][W].
  *   gl_multiplane_loglike     the forward half of gl_loglike_fwd_bwd on that image (materialised in the workspace, then the
  *       image-statistics and finalize launches of the PSF path): loglike, chi2 [B].
- * Forward only.  All three enqueue on the caller's stream, without allocation or host synchronisation; the last two take a
- * workspace of gl_workspace_bytes(m, B).  Deterministic: two calls give identical bits.  GL_EINVAL before gl_model_set_lens_planes. */
+ *   gl_multiplane_simulate_bwd     the twin of gl_simulate_bwd (every part): grad_img [B][H][W] -> grad_params [B][P], the VJP
+ *       through the plane recursion (csrc/gl_multiplane_bwd.hip.h) of the image gl_multiplane_simulate returns.
+ *   gl_multiplane_loglike_fwd_bwd  gl_multiplane_loglike plus, when grad_params_or_null != NULL, d loglike / d params [B][P]:
+ *       render -> PSF + pooling -> image statistics with cotangent -> their transposes -> the VJP kernel -> finalize.  loglike and
+ *       chi2 are the bits of gl_multiplane_loglike.
+ *   gl_multiplane_logprob_fwd_bwd  the twin of gl_logprob_fwd_bwd for the pixel term: z [B][d] in (gl_model_set_prior), logprob,
+ *       loglike, red_chi2 and, when grad_z_or_null != NULL, d logprob / d z out; bijector and prior fused into the front end and
+ *       finalize.  GL_EINVAL if terms asks for GL_TERM_POSITIONS: no multi-plane position likelihood exists.
+ * All enqueue on the caller's stream, without allocation or host synchronisation (a HIP graph may capture them); all but the
+ * maps take a workspace of gl_workspace_bytes(m, B).  Deterministic: two calls give identical bits.  GL_EINVAL before
+ * gl_model_set_lens_planes. */
 int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, int n_planes, const float* lens_scales,
                              const float* source_scales, int n_src);
 int gl_multiplane_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
@@ -358,6 +367,15 @@ int gl_multiplane_simulate(const gl_model* m, const float* params, int B, unsign
 int gl_multiplane_loglike(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
                           const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
                           void* workspace, size_t workspace_bytes, void* hip_stream);
+int gl_multiplane_simulate_bwd(const gl_model* m, const float* params, const float* grad_img, int B, float* grad_params,
+                               void* workspace, size_t workspace_bytes, void* hip_stream);
+int gl_multiplane_loglike_fwd_bwd(const gl_model* m, const float* params, const float* obs, const float* err_or_null,
+                                  const float* mask_or_null, float bg_rms, float exp_time, int B, float* loglike, float* chi2,
+                                  float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
+int gl_multiplane_logprob_fwd_bwd(const gl_model* m, const float* z, const float* obs, const float* err_or_null,
+                                  const float* mask_or_null, float bg_rms, float exp_time, int B, float* logprob, float* loglike,
+                                  float* red_chi2, float* grad_z_or_null, float chi2_divisor, unsigned terms, void* workspace,
+                                  size_t workspace_bytes, void* hip_stream);
 
 /* Lensing potential psi summed over the model's lenses (beyond the reference, which has none): out [n_pts][B].  Arguments and
  * conventions exactly those of gl_lens_maps, x = y = NULL for the model's own grid included.  psi is the potential whose gradient
