@@ -759,64 +759,24 @@ class Model:
 
     def multiplane_simulate(self, params, parts=7):
         """gl_multiplane_simulate: the image ``[B, H, W]`` of ``parts`` (1 deflect, 2 lens light, 4 source light)."""
-        params = self._params(params)
-        B = params.shape[0]
-        ws = self._workspace(B)
-        img = torch.empty((B, self.out_h, self.out_w), dtype=torch.float32, device=params.device)
-        _check_potential(lib().gl_multiplane_simulate(self._h, _ptr(params), B, int(parts), _ptr(img), _ptr(ws), ws.numel(), _stream()))
-        return img
+        return self._render(lib().gl_multiplane_simulate, _check_potential, params, parts)
 
     def multiplane_loglike(self, params, obs, err, mask, bg_rms, exp_time):
         """gl_multiplane_loglike: ``(loglike, chi2)`` ``[B]`` of the multi-plane image, forward only."""
-        params = self._params(params)
-        B = params.shape[0]
-        ws = self._workspace(B)
-        ll = torch.empty(B, dtype=torch.float32, device=params.device)
-        chi2 = torch.empty_like(ll)
-        _check_potential(lib().gl_multiplane_loglike(self._h, _ptr(params), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
-                                                     float(exp_time), B, _ptr(ll), _ptr(chi2), _ptr(ws), ws.numel(), _stream()))
-        return ll, chi2
+        return self._loglike(lib().gl_multiplane_loglike, _check_potential, params, obs, err, mask, bg_rms, exp_time, None)[:2]
 
     def multiplane_simulate_bwd(self, params, grad_img):
         """gl_multiplane_simulate_bwd: the VJP of ``multiplane_simulate`` (every part), ``grad_img`` ``[B, H, W]`` -> ``[B, P]``."""
-        params = self._params(params)
-        B = params.shape[0]
-        ws = self._workspace(B)
-        grad_img = grad_img.to(device=params.device, dtype=torch.float32).expand(B, self.out_h, self.out_w).contiguous()
-        grad = torch.empty_like(params)
-        _check_potential(lib().gl_multiplane_simulate_bwd(self._h, _ptr(params), _ptr(grad_img), B, _ptr(grad), _ptr(ws), ws.numel(),
-                                                          _stream()))
-        return grad
+        return self._render_bwd(lib().gl_multiplane_simulate_bwd, _check_potential, params, grad_img)
 
     def multiplane_loglike_grad(self, params, obs, err, mask, bg_rms, exp_time):
         """gl_multiplane_loglike_fwd_bwd: ``(loglike, chi2, d loglike / d params)``; the first two are ``multiplane_loglike``'s bits."""
-        params = self._params(params)
-        B = params.shape[0]
-        ws = self._workspace(B)
-        ll = torch.empty(B, dtype=torch.float32, device=params.device)
-        chi2 = torch.empty_like(ll)
-        grad = torch.empty_like(params)
-        _check_potential(lib().gl_multiplane_loglike_fwd_bwd(self._h, _ptr(params), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
-                                                             float(exp_time), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(ws), ws.numel(),
-                                                             _stream()))
-        return ll, chi2, grad
+        return self._loglike(lib().gl_multiplane_loglike_fwd_bwd, _check_potential, params, obs, err, mask, bg_rms, exp_time, True)
 
     def multiplane_logprob(self, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor=1.0):
         """gl_multiplane_logprob_fwd_bwd (the pixel term): ``(logprob, loglike, red_chi2, d logprob / d z or None)``."""
-        _require_cuda(z, "z")
-        if z.dtype != torch.float32 or z.dim() != 2 or z.shape[1] != self.d_z:
-            raise NativeLibraryError(f"z must be float32 [B,{self.d_z}], got {z.dtype} {tuple(z.shape)}")
-        z = z.contiguous()
-        B = z.shape[0]
-        ws = self._workspace(B)
-        lp = torch.empty(B, dtype=torch.float32, device=z.device)
-        ll = torch.empty_like(lp)
-        chi2 = torch.empty_like(lp)
-        grad = torch.empty_like(z) if want_grad else None
-        _check_potential(lib().gl_multiplane_logprob_fwd_bwd(self._h, _ptr(z), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
-                                                             float(exp_time), B, _ptr(lp), _ptr(ll), _ptr(chi2), _ptr(grad),
-                                                             float(chi2_divisor), 1, _ptr(ws), ws.numel(), _stream()))
-        return lp, ll, chi2, grad
+        return self._logprob(lib().gl_multiplane_logprob_fwd_bwd, _check_potential, z, obs, err, mask, bg_rms, exp_time, want_grad,
+                             chi2_divisor, 1)
 
     def set_position_scales(self, scales):
         """One deflection scale per image family (gl_model_set_position_scales; after ``set_positions``, which resets them)."""
@@ -990,20 +950,7 @@ class Model:
 
     def logprob(self, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor=1.0, terms=1):
         self._single_plane("logprob")
-        _require_cuda(z, "z")
-        if z.dtype != torch.float32 or z.dim() != 2 or z.shape[1] != self.d_z:
-            raise NativeLibraryError(f"z must be float32 [B,{self.d_z}], got {z.dtype} {tuple(z.shape)}")
-        z = z.contiguous()
-        B = z.shape[0]
-        ws = self._workspace(B)
-        lp = torch.empty(B, dtype=torch.float32, device=z.device)
-        ll = torch.empty_like(lp)
-        chi2 = torch.empty_like(lp)
-        grad = torch.empty_like(z) if want_grad else None
-        _check(lib().gl_logprob_fwd_bwd(self._h, _ptr(z), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
-                                        float(exp_time), B, _ptr(lp), _ptr(ll), _ptr(chi2), _ptr(grad),
-                                        float(chi2_divisor), int(terms), _ptr(ws), ws.numel(), _stream()))
-        return lp, ll, chi2, grad
+        return self._logprob(lib().gl_logprob_fwd_bwd, _check, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor, terms)
 
     def set_timing(self, slots=1, stride=1):
         """Ring of ``slots`` HIP-event pairs around every ``stride``-th main-kernel launch (0 / False: off)."""
@@ -1087,34 +1034,58 @@ class Model:
 
     def simulate_parts(self, params, parts):
         self._single_plane("simulate_parts")
+        return self._render(lib().gl_simulate_parts_fwd, _check, params, parts)
+
+    def simulate_bwd(self, params, grad_img):
+        self._single_plane("simulate_bwd")
+        return self._render_bwd(lib().gl_simulate_bwd, _check, params, grad_img)
+
+    def loglike(self, params, obs, err, mask, bg_rms, exp_time, want_grad):
+        self._single_plane("loglike")
+        return self._loglike(lib().gl_loglike_fwd_bwd, _check, params, obs, err, mask, bg_rms, exp_time, bool(want_grad))
+
+    # behind the single-plane methods and their multiplane_* twins: `fn` the family's entry, `check` how it raises error codes
+    def _render(self, fn, check, params, parts):
         params = self._params(params)
         B = params.shape[0]
         ws = self._workspace(B)
         img = torch.empty((B, self.out_h, self.out_w), dtype=torch.float32, device=params.device)
-        _check(lib().gl_simulate_parts_fwd(self._h, _ptr(params), B, int(parts), _ptr(img), _ptr(ws), ws.numel(),
-                                           _stream()))
+        check(fn(self._h, _ptr(params), B, int(parts), _ptr(img), _ptr(ws), ws.numel(), _stream()))
         return img
 
-    def simulate_bwd(self, params, grad_img):
-        self._single_plane("simulate_bwd")
+    def _render_bwd(self, fn, check, params, grad_img):
         params = self._params(params)
         B = params.shape[0]
         ws = self._workspace(B)
-        grad_img = grad_img.to(torch.float32).expand(B, self.out_h, self.out_w).contiguous()
+        grad_img = grad_img.to(device=params.device, dtype=torch.float32).expand(B, self.out_h, self.out_w).contiguous()
         grad = torch.empty_like(params)
-        _check(lib().gl_simulate_bwd(self._h, _ptr(params), _ptr(grad_img), B, _ptr(grad), _ptr(ws), ws.numel(),
-                                     _stream()))
+        check(fn(self._h, _ptr(params), _ptr(grad_img), B, _ptr(grad), _ptr(ws), ws.numel(), _stream()))
         return grad
 
-    def loglike(self, params, obs, err, mask, bg_rms, exp_time, want_grad):
-        self._single_plane("loglike")
+    def _loglike(self, fn, check, params, obs, err, mask, bg_rms, exp_time, want_grad):
+        """``(loglike, chi2, gradient or None)``; ``want_grad`` None: ``fn`` is a forward-only entry without a gradient argument."""
         params = self._params(params)
         B = params.shape[0]
         ws = self._workspace(B)
         ll = torch.empty(B, dtype=torch.float32, device=params.device)
-        chi2 = torch.empty(B, dtype=torch.float32, device=params.device)
+        chi2 = torch.empty_like(ll)
         grad = torch.empty_like(params) if want_grad else None
-        _check(lib().gl_loglike_fwd_bwd(self._h, _ptr(params), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms),
-                                        float(exp_time), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(ws), ws.numel(),
-                                        _stream()))
+        grad_arg = () if want_grad is None else (_ptr(grad),)
+        check(fn(self._h, _ptr(params), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms), float(exp_time), B, _ptr(ll), _ptr(chi2),
+                 *grad_arg, _ptr(ws), ws.numel(), _stream()))
         return ll, chi2, grad
+
+    def _logprob(self, fn, check, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor, terms):
+        _require_cuda(z, "z")
+        if z.dtype != torch.float32 or z.dim() != 2 or z.shape[1] != self.d_z:
+            raise NativeLibraryError(f"z must be float32 [B,{self.d_z}], got {z.dtype} {tuple(z.shape)}")
+        z = z.contiguous()
+        B = z.shape[0]
+        ws = self._workspace(B)
+        lp = torch.empty(B, dtype=torch.float32, device=z.device)
+        ll = torch.empty_like(lp)
+        chi2 = torch.empty_like(lp)
+        grad = torch.empty_like(z) if want_grad else None
+        check(fn(self._h, _ptr(z), _ptr(obs), _ptr(err), _ptr(mask), float(bg_rms), float(exp_time), B, _ptr(lp), _ptr(ll),
+                 _ptr(chi2), _ptr(grad), float(chi2_divisor), int(terms), _ptr(ws), ws.numel(), _stream()))
+        return lp, ll, chi2, grad

@@ -1,0 +1,559 @@
+// gl_api_points.hip -- the entry points of the point family: everything that evaluates the lenses of a model (or one free-standing
+// profile) at points through gl_positions.hip.h -- image-position likelihood, lens maps, Hessians, potential, the lens-equation
+// solver, critical curves, and the lens planes (maps, render and its VJP).
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "gl_host.hip.h"
+#include "gl_positions.hip.h"
+#include "gl_images.hip.h"
+#include "gl_critical.hip.h"
+#include "gl_potential.hip.h"
+#include "gl_multiplane.hip.h"
+#include "gl_multiplane_bwd.hip.h"
+
+using namespace glk;
+
+namespace {
+// What every point kernel reads of a model (gl_positions.hip.h PosArgs): the lenses, the packed rows, the catalogues, the series
+// fields.  `series` is set for every user; it is non-null only in gl_lens_maps on the model's own grid, the one user that serves
+// series-expansion lenses -- the others (run_positions, gl_lens_potential, gl_image_positions, gl_critical_curves) refuse a model
+// that holds one before they launch, and a model without one has no d_series.
+PosArgs point_args(const gl_model* m, const float* params, int B) {
+  PosArgs a{};
+  a.comps = m->d_comps;
+  a.n_lens = m->n_lens;
+  a.P = m->P;
+  a.B = B;
+  a.params = params;
+  a.cats = m->d_cats;
+  a.gal_table = m->d_gal_table;
+  a.gal_static = m->d_gal_static;
+  a.series = m->d_series;
+  return a;
+}
+
+// the window of the lens-equation solver (`search` wording) and of the critical curves
+int check_window(bool search, float x_lo, float x_hi, float y_lo, float y_hi) {
+  if ((x_hi > x_lo) && (y_hi > y_lo) && std::isfinite(x_hi - x_lo) && std::isfinite(y_hi - y_lo)) return GL_OK;
+  return search ? fail(GL_EINVAL, "empty or non-finite search window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi)
+                : fail(GL_EINVAL, "empty or non-finite window [%g, %g] x [%g, %g]", x_lo, x_hi, y_lo, y_hi);
+}
+
+bool potential_kind(int kind) {
+  return (kind >= GL_EPL && kind <= GL_DPIEP) || kind == GL_NFW_ELLIPSE || kind == GL_TNFW;
+}
+
+struct ImgLayout { size_t map, cand, n_cand, n_over, scale, bytes; };
+ImgLayout img_layout(int B, int n_src, int n_cells) {
+  ImgLayout l{};
+  const size_t V = (size_t)(n_cells + 1) * (size_t)(n_cells + 1), BS = (size_t)B * (size_t)n_src;
+  l.map = 0;
+  l.cand = l.map + align_up((size_t)B * V * sizeof(float2), 256);
+  l.n_cand = l.cand + align_up(BS * IMG_MAXC * sizeof(float2), 256);
+  l.n_over = l.n_cand + align_up(BS * sizeof(int), 256);
+  l.scale = l.n_over + align_up(BS * sizeof(int), 256);  // [n_src] deflection scales of gl_image_positions_scaled
+  l.bytes = l.scale + align_up((size_t)n_src * sizeof(float), 256);
+  return l;
+}
+constexpr int IMG_MAX_CELLS = 8192;
+
+struct CritLayout { size_t dmap, edge_id, edge_pt, edge_omk, n_edges, n_edge_over, bytes; };
+CritLayout crit_layout(int B, int n_cells, int max_segments) {
+  CritLayout l{};
+  const size_t V = (size_t)(n_cells + 1) * (size_t)(n_cells + 1), BE = (size_t)B * 2 * (size_t)max_segments;
+  l.dmap = 0;
+  l.edge_id = l.dmap + align_up((size_t)B * V * sizeof(float), 256);
+  l.edge_pt = l.edge_id + align_up(BE * sizeof(int), 256);
+  l.edge_omk = l.edge_pt + align_up(BE * sizeof(float4), 256);
+  l.n_edges = l.edge_omk + align_up(BE * sizeof(float), 256);
+  l.n_edge_over = l.n_edges + align_up((size_t)B * sizeof(int), 256);
+  l.bytes = l.n_edge_over + align_up((size_t)B * sizeof(int), 256);
+  return l;
+}
+constexpr int CRIT_MAX_SEGMENTS = 1 << 20;
+}  // namespace
+
+namespace glk {
+
+int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream) {
+  if (m->n_series) return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image-position likelihood");
+  if (m->has_user)  // the four kernels below, compiled at run time with the user's bodies on the nested duals (once per model text)
+    if (int rc = compile_user_points(m)) return rc;
+  PosArgs a = point_args(m, params, B);  // + the position tables and the likelihood's workspace
+  a.J = m->pos_J;
+  a.F = m->pos_F;
+  a.px = m->d_pos;
+  a.py = m->d_pos + m->pos_J;
+  a.ex = m->d_pos + 2 * m->pos_J;
+  a.ey = m->d_pos + 3 * m->pos_J;
+  a.fam_off = m->d_fam;
+  a.fam_scale = m->pos_scaled ? m->d_pos_scale.get() : nullptr;
+  a.w_pos = w.pos_w;
+  a.w_adj = w.pos_adj;
+  a.w_g = w.pos_g;
+  a.w_fam = w.pos_fam;
+  a.ll = w.pos_ll;
+  a.chi2 = w.pos_chi2;
+  a.grad = want_grad ? w.pos_grad : nullptr;
+  auto blocks = [](long long n) { return dim3((unsigned)((n + 63) / 64)); };
+  if (m->has_user) {
+    int lens_params = m->lens_params;
+    void* args1[] = {&a};
+    void* args2[] = {&a, &lens_params};
+    auto go = [&](int k, long long n, void** args) {
+      return hipModuleLaunchKernel(m->user_point_fn[k], blocks(n).x, 1, 1, 64, 1, 1, 0, stream, args, nullptr);
+    };
+    GL_HIP(go(0, (long long)B * a.J, args1));
+    GL_HIP(go(1, (long long)B * a.F, args1));
+    if (want_grad && m->lens_params) GL_HIP(go(2, (long long)B * a.J * m->lens_params, args2));
+    GL_HIP(go(3, (long long)B * (a.P + 1), args2));
+    return GL_OK;
+  }
+  hipLaunchKernelGGL(gl_pos_p1_kernel, blocks((long long)B * a.J), dim3(64), 0, stream, a);
+  hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
+  if (want_grad && m->lens_params)
+    hipLaunchKernelGGL(gl_pos_p3_kernel, blocks((long long)B * a.J * m->lens_params), dim3(64), 0, stream, a,
+                       m->lens_params);
+  hipLaunchKernelGGL(gl_pos_p4_kernel, blocks((long long)B * (a.P + 1)), dim3(64), 0, stream, a, m->lens_params);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+}  // namespace glk
+
+extern "C" {
+
+int gl_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
+                         float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rp = refuse_planes(m, "gl_positions_fwd_bwd")) return rp;
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
+  if (rc) return rc;
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream))) return rc;
+  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  if (grad_params_or_null)
+    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+
+int gl_profile_hessian(const gl_component* comp, const float* x, const float* y, int64_t n_pts, int B, int xy_batched,
+                       const float* params, float* out, void* hip_stream) {
+  if (!comp || !x || !y || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (n_pts <= 0 || B <= 0) return fail(GL_EINVAL, "n_pts and B must be positive");
+  if (!((comp->kind >= GL_EPL && comp->kind <= GL_DPIEP) || comp->kind == GL_NFW_ELLIPSE || comp->kind == GL_TNFW))
+    return fail(GL_EINVAL, "kind %d is not a free-standing mass profile", comp->kind);
+  const CompDesc cd = point_comp(comp);
+  const long long total = (long long)n_pts * B;
+  hipLaunchKernelGGL(gl_profile_hessian_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream,
+                     cd, x, y, (long long)n_pts, B, xy_batched, params, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+int gl_scaled_hessian(int base_kind, int n_galaxies, const int32_t scale_col[3], const float* table_dev, const float* x,
+                      const float* y, int64_t n_pts, int B, int xy_batched, const float* scales, int n_scales,
+                      float* out, void* hip_stream) {
+  if (!scale_col || !table_dev || !x || !y || !scales || !out) return fail(GL_EINVAL, "null argument");
+  if (int rc = check_catalogue_args(false, base_kind, n_galaxies > 0 && n_pts > 0 && B > 0, 0, scale_col, n_scales)) return rc;
+  ScaledDesc sd{base_kind, n_galaxies, {scale_col[0], scale_col[1], scale_col[2]}};
+  long long total = (long long)n_pts * B;
+  hipLaunchKernelGGL(gl_scaled_hessian_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream,
+                     sd, table_dev, x, y, (long long)n_pts, B, xy_batched, scales, n_scales, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
+                 int xy_batched, float* out, void* hip_stream) {
+  if (!m || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_lens_maps")) return rp;
+  if (m->has_user)  // the kernel below compiled at run time with the user's bodies (Hessians from the duals)
+    if (int rc = compile_user_points(m)) return rc;
+  if ((x == nullptr) != (y == nullptr)) return fail(GL_EINVAL, "x and y must both be given or both be null");
+  if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
+  if (int rc = check_ready(m, false, false)) return rc;
+  if (!x) {
+    if (n_pts != m->N || xy_batched) return fail(GL_EINVAL, "the model grid has %d points and is not batched", m->N);
+    x = m->d_gx;
+    y = m->d_gy;
+    for (const SeriesDev& sv : m->series)
+      if (!sv.coef || !sv.hcoef)
+        return fail(GL_EINVAL, "GL_SERIES lens without its deflection / Hessian field (gl_model_set_series, gl_model_set_series_hessian)");
+  } else if (m->n_series) {
+    return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the model grid only (series_profile.py:76-89): pass x = y = NULL");
+  }
+  PosArgs a = point_args(m, params, B);
+  const long long total = (long long)n_pts * B;
+  if (m->has_user) {
+    long long n_pts_ll = (long long)n_pts;
+    void* args[] = {&a, &x, &y, &n_pts_ll, &xy_batched, &out};
+    GL_HIP(hipModuleLaunchKernel(m->user_point_fn[4], (unsigned)((total + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)hip_stream, args, nullptr));
+    return GL_OK;
+  }
+  hipLaunchKernelGGL(gl_lens_maps_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, a,
+                     x, y, (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- lensing potential (gl_potential.hip.h) --------------------------------------------------------------------
+int gl_lens_potential(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
+                      int xy_batched, float* out, void* hip_stream) {
+  if (!m || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_lens_potential")) return rp;
+  if ((x == nullptr) != (y == nullptr)) return fail(GL_EINVAL, "x and y must both be given or both be null");
+  if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
+  for (int l = 0; l < m->n_lens; ++l) {
+    const int kind = m->comps[l].kind;
+    if (kind == GL_SERIES)
+      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its precomputed field holds the deflection, no potential", l);
+    if (kind == GL_USER_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
+                                   "a body defines the deflection only, no potential", l);
+    if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
+  }
+  if (int rc = check_ready(m, false, false)) return rc;
+  if (!x) {
+    if (n_pts != m->N || xy_batched) return fail(GL_EINVAL, "the model grid has %d points and is not batched", m->N);
+    x = m->d_gx;
+    y = m->d_gy;
+  }
+  const long long total = (long long)n_pts * B, blocks = (total + POT_WG - 1) / POT_WG;
+  if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
+  PosArgs a = point_args(m, params, B);
+  hipLaunchKernelGGL(gl_lens_potential_kernel, dim3((unsigned)blocks), dim3(POT_WG), 0, (hipStream_t)hip_stream, a, x, y,
+                     (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+int gl_profile_potential(const gl_component* comp, const float* x, const float* y, int64_t n_pts, int B, int xy_batched,
+                         const float* params, float* out, void* hip_stream) {
+  if (!comp || !x || !y || !params || !out) return fail(GL_EINVAL, "null argument");
+  if (n_pts <= 0 || B <= 0) return fail(GL_EINVAL, "n_pts and B must be positive");
+  if (comp->kind == GL_SCALED || comp->kind == GL_SERIES || comp->kind == GL_USER_MASS)
+    return fail(GL_EUNSUPPORTED, "kind %d has no plugin-level potential (free-standing built-in mass kinds only; catalogues: "
+                                 "gl_lens_potential on a model)", comp->kind);
+  if (!potential_kind(comp->kind)) return fail(GL_EINVAL, "kind %d is not a free-standing mass profile", comp->kind);
+  const long long total = (long long)n_pts * B, blocks = (total + POT_WG - 1) / POT_WG;
+  if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
+  const CompDesc cd = point_comp(comp);
+  hipLaunchKernelGGL(gl_profile_potential_kernel, dim3((unsigned)blocks), dim3(POT_WG), 0, (hipStream_t)hip_stream, cd, x, y,
+                     (long long)n_pts, B, xy_batched, params, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- lens-equation solver (gl_images.hip.h) -----------------------------------------------------------------
+size_t gl_image_positions_workspace_bytes(const gl_model* m, int B, int n_src, int n_cells, int max_images) {
+  if (!m || B <= 0 || n_src <= 0 || n_cells <= 0 || n_cells > IMG_MAX_CELLS || max_images < 1) return 0;
+  return img_layout(B, n_src, n_cells).bytes;
+}
+
+int gl_image_positions(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                       float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images, float tol, int max_iter,
+                       float* out, int* n_images, int* n_dropped, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  return gl_image_positions_scaled(m, params, B, src_x, src_y, n_src, nullptr, x_lo, x_hi, y_lo, y_hi, n_cells, max_images, tol,
+                                   max_iter, out, n_images, n_dropped, workspace, workspace_bytes, hip_stream);
+}
+
+int gl_image_positions_scaled(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                              const float* src_scale, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images,
+                              float tol, int max_iter, float* out, int* n_images, int* n_dropped, void* workspace,
+                              size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !src_x || !src_y || !out || !n_images || !n_dropped) return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_image_positions")) return rp;
+  if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  if (max_images < 1 || max_images > IMG_MAXC) return fail(GL_EINVAL, "max_images %d outside [1, %d]", max_images, IMG_MAXC);
+  if (int rc = check_window(true, x_lo, x_hi, y_lo, y_hi)) return rc;
+  if (!(tol > 0.f) || max_iter < 1) return fail(GL_EINVAL, "tol must be > 0 and max_iter >= 1 (got %g, %d)", tol, max_iter);
+  if (m->n_series)
+    return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image finder");
+  if (int rc = check_ready(m, false, false)) return rc;
+  const ImgLayout lay = img_layout(B, n_src, n_cells);
+  if (!workspace) return fail(GL_EINVAL, "workspace is null");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  const long long V = (long long)(n_cells + 1) * (n_cells + 1);
+  const long long map_blocks = (V * B + 255) / 256, pairs = (long long)B * n_src;
+  if (map_blocks > 0x7fffffffLL || pairs > 0x7fffffffLL) return fail(GL_EINVAL, "too many samples / vertices / sources for one call");
+  if (m->has_user)  // map and Newton kernels compiled at run time with the user's bodies (the scan does not touch the lens)
+    if (int rc = compile_user_points(m)) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  PosArgs a = point_args(m, params, B);
+  ImgArgs g{};
+  if (src_scale) {  // one scale per source, host -> the call's own workspace on the caller's stream (all 1: the unscaled path)
+    bool any;
+    if (int rc = check_scales(src_scale, n_src, n_src, "source(s)", &any)) return rc;
+    if (any) {
+      float* d_scale = (float*)((char*)workspace + lay.scale);
+      GL_HIP(hipMemcpyAsync(d_scale, src_scale, sizeof(float) * (size_t)n_src, hipMemcpyHostToDevice, stream));
+      g.src_scale = d_scale;
+    }
+  }
+  g.src_x = src_x;
+  g.src_y = src_y;
+  g.S = n_src;
+  g.n = n_cells;
+  g.x_lo = x_lo; g.x_hi = x_hi; g.y_lo = y_lo; g.y_hi = y_hi;
+  g.hx = (x_hi - x_lo) / (float)n_cells;
+  g.hy = (y_hi - y_lo) / (float)n_cells;
+  g.max_images = max_images;
+  g.max_iter = max_iter;
+  g.tol = tol;
+  char* base = (char*)workspace;
+  g.map = (float2*)(base + lay.map);
+  g.cand = (float2*)(base + lay.cand);
+  g.n_cand = (int*)(base + lay.n_cand);
+  g.n_over = (int*)(base + lay.n_over);
+  g.out = out;
+  g.n_images = n_images;
+  g.n_dropped = n_dropped;
+  if (m->has_user) {
+    void* args[] = {&a, &g};
+    GL_HIP(hipModuleLaunchKernel(m->user_point_fn[5], (unsigned)map_blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr));
+  } else {
+    hipLaunchKernelGGL(gl_img_map_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
+  }
+  hipLaunchKernelGGL(gl_img_scan_kernel, dim3((unsigned)pairs), dim3(IMG_SCAN_WG), 0, stream, g);
+  if (m->has_user) {
+    void* args[] = {&a, &g};
+    GL_HIP(hipModuleLaunchKernel(m->user_point_fn[6], (unsigned)pairs, 1, 1, 64, 1, 1, 0, stream, args, nullptr));
+  } else {
+    hipLaunchKernelGGL(gl_img_newton_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, a, g);
+  }
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- critical curves and caustics (gl_critical.hip.h) ----------------------------------------------------------
+size_t gl_critical_curves_workspace_bytes(const gl_model* m, int B, int n_cells, int max_segments) {
+  if (!m || B <= 0 || n_cells <= 0 || n_cells > IMG_MAX_CELLS || max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS) return 0;
+  return crit_layout(B, n_cells, max_segments).bytes;
+}
+
+int gl_critical_curves(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
+                       int max_segments, float* seg, float* cau, int* kind, int* n_seg, int* n_dropped, int* n_flagged, int* open,
+                       float* area, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  return gl_critical_curves_scaled(m, params, B, x_lo, x_hi, y_lo, y_hi, n_cells, max_segments, 1.f, seg, cau, kind, n_seg, n_dropped,
+                                   n_flagged, open, area, workspace, workspace_bytes, hip_stream);
+}
+
+int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, float x_lo, float x_hi, float y_lo, float y_hi,
+                              int n_cells, int max_segments, float scale, float* seg, float* cau, int* kind, int* n_seg,
+                              int* n_dropped, int* n_flagged, int* open, float* area, void* workspace, size_t workspace_bytes,
+                              void* hip_stream) {
+  if (!m || !params || !seg || !cau || !kind || !n_seg || !n_dropped || !n_flagged || !open || !area)
+    return fail(GL_EINVAL, "null argument");
+  if (int rp = refuse_planes(m, "gl_critical_curves")) return rp;
+  if (!(std::isfinite(scale) && scale > 0.f)) return fail(GL_EINVAL, "scale (%g) is not finite and > 0", scale);
+  if (B <= 0) return fail(GL_EINVAL, "B (%d) must be positive", B);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  if (max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS)
+    return fail(GL_EINVAL, "max_segments %d outside [1, %d]", max_segments, CRIT_MAX_SEGMENTS);
+  if (int rc = check_window(false, x_lo, x_hi, y_lo, y_hi)) return rc;
+  if (m->n_series)
+    return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no critical curves");
+  if (m->has_user)
+    return fail(GL_EUNSUPPORTED, "user-written bodies (and the run-time compiled ScalingRelation member loops) are not served by the "
+                                 "critical-curve kernels");
+  if (int rc = check_ready(m, false, false)) return rc;
+  const CritLayout lay = crit_layout(B, n_cells, max_segments);
+  if (!workspace) return fail(GL_EINVAL, "workspace is null");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  const long long V = (long long)(n_cells + 1) * (n_cells + 1);
+  const long long map_blocks = (V * B + 255) / 256;
+  const int max_edges = 2 * max_segments;
+  const long long refine_blocks = (long long)B * ((max_edges + 63) / 64);
+  if (map_blocks > 0x7fffffffLL || refine_blocks > 0x7fffffffLL)
+    return fail(GL_EINVAL, "too many samples x vertices (or x max_segments) for one call");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  PosArgs a = point_args(m, params, B);
+  CritArgs g{};
+  g.n = n_cells;
+  g.scale = scale;
+  g.max_segments = max_segments;
+  g.max_edges = max_edges;
+  g.x_lo = x_lo; g.x_hi = x_hi; g.y_lo = y_lo; g.y_hi = y_hi;
+  g.hx = (x_hi - x_lo) / (float)n_cells;
+  g.hy = (y_hi - y_lo) / (float)n_cells;
+  g.bracket = CRIT_BRACKET_ULP * std::numeric_limits<float>::epsilon() *
+              std::max(std::max(std::fabs(x_lo), std::fabs(x_hi)), std::max(std::fabs(y_lo), std::fabs(y_hi)));
+  char* base = (char*)workspace;
+  g.dmap = (float*)(base + lay.dmap);
+  g.edge_id = (int*)(base + lay.edge_id);
+  g.edge_pt = (float4*)(base + lay.edge_pt);
+  g.edge_omk = (float*)(base + lay.edge_omk);
+  g.n_edges = (int*)(base + lay.n_edges);
+  g.n_edge_over = (int*)(base + lay.n_edge_over);
+  g.seg = seg; g.cau = cau; g.kind = kind;
+  g.n_seg = n_seg; g.n_dropped = n_dropped; g.n_flagged = n_flagged; g.open = open;
+  g.area = area;
+  const bool cat = m->n_scaled > 0;  // catalogues take the build whose evaluation is a function call (gl_critical.hip.h, crit_eval)
+  if (cat) hipLaunchKernelGGL(gl_crit_map_kernel<true>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
+  else hipLaunchKernelGGL(gl_crit_map_kernel<false>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
+  hipLaunchKernelGGL(gl_crit_scan_kernel, dim3((unsigned)B), dim3(CRIT_WG), 0, stream, g);
+  if (cat) hipLaunchKernelGGL(gl_crit_refine_kernel<true>, dim3((unsigned)refine_blocks), dim3(64), 0, stream, a, g);
+  else hipLaunchKernelGGL(gl_crit_refine_kernel<false>, dim3((unsigned)refine_blocks), dim3(64), 0, stream, a, g);
+  hipLaunchKernelGGL(gl_crit_cells_kernel, dim3((unsigned)B), dim3(CRIT_WG), 0, stream, g);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+}  // extern "C"
+
+// ---- lens planes at redshifts of their own (gl_multiplane.hip.h, gl_multiplane_bwd.hip.h) ------------------------------
+namespace {
+MpArgs mp_args(const gl_model* m) {
+  MpArgs a{};
+  a.order = m->d_mp_lens;
+  a.plane = m->d_mp_lens + m->n_lens;
+  a.scale = m->d_mp_scale;
+  return a;
+}
+}  // namespace
+
+namespace glk {
+
+int mp_render(const gl_model* m, const float* params, int B, unsigned parts, float* img, const Workspace& w, hipStream_t stream) {
+  MpRender r{};
+  r.gx = m->d_gx;
+  r.gy = m->d_gy;
+  r.pix = m->d_pix;
+  r.N = m->N;
+  r.n_ll = m->n_ll;
+  r.n_src = m->n_src;
+  r.parts = parts;
+  r.img_stride = (long long)m->height * m->width;
+  r.img = m->has_post ? w.img_ss : img;
+  r.out_scale = m->has_post ? 1.f : m->conversion_factor;  // (with a PSF the det(T) scale is applied after pooling, as in render_ss)
+  if (m->d_pix) GL_HIP(hipMemsetAsync(r.img, 0, sizeof(float) * (size_t)B * m->height * m->width, stream));
+  hipLaunchKernelGGL(gl_mp_render_kernel, dim3((unsigned)((m->N + MP_WG - 1) / MP_WG), (unsigned)B), dim3(MP_WG), 0, stream,
+                     point_args(m, params, B), mp_args(m), r);
+  GL_HIP(hipGetLastError());
+  return m->has_post ? post_fwd(m, B, w.img_ss, img, stream, m->conversion_factor) : GL_OK;
+}
+
+int mp_render_bwd(const gl_model* m, int B, const LaunchPlan& plan, const Workspace& w, const float* gimg, float out_scale,
+                  hipStream_t stream) {
+  MpBwd r{};
+  r.comps = m->d_comps;
+  r.n_lens = m->n_lens;
+  r.n_ll = m->n_ll;
+  r.n_src = m->n_src;
+  r.derived = w.derived;
+  r.D = m->D;
+  r.A = m->A;
+  r.Apad = m->Apad;
+  r.ncols = m->ncols;
+  r.gx = m->d_gx;
+  r.gy = m->d_gy;
+  r.pix = m->d_pix;
+  r.N = m->N;
+  r.chunk = plan.chunk;
+  r.gimg = gimg;
+  r.img_stride = (long long)m->height * m->width;
+  r.out_scale = out_scale;
+  r.partial = w.partial;
+  bool xf = false;  // the instantiation that carries the NFW_ELLIPSE / TNFW / CoreSersic VJPs
+  for (const CompDesc& c : m->comps) xf = xf || c.kind == K_NFW_ELLIPSE || c.kind == K_TNFW || c.kind == K_CORE_SERSIC;
+  const size_t shmem = (size_t)(((m->D + 3) & ~3) + m->ncols * m->Apad) * sizeof(float);
+  const dim3 grid((unsigned)plan.n_chunks, (unsigned)B), block(MP_WG);
+  if (xf) hipLaunchKernelGGL(gl_mp_bwd_kernel<true>, grid, block, shmem, stream, mp_args(m), r);
+  else hipLaunchKernelGGL(gl_mp_bwd_kernel<false>, grid, block, shmem, stream, mp_args(m), r);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+}  // namespace glk
+
+extern "C" {
+
+int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, int n_planes, const float* lens_scales,
+                             const float* source_scales, int n_src) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  if (n_planes > MP_MAXK) return fail(GL_EUNSUPPORTED, "%d lens planes: at most %d are served", n_planes, MP_MAXK);
+  if (n_planes < 2) return fail(GL_EINVAL, "%d lens plane(s): two or more (one plane: gl_model_set_source_scales)", n_planes);
+  if (!plane_of_lens || !lens_scales || (!source_scales && n_src > 0)) return fail(GL_EINVAL, "null argument");
+  if (n_lens != m->n_lens) return fail(GL_EINVAL, "%d plane indices for %d lens(es)", n_lens, m->n_lens);
+  if (n_src != m->n_src) return fail(GL_EINVAL, "source couplings of %d source(s) for %d source light component(s)", n_src, m->n_src);
+  const int K = n_planes;
+  if (m->has_user) return fail(GL_EUNSUPPORTED, "lens planes are not served for models with user-written profiles");
+  if (m->n_series)
+    return fail(GL_EUNSUPPORTED, "a series-expansion lens stores its field on the image-plane grid theta, not on the ray's position "
+                                 "theta_j on its own plane: not served on lens planes");
+  if (m->src_scaled) return fail(GL_EINVAL, "the model carries per-source deflection scales (gl_model_set_source_scales): the source couplings of the planes replace them");
+  for (int l = 0; l < m->n_lens; ++l)
+    if (m->comps[l].kind == K_SCALED)
+      return fail(GL_EUNSUPPORTED, "lens %d: galaxy catalogues (GL_SCALED) are not served on lens planes", l);
+  for (int c = m->n_lens; c < (int)m->comps.size(); ++c) {
+    const int kind = m->comps[c].kind;
+    if (kind != K_SERSIC && kind != K_SERSIC_ELLIPSE && kind != K_CORE_SERSIC)
+      return fail(GL_EUNSUPPORTED, "light component %d (kind %d): lens planes serve Sersic, SersicEllipse and CoreSersic lights", c, kind);
+  }
+  std::vector<int> count(K, 0);
+  for (int l = 0; l < n_lens; ++l) {
+    if (plane_of_lens[l] < 0 || plane_of_lens[l] >= K) return fail(GL_EINVAL, "plane_of_lens[%d] = %d outside [0, %d)", l, plane_of_lens[l], K);
+    ++count[plane_of_lens[l]];
+  }
+  for (int i = 0; i < K; ++i)
+    if (!count[i]) return fail(GL_EINVAL, "lens plane %d holds no lens", i);
+  std::vector<float> scale((size_t)MP_MAXK * MP_MAXK + (size_t)MP_MAXK * std::max(n_src, 0), 0.f);
+  for (int i = 0; i < K; ++i)
+    for (int j = 0; j < K; ++j) {
+      const float c = lens_scales[i * K + j];
+      if (i >= j ? c != 0.f : !(std::isfinite(c) && c > 0.f))
+        return fail(GL_EINVAL, "lens_scales[%d][%d] = %g: strictly upper triangular, finite and > 0 above the diagonal", i, j, c);
+      scale[(size_t)i * MP_MAXK + j] = c;
+    }
+  for (int s = 0; s < n_src; ++s)
+    for (int i = 0; i < K; ++i) {
+      const float c = source_scales[(size_t)i * n_src + s];
+      // a plane at or behind a source does not deflect it: zero from that plane on; the first plane lies in front of every source
+      const bool ok = std::isfinite(c) && c >= 0.f && (i == 0 ? c > 0.f : (c == 0.f || source_scales[(size_t)(i - 1) * n_src + s] > 0.f));
+      if (!ok) return fail(GL_EINVAL, "source_scales[%d][%d] = %g: finite, > 0 on the first plane, 0 from the first plane behind the source on", i, s, c);
+      scale[(size_t)MP_MAXK * MP_MAXK + (size_t)i * n_src + s] = c;
+    }
+  std::vector<int> lens((size_t)2 * std::max(n_lens, 1));
+  int t = 0;
+  for (int i = 0; i < K; ++i)
+    for (int l = 0; l < n_lens; ++l)
+      if (plane_of_lens[l] == i) lens[t++] = l;
+  for (int l = 0; l < n_lens; ++l) lens[(size_t)n_lens + l] = plane_of_lens[l];
+  GL_HIP(m->d_mp_lens.upload(lens.data(), lens.size()));
+  GL_HIP(m->d_mp_scale.upload(scale.data(), scale.size()));
+  m->mp_K = K;
+  return GL_OK;
+}
+
+int gl_multiplane_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
+                       const float* target_scales, int n_planes, float* out, void* hip_stream) {
+  if (!m || !params || !x || !y || !target_scales || !out) return fail(GL_EINVAL, "null argument");
+  if (int rc = check_planes_set(m)) return rc;
+  if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
+  if (n_planes != m->mp_K) return fail(GL_EINVAL, "%d target couplings for %d lens planes", n_planes, m->mp_K);
+  if (int rc = check_ready(m, false, false)) return rc;
+  MpTarget tg{};
+  for (int i = 0; i < n_planes; ++i) {
+    const float c = target_scales[i];
+    if (!(std::isfinite(c) && c >= 0.f) || (i > 0 && c != 0.f && target_scales[i - 1] == 0.f))
+      return fail(GL_EINVAL, "target_scales[%d] = %g: finite and >= 0, 0 from the first plane at or behind the target on", i, c);
+    tg.c[i] = c;
+  }
+  const long long total = (long long)n_pts * B, blocks = (total + MP_MAPS_WG - 1) / MP_MAPS_WG;
+  if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many points x samples for one call");
+  hipLaunchKernelGGL(gl_mp_maps_kernel, dim3((unsigned)blocks), dim3(MP_MAPS_WG), 0, (hipStream_t)hip_stream, point_args(m, params, B),
+                     mp_args(m), tg, x, y, (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+}  // extern "C"

@@ -54,7 +54,13 @@ struct SeriesDev {
 // image table of one K_INTERPOL light (gl_model_set_light_image): tab[(h + 4)][(w + 4)] with its zero apron; CompDesc::iparam indexes it
 using InterpDev = InterpTab<float>;
 
-struct ZCol;
+// One ZCol per column k of z (the k-th leaf of the prior in tf.nest.flatten order, tf/model.py:76-87); evaluated by z_eval (gl_frontend.hip.h)
+struct ZCol {
+  int param_col;  // destination column in the packed [B,P] row
+  int bijector;   // 0 identity, 1 exp, 2 sigmoid(lo,hi)
+  int prior;      // 0 normal, 1 lognormal, 2 uniform, 3 truncated normal
+  float a, b, lo, hi, log_norm;
+};
 struct FinArgs {
   int n_comp, P, A, d_z;
   const float* params;
@@ -212,440 +218,6 @@ template <int G> __device__ __forceinline__ void wave_acc(float (&acc)[G], const
       if (k < n) dst[k] += acc[k];
   }
 }
-
-#ifdef GL_AUX_KERNELS  // the non-template kernels around the main one: compiled into the main translation unit only
-// ---- per-sample prep: raw parameter rows -> derived constants --------------------------------
-// `cost` (optional): per-sample dispatch cost = the EPL trip count, written by the thread of component `cost_comp`
-// (models with exactly one EPL), so that gl_order_kernel reads one coalesced int array
-__global__ void __launch_bounds__(128) gl_prep_kernel(const CompDesc* __restrict__ comps, int n_comp,
-                                                      const float* __restrict__ params, int P, int B,
-                                                      float* __restrict__ derived, int D, int* __restrict__ cost,
-                                                      int cost_comp, const InterpDev* __restrict__ interp) {
-  int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= B * n_comp) return;
-  int b = i / n_comp, c = i - b * n_comp;
-  CompDesc cd = comps[c];
-  const float* p = params + (size_t)b * P + cd.p_off;
-  float* d = derived + (size_t)b * D + cd.d_off;
-  switch (cd.kind) {
-    case K_EPL: epl_prep<float>(p, cd.iparam, d); break;
-    case K_SIE: sie_prep<float>(p, d); break;
-    case K_NFW: nfw_prep<float>(p, d); break;
-    case K_SHEAR: shear_prep<float>(p, d); break;
-    case K_SIS: sis_prep<float>(p, d); break;
-    case K_DPIS: case K_DPIE: case K_DPIEP: dpie_prep<float>(cd.kind, p, d); break;
-    case K_SCALED: d[0] = d[1] = d[2] = d[3] = 0.f; break;
-    case K_SERIES: d[0] = p[0]; d[1] = p[1]; d[2] = d[3] = 0.f; break;
-    case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, d); break;
-    case K_TNFW: tnfw_prep<float>(p, d); break;
-    case K_CORE_SERSIC: core_sersic_prep<float>(p, d); break;
-    case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, d); break;
-    case K_SERSIC: sersic_prep<float>(p, false, d); break;
-    case K_SERSIC_ELLIPSE: sersic_prep<float>(p, true, d); break;
-    case K_SHAPELETS: shapelets_prep<float>(p, cd.iparam, d); break;
-    case K_USER_MASS: case K_USER_LIGHT: for (int k = 0; k < cd.iparam; ++k) d[k] = p[k]; break;  // the body reads its parameters
-  }
-  if (cost && c == cost_comp) cost[b] = reinterpret_cast<const int*>(d)[EPL_KI];
-}
-
-// ---- unconstrained-space front/back end: bijector + prior fused into prep / finalize -------------
-// One ZCol per column k of z (the k-th leaf of the prior in tf.nest.flatten order, tf/model.py:76-87).
-// Default event-space bijectors and log-densities restate TFP's (Identity / Exp / Sigmoid(lo,hi);
-// Normal / LogNormal / Uniform / TruncatedNormal) -- see gigalens_amd/prior.py for the same maths in torch.
-struct ZCol {
-  int param_col;  // destination column in the packed [B,P] row
-  int bijector;   // 0 identity, 1 exp, 2 sigmoid(lo,hi)
-  int prior;      // 0 normal, 1 lognormal, 2 uniform, 3 truncated normal
-  float a, b, lo, hi, log_norm;
-};
-
-struct ZEval { float x, dxdz, logp_plus_fldj, dlogp_dx, dfldj_dz; };
-
-__device__ __forceinline__ ZEval z_eval(const ZCol& c, float z) {
-  ZEval o;
-  float fldj;
-  float lnx = 0.f;
-  if (c.bijector == 0) {
-    o.x = z; o.dxdz = 1.f; fldj = 0.f; o.dfldj_dz = 0.f;
-  } else if (c.bijector == 1) {
-    o.x = expf(z); o.dxdz = o.x; fldj = z; o.dfldj_dz = 1.f; lnx = z;
-  } else {
-    float sg = 1.f / (1.f + expf(-z));
-    float w = c.hi - c.lo;
-    o.x = c.lo + w * sg;
-    o.dxdz = w * sg * (1.f - sg);
-    // log(hi-lo) - softplus(-z) - softplus(z)
-    float az = fabsf(z);
-    fldj = logf(w) - az - 2.f * log1pf(expf(-az));
-    o.dfldj_dz = 1.f - 2.f * sg;
-  }
-  const float half_log_2pi = 0.91893853320467274178f;
-  float logp;
-  if (c.prior == 0 || c.prior == 3) {
-    float u = (o.x - c.a) / c.b;
-    logp = -0.5f * u * u - logf(c.b) - half_log_2pi - (c.prior == 3 ? c.log_norm : 0.f);
-    o.dlogp_dx = -u / c.b;
-    if (c.prior == 3 && !(o.x >= c.lo && o.x <= c.hi)) { logp = -INFINITY; o.dlogp_dx = 0.f; }
-  } else if (c.prior == 1) {
-    if (c.bijector != 1) lnx = logf(o.x);
-    float u = (lnx - c.a) / c.b;
-    logp = -0.5f * u * u - logf(c.b) - half_log_2pi - lnx;
-    o.dlogp_dx = (-u / c.b - 1.f) / o.x;
-  } else {
-    bool in = (o.x >= c.lo && o.x <= c.hi);
-    logp = in ? -logf(c.hi - c.lo) : -INFINITY;
-    o.dlogp_dx = 0.f;
-  }
-  o.logp_plus_fldj = logp + fldj;
-  return o;
-}
-
-// the constrained value alone (the front end needs nothing else of z_eval)
-__device__ __forceinline__ float z_eval_x(const ZCol& c, float z) {
-  if (c.bijector == 0) return z;
-  if (c.bijector == 1) return expf(z);
-  return c.lo + (c.hi - c.lo) * (1.f / (1.f + expf(-z)));
-}
-
-// z [B,d] -> packed constrained rows [B,P] (also kept for finalize) -> derived constants
-__global__ void __launch_bounds__(128) gl_zprep_kernel(const CompDesc* __restrict__ comps, int n_comp,
-                                                       const float* __restrict__ z, int d_z,
-                                                       const ZCol* __restrict__ zcols, const int* __restrict__ src,
-                                                       const float* __restrict__ const_row, int P, int B,
-                                                       float* __restrict__ params, float* __restrict__ derived, int D,
-                                                       int* __restrict__ cost, int cost_comp, const InterpDev* __restrict__ interp) {
-  int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= B * n_comp) return;
-  int b = i / n_comp, c = i - b * n_comp;
-  CompDesc cd = comps[c];
-  float* p = params + (size_t)b * P + cd.p_off;
-  for (int j = 0; j < cd.n_par; ++j) {
-    int col = cd.p_off + j;
-    int k = src[col];
-    p[j] = (k >= 0) ? z_eval(zcols[k], z[(size_t)b * d_z + k]).x : const_row[col];
-  }
-  float* dd = derived + (size_t)b * D + cd.d_off;
-  switch (cd.kind) {
-    case K_EPL: epl_prep<float>(p, cd.iparam, dd); break;
-    case K_SIE: sie_prep<float>(p, dd); break;
-    case K_NFW: nfw_prep<float>(p, dd); break;
-    case K_SHEAR: shear_prep<float>(p, dd); break;
-    case K_SIS: sis_prep<float>(p, dd); break;
-    case K_DPIS: case K_DPIE: case K_DPIEP: dpie_prep<float>(cd.kind, p, dd); break;
-    case K_SCALED: dd[0] = dd[1] = dd[2] = dd[3] = 0.f; break;
-    case K_SERIES: dd[0] = p[0]; dd[1] = p[1]; dd[2] = dd[3] = 0.f; break;
-    case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, dd); break;
-    case K_TNFW: tnfw_prep<float>(p, dd); break;
-    case K_CORE_SERSIC: core_sersic_prep<float>(p, dd); break;
-    case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, dd); break;
-    case K_SERSIC: sersic_prep<float>(p, false, dd); break;
-    case K_SERSIC_ELLIPSE: sersic_prep<float>(p, true, dd); break;
-    case K_SHAPELETS: shapelets_prep<float>(p, cd.iparam, dd); break;
-    case K_USER_MASS: case K_USER_LIGHT: for (int k = 0; k < cd.iparam; ++k) dd[k] = p[k]; break;
-  }
-  if (cost && c == cost_comp) cost[b] = reinterpret_cast<const int*>(dd)[EPL_KI];
-}
-
-// ---- wave-per-sample front end (models with EPL lenses) --------------------------------------------------------------
-// The thread-per-component kernels above leave the EPL coefficient table to ONE thread: ~15-50 dependent iterations with a
-// division each, 7.5 us of latency in front of a 90 us main kernel.  Here one wavefront owns a sample: lane c does what the
-// thread of component c does above except the table, then all 64 lanes build the table of each EPL lens -- lane n takes
-// row n: its factors (one division), and the running products by an inclusive scan over the lanes.  The recurrence
-//   (c, cf, ct) <- (c p, cf p + c r, ct p + c dp/dt)      [r = p / f = dp/df]
-// is the product of matrices [[p,0,0],[r,p,0],[dpdt,0,p]], closed under (P, Qf, Qt) o (P', Qf', Qt') =
-// (P P', Qf P' + P Qf', Qt P' + P Qt'): associative, so six shuffle steps replace the chain (no division by p or f:
-// f = 0 and gamma = 1 stay finite exactly like the sequential form).
-struct EplScan { float P, Qf, Qt; };
-__device__ __forceinline__ EplScan epl_scan_combine(const EplScan& lo, const EplScan& hi) {  // rows of `lo` come first
-  return EplScan{lo.P * hi.P, lo.Qf * hi.P + lo.P * hi.Qf, lo.Qt * hi.P + lo.P * hi.Qt};
-}
-__device__ __forceinline__ void epl_table_wave(float f, float two_mt, int K, float* __restrict__ tab, int lane) {
-  EplScan carry{1.f, 0.f, 0.f};
-  for (int base = 0; base <= K + 3; base += 64) {
-    const int n = base + lane;
-    EplScan v{1.f, 0.f, 0.f};  // row 0: c_0 = 1, derivatives 0
-    if (n >= 1 && n <= K) {
-      float r, pn, dpdt;
-      epl_row_factors<float>(n, f, two_mt, r, pn, dpdt);
-      v = EplScan{pn, r, dpdt};
-    }
-#pragma unroll
-    for (int delta = 1; delta < 64; delta <<= 1) {
-      EplScan u{__shfl_up(v.P, delta), __shfl_up(v.Qf, delta), __shfl_up(v.Qt, delta)};
-      if (lane >= delta) v = epl_scan_combine(u, v);
-    }
-    v = epl_scan_combine(carry, v);
-    if (n <= K) {
-      reinterpret_cast<float4*>(tab)[n] = float4{v.P, (float)(2 * n + 1) * v.P, v.Qf, v.Qt};
-    } else if (n <= K + 3) {
-      reinterpret_cast<float4*>(tab)[n] = float4{0.f, 0.f, 0.f, 0.f};  // the four-row trips of the Clenshaw loop may start above K
-    }
-    carry = EplScan{__shfl(v.P, 63), __shfl(v.Qf, 63), __shfl(v.Qt, 63)};
-  }
-}
-
-// counting sort of the samples on their cost (<= 255), heaviest first, by ONE workgroup of NT threads: LDS histogram, one
-// wavefront's scan over the 256 bins in descending order (four bins per lane + a shuffle scan), scatter through the bins'
-// running offsets.  cost_of(b) is evaluated twice per sample (no staging array).
-// split_rank >= 0 (B <= 4 NT, NT = 256): the order inside the cost bin that straddles that rank is made the sample order instead
-// of the order of arrival of the atomics, so WHICH samples have a rank below split_rank is the same on every launch
-// (tail_plan: they are summed over other pixel chunks than the rest, and results stay bitwise reproducible).
-template <int NT, class F>
-__device__ __forceinline__ void gl_order_sort(F&& cost_of, int B, int* __restrict__ order, int split_rank = -1) {
-  __shared__ int hist[256];
-  __shared__ int offs[256];
-  __shared__ int s_split, s_group[4 * NT / 64];
-  const int tid = threadIdx.x;
-  for (int i = tid; i < 256; i += NT) hist[i] = 0;
-  if (tid == 0) s_split = -1;
-  __syncthreads();
-  // the first four samples of a thread stay in registers between the two passes (B <= 4 NT: all of them), their loads in flight together
-  int mine[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int b = tid + i * NT;
-    mine[i] = b < B ? max(0, min(cost_of(b), 255)) : 0;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (tid + i * NT < B) atomicAdd(&hist[mine[i]], 1);
-  for (int b = tid + 4 * NT; b < B; b += NT) atomicAdd(&hist[max(0, min(cost_of(b), 255))], 1);
-  __syncthreads();
-  if (tid < 64) {
-    const int top = 255 - 4 * tid;  // this lane's bins, heaviest first: top, top - 1, top - 2, top - 3
-    const int h0 = hist[top], h1 = hist[top - 1], h2 = hist[top - 2], h3 = hist[top - 3];
-    const int sum = h0 + h1 + h2 + h3;
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (tid >= d) incl += t;
-    }
-    const int excl = incl - sum;  // samples in strictly heavier bins of other lanes
-    offs[top] = excl;
-    offs[top - 1] = excl + h0;
-    offs[top - 2] = excl + h0 + h1;
-    offs[top - 3] = excl + h0 + h1 + h2;
-  }
-  __syncthreads();
-  int sb = -1;
-  if (split_rank >= 0 && NT == 256) {  // wave-uniform
-    if (offs[tid] < split_rank && split_rank < offs[tid] + hist[tid]) s_split = tid;  // at most one bin
-    __syncthreads();
-    sb = s_split;
-  }
-  if (sb >= 0) {
-    // stable ranks inside bin sb: samples 64 g .. 64 g + 63 are group g = 4 i + wavefront; per-group counts, then a prefix
-    const int lane = tid & 63, wv = tid >> 6;
-    int rk[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned long long mk = __ballot(tid + i * NT < B && mine[i] == sb);
-      rk[i] = __popcll(mk & ((1ull << lane) - 1ull));
-      if (lane == 0) s_group[i * (NT / 64) + wv] = __popcll(mk);
-    }
-    __syncthreads();
-    const int base = offs[sb];  // no atomic touches this bin's counter below
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (tid + i * NT < B && mine[i] == sb) {
-        int pre = 0;
-        for (int g = 0; g < i * (NT / 64) + wv; ++g) pre += s_group[g];
-        order[base + pre + rk[i]] = tid + i * NT;
-      }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (tid + i * NT < B && mine[i] != sb) order[atomicAdd(&offs[mine[i]], 1)] = tid + i * NT;
-  for (int b = tid + 4 * NT; b < B; b += NT) order[atomicAdd(&offs[max(0, min(cost_of(b), 255))], 1)] = b;
-}
-
-// params != null: packed constrained rows in (gl_prep_kernel's job); else z -> params_out through the bijectors
-// (gl_zprep_kernel's job).  n_comp <= 64.
-__global__ void __launch_bounds__(256) gl_prep_wave_kernel(const CompDesc* __restrict__ comps, int n_comp,
-                                                           const float* __restrict__ params_in, const float* __restrict__ z,
-                                                           int d_z, const ZCol* __restrict__ zcols,
-                                                           const int* __restrict__ src, const float* __restrict__ const_row,
-                                                           int P, int B, float* __restrict__ params_out,
-                                                           float* __restrict__ derived, int D, int* __restrict__ cost,
-                                                           int cost_comp, int* __restrict__ order, int row_lds, int split_rank,
-                                                           const InterpDev* __restrict__ interp) {
-  // Cost-ordered dispatch without a launch of its own: with `order` the grid carries ONE extra workgroup that sorts the samples
-  // by the trip count of their EPL series while the others build the samples' constants.  It needs no result of theirs: the count
-  // depends on (e1, e2) alone (epl_cost), which it takes from the parameter rows -- or, on the z path, through the two columns'
-  // bijectors.  (A "last workgroup to arrive sorts" scheme was measured first: 256 device-scope atomics on one counter, 0.5 ms.)
-  if (order && blockIdx.x == gridDim.x - 1) {
-    const CompDesc ce = comps[cost_comp];
-    const int c1 = ce.p_off + 2, c2 = ce.p_off + 3, cap = ce.iparam;
-    // what is the same for every sample is fetched once: where e1 and e2 come from (a z column and its bijector, or a constant)
-    int k1 = -1, k2 = -1;
-    ZCol z1{}, z2{};
-    float k1c = 0.f, k2c = 0.f;
-    if (!params_in) {
-      k1 = src[c1];
-      k2 = src[c2];
-      if (k1 >= 0) z1 = zcols[k1]; else k1c = const_row[c1];
-      if (k2 >= 0) z2 = zcols[k2]; else k2c = const_row[c2];
-    }
-    gl_order_sort<256>([&](int b) {
-      float e1, e2;
-      if (params_in) {
-        e1 = params_in[(size_t)b * P + c1];
-        e2 = params_in[(size_t)b * P + c2];
-      } else {
-        e1 = k1 >= 0 ? z_eval_x(z1, z[(size_t)b * d_z + k1]) : k1c;
-        e2 = k2 >= 0 ? z_eval_x(z2, z[(size_t)b * d_z + k2]) : k2c;
-      }
-      return epl_cost<float>(e1, e2, cap);
-    }, B, order, split_rank);
-    return;
-  }
-  const int b = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (b >= B) return;  // whole wavefronts leave together
-  float f = 0.f, two_mt = 0.f;
-  int K = 0;
-  // The constrained row of the sample goes to params_out (the finalize kernel reads it) AND, with row_lds, into the wavefront's own
-  // LDS row: the component lanes take their parameters from there instead of reading the global row back (a round trip through
-  // the L2 behind a store), and the component descriptors are requested before the bijector loads, not after them -- the
-  // front end is a chain of dependent memory round trips and nothing else (5.7 us at C2 with four of them in a row).
-  extern __shared__ float s_rows[];  // [4 wavefronts][P], or nothing
-  float* row = row_lds ? s_rows + (threadIdx.x >> 6) * P : nullptr;
-  CompDesc cd{};
-  if (lane < n_comp) cd = comps[lane];
-  if (!params_in) {
-    // z -> constrained row, one COLUMN per lane: the bijectors of a sample's columns are independent, so their loads
-    // (column descriptor, z) and transcendentals overlap instead of forming one lane's chain of n_par dependent round trips
-    float* po = params_out + (size_t)b * P;
-    for (int k = lane; k < d_z; k += 64) {
-      const ZCol zc = zcols[k];
-      const float v = z_eval_x(zc, z[(size_t)b * d_z + k]);
-      po[zc.param_col] = v;
-      if (row) row[zc.param_col] = v;
-    }
-    for (int col = lane; col < P; col += 64)
-      if (src[col] < 0) {
-        const float v = const_row[col];
-        po[col] = v;
-        if (row) row[col] = v;
-      }
-    if (!row) __threadfence_block();  // the component lanes below read the global row back (same wavefront, same L1)
-  } else if (row) {
-    for (int col = lane; col < P; col += 64) row[col] = params_in[(size_t)b * P + col];
-  }
-  // a wavefront's LDS accesses execute in order: the fence only keeps the compiler from moving the reads above the writes
-  if (row) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  const float* prow = row ? row : (params_in ? params_in : params_out) + (size_t)b * P;
-  if (lane < n_comp) {
-    const float* p = prow + cd.p_off;
-    float* d = derived + (size_t)b * D + cd.d_off;
-    switch (cd.kind) {
-      case K_EPL: K = epl_prep_head<float>(p, cd.iparam, d, f, two_mt); break;
-      case K_SIE: sie_prep<float>(p, d); break;
-      case K_NFW: nfw_prep<float>(p, d); break;
-      case K_SHEAR: shear_prep<float>(p, d); break;
-      case K_SIS: sis_prep<float>(p, d); break;
-      case K_DPIS: case K_DPIE: case K_DPIEP: dpie_prep<float>(cd.kind, p, d); break;
-      case K_SCALED: d[0] = d[1] = d[2] = d[3] = 0.f; break;
-      case K_SERIES: d[0] = p[0]; d[1] = p[1]; d[2] = d[3] = 0.f; break;
-      case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, d); break;
-      case K_TNFW: tnfw_prep<float>(p, d); break;
-      case K_CORE_SERSIC: core_sersic_prep<float>(p, d); break;
-      case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, d); break;
-      case K_SERSIC: sersic_prep<float>(p, false, d); break;
-      case K_SERSIC_ELLIPSE: sersic_prep<float>(p, true, d); break;
-      case K_USER_MASS: case K_USER_LIGHT: for (int k = 0; k < cd.iparam; ++k) d[k] = p[k]; break;
-      case K_SHAPELETS:  // the four constants here; the amplitude blocks below, by the whole wavefront
-        d[SHP_CX] = p[1]; d[SHP_CY] = p[2]; d[SHP_IB] = 1.f / p[0]; d[SHP_NMAX] = (float)cd.iparam;
-        break;
-    }
-    if (cost && lane == cost_comp) cost[b] = K;
-  }
-  for (int c = 0; c < n_comp; ++c) {  // wave-uniform: every lane joins the amplitude blocks of every shapelet component
-    if (comps[c].kind != K_SHAPELETS) continue;  // (one lane copying 66 + 144 values one by one: 18.6 us of prep at C3)
-    const CompDesc cs = comps[c];
-    const float* p = prow + cs.p_off;
-    float* d = derived + (size_t)b * D + cs.d_off;
-    const int n_max = cs.iparam, L = sh_layers(n_max);
-    const int tri = n_max > SH_CAP ? ((SH_MAXLB + 3) & ~3) : ((SH_MAXL + 3) & ~3);
-    for (int i = lane; i < tri; i += 64) d[SHP_AMP + i] = i < L ? p[3 + i] : 0.f;
-    if (n_max <= SH_CAP)
-      for (int e = lane; e < SH_SQ * SH_SQ; e += 64) {
-        const int n1 = e / SH_SQ, n2 = e - n1 * SH_SQ, n = n1 + n2;
-        d[SHP_SQ + e] = n <= n_max ? p[3 + n * (n + 1) / 2 + n2] * (SH_K[n1] * SH_K[n2]) : 0.f;  // scaled for the monic basis of gl_shp.hip.h
-      }
-  }
-  for (int c = 0; c < n_comp; ++c) {  // wave-uniform: every lane joins the table of every EPL lens
-    if (comps[c].kind != K_EPL) continue;
-    const float fc = __shfl(f, c), tc = __shfl(two_mt, c);
-    const int Kc = __shfl(K, c);
-    epl_table_wave(fc, tc, Kc, derived + (size_t)b * D + comps[c].d_off + EPL_TAB, lane);
-  }
-}
-
-// per (sample, galaxy) constants of the catalogue members: radii, amplitude and the map to the scale gradients
-__global__ void __launch_bounds__(128) gl_galprep_kernel(const CompDesc* __restrict__ comps,
-                                                         const CatDev* __restrict__ cats, int n_cats,
-                                                         const float* __restrict__ params, int P, int B,
-                                                         const float* __restrict__ table,
-                                                         const float* __restrict__ gal_static,
-                                                         float* __restrict__ gal_dyn, int G) {
-  int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= B * G) return;
-  int b = i / G, g = i - b * G;
-  int c = 0;
-  while (c + 1 < n_cats && g >= cats[c + 1].g_off) ++c;
-  const CatDev cat = cats[c];
-  ScaledDesc sd{cat.base_kind, cat.n_gal, {cat.col[0], cat.col[1], cat.col[2]}};
-  member_dyn(sd, table + (size_t)7 * g, gal_static + (size_t)g * DP_NS, params + (size_t)b * P + comps[cat.comp].p_off,
-             gal_dyn + ((size_t)b * G + g) * GM_ND);
-}
-
-// cost-ordered dispatch: samples sorted by descending EPL trip count (the only data-dependent cost on the
-// path), so the heaviest workgroups start first and the tail of the launch is filled with light ones.
-constexpr int ORDER_WG = 1024;
-__global__ void __launch_bounds__(ORDER_WG) gl_order_kernel(const CompDesc* __restrict__ comps, int n_lens,
-                                                            const float* __restrict__ derived, int D, int B,
-                                                            int* __restrict__ order, const int* __restrict__ cost_in) {
-  // counting sort on the cost (<= 255), three barriers in all: LDS histogram, one wavefront's scan over the 256 bins in
-  // descending order (four bins per lane + a shuffle scan), scatter through the bins' running offsets
-  __shared__ int hist[256];
-  __shared__ int offs[256];
-  const int tid = threadIdx.x;
-  if (tid < 256) hist[tid] = 0;
-  __syncthreads();
-  auto cost = [&](int b) {
-    if (cost_in) return min(cost_in[b], 255);
-    int k = 0;
-    for (int l = 0; l < n_lens; ++l)
-      if (comps[l].kind == K_EPL) k += reinterpret_cast<const int*>(derived + (size_t)b * D + comps[l].d_off)[EPL_KI];
-    return min(k, 255);
-  };
-  const int c0 = tid < B ? cost(tid) : 0;  // the first sample of a thread stays in a register (B <= 1024: the only one)
-  if (tid < B) atomicAdd(&hist[c0], 1);
-  for (int b = tid + ORDER_WG; b < B; b += ORDER_WG) atomicAdd(&hist[cost(b)], 1);
-  __syncthreads();
-  if (tid < 64) {
-    const int top = 255 - 4 * tid;  // this lane's bins, heaviest first: top, top - 1, top - 2, top - 3
-    const int h0 = hist[top], h1 = hist[top - 1], h2 = hist[top - 2], h3 = hist[top - 3];
-    const int sum = h0 + h1 + h2 + h3;
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (tid >= d) incl += t;
-    }
-    const int excl = incl - sum;  // samples in strictly heavier bins of other lanes
-    offs[top] = excl;
-    offs[top - 1] = excl + h0;
-    offs[top - 2] = excl + h0 + h1;
-    offs[top - 3] = excl + h0 + h1 + h2;
-  }
-  __syncthreads();
-  if (tid < B) order[atomicAdd(&offs[c0], 1)] = tid;
-  for (int b = tid + ORDER_WG; b < B; b += ORDER_WG) order[atomicAdd(&offs[cost(b)], 1)] = b;
-}
-
-#endif  // GL_AUX_KERNELS
 
 // ---- T-pixel EPL: series loop outermost so one LDS table read serves T pixels -------------------
 template <int T> __device__ __forceinline__ void epl_fwd_T(const float* d, const float (&x)[T], const float (&y)[T],
@@ -1335,515 +907,5 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
     out[k] = v;
   }
 }
-
-#ifdef GL_AUX_KERNELS
-// ---- finalize: sum chunk partials (fixed order), chain rule to raw parameters -------------------
-// With zcols != null the gradient is carried on to the unconstrained vector z and the log-prior
-// + log|J| is added:  log_prob = loglike + sum_k [log p_k(x_k) + fldj_k(z_k)]   (tf/model.py:164-167).
-
-// one sample, executed by NT threads of one workgroup; `s`: LDS scratch of A + P + d_z (+12) floats
-// BASIC: only EPL / SIE / Shear / SIS / Sersic in the model -- the other families' chain rules (TNFW's float64 core, shapelets,
-// dPIE, ...) stay out of the kernel: a third of the code, and the finalize launch is instruction-fetch bound
-template <int NT, bool BASIC = false>
-__device__ __forceinline__ void finalize_sample(const CompDesc* __restrict__ comps, const FinArgs& f,
-                                                const float* __restrict__ partial, int n_chunks, int b, int tid,
-                                                float* s) {
-  const int A = f.A, P = f.P, d_z = f.d_z;
-  float* s_g = s + ((A + 3) & ~3);
-  float* s_t = s_g + ((P + 3) & ~3);
-  float* s_e = s_t + ((d_z + 3) & ~3);  // [4][d_z]: dlogp/dx, dx/dz, dfldj/dz, parameter column of every column of z
-  const float* src = partial + (size_t)b * n_chunks * A;
-  // Phase 0 -- three independent jobs on three groups of threads, so their global round trips and transcendentals overlap
-  // instead of queueing behind two barriers: (a) sum the chunk partials, (b) bijector / prior terms of z (they do not depend
-  // on the accumulators), (c) fetch the component descriptors
-  for (int k = tid; k < A; k += NT) {
-    float v = 0.f;
-    if (f.use_partial)
-      for (int ch = 0; ch < n_chunks; ++ch) v += src[(size_t)ch * A + k];
-    if (f.extra_stats && k < 2) v += f.extra_stats[2 * b + k];  // chi2 / normalisation of a materialised image (PSF path)
-    s[k] = v;
-  }
-  constexpr int ZT0 = NT / 2;  // the upper half of the workgroup serves the columns of z
-  if (f.zcols && tid >= ZT0) {
-    for (int k = tid - ZT0; k < d_z; k += NT - ZT0) {
-      const ZCol c = f.zcols[k];
-      const ZEval e = z_eval(c, f.z[(size_t)b * d_z + k]);
-      s_t[k] = e.logp_plus_fldj;
-      s_e[k] = e.dlogp_dx;
-      s_e[d_z + k] = e.dxdz;
-      s_e[2 * d_z + k] = e.dfldj_dz;
-      s_e[3 * d_z + k] = __int_as_float(c.param_col);
-    }
-  }
-  const bool want_grad = f.grad != nullptr || f.grad_z != nullptr;
-  CompDesc cd{};
-  // the sample's parameter row goes to LDS whole, requested together with everything else (the components' own slices would
-  // be a round trip that can only start once their descriptors have arrived)
-  float* s_p = s_e + 4 * d_z + 4;
-  if (want_grad) {
-    for (int k = tid; k < P; k += NT) s_p[k] = f.params[(size_t)b * P + k];
-    if (tid < f.n_comp) cd = comps[tid];
-  }
-  __syncthreads();
-  if (want_grad) {
-    for (int c = tid; c < f.n_comp; c += NT) {
-      if (c != tid) cd = comps[c];
-      const float* p = s_p + cd.p_off;
-      float* g = s_g + cd.p_off;
-      const float* acc = s + cd.a_off;
-      switch (cd.kind) {
-        case K_EPL: epl_finalize<float>(p, acc, g); break;
-        case K_SIE: sie_finalize<float>(p, acc, g); break;
-        case K_NFW: if constexpr (!BASIC) nfw_finalize<float>(p, acc, g); break;
-        case K_SHEAR: shear_finalize<float>(p, acc, g); break;
-        case K_SIS: sis_finalize<float>(p, acc, g); break;
-        case K_DPIS: case K_DPIE: case K_DPIEP: if constexpr (!BASIC) dpie_finalize<float>(cd.kind, p, acc, g); break;
-        case K_SCALED:
-          if constexpr (!BASIC) {
-            const CatDev cat = f.cats[cd.iparam];
-            for (int k = 0; k < 3; ++k)
-              if (cat.col[k] >= 0) g[cat.col[k]] = acc[k];
-          }
-          break;
-        case K_SERIES: if constexpr (!BASIC) { g[0] = acc[0]; g[1] = acc[1]; } break;
-        case K_NFW_ELLIPSE: if constexpr (!BASIC) nfw_ell_finalize<float>(p, acc, g); break;
-        case K_TNFW: if constexpr (!BASIC) tnfw_finalize<float>(p, acc, g); break;
-        case K_CORE_SERSIC: if constexpr (!BASIC) core_sersic_finalize<float>(p, acc, g); break;
-        case K_INTERPOL: if constexpr (!BASIC) interp_finalize<float>(p, acc, g); break;
-        case K_SERSIC: sersic_finalize<float>(p, false, acc, g); break;
-        case K_SERSIC_ELLIPSE: sersic_finalize<float>(p, true, acc, g); break;
-        case K_SHAPELETS: if constexpr (!BASIC) shapelets_finalize<float>(p, cd.iparam, acc, g); break;
-        case K_USER_MASS: case K_USER_LIGHT: if constexpr (!BASIC) { for (int k = 0; k < cd.iparam; ++k) g[k] = acc[k]; } break;  // d/dp_k as summed
-      }
-    }
-    __syncthreads();
-    if (f.pos_grad) {  // image-position likelihood: its parameter gradient joins before the chain to z
-      for (int k = tid; k < P; k += NT) s_g[k] += f.pos_grad[(size_t)b * P + k];
-      __syncthreads();
-    }
-    // A NaN log-likelihood (sigma^2 = bg^2 + model / t < 0 somewhere: tf/model.py:96 takes its square root) has a NaN gradient
-    // in the reference -- the square root's derivative is NaN there and NaN x 0 stays NaN through every pixel sum -- while the
-    // cotangent the kernels form (from 1 / sigma^2) stays finite: the whole row follows the reference.
-    const float poison = (s[0] + s[1]) != (s[0] + s[1]) ? __int_as_float(0x7fc00000) : 0.f;
-    if (f.grad)
-      for (int k = tid; k < P; k += NT) f.grad[(size_t)b * P + k] = s_g[k] + poison;
-    if (f.zcols && f.grad_z && tid >= ZT0)
-      for (int k = tid - ZT0; k < d_z; k += NT - ZT0)
-        f.grad_z[(size_t)b * d_z + k] = (s_g[__float_as_int(s_e[3 * d_z + k])] + s_e[k]) * s_e[d_z + k] + s_e[2 * d_z + k] + poison;
-  }
-  if (tid == 0 && f.loglike) {
-    float ll = -0.5f * (s[0] + s[1]);  // tf/model.py:99
-    float c2 = s[0] * f.chi2_scale;
-    if (f.pos_ll) {  // tf/model.py:157-162
-      ll += f.pos_ll[b];
-      c2 += f.pos_chi2[b] * f.pos_chi2_scale;
-    }
-    f.loglike[b] = ll;
-    f.chi2[b] = c2;
-    if (f.zcols && f.logprob) {
-      float lp = 0.f;
-      for (int k = 0; k < d_z; ++k) lp += s_t[k];
-      f.logprob[b] = ll + lp;
-    }
-  }
-}
-
-template <bool BASIC>
-__global__ void __launch_bounds__(128) gl_finalize_kernel(const CompDesc* __restrict__ comps, FinArgs f,
-                                                          const float* __restrict__ partial, int n_chunks) {
-  extern __shared__ float s[];  // [A] accumulators, [P] parameter gradients, [d_z] prior terms, [4][d_z] bijector / prior derivatives, [P] parameters
-#ifdef GL_EXPERIMENTS
-  if (n_chunks < 0) return;  // GIGALENS_HIP_DBGFLAGS & 8: the cost of the bare launch (results undefined)
-#endif
-  finalize_sample<128, BASIC>(comps, f, partial, n_chunks, blockIdx.x, threadIdx.x, s);
-}
-
-// Fused form (specialised kernels, likelihood modes): the LAST workgroup of a sample to publish its partial row runs
-// the sample's finalize in its own tail -- one kernel launch less on the critical path of every step.
-// (Fusing this into the tail of each sample's last main-kernel workgroup was measured and dropped: with one L2 per XCD
-// the hand-over of the partial rows needs agent-scope release / L2-bypassing traffic per workgroup, which cost more
-// (0.172 ms per step) than the separate 5 us launch (0.137 ms).)
-
-// ---- the optimiser update of the MAP / SVI loops (tf/inference.py:33-39 hands the gradient to a Keras Adam) ----------
-// One launch instead of ~10 elementwise ones: x -= lr * (m / c1) / (sqrt(v / c2) + eps) with m, v updated in place,
-// grad scaled by grad_scale first; c1 = 1 - b1^t, c2 = 1 - b2^t with t from the host or, inside a captured graph,
-// from a device counter that thread 0 of block 0 advances AFTER every block has read it (it is read at kernel start
-// and written only by the last block to finish, see the ticket).
-__global__ void __launch_bounds__(256) gl_adam_kernel(float* __restrict__ x, const float* __restrict__ grad,
-                                                      float* __restrict__ m, float* __restrict__ v, long long n,
-                                                      float grad_scale, float lr, float b1, float b2, float eps,
-                                                      double t_host, double* __restrict__ t_dev,
-                                                      unsigned* __restrict__ ticket, float c1_host, float c2_host) {
-  // the bias corrections 1 - beta^t: from the host when it knows the step count (two double-precision pow per THREAD were most
-  // of this kernel's 4.5 us), on the device only under graph replay, where the count lives in t_dev
-  const double t = (t_dev ? t_dev[0] : t_host) + (t_dev ? 1.0 : 0.0);
-  float c1 = c1_host, c2 = c2_host;
-  if (t_dev) {
-    c1 = (float)(1.0 - ::pow((double)b1, t));
-    c2 = (float)(1.0 - ::pow((double)b2, t));
-  }
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
-    const float g = grad[i] * grad_scale;
-    const float mi = m[i] * b1 + g * (1.0f - b1);
-    const float vi = v[i] * b2 + (g * g) * (1.0f - b2);
-    m[i] = mi;
-    v[i] = vi;
-    x[i] -= lr * (mi / c1) / (sqrtf(vi / c2) + eps);
-  }
-  if (t_dev) {  // advance the device counter once per launch, after the last reader
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      __threadfence();
-      const unsigned done = atomicAdd(ticket, 1u);
-      if (done == gridDim.x - 1) {
-        t_dev[0] = t;
-        *ticket = 0u;
-      }
-    }
-  }
-}
-
-// ---- the Gaussian surrogate of the SVI loop (tf/inference.py:64-91; jax/inference.py:98-128) ---------------------------
-// q(z) = N(mu, L L^T) with L = FillScaleTriL(diag_bijector=Exp, diag_shift) over the row-major lower-triangle packing
-// (full rank) or L = diag(exp(p)) (mean field).  Two small launches bracket the native forward+gradient call:
-//   gl_svi_sample_kernel  z_i = mu + L eps_i
-//   gl_svi_grad_kernel    the fused collective buffer  [ELBO, dELBO/dmu (d), dELBO/dp (packed)]  from eps, log p(z_i) and
-//                         G_i = d log p / d z_i:  dELBO/dmu = -mean G,  dELBO/dL_jk = -mean G_ij eps_ik (k <= j), Exp diagonal
-//                         and -log det L of log q in closed form.  One workgroup per output, fixed-order reduction over i.
-__device__ __forceinline__ void tril_jk(int t, int& j, int& k) {
-  j = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-  while ((j + 1) * (j + 2) / 2 <= t) ++j;
-  while (j * (j + 1) / 2 > t) --j;
-  k = t - j * (j + 1) / 2;
-}
-
-__global__ void __launch_bounds__(256) gl_svi_sample_kernel(const float* __restrict__ mu, const float* __restrict__ lp,
-                                                            int d, int full_rank, const float* __restrict__ eps, int n,
-                                                            float diag_shift, float* __restrict__ z) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)n * d) return;
-  const int r = (int)(i / d), j = (int)(i - (long long)r * d);
-  const float* e = eps + (size_t)r * d;
-  float v = mu[j];
-  if (full_rank) {
-    const float* row = lp + j * (j + 1) / 2;
-    for (int k = 0; k < j; ++k) v += row[k] * e[k];
-    v += (expf(row[j]) + diag_shift) * e[j];
-  } else {
-    v += expf(lp[j]) * e[j];
-  }
-  z[i] = v;
-}
-
-__global__ void __launch_bounds__(256) gl_svi_grad_kernel(const float* __restrict__ lp, int d, int full_rank,
-                                                          const float* __restrict__ eps, const float* __restrict__ logp,
-                                                          const float* __restrict__ G, int n, float diag_shift,
-                                                          float* __restrict__ buf) {
-  __shared__ float red[4];
-  const int o = blockIdx.x, tid = threadIdx.x;
-  int j = 0, k = 0;
-  const int kind = o == 0 ? 0 : (o <= d ? 1 : 2);  // ELBO, d/dmu_j, d/dp_t
-  if (kind == 1) j = o - 1;
-  if (kind == 2) {
-    if (full_rank) tril_jk(o - 1 - d, j, k);
-    else j = k = o - 1 - d;
-  }
-  float acc = 0.f;
-  for (int i = tid; i < n; i += 256) {
-    if (kind == 0) {
-      const float* e = eps + (size_t)i * d;
-      float q = 0.f;
-      for (int c = 0; c < d; ++c) q += e[c] * e[c];
-      acc += -0.5f * q - logp[i];
-    } else if (kind == 1) {
-      acc -= G[(size_t)i * d + j];
-    } else {
-      acc -= G[(size_t)i * d + j] * eps[(size_t)i * d + k];
-    }
-  }
-  acc = wave_sum63(acc);
-  if ((tid & 63) == 63) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid != 0) return;
-  float v = (red[0] + red[1] + red[2] + red[3]) / (float)n;
-  if (kind == 0) {
-    float log_det = 0.f;
-    for (int c = 0; c < d; ++c) log_det += full_rank ? logf(expf(lp[c * (c + 1) / 2 + c]) + diag_shift) : lp[c];
-    v += -log_det - 0.5f * (float)d * 1.8378770664093453f;  // log 2 pi
-  } else if (kind == 2 && j == k) {
-    const float p = lp[full_rank ? j * (j + 1) / 2 + j : j];
-    const float e = expf(p);
-    v = full_rank ? v * e - e / (e + diag_shift) : v * e - 1.f;
-  }
-  buf[o] = v;
-}
-
-// ---- the leapfrog of the preconditioned HMC loop (tf/inference.py:95-182) ----------------------------------------------
-// Momentum precision = the surrogate covariance Sigma = L L^T, so a drift is z += eps * (p Sigma).  One launch does the
-// momentum kick that precedes a drift and the drift itself; one launch closes a transition: last half kick, kinetic
-// energies 1/2 |p L|^2, Metropolis test against the supplied uniforms, and the in-place selection of the state.
-// One workgroup per chain, any d (cluster models: d = 132): the chain's momentum row is staged in LDS, thread j owns
-// column j, so the rows of Sigma / L are read coalesced and every output element is read and written by the same
-// thread (the calls may run in place: p_out == p_in, z_out == z_in).
-constexpr int HMC_WG = 128;
-
-__global__ void __launch_bounds__(HMC_WG) gl_hmc_kick_drift_kernel(const float* p_in, const float* __restrict__ grad,
-                                                                   float kick, const float* z_in,
-                                                                   const float* __restrict__ sigma, float eps, int n, int d,
-                                                                   float* p_out, float* z_out) {
-  extern __shared__ float s_p[];  // [d]
-  const int i = blockIdx.x, tid = threadIdx.x;
-  const size_t row = (size_t)i * d;
-  for (int j = tid; j < d; j += HMC_WG) {
-    const float v = p_in[row + j] + kick * grad[row + j];
-    s_p[j] = v;
-    p_out[row + j] = v;
-  }
-  __syncthreads();
-  for (int j = tid; j < d; j += HMC_WG) {
-    float s = 0.f;
-    for (int k = 0; k < d; ++k) s += s_p[k] * sigma[(size_t)k * d + j];
-    z_out[row + j] = z_in[row + j] + eps * s;
-  }
-}
-
-__global__ void __launch_bounds__(HMC_WG) gl_hmc_accept_kernel(float* z, float* g, float* lp, const float* __restrict__ zn,
-                                                               const float* __restrict__ gn, const float* __restrict__ lpn,
-                                                               const float* __restrict__ p0, const float* __restrict__ pn,
-                                                               float kick, const float* __restrict__ L,
-                                                               const float* __restrict__ u, int n, int d,
-                                                               float* __restrict__ acc_prob) {
-  extern __shared__ float s_ab[];  // [2][d] momenta at both ends, then [4] reduction slots
-  float* s_a = s_ab;
-  float* s_b = s_ab + d;
-  __shared__ float red[2][HMC_WG / 64];
-  __shared__ int s_take;
-  const int i = blockIdx.x, tid = threadIdx.x;
-  const size_t row = (size_t)i * d;
-  for (int j = tid; j < d; j += HMC_WG) {
-    s_a[j] = p0[row + j];
-    s_b[j] = pn[row + j] + kick * gn[row + j];
-  }
-  __syncthreads();
-  float ke0 = 0.f, ke1 = 0.f;
-  for (int k = tid; k < d; k += HMC_WG) {  // (p L)_k = sum_{j >= k} p_j L_jk, L lower triangular
-    float s0 = 0.f, s1 = 0.f;
-    for (int j = k; j < d; ++j) {
-      const float l = L[(size_t)j * d + k];
-      s0 += s_a[j] * l;
-      s1 += s_b[j] * l;
-    }
-    ke0 += s0 * s0;
-    ke1 += s1 * s1;
-  }
-  ke0 = wave_sum63(ke0);
-  ke1 = wave_sum63(ke1);
-  if ((tid & 63) == 63) { red[0][tid >> 6] = ke0; red[1][tid >> 6] = ke1; }
-  __syncthreads();
-  if (tid == 0) {
-    float k0 = 0.f, k1 = 0.f;
-    for (int w = 0; w < HMC_WG / 64; ++w) { k0 += red[0][w]; k1 += red[1][w]; }
-    float log_acc = (lpn[i] - 0.5f * k1) - (lp[i] - 0.5f * k0);
-    if (!(fabsf(log_acc) <= 3.0e38f)) log_acc = -INFINITY;  // NaN / inf proposals are rejected
-    acc_prob[i] = expf(fminf(log_acc, 0.f));
-    const int take = logf(u[i]) < log_acc;
-    s_take = take;
-    if (take) lp[i] = lpn[i];
-  }
-  __syncthreads();
-  if (s_take)
-    for (int j = tid; j < d; j += HMC_WG) {
-      z[row + j] = zn[row + j];
-      g[row + j] = gn[row + j];
-    }
-}
-
-// ---- plugin-level point evaluation (MassProfile.deriv / LightProfile.light on arbitrary points) ----
-__global__ void __launch_bounds__(256) gl_point_kernel(CompDesc cd, const float* __restrict__ x,
-                                                       const float* __restrict__ y, long long n_pts, int B,
-                                                       int xy_batched, const float* __restrict__ params,
-                                                       float* __restrict__ out0, float* __restrict__ out1,
-                                                       const float* __restrict__ shp_tab, int shp_stride, InterpDev itab) {
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pts * B) return;
-  long long pt = i / B;
-  int b = (int)(i - pt * B);
-  float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  const float* p = params + (size_t)b * cd.n_par;
-  float o0 = 0.f, o1 = 0.f;
-  switch (cd.kind) {
-    case K_EPL: epl_point<float>(p, cd.iparam, px, py, o0, o1); break;
-    case K_SIE: { float d[SIE_ND + 1]; sie_prep<float>(p, d); sie_fwd(d, px, py, o0, o1); } break;
-    case K_NFW: { float d[NFW_ND]; nfw_prep<float>(p, d); nfw_fwd(d, px, py, o0, o1); } break;
-    case K_SHEAR: { float d[4]; shear_prep<float>(p, d); shear_fwd(d, px, py, o0, o1); } break;
-    case K_SIS: { float d[4]; sis_prep<float>(p, d); sis_fwd(d, px, py, o0, o1); } break;
-    case K_DPIS: case K_DPIE: case K_DPIEP: { float d[DPX_ND]; dpie_prep<float>(cd.kind, p, d); dpie_fwd<float>(cd.kind, d, px, py, o0, o1); } break;
-    case K_NFW_ELLIPSE: { float d[NFE_ND]; nfw_ell_prep<float>(p, d); nfw_ell_fwd<float>(d, px, py, o0, o1); } break;
-    case K_TNFW: { float d[TNF_ND]; tnfw_prep<float>(p, d); tnfw_fwd<float>(d, px, py, o0, o1); } break;
-    case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(p, d); o0 = core_sersic_fwd<float>(d, px, py); } break;
-    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(p, itab.h, itab.w, d); o0 = interp_fwd<float>(d, itab, cd.flags & 1u, px, py); } break;
-    case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(p, false, d); o0 = sersic_fwd(d, px, py); } break;
-    case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(p, true, d); o0 = sersic_fwd(d, px, py); } break;
-    case K_SHAPELETS: {
-      if (cd.iparam > SH_CAP) {  // runtime-order path; amplitudes straight from the parameter row (same triangle order)
-        float d[SHP_AMP];
-        d[SHP_CX] = p[1]; d[SHP_CY] = p[2]; d[SHP_IB] = 1.f / p[0]; d[SHP_NMAX] = (float)cd.iparam;
-        o0 = shapelets_fwd_amp<float, SH_CAPB>(d, p + 3, shp_tab, shp_stride, cd.flags & 1u, px, py);
-      } else {
-        float d[SHP_SQ + SH_SQ * SH_SQ];
-        shapelets_prep<float>(p, cd.iparam, d);
-        o0 = shapelets_fwd<float, SH_CAP>(d, shp_tab, shp_stride, cd.flags & 1u, px, py);
-      }
-    } break;
-  }
-  out0[i] = o0;
-  if (out1) out1[i] = o1;
-}
-
-// LightProfile.light of a use_lstsq profile at plugin level: the unit-amplitude basis images (sersic.py:30-34
-// `Ie = ones`, `ret[tf.newaxis]`; shapelets.py:61-62,71-72), out[depth][n_pts][B]; amplitude columns are not read
-__global__ void __launch_bounds__(256) gl_basis_point_kernel(CompDesc cd, const float* __restrict__ x,
-                                                             const float* __restrict__ y, long long n_pts, int B,
-                                                             int xy_batched, const float* __restrict__ params,
-                                                             float* __restrict__ out,
-                                                             const float* __restrict__ shp_tab, int shp_stride, InterpDev itab) {
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = n_pts * B;
-  if (i >= total) return;
-  long long pt = i / B;
-  int b = (int)(i - pt * B);
-  float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  const float* p = params + (size_t)b * cd.n_par;
-  if (cd.kind == K_SHAPELETS) {
-    float d[SHP_AMP];
-    d[SHP_CX] = p[1];
-    d[SHP_CY] = p[2];
-    d[SHP_IB] = 1.f / p[0];
-    d[SHP_NMAX] = (float)cd.iparam;
-    if (cd.iparam > SH_CAP)
-      shapelets_basis<float, SH_CAPB>(d, shp_tab, shp_stride, cd.flags & 1u, px, py,
-                                      [&](int k, float v) { out[(size_t)k * total + i] = v; });
-    else
-      shapelets_basis<float, SH_CAP>(d, shp_tab, shp_stride, cd.flags & 1u, px, py,
-                                     [&](int k, float v) { out[(size_t)k * total + i] = v; });
-    return;
-  }
-  float q[10];
-  for (int k = 0; k < cd.n_par; ++k) q[k] = p[k];
-  q[kind_linear_col(cd.kind, cd.iparam)] = 1.f;
-  float v = 0.f;
-  switch (cd.kind) {
-    case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(q, d); v = core_sersic_fwd<float>(d, px, py); } break;
-    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(q, itab.h, itab.w, d); v = interp_fwd_unit<float>(d, itab, cd.flags & 1u, px, py); } break;
-    case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(q, false, d); v = sersic_fwd(d, px, py); } break;
-    case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(q, true, d); v = sersic_fwd(d, px, py); } break;
-  }
-  out[i] = v;
-}
-
-// ScalingRelation.deriv on arbitrary points (scaling_relation.py:61-70)
-__global__ void __launch_bounds__(256) gl_scaled_point_kernel(ScaledDesc sd, const float* __restrict__ table,
-                                                              const float* __restrict__ x, const float* __restrict__ y,
-                                                              long long n_pts, int B, int xy_batched,
-                                                              const float* __restrict__ scales, int n_scales,
-                                                              float* __restrict__ out0, float* __restrict__ out1) {
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pts * B) return;
-  long long pt = i / B;
-  int b = (int)(i - pt * B);
-  float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  const float* sc = scales + (size_t)b * n_scales;
-  float sx = 0.f, sy = 0.f;
-  for (int g = 0; g < sd.n_gal; ++g) {
-    float ds[DP_NS], dd[DP_ND], ax, ay;
-    scaled_static<float>(sd.base_kind, table + (size_t)7 * g, ds);
-    scaled_dyn<float>(sd, table + (size_t)7 * g, sc, dd);
-    if (sd.base_kind == K_DPIE) piemd_fwd<float>(ds, dd, px, py, ax, ay);
-    else piep_fwd<float>(ds, dd, px, py, ax, ay);
-    sx += ax;
-    sy += ay;
-  }
-  out0[i] = sx;
-  out1[i] = sy;
-}
-
-// Taylor coefficients of the population deflection at arbitrary points: coeffs[2][order+1][n_pts]
-template <int N>
-__global__ void __launch_bounds__(64) gl_series_precompute_kernel(ScaledDesc sd, const float* __restrict__ table,
-                                                                 float s0, float s1, float s2, int order,
-                                                                 const float* __restrict__ x, const float* __restrict__ y,
-                                                                 long long n_pts, float* __restrict__ coeffs) {
-  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
-  if (i >= n_pts) return;
-  // float64 jets: near a member's foci (removable 0/0 of the Kassiola-Kovner form) the k-th coefficient loses
-  // ~(1/distance)^k digits -- in fp32 orders >= 2 are noise at ~1 % of the pixels; the one-off precompute can afford
-  // CDNA4's full-rate fp64, the stored field is fp32 like every other operand of the path
-  const double scales[3] = {(double)s0, (double)s1, (double)s2};
-  double cx[N + 1], cy[N + 1];
-  series_point<N, double>(sd, table, scales, (double)x[i], (double)y[i], cx, cy);
-  for (int n = 0; n <= order; ++n) {
-    coeffs[(size_t)n * n_pts + i] = (float)cx[n];
-    coeffs[(size_t)(order + 1 + n) * n_pts + i] = (float)cy[n];
-  }
-}
-
-// Taylor coefficients of the population Hessian: coeffs[3][order+1][n_pts] = f_xx, f_xy, f_yy (one-off, fp64 jets)
-template <int N>
-__global__ void __launch_bounds__(64) gl_series_hessian_precompute_kernel(ScaledDesc sd, const float* __restrict__ table,
-                                                                         float s0, float s1, float s2, int order,
-                                                                         const float* __restrict__ x,
-                                                                         const float* __restrict__ y, long long n_pts,
-                                                                         float* __restrict__ coeffs) {
-  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
-  if (i >= n_pts) return;
-  const double scales[3] = {(double)s0, (double)s1, (double)s2};
-  double hxx[N + 1], hxy[N + 1], hyy[N + 1];
-  series_point_hessian<N, double>(sd, table, scales, (double)x[i], (double)y[i], hxx, hxy, hyy);
-  for (int n = 0; n <= order; ++n) {
-    coeffs[(size_t)n * n_pts + i] = (float)hxx[n];
-    coeffs[(size_t)(order + 1 + n) * n_pts + i] = (float)hxy[n];
-    coeffs[(size_t)(2 * (order + 1) + n) * n_pts + i] = (float)hyy[n];
-  }
-}
-
-// theta_E[b] * sum_n coeffs[f][n][pt] (r_cut[b] - r0)^n for n_fields fields: out[n_fields][n_pts][B]
-__global__ void __launch_bounds__(256) gl_series_fields_kernel(const float* __restrict__ coeffs, int n_fields, int order,
-                                                               long long n_pts, int B,
-                                                               const float* __restrict__ theta_E,
-                                                               const float* __restrict__ r_cut, float r0,
-                                                               float* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pts * B) return;
-  const long long pt = i / B;
-  const int b = (int)(i - pt * B);
-  const float dl = r_cut[b] - r0, te = theta_E[b];
-  for (int f = 0; f < n_fields; ++f) {
-    const float* c = coeffs + (size_t)f * (order + 1) * n_pts + pt;
-    float v = c[(size_t)order * n_pts];
-    for (int n = order - 1; n >= 0; --n) v = v * dl + c[(size_t)n * n_pts];
-    out[(size_t)f * n_pts * B + i] = te * v;
-  }
-}
-
-__global__ void __launch_bounds__(256) gl_series_eval_kernel(const float* __restrict__ coeffs, int order, long long n_pts,
-                                                             int B, const float* __restrict__ theta_E,
-                                                             const float* __restrict__ r_cut, float r0,
-                                                             float* __restrict__ out0, float* __restrict__ out1) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pts * B) return;
-  const long long pt = i / B;
-  const int b = (int)(i - pt * B);
-  const float dl = r_cut[b] - r0;
-  float ax = coeffs[(size_t)order * n_pts + pt], ay = coeffs[(size_t)(2 * order + 1) * n_pts + pt];
-  for (int n = order - 1; n >= 0; --n) {
-    ax = ax * dl + coeffs[(size_t)n * n_pts + pt];
-    ay = ay * dl + coeffs[(size_t)(order + 1 + n) * n_pts + pt];
-  }
-  out0[i] = theta_E[b] * ax;
-  out1[i] = theta_E[b] * ay;
-}
-
-#endif  // GL_AUX_KERNELS
 
 }  // namespace glk

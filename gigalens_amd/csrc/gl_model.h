@@ -1,7 +1,9 @@
 // gl_model.h -- the library-internal model descriptor, the owner type of its device buffers (DevBuf) and the error helper shared
-// by the translation units of libgigalens_hip.so (gigalens_hip.hip: C ABI + host logic; gl_launch_mode*.hip /
-// gl_generic_noslp_mode*.hip: one instantiation of a main-kernel launcher per mode, compiled in parallel; gl_user.hip: the run-time
-// compiler of user-written profiles).  The model owns every device allocation it holds: destroying it frees them.
+// by the translation units of libgigalens_hip.so (gigalens_hip.hip: models, launch plan, front end / finalize / PSF launchers, the
+// render, likelihood and log-prob entries; gl_api_points.hip, gl_api_lstsq.hip, gl_api_pixsrc.hip, gl_api_plugin.hip: the entry
+// points of one feature family each, sharing gl_host.hip.h; gl_launch_mode*.hip / gl_generic_noslp_mode*.hip: one instantiation of
+// a main-kernel launcher per mode; gl_user.hip: the run-time compiler of user-written profiles -- all compiled in parallel).  The
+// model owns every device allocation it holds: destroying it frees them.
 #pragma once
 #include <hip/hip_runtime.h>
 

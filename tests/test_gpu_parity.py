@@ -258,6 +258,44 @@ def test_fused_log_prob_matches_unfused(gl, name, kw):
     assert torch.equal(lp2, lpa.detach()) and torch.equal(red2, reda.detach()) and torch.equal(g2, za.grad)
 
 
+@pytest.mark.parametrize("lens", ["SIE", "EPL"])  # thread-per-component front end (gl_prep_kernel) / wavefront-per-sample (gl_prep_wave_kernel)
+def test_front_end_from_z_equals_front_end_from_packed_rows(gl, lens):
+    """One front-end kernel takes `z` or the packed rows.  Under a prior of Normal columns every bijector is the identity, so the
+    packed rows ARE z, bit for bit: gl_logprob_fwd_bwd and gl_loglike_fwd_bwd then run the same main kernel in the same mode on
+    derived rows that must be the same bits, and nothing may round differently -- loglike and chi2 are compared bitwise.
+    B = 45 samples of three components: 135 threads cross the 128-thread workgroup of gl_prep_kernel, and the last workgroup
+    of gl_prep_wave_kernel (four samples each) is partly empty."""
+    from gigalens_amd import prior as tfd
+    from gigalens_amd.model import PhysicalModel
+    from gigalens_amd.profiles.light.sersic import Sersic
+    from gigalens_amd.profiles.mass.epl import EPL
+    from gigalens_amd.profiles.mass.shear import Shear
+    from gigalens_amd.profiles.mass.sie import SIE
+    from gigalens_amd.simulator import SimulatorConfig
+    J, S, N = tfd.JointDistributionNamed, tfd.JointDistributionSequential, tfd.Normal
+    main = dict(theta_E=N(0.4, 0.02), e1=N(0.1, 0.02), e2=N(-0.05, 0.02), center_x=N(0, 0.02), center_y=N(0, 0.02))
+    if lens == "EPL":
+        main["gamma"] = N(2.0, 0.05)
+    prior = J(dict(lens_mass=S([J(main), J(dict(gamma1=N(0, 0.02), gamma2=N(0, 0.02)))]),
+                   source_light=S([J(dict(R_sersic=N(0.25, 0.01), n_sersic=N(2.0, 0.1), center_x=N(0, 0.03), center_y=N(0, 0.03),
+                                          Ie=N(50.0, 2.0)))])))
+    phys = PhysicalModel([EPL() if lens == "EPL" else SIE(), Shear()], [], [Sersic()])
+    B = 45
+    wl = gl.workloads.Workload("PREP", phys, prior, SimulatorConfig(delta_pix=0.07, num_pix=16), B)
+    obs, _, _ = gl.workloads.synthetic_observation(wl, gl.LensSimulator)
+    sim = gl.LensSimulator(phys, wl.sim_config, bs=B)
+    pm = gl.ForwardProbModel(prior, obs.cpu().numpy(), wl.background_rms, wl.exp_time, include_positions=False)
+    z = pm.bij.inverse(prior.sample(B, seed=5)).to("cuda").contiguous()
+    packed = sim.pack(pm.bij.forward(z)).contiguous()
+    assert sorted(packed[7].tolist()) == sorted(z[7].tolist())  # identity bijectors: the same numbers in the packed order
+    model = pm._bind_prior(sim)
+    args = (pm.observed_image, pm.error_map, pm._mask(sim), wl.background_rms, wl.exp_time, True)
+    _, ll_z, chi2_z, grad_z = model.logprob(z, *args)
+    ll_p, chi2_p, grad_p = model.loglike(packed, *args)
+    assert torch.isfinite(ll_z).all() and torch.isfinite(grad_z).all() and torch.isfinite(grad_p).all()
+    assert torch.equal(ll_z, ll_p) and torch.equal(chi2_z, chi2_p)
+
+
 @pytest.mark.parametrize("name,kw", [("C1", dict(num_pix=40, batch=9)), ("C2", dict(num_pix=50, batch=17)),
                                      ("C3", dict(num_pix=32, batch=5, interpolate=False)),
                                      ("C3", dict(num_pix=32, batch=5, interpolate=True, n_max=7)),

@@ -64,3 +64,21 @@ def test_no_unexpected_spills(metadata):
         if md["vgpr_spill_count"] and not any(re.search(p, name) for p, _ in ALLOWED_SPILLS):
             bad.append((name[:120], md["vgpr_spill_count"]))
     assert not bad, bad
+
+
+def test_every_kernel_lives_in_one_code_object():
+    """The library is one code object per translation unit and the units share headers: a kernel (a template instantiation above
+    all) that two units compile links without a word and ships twice.  Counted per code object -- the merged dictionary of the
+    `metadata` fixture keeps one entry per name and hides a duplicate."""
+    import collections
+
+    import isa_flops as isa
+    if not os.path.exists(isa.LIB):
+        pytest.skip("library not built")
+    homes = collections.defaultdict(list)
+    for i, co in enumerate(isa.code_object()):
+        for name in isa.kernel_metadata(co):
+            homes[name].append(i)
+    assert len(homes) > 300, len(homes)  # (the notes were read at all)
+    twice = {name[:120]: cos for name, cos in homes.items() if len(cos) != 1}
+    assert not twice, twice

@@ -75,7 +75,7 @@ def carve_rule(HW, B, wgs):
 
 
 def dispatch_rule(case):
-    """The ladder of the solve (csrc/gigalens_hip.hip) restated: (normal, Cholesky, eigen, partial sum?)"""
+    """The ladder of the solve (csrc/gl_api_lstsq.hip) restated: (normal, Cholesky, eigen, partial sum?)"""
     C = case.D + 1
     vec = case.HW % 4 == 0 and case.offset % 4 == 0
     tf = "true" if vec else "false"
