@@ -109,6 +109,9 @@ SYMBOLS = {
                                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_multiplane_logprob_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_float, c_uint32, c_void_p, c_size_t, c_void_p]),
+    "gl_model_set_position_targets": (c_int, [c_void_p, POINTER(c_float), c_int, c_int]),
+    "gl_multiplane_positions_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                c_void_p]),
     "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "gl_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
@@ -717,7 +720,8 @@ class Model:
         """Lens planes at redshifts of their own (gl_model_set_lens_planes): ``plane_of_lens`` one int per lens, ``lens_scales``
         ``[K, K]``, ``source_scales`` ``[K, n_src]`` (``gigalens_amd.cosmology.MultiPlane``).  From here on the model is served by
         ``multiplane_maps`` / ``multiplane_simulate`` / ``multiplane_loglike`` and the gradients ``multiplane_simulate_bwd`` /
-        ``multiplane_loglike_grad`` / ``multiplane_logprob``; the single-plane calls raise ``UnsupportedLensError``."""
+        ``multiplane_loglike_grad`` / ``multiplane_logprob`` / ``multiplane_positions``; the single-plane calls raise
+        ``UnsupportedLensError``."""
         pl = np.ascontiguousarray(plane_of_lens, dtype=np.int32).reshape(-1)
         C = np.ascontiguousarray(lens_scales, dtype=np.float32)
         S = np.ascontiguousarray(source_scales, dtype=np.float32)
@@ -773,10 +777,26 @@ class Model:
         """gl_multiplane_loglike_fwd_bwd: ``(loglike, chi2, d loglike / d params)``; the first two are ``multiplane_loglike``'s bits."""
         return self._loglike(lib().gl_multiplane_loglike_fwd_bwd, _check_potential, params, obs, err, mask, bg_rms, exp_time, True)
 
-    def multiplane_logprob(self, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor=1.0):
-        """gl_multiplane_logprob_fwd_bwd (the pixel term): ``(logprob, loglike, red_chi2, d logprob / d z or None)``."""
+    def multiplane_logprob(self, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor=1.0, terms=1):
+        """gl_multiplane_logprob_fwd_bwd: ``(logprob, loglike, red_chi2, d logprob / d z or None)`` of ``terms`` (1 pixels, 2 image
+        positions -- after ``set_positions`` and ``set_position_targets`` --, 3 both)."""
         return self._logprob(lib().gl_multiplane_logprob_fwd_bwd, _check_potential, z, obs, err, mask, bg_rms, exp_time, want_grad,
-                             chi2_divisor, 1)
+                             chi2_divisor, terms)
+
+    def set_position_targets(self, targets):
+        """The couplings ``[F, K]`` of every image family's plane (gl_model_set_position_targets; after ``set_positions`` and
+        ``set_lens_planes``, either of which resets them): row f = ``MultiPlane.target_scales(z_f)``."""
+        t = np.ascontiguousarray(targets, dtype=np.float32)
+        if t.ndim != 2:
+            raise ValueError(f"targets must be [n_families, n_planes], got {t.shape}")
+        with torch.cuda.device(self.device):
+            _check_potential(lib().gl_model_set_position_targets(self._h, t.ctypes.data_as(POINTER(c_float)), int(t.shape[0]),
+                                                                 int(t.shape[1])))
+
+    def multiplane_positions(self, params, want_grad):
+        """gl_multiplane_positions_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the image-position likelihood with
+        every family traced through the lens planes in front of it."""
+        return self._positions(lib().gl_multiplane_positions_fwd_bwd, _check_potential, params, want_grad)
 
     def set_position_scales(self, scales):
         """One deflection scale per image family (gl_model_set_position_scales; after ``set_positions``, which resets them)."""
@@ -938,14 +958,16 @@ class Model:
 
     def positions(self, params, want_grad):
         self._single_plane("positions")
+        return self._positions(lib().gl_positions_fwd_bwd, _check, params, want_grad)
+
+    def _positions(self, fn, check, params, want_grad):
         params = self._params(params)
         B = params.shape[0]
         ws = self._workspace(B)
         ll = torch.empty(B, dtype=torch.float32, device=params.device)
         chi2 = torch.empty_like(ll)
         grad = torch.empty_like(params) if want_grad else None
-        _check(lib().gl_positions_fwd_bwd(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(ws),
-                                          ws.numel(), _stream()))
+        check(fn(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(ws), ws.numel(), _stream()))
         return ll, chi2, grad
 
     def logprob(self, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor=1.0, terms=1):

@@ -552,13 +552,14 @@ int logprob_grad(const gl_model* m, const float* z, const float* obs, const floa
                  float exp_time, int B, float* logprob, float* loglike, float* chi2, float* grad_z, float chi2_divisor, unsigned terms,
                  const LaunchPlan& plan, const Workspace& w, hipStream_t stream) {
   const bool planes = m->mp_K >= 2;
-  if (planes && terms != GL_TERM_PIXELS)
-    return fail(GL_EINVAL, "terms = %u: a model with lens planes has the pixel term alone (no multi-plane position likelihood)", terms);
   const bool pix = terms & GL_TERM_PIXELS, pos = terms & GL_TERM_POSITIONS;
   if (!pix && !pos) return fail(GL_EINVAL, "terms selects no likelihood term");
   if (pix && !(chi2_divisor > 0.f)) return fail(GL_EINVAL, "chi2_divisor must be positive");
   if (!m->d_zcols) return fail(GL_EINVAL, "gl_model_set_prior has not been called on this model");
   if (pos && !m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (pos && planes && !m->pos_targets)
+    return fail(GL_EINVAL, "the image positions of a model with lens planes need the couplings of their families: "
+                           "gl_model_set_position_targets has not been called");
   if ((pix && !obs) || !logprob || !loglike || !chi2)
     return fail(GL_EINVAL, "obs / logprob / loglike / %s is null", planes ? "red_chi2" : "chi2");
   int rc;
@@ -1353,6 +1354,8 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
   m->pos_fam_off = off;
   m->pos_scaled = false;  // new tables: every family back on the reference plane
   m->d_pos_scale.reset();
+  m->pos_targets = false;  // ... and, behind lens planes, without couplings until gl_model_set_position_targets
+  m->d_pos_target.reset();
   return GL_OK;
 }
 
@@ -1377,6 +1380,9 @@ int gl_model_set_source_scales(gl_model* m, const float* scales, int n_src) {
 int gl_model_set_position_scales(gl_model* m, const float* scales, int n_families) {
   if (!m) return fail(GL_EINVAL, "model is null");
   if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (m->mp_K >= 2)
+    return fail(GL_EINVAL, "the model has lens planes (gl_model_set_lens_planes): one scale names no plane, the families take their "
+                           "couplings from gl_model_set_position_targets");
   bool any;
   if (int rc = check_scales(scales, n_families, m->pos_F, "image famil(ies)", &any)) return rc;
   if (any) {

@@ -13,6 +13,7 @@
 #include "gl_potential.hip.h"
 #include "gl_multiplane.hip.h"
 #include "gl_multiplane_bwd.hip.h"
+#include "gl_multiplane_pos.hip.h"
 
 using namespace glk;
 
@@ -74,6 +75,15 @@ CritLayout crit_layout(int B, int n_cells, int max_segments) {
   return l;
 }
 constexpr int CRIT_MAX_SEGMENTS = 1 << 20;
+
+// what the kernels of a model with lens planes read of them (gl_multiplane.hip.h MpArgs)
+MpArgs mp_args(const gl_model* m) {
+  MpArgs a{};
+  a.order = m->d_mp_lens;
+  a.plane = m->d_mp_lens + m->n_lens;
+  a.scale = m->d_mp_scale;
+  return a;
+}
 }  // namespace
 
 namespace glk {
@@ -90,7 +100,8 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
   a.ex = m->d_pos + 2 * m->pos_J;
   a.ey = m->d_pos + 3 * m->pos_J;
   a.fam_off = m->d_fam;
-  a.fam_scale = m->pos_scaled ? m->d_pos_scale.get() : nullptr;
+  const bool planes = m->mp_K >= 2;  // families at redshifts of their own behind lens planes (gl_multiplane_pos.hip.h)
+  a.fam_scale = !planes && m->pos_scaled ? m->d_pos_scale.get() : nullptr;
   a.w_pos = w.pos_w;
   a.w_adj = w.pos_adj;
   a.w_g = w.pos_g;
@@ -99,6 +110,20 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
   a.chi2 = w.pos_chi2;
   a.grad = want_grad ? w.pos_grad : nullptr;
   auto blocks = [](long long n) { return dim3((unsigned)((n + 63) / 64)); };
+  if (planes) {  // P1 and P3 through the plane recursion, P2 and P4 as on one plane
+    if (!m->pos_targets)
+      return fail(GL_EINVAL, "the image positions of a model with lens planes need the couplings of their families: "
+                             "gl_model_set_position_targets has not been called");
+    const float* tg = m->d_pos_target;
+    hipLaunchKernelGGL(gl_mp_pos_p1_kernel, blocks((long long)B * a.J), dim3(MP_POS_WG), 0, stream, a, mp_args(m), tg);
+    hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
+    if (want_grad && m->lens_params)
+      hipLaunchKernelGGL(gl_mp_pos_p3_kernel, blocks((long long)B * a.J * m->lens_params), dim3(MP_POS_WG), 0, stream, a, mp_args(m),
+                         tg, m->lens_params);
+    hipLaunchKernelGGL(gl_pos_p4_kernel, blocks((long long)B * (a.P + 1)), dim3(64), 0, stream, a, m->lens_params);
+    GL_HIP(hipGetLastError());
+    return GL_OK;
+  }
   if (m->has_user) {
     int lens_params = m->lens_params;
     void* args1[] = {&a};
@@ -133,6 +158,24 @@ int gl_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* l
   Workspace w;
   int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
   if (rc) return rc;
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream))) return rc;
+  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  if (grad_params_or_null)
+    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+
+int gl_multiplane_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
+                                    float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
+  if (rc) return rc;
+  if ((rc = check_planes_set(m))) return rc;
   if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
   if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -411,16 +454,6 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
 }  // extern "C"
 
 // ---- lens planes at redshifts of their own (gl_multiplane.hip.h, gl_multiplane_bwd.hip.h) ------------------------------
-namespace {
-MpArgs mp_args(const gl_model* m) {
-  MpArgs a{};
-  a.order = m->d_mp_lens;
-  a.plane = m->d_mp_lens + m->n_lens;
-  a.scale = m->d_mp_scale;
-  return a;
-}
-}  // namespace
-
 namespace glk {
 
 int mp_render(const gl_model* m, const float* params, int B, unsigned parts, float* img, const Workspace& w, hipStream_t stream) {
@@ -531,6 +564,29 @@ int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, 
   GL_HIP(m->d_mp_lens.upload(lens.data(), lens.size()));
   GL_HIP(m->d_mp_scale.upload(scale.data(), scale.size()));
   m->mp_K = K;
+  m->pos_targets = false;  // new planes: the couplings of the image families are given again
+  m->d_pos_target.reset();
+  return GL_OK;
+}
+
+int gl_model_set_position_targets(gl_model* m, const float* targets, int n_families, int n_planes) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  if (int rc = check_planes_set(m)) return rc;
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!targets) return fail(GL_EINVAL, "targets is null");
+  if (n_families != m->pos_F || n_planes != m->mp_K)
+    return fail(GL_EINVAL, "target couplings [%d][%d] for %d image famil(ies) and %d lens planes", n_families, n_planes, m->pos_F, m->mp_K);
+  std::vector<float> per_image((size_t)m->pos_J * MP_MAXK, 0.f);
+  for (int f = 0; f < n_families; ++f) {
+    const float* T = targets + (size_t)f * n_planes;
+    for (int i = 0; i < n_planes; ++i)
+      if (!(std::isfinite(T[i]) && T[i] >= 0.f) || (i > 0 && T[i] != 0.f && T[i - 1] == 0.f))
+        return fail(GL_EINVAL, "targets[%d][%d] = %g: finite and >= 0, 0 from the first plane at or behind the family on", f, i, T[i]);
+    if (T[0] == 0.f) return fail(GL_EINVAL, "image family %d: every coupling is zero (the family lies behind no lens plane)", f);
+    for (int j = m->pos_fam_off[f]; j < m->pos_fam_off[f + 1]; ++j) std::copy(T, T + n_planes, per_image.begin() + (size_t)j * MP_MAXK);
+  }
+  GL_HIP(m->d_pos_target.upload(per_image.data(), per_image.size()));
+  m->pos_targets = true;
   return GL_OK;
 }
 

@@ -141,9 +141,28 @@ template <class R> GL_HD void tnfw_g_impl(R X, R tau, R& g, R& gX, R& gT) {
 // The bracket cancels from O(ln X) down to O(X^2 ln X) as X -> 0: in fp32 nothing is left below X ~ 0.1 (the
 // reference's fp32 graph has the same cancellation).  Those pixels are evaluated in fp64 -- full rate on CDNA4 and
 // only the core of the halo -- which keeps the result at fp32 rounding of the exact value everywhere.
+// A number type may ask for the fp64 core as a call of its own (TnfwCoreOutlined<R>::value, false unless specialised) instead of
+// inlined code.  Arguments and results travel by value in registers -- R, widened and narrowed inside -- so the call needs no
+// stack.  For a kernel that evaluates lenses in a loop: inlined there, the fp64 constants of the core are hoisted out of the loop
+// and held across every other profile (gl_multiplane_pos.hip.h).
+template <class R> struct TnfwCoreOutlined { static constexpr bool value = false; };
+template <class R> struct TnfwG3 { R g, gX, gT; };
+template <class R> GL_HD __attribute__((noinline)) TnfwG3<R> tnfw_g_wide_call(R X, R tau) {
+  using W = typename Wide<R>::type;
+  W gw, gxw, gtw;
+  tnfw_g_impl<W>(Wide<R>::up(X), Wide<R>::up(tau), gw, gxw, gtw);
+  return TnfwG3<R>{Wide<R>::down(gw), Wide<R>::down(gxw), Wide<R>::down(gtw)};
+}
 template <class R> GL_HD void tnfw_g(R X, R tau, R& g, R& gX, R& gT) {
   using W = typename Wide<R>::type;
   if (sizeof(W) != sizeof(R) && X < (R)0.15) {
+    if constexpr (TnfwCoreOutlined<R>::value) {
+      const TnfwG3<R> r = tnfw_g_wide_call<R>(X, tau);
+      g = r.g;
+      gX = r.gX;
+      gT = r.gT;
+      return;
+    }
     W gw, gxw, gtw;
     tnfw_g_impl<W>(Wide<R>::up(X), Wide<R>::up(tau), gw, gxw, gtw);
     g = Wide<R>::down(gw);

@@ -166,6 +166,9 @@ struct gl_model {
   int mp_K = 0;
   glk::DevBuf<int> d_mp_lens;     // [2][n_lens]: the lenses sorted by plane, the plane of every lens
   glk::DevBuf<float> d_mp_scale;  // [4][4] plane couplings, then [4][n_src] source couplings (zero-padded rows)
+  // image families behind lens planes (gl_model_set_position_targets): the couplings T_f of every image's family
+  bool pos_targets = false;
+  glk::DevBuf<float> d_pos_target;  // [J][4], zero-padded rows; allocated only while pos_targets
   bool has_epl = false;
   int epl_comp = -1;     // the model's only EPL component, or -1 (none / several)
   int fam = 0;  // family level of the interpreter variant (gl_main_kernel FAM): 1 dPIE family / catalogues / series, 2 gl_extra.h

@@ -110,8 +110,9 @@ struct MpLdsSums {
   }
 };
 
-// the plane recursion for sample b of a.params from (tx, ty): on return `sums` holds every a_i (zero for the planes the model lacks)
-template <class R, class Sums>
+// the plane recursion for sample b of a.params from (tx, ty): on return `sums` holds every a_i (zero for the planes the model lacks).
+// CATS: lens_point's (no model with planes holds a catalogue; false leaves the catalogue loop out of the kernel)
+template <class R, bool CATS = true, class Sums>
 __device__ __forceinline__ void mp_trace(const PosArgs& a, const MpArgs& mp, int b, const R& tx, const R& ty, Sums& sums) {
   for (int t = 0; t < a.n_lens; ++t) {
     const int l = mp.order[t], pl = mp.plane[l];
@@ -126,7 +127,7 @@ __device__ __forceinline__ void mp_trace(const PosArgs& a, const MpArgs& mp, int
       p[k] = R(pf[k]);
     }
     R ax, ay;
-    lens_point<R>(a, cd, p, x, y, ax, ay);
+    lens_point<R, CATS>(a, cd, p, x, y, ax, ay);
     if constexpr (!std::is_same<R, float>::value)
       mp_add_excess(ax, ay, x, y, lens_kappa_excess<float>(a, cd, pf, mp_value(x), mp_value(y)));
     sums.add(pl, ax, ay);

@@ -53,8 +53,10 @@ constexpr int POS_MAXP = 16;
 constexpr int POS_MAXP = 7;
 #endif
 
-// deflection of one lens at (x, y) with raw parameters p, generic in the real type (catalogues are summed)
-template <class R> __device__ void lens_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y, R& ax, R& ay) {
+// deflection of one lens at (x, y) with raw parameters p, generic in the real type (catalogues are summed).  CATS = false: for
+// models that hold no catalogue (lens planes refuse them) -- the member loop indexes p at run time, which alone keeps the
+// parameter array of a caller in private memory
+template <class R, bool CATS = true> __device__ void lens_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y, R& ax, R& ay) {
   using namespace glp;
   switch (cd.kind) {
 #ifdef GL_HAVE_USER_POINT
@@ -69,7 +71,9 @@ template <class R> __device__ void lens_point(const PosArgs& a, const CompDesc& 
     case K_DPIEP: { R d[DPX_ND]; dpie_prep<R>(cd.kind, p, d); dpie_fwd<R>(cd.kind, d, x, y, ax, ay); } break;
     case K_NFW_ELLIPSE: { R d[NFE_ND]; nfw_ell_prep<R>(p, d); nfw_ell_fwd<R>(d, x, y, ax, ay); } break;
     case K_TNFW: { R d[TNF_ND]; tnfw_prep<R>(p, d); tnfw_fwd<R>(d, x, y, ax, ay); } break;
-    case K_SCALED: {
+    case K_SCALED: if constexpr (!CATS) {
+      ax = ay = R(__builtin_nanf(""));  // (not reached)
+    } else {
       const CatDev cat = a.cats[cd.iparam];
       const ScaledDesc sd{cat.base_kind, cat.n_gal, {cat.col[0], cat.col[1], cat.col[2]}};
       ax = R(0.f);

@@ -87,12 +87,14 @@ class PhysicalModel(PhysicalModelBase):
         With one plane it is rewritten here into ``source_light_scales`` (the existing kernels, the existing bits).  With two to four
         planes ``LensSimulator`` traces every ray through them in redshift order (``self.multiplane``): lens maps, renders with
         ``LensSimulator.simulate_vjp``, ``ForwardProbModel.stats_pixels`` and, on a ``ForwardProbModel`` without image positions, the
-        fused ``log_prob`` / ``log_prob_and_grad`` / ``term_log_prob_and_grad(..., "pixels")`` that MAP, SVI and HMC run on.  The
-        image-position likelihood, ``BackwardProbModel`` / ``lstsq_simulate``, the solver, curves, potentials and
-        ``reconstruct_source`` raise ``_native.UnsupportedLensError``."""
+        fused ``log_prob`` / ``log_prob_and_grad`` / ``term_log_prob_and_grad`` that MAP, SVI, HMC and SMC run on -- with the
+        image-position likelihood when the ``ForwardProbModel`` places its families by ``centroids_redshifts``.
+        ``BackwardProbModel`` / ``lstsq_simulate``, the solver, curves, potentials and ``reconstruct_source`` raise
+        ``_native.UnsupportedLensError``."""
         super().__init__(lenses, lens_light, source_light, lenses_constants, lens_light_constants,
                          source_light_constants)
         self.multiplane = None
+        self._multiplane_single = None  # a one-plane MultiPlane, kept for ForwardProbModel(centroids_redshifts=...)
         if multiplane is not None:
             if source_light_scales is not None:
                 raise ValueError("multiplane and source_light_scales are two ways to place the sources: give one")
@@ -101,6 +103,7 @@ class PhysicalModel(PhysicalModelBase):
                                  f"has {len(lenses)} and {len(source_light)}")
             if multiplane.K == 1:
                 source_light_scales = multiplane.source_scales[0]
+                self._multiplane_single = multiplane
             else:
                 self.multiplane = multiplane
         self.source_light_scales = _native.deflection_scales(source_light_scales, len(source_light), "source_light_scales")
@@ -164,12 +167,12 @@ class _LogProbFn(torch.autograd.Function):
 
 
 class _MpLogProbFn(torch.autograd.Function):
-    """autograd glue around gl_multiplane_logprob_fwd_bwd (lens planes at redshifts of their own: the pixel term)."""
+    """autograd glue around gl_multiplane_logprob_fwd_bwd (lens planes at redshifts of their own)."""
 
     @staticmethod
-    def forward(ctx, z, model, obs, err, mask, bg_rms, exp_time, n_eff):
+    def forward(ctx, z, model, obs, err, mask, bg_rms, exp_time, n_eff, terms):
         want = z.requires_grad
-        lp, ll, chi2, grad = model.multiplane_logprob(z.detach(), obs, err, mask, bg_rms, exp_time, want, n_eff)
+        lp, ll, chi2, grad = model.multiplane_logprob(z.detach(), obs, err, mask, bg_rms, exp_time, want, n_eff, terms)
         if want:
             ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(ll, chi2)
@@ -178,7 +181,7 @@ class _MpLogProbFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_lp, g_ll, g_chi2):
         (grad,) = ctx.saved_tensors
-        return g_lp[:, None] * grad, None, None, None, None, None, None, None
+        return g_lp[:, None] * grad, None, None, None, None, None, None, None, None
 
 
 class _PositionsFn(torch.autograd.Function):
@@ -188,6 +191,24 @@ class _PositionsFn(torch.autograd.Function):
     def forward(ctx, packed, model):
         want = packed.requires_grad
         ll, chi2, grad = model.positions(packed.detach(), want)
+        if want:
+            ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(chi2)
+        return ll, chi2
+
+    @staticmethod
+    def backward(ctx, g_ll, g_chi2):
+        (grad,) = ctx.saved_tensors
+        return g_ll[:, None] * grad, None
+
+
+class _MpPositionsFn(torch.autograd.Function):
+    """autograd glue around gl_multiplane_positions_fwd_bwd (image-position likelihood behind lens planes)."""
+
+    @staticmethod
+    def forward(ctx, packed, model):
+        want = packed.requires_grad
+        ll, chi2, grad = model.multiplane_positions(packed.detach(), want)
         if want:
             ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(chi2)
@@ -235,10 +256,18 @@ class ForwardProbModel(ProbabilisticModel):
 
     def __init__(self, prior, observed_image=None, background_rms=None, exp_time=None, error_map=None,
                  centroids_x=None, centroids_y=None, centroids_errors_x=None, centroids_errors_y=None,
-                 include_pixels=True, include_positions=True, centroids_scales=None):
+                 include_pixels=True, include_positions=True, centroids_scales=None, centroids_redshifts=None):
         """``centroids_scales`` (beyond the reference): one deflection scale per image family of ``centroids_x`` -- a family at its
         own redshift is traced with ``beta = theta - c_f alpha`` and ``A = I - c_f H`` in the position likelihood, the predicted
-        positions and the image-plane rms.  Default: all 1."""
+        positions and the image-plane rms.  Default: all 1.
+
+        ``centroids_redshifts`` (beyond the reference; instead of ``centroids_scales``): one redshift per image family, for a
+        ``PhysicalModel`` built with a ``cosmology.MultiPlane``.  When the model is bound to a simulator the family's couplings are
+        ``MultiPlane.target_scales(z_f)``: on two to four lens planes every observed image is traced back through the planes in
+        front of its family (``beta = theta - sum_i T_f,i a_i``, ``A = d beta / d theta``) in ``stats_positions`` and the fused
+        ``log_prob`` / ``log_prob_and_grad`` / ``term_log_prob_and_grad``; on one plane they are the ``centroids_scales``.
+        ``ValueError``: a redshift that is not finite, given together with ``centroids_scales`` or without centroids; at bind time, a
+        family at or in front of the first plane, or a model without a ``MultiPlane`` (use ``centroids_scales``)."""
         super().__init__(prior)
         self.include_pixels = include_pixels
         self.include_positions = include_positions
@@ -271,6 +300,18 @@ class ForwardProbModel(ProbabilisticModel):
         n_fam = len(self.centroids_x) if self.centroids_x is not None else 0
         self.centroids_scales = _native.deflection_scales(centroids_scales, n_fam, "centroids_scales")
         self._centroids_scales_given = centroids_scales is not None
+        self.centroids_redshifts = None
+        if centroids_redshifts is not None:
+            if centroids_scales is not None:
+                raise ValueError("centroids_redshifts and centroids_scales are two ways to place the image families: give one")
+            if self.centroids_x is None:
+                raise ValueError("centroids_redshifts needs centroids_x/centroids_y (include_positions=True)")
+            zf = np.atleast_1d(np.asarray(centroids_redshifts, dtype=np.float64))
+            if zf.shape != (n_fam,):
+                raise ValueError(f"centroids_redshifts: one redshift per image family ({n_fam}), got shape {zf.shape}")
+            if not np.all(np.isfinite(zf)):
+                raise ValueError(f"centroids_redshifts: every redshift must be finite, got {zf.tolist()}")
+            self.centroids_redshifts = zf
         self._flat = prior.flat(self.device)
         example = prior.sample(seed=0)
         self.pack_bij = _PackBijector(example)
@@ -330,30 +371,64 @@ class ForwardProbModel(ProbabilisticModel):
     def _fused_ok(self, simulator):
         return self.include_pixels or self.include_positions
 
+    def position_targets(self, multiplane):
+        """``[F, K]`` couplings of the image families on the planes of ``multiplane``: row f = ``multiplane.target_scales(z_f)``, 0 for
+        the planes at or behind family f.  ``ValueError`` for a family at or in front of the first plane."""
+        if self.centroids_redshifts is None:
+            raise ValueError("position_targets needs a model built with centroids_redshifts")
+        return np.stack([multiplane.target_scales(z) for z in self.centroids_redshifts], axis=0)
+
+    def _family_scales(self, simulator):
+        """``(scales [F], given)``: the deflection scale of every image family on a single-plane simulator -- ``centroids_scales``, or
+        ``centroids_redshifts`` through the one-plane ``MultiPlane`` the physical model was built with."""
+        if self.centroids_redshifts is None:
+            return self.centroids_scales, self._centroids_scales_given
+        if getattr(simulator, "_mp", None) is not None:
+            raise _native.UnsupportedLensError(f"a model with {simulator._mp.K} lens planes: one deflection scale per family exists on a "
+                                               "single plane alone (the solver, the predicted positions and their users)")
+        mp = getattr(simulator.phys_model, "_multiplane_single", None)
+        if mp is None:
+            raise ValueError("centroids_redshifts needs a PhysicalModel built with a cosmology.MultiPlane (its planes turn the "
+                             "redshifts into couplings); on a model without one give centroids_scales")
+        return _native.deflection_scales(self.position_targets(mp)[:, 0], len(self.centroids_x), "centroids_redshifts"), True
+
     def _bind_positions(self, simulator):
         model = simulator._model
         if getattr(model, "_positions_owner", None) is not self:
+            mp = getattr(simulator, "_mp", None)
+            # (validated before anything is handed over: a refusal leaves the native model as it was)
+            targets = self.position_targets(mp) if mp is not None and self.centroids_redshifts is not None else None
+            scales, given = self._family_scales(simulator) if mp is None else (None, False)
             model.set_positions(self.centroids_x, self.centroids_y, self.centroids_errors_x, self.centroids_errors_y)
-            if self._centroids_scales_given:
-                model.set_position_scales(self.centroids_scales)
+            if targets is not None:
+                model.set_position_targets(targets)
+            elif given:
+                model.set_position_scales(scales)
             model._positions_owner = self
         return model
 
     def _on_planes(self, simulator):
-        """True for a simulator with several lens planes, whose fused log-probability is the pixel term of the multi-plane entries;
-        a model that carries image positions is refused there (no multi-plane position likelihood exists)."""
+        """True for a simulator with several lens planes, whose fused log-probability comes from the multi-plane entries.  A model
+        that carries image positions is served there when its families have redshifts (``centroids_redshifts``); without them it is
+        refused -- a family names no plane."""
         mp = getattr(simulator, "_mp", None)
         if mp is None:
             return False
-        if self.include_positions or not self.include_pixels:
-            raise _native.UnsupportedLensError(f"a model with {mp.K} lens planes has the pixel likelihood alone: the image-position "
-                                               "likelihood is not served on lens planes (include_positions=False)")
+        if not (self.include_pixels or self.include_positions):
+            raise _native.UnsupportedLensError(f"a model with {mp.K} lens planes and no likelihood term")
+        if self.include_positions and self.centroids_redshifts is None:
+            raise _native.UnsupportedLensError(f"a model with {mp.K} lens planes traces an image family through the planes in front of "
+                                               "it: its image positions need centroids_redshifts (or include_positions=False); a "
+                                               "family without a redshift names no plane")
         return True
 
-    def _mp_logprob(self, simulator, z, want_grad):
+    def _mp_logprob(self, simulator, z, want_grad, terms):
         model = self._bind_prior(simulator)
+        if terms & 2:
+            self._bind_positions(simulator)
         return model.multiplane_logprob(z.detach(), self.observed_image, self.error_map, self._mask(simulator),
-                                        self.background_rms or 0.0, self.exp_time or 1.0, want_grad, self._n_eff(simulator))
+                                        self.background_rms or 0.0, self.exp_time or 1.0, want_grad,
+                                        self._n_eff(simulator) if terms & 1 else 1.0, terms)
 
     def _terms(self):
         return (1 if self.include_pixels else 0) | (2 if self.include_positions else 0)
@@ -361,7 +436,8 @@ class ForwardProbModel(ProbabilisticModel):
     def stats_positions(self, simulator, params):
         """tf/model.py:103-124: ``(log_like, red_chi2)`` of the image-position term."""
         packed = params if torch.is_tensor(params) else simulator.pack(params)
-        ll, chi2 = _PositionsFn.apply(packed, self._bind_positions(simulator))
+        fn = _MpPositionsFn if self.centroids_x is not None and self._on_planes(simulator) else _PositionsFn
+        ll, chi2 = fn.apply(packed, self._bind_positions(simulator))
         return ll, chi2 / self.n_position
 
     def predicted_positions(self, simulator, params, **solver_kwargs):
@@ -373,15 +449,16 @@ class ForwardProbModel(ProbabilisticModel):
             raise ValueError("predicted_positions needs a model built with centroids_x/centroids_y")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         sx, sy = self._family_sources(simulator, packed)
-        if self._centroids_scales_given:  # every family on its own plane
-            solver_kwargs = dict(solver_kwargs, deflection_scale=self.centroids_scales)
+        scales, given = self._family_scales(simulator)
+        if given:  # every family on its own plane
+            solver_kwargs = dict(solver_kwargs, deflection_scale=scales)
         x, y, mu, n = simulator.image_positions(packed, sx, sy, **solver_kwargs)
         return [(x[:, f], y[:, f], mu[:, f], n[:, f]) for f in range(len(self.centroids_x))]
 
     def _family_sources(self, simulator, packed):
         """Source of every family: the barycentre of its back-traced observed images (on the family's own plane), ``[B, F]`` x and y."""
         sx, sy = [], []
-        for cx, cy, c in zip(self.centroids_x, self.centroids_y, self.centroids_scales):
+        for cx, cy, c in zip(self.centroids_x, self.centroids_y, self._family_scales(simulator)[0]):
             maps = simulator._model.lens_maps(packed, cx.reshape(-1, 1), cy.reshape(-1, 1))  # (6, J_f, B)
             bx, by = maps[0], maps[1]
             if c != 1.0:  # beta = theta + c (beta_1 - theta)
@@ -399,7 +476,7 @@ class ForwardProbModel(ProbabilisticModel):
         scalar or ``[B]``), in days (``LensSimulator.time_delays``, which ``solver_kwargs`` go to).  Forward only."""
         if self.centroids_x is None:
             raise ValueError("predicted_time_delays needs a model built with centroids_x/centroids_y")
-        if np.any(self.centroids_scales != 1.0):
+        if np.any(self._family_scales(simulator)[0] != 1.0):
             raise NotImplementedError("predicted_time_delays: the Fermat potential of a scaled source plane (centroids_scales != 1) "
                                       "is not served; time delays stay single-plane")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
@@ -461,9 +538,12 @@ class ForwardProbModel(ProbabilisticModel):
         """tf/model.py:126-167: ``z`` is ``(bs, d)`` unconstrained; returns ``(log_prob, red_chi2)``."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
         if self._on_planes(simulator):
-            lp, _, red_chi2 = _MpLogProbFn.apply(z, self._bind_prior(simulator), self.observed_image, self.error_map,
+            model = self._bind_prior(simulator)
+            if self.include_positions:
+                self._bind_positions(simulator)
+            lp, _, red_chi2 = _MpLogProbFn.apply(z, model, self.observed_image, self.error_map,
                                                  self._mask(simulator), self.background_rms or 0.0, self.exp_time or 1.0,
-                                                 self._n_eff(simulator))
+                                                 self._n_eff(simulator) if self.include_pixels else 1.0, self._terms())
             return lp, red_chi2
         if self._fused_ok(simulator):
             # bijector -> prep -> fused render/chi2/VJP -> finalize + prior, all inside the native library
@@ -485,9 +565,10 @@ class ForwardProbModel(ProbabilisticModel):
         (tf/inference.py:213-238,292-303)."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
         if self._on_planes(simulator):
-            if term != "pixels":
-                raise _native.UnsupportedLensError("the image-position likelihood is not served on lens planes")
-            lp, ll, _, grad = self._mp_logprob(simulator, z, True)
+            if term == "positions" and not self.include_positions:
+                raise _native.UnsupportedLensError("the model carries no image positions: on lens planes the position term needs "
+                                                   "centroids_x/centroids_y with centroids_redshifts")
+            lp, ll, _, grad = self._mp_logprob(simulator, z, True, {"pixels": 1, "positions": 2}[term])
             return lp, ll, grad
         model = self._bind_prior(simulator)
         bit = {"pixels": 1, "positions": 2}[term]
@@ -507,13 +588,15 @@ class ForwardProbModel(ProbabilisticModel):
         (simulator, shape of ``z``) in a HIP graph and replayed.  The contract is that of torch's CUDA graphs: the three returned
         tensors are the graph's STATIC outputs, overwritten by the next call with ``graph=True`` on the same simulator; ``z`` is
         copied into the graph's static input unless it already IS that tensor (``graph_input(simulator, z)`` hands it out, for loops
-        that update ``z`` in place)."""
+        that update ``z`` in place).  The graph holds the device buffers the simulator's native model had when it was captured: its
+        image positions and, on lens planes, their families' couplings are uploaded again whenever ANOTHER ``ForwardProbModel`` with
+        positions is bound to the same simulator, so keep one such model per simulator while its graph is in use."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
         on_planes = self._on_planes(simulator)
         if graph and z.is_cuda and self._fused_ok(simulator):
             return self._log_prob_and_grad_graph(simulator, z)
         if on_planes:
-            lp, _, red, grad = self._mp_logprob(simulator, z, True)
+            lp, _, red, grad = self._mp_logprob(simulator, z, True, self._terms())
             return lp, red, grad
         if self._fused_ok(simulator):
             model = self._bind_prior(simulator)

@@ -352,9 +352,22 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
  *   gl_multiplane_loglike_fwd_bwd  gl_multiplane_loglike plus, when grad_params_or_null != NULL, d loglike / d params [B][P]:
  *       render -> PSF + pooling -> image statistics with cotangent -> their transposes -> the VJP kernel -> finalize.  loglike and
  *       chi2 are the bits of gl_multiplane_loglike.
- *   gl_multiplane_logprob_fwd_bwd  the twin of gl_logprob_fwd_bwd for the pixel term: z [B][d] in (gl_model_set_prior), logprob,
- *       loglike, red_chi2 and, when grad_z_or_null != NULL, d logprob / d z out; bijector and prior fused into the front end and
- *       finalize.  GL_EINVAL if terms asks for GL_TERM_POSITIONS: no multi-plane position likelihood exists.
+ *   gl_multiplane_logprob_fwd_bwd  the twin of gl_logprob_fwd_bwd: z [B][d] in (gl_model_set_prior), logprob, loglike, red_chi2
+ *       and, when grad_z_or_null != NULL, d logprob / d z out; bijector and prior fused into the front end and finalize.  terms as
+ *       there: GL_TERM_PIXELS, GL_TERM_POSITIONS or both, red_chi2 = (red_pix + red_pos) / n_terms.  GL_EINVAL if terms asks for
+ *       GL_TERM_POSITIONS on a model without image positions (gl_model_set_positions) or without the couplings of their families
+ *       (gl_model_set_position_targets).
+ *   gl_model_set_position_targets  image families at redshifts of their own behind the planes: targets [n_families][n_planes]
+ *       (HOST, copied), row f = the couplings T_f of family f (> 0 on plane 0, 0 from the first plane at or behind the family on).
+ *       After gl_model_set_positions and gl_model_set_lens_planes, either of which resets the couplings.  GL_EINVAL: counts that do
+ *       not match the model, a coupling that is not finite or negative or breaks the rule above, a family whose couplings are all
+ *       zero.  gl_model_set_position_scales answers GL_EINVAL on a model with planes: one scale names no plane.
+ *   gl_multiplane_positions_fwd_bwd  the twin of gl_positions_fwd_bwd (which keeps refusing planes): every observed image of
+ *       family f is traced back with beta = theta - sum_i T_f,i a_i and A = d beta / d theta through the plane recursion
+ *       (csrc/gl_multiplane_pos.hip.h), a dPIS lens adding its convergence excess times d theta_j / d theta on its own plane as in
+ *       gl_multiplane_maps; the likelihood is that of gl_positions_fwd_bwd.  loglike, chi2 [B] and, when grad_params_or_null != NULL,
+ *       d loglike / d params [B][P] (exactly zero in the columns of a lens at or behind every family that could meet it).  GL_EINVAL
+ *       before gl_model_set_positions or gl_model_set_position_targets.
  * All enqueue on the caller's stream, without allocation or host synchronisation (a HIP graph may capture them); all but the
  * maps take a workspace of gl_workspace_bytes(m, B).  Deterministic: two calls give identical bits.  GL_EINVAL before
  * gl_model_set_lens_planes. */
@@ -376,6 +389,9 @@ int gl_multiplane_logprob_fwd_bwd(const gl_model* m, const float* z, const float
                                   const float* mask_or_null, float bg_rms, float exp_time, int B, float* logprob, float* loglike,
                                   float* red_chi2, float* grad_z_or_null, float chi2_divisor, unsigned terms, void* workspace,
                                   size_t workspace_bytes, void* hip_stream);
+int gl_model_set_position_targets(gl_model* m, const float* targets, int n_families, int n_planes);
+int gl_multiplane_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
+                                    float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Lensing potential psi summed over the model's lenses (beyond the reference, which has none): out [n_pts][B].  Arguments and
  * conventions exactly those of gl_lens_maps, x = y = NULL for the model's own grid included.  psi is the potential whose gradient
