@@ -70,6 +70,9 @@ SYMBOLS = {
                                        POINTER(c_float), POINTER(c_float)]),
     "gl_model_set_source_scales": (c_int, [c_void_p, POINTER(c_float), c_int]),
     "gl_model_set_position_scales": (c_int, [c_void_p, POINTER(c_float), c_int]),
+    "gl_model_set_position_fluxes": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_int]),
+    "gl_position_fluxes_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
     "gl_image_positions_scaled": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_float), c_float, c_float,
                                           c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),
@@ -804,6 +807,35 @@ class Model:
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_position_scales(self._h, s.ctypes.data_as(POINTER(c_float)), int(s.size)))
 
+    def set_position_fluxes(self, fluxes, errors):
+        """The measured fluxes of the images and their errors (gl_model_set_position_fluxes; after ``set_positions``, which clears
+        them): ``[J]`` arrays in the concatenated image order, NaN for an image without a measurement; ``None``: no fluxes."""
+        fp = lambda a: a.ctypes.data_as(POINTER(c_float))
+        with torch.cuda.device(self.device):
+            if fluxes is None:
+                _check(lib().gl_model_set_position_fluxes(self._h, None, None, 0))
+                return
+            F = np.ascontiguousarray(fluxes, dtype=np.float32).reshape(-1)
+            s = np.ascontiguousarray(errors, dtype=np.float32).reshape(-1)
+            if F.size != s.size:
+                raise NativeLibraryError("fluxes and their errors must have the same length")
+            _check(lib().gl_model_set_position_fluxes(self._h, fp(F), fp(s), int(F.size)))
+
+    def position_fluxes(self, params, want_grad, want_model=False):
+        """gl_position_fluxes_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the flux-ratio term on one plane or on
+        lens planes; with ``want_model`` also ``(amplitude [B, F], model_flux [B, J])``."""
+        params = self._params(params)
+        B = params.shape[0]
+        ws = self._workspace(B)
+        ll = torch.empty(B, dtype=torch.float32, device=params.device)
+        chi2 = torch.empty_like(ll)
+        grad = torch.empty_like(params) if want_grad else None
+        amp = torch.empty((B, self.n_families), dtype=torch.float32, device=params.device) if want_model else None
+        mf = torch.empty((B, self.n_images), dtype=torch.float32, device=params.device) if want_model else None
+        _check_potential(lib().gl_position_fluxes_fwd_bwd(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(amp), _ptr(mf),
+                                                          _ptr(ws), ws.numel(), _stream()))
+        return (ll, chi2, grad, amp, mf) if want_model else (ll, chi2, grad)
+
     def image_positions(self, params, src_x, src_y, window, n_cells, max_images, tol, max_iter, scales=None):
         """gl_image_positions[_scaled]: ``src_x, src_y`` [B, S] on the device, ``window`` = (x_lo, x_hi, y_lo, y_hi), ``scales``
         [S] on the host or None.  Returns
@@ -954,6 +986,7 @@ class Model:
             _check(lib().gl_model_set_positions(self._h, len(sizes), sizes.ctypes.data_as(POINTER(c_int32)), fp(x), fp(y),
                                                 fp(ex), fp(ey)))
         self.n_images = int(sizes.sum())
+        self.n_families = int(sizes.size)
         self._ws = {}  # workspace layout changed
 
     def positions(self, params, want_grad):

@@ -572,10 +572,14 @@ int logprob_grad(const gl_model* m, const float* z, const float* obs, const floa
   if (pix && (rc = run_likelihood(m, w.params, B, plan, w, obs, err, mask, bg_rms, exp_time, want_grad, stream, &extra, &use_partial,
                                   &fin_rows)))
     return rc;
-  if (pos && (rc = run_positions(m, w.params, B, w, want_grad, stream))) return rc;
+  // a model that holds fluxes (gl_model_set_position_fluxes): the flux ratios are part of the point-image term, whose reduced chi2
+  // then divides by 2 J + n_flux
+  const bool flux = pos && m->pos_n_flux > 0;
+  if (pos && (rc = run_positions(m, w.params, B, w, want_grad, stream, flux ? POS_BOTH : POS_POSITIONS))) return rc;
+  const float n_point = flux ? 2.0f * (float)m->pos_J + (float)m->pos_n_flux : 2.0f * (float)m->pos_J;
   return run_finalize(m, w.params, B, fin_rows, w, loglike, chi2, nullptr, stream, z, logprob, grad_z,
                       pix ? 1.0f / (chi2_divisor * n_chi) : 0.f, extra, use_partial, pos,
-                      pos ? 1.0f / (2.0f * (float)m->pos_J * n_chi) : 0.f);
+                      pos ? 1.0f / (n_point * n_chi) : 0.f);
 }
 
 }  // namespace
@@ -1356,6 +1360,46 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
   m->d_pos_scale.reset();
   m->pos_targets = false;  // ... and, behind lens planes, without couplings until gl_model_set_position_targets
   m->d_pos_target.reset();
+  m->pos_n_flux = 0;  // ... and without fluxes until gl_model_set_position_fluxes
+  m->d_pos_flux.reset();
+  return GL_OK;
+}
+
+int gl_model_set_position_fluxes(gl_model* m, const float* flux, const float* flux_err, int n_images) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!flux) {  // no fluxes: the model as gl_model_set_positions left it
+    m->pos_n_flux = 0;
+    m->d_pos_flux.reset();
+    return GL_OK;
+  }
+  if (!flux_err) return fail(GL_EINVAL, "flux_err is null");
+  if (n_images != m->pos_J) return fail(GL_EINVAL, "%d fluxes for %d image(s)", n_images, m->pos_J);
+  int n_flux = 0;
+  for (int f = 0; f < m->pos_F; ++f) {
+    int n = 0;
+    for (int j = m->pos_fam_off[f]; j < m->pos_fam_off[f + 1]; ++j) {
+      if (std::isnan(flux[j])) continue;  // not measured
+      if (!std::isfinite(flux[j])) return fail(GL_EINVAL, "flux %d (%g) is not finite", j, flux[j]);
+      if (!(std::isfinite(flux_err[j]) && flux_err[j] > 0.f))
+        return fail(GL_EINVAL, "flux error %d (%g) is not finite and > 0", j, flux_err[j]);
+      ++n;
+    }
+    if (n == 1)
+      return fail(GL_EINVAL, "image family %d has one measured flux: the term constrains flux ratios, a family takes two or more, or none", f);
+    n_flux += n;
+  }
+  if (!n_flux) {  // every flux is NaN: none
+    m->pos_n_flux = 0;
+    m->d_pos_flux.reset();
+    return GL_OK;
+  }
+  std::vector<float> tab((size_t)2 * m->pos_J);
+  std::copy(flux, flux + m->pos_J, tab.begin());
+  std::copy(flux_err, flux_err + m->pos_J, tab.begin() + m->pos_J);
+  m->pos_n_flux = 0;
+  GL_HIP(m->d_pos_flux.upload(tab.data(), tab.size()));
+  m->pos_n_flux = n_flux;
   return GL_OK;
 }
 

@@ -8,6 +8,7 @@
 
 #include "gl_host.hip.h"
 #include "gl_positions.hip.h"
+#include "gl_fluxes.hip.h"
 #include "gl_images.hip.h"
 #include "gl_critical.hip.h"
 #include "gl_potential.hip.h"
@@ -88,8 +89,10 @@ MpArgs mp_args(const gl_model* m) {
 
 namespace glk {
 
-int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream) {
+int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream, int what,
+                  float* amp, float* model_flux) {
   if (m->n_series) return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image-position likelihood");
+  if ((what & POS_FLUXES) && !m->pos_n_flux) return fail(GL_EINVAL, "gl_model_set_position_fluxes has not been called on this model");
   if (m->has_user)  // the four kernels below, compiled at run time with the user's bodies on the nested duals (once per model text)
     if (int rc = compile_user_points(m)) return rc;
   PosArgs a = point_args(m, params, B);  // + the position tables and the likelihood's workspace
@@ -110,13 +113,21 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
   a.chi2 = w.pos_chi2;
   a.grad = want_grad ? w.pos_grad : nullptr;
   auto blocks = [](long long n) { return dim3((unsigned)((n + 63) / 64)); };
+  // P2 of the terms asked for: the position statistics, the flux ratios (gl_fluxes.hip.h; from the static library for every model --
+  // it evaluates no lens) or the former with the latter added by the thread that owns the same elements
+  auto fluxes = [&]() {
+    if (what & POS_FLUXES)
+      hipLaunchKernelGGL(gl_pos_flux_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a, (const float*)m->d_pos_flux.get(),
+                         (const float*)(m->d_pos_flux.get() + m->pos_J), (what & POS_POSITIONS) ? 1 : 0, amp, model_flux);
+  };
   if (planes) {  // P1 and P3 through the plane recursion, P2 and P4 as on one plane
     if (!m->pos_targets)
       return fail(GL_EINVAL, "the image positions of a model with lens planes need the couplings of their families: "
                              "gl_model_set_position_targets has not been called");
     const float* tg = m->d_pos_target;
     hipLaunchKernelGGL(gl_mp_pos_p1_kernel, blocks((long long)B * a.J), dim3(MP_POS_WG), 0, stream, a, mp_args(m), tg);
-    hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
+    if (what & POS_POSITIONS) hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
+    fluxes();
     if (want_grad && m->lens_params)
       hipLaunchKernelGGL(gl_mp_pos_p3_kernel, blocks((long long)B * a.J * m->lens_params), dim3(MP_POS_WG), 0, stream, a, mp_args(m),
                          tg, m->lens_params);
@@ -132,13 +143,16 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
       return hipModuleLaunchKernel(m->user_point_fn[k], blocks(n).x, 1, 1, 64, 1, 1, 0, stream, args, nullptr);
     };
     GL_HIP(go(0, (long long)B * a.J, args1));
-    GL_HIP(go(1, (long long)B * a.F, args1));
+    if (what & POS_POSITIONS) GL_HIP(go(1, (long long)B * a.F, args1));
+    fluxes();
     if (want_grad && m->lens_params) GL_HIP(go(2, (long long)B * a.J * m->lens_params, args2));
     GL_HIP(go(3, (long long)B * (a.P + 1), args2));
+    if (what & POS_FLUXES) GL_HIP(hipGetLastError());  // (the flux launch between the module's kernels)
     return GL_OK;
   }
   hipLaunchKernelGGL(gl_pos_p1_kernel, blocks((long long)B * a.J), dim3(64), 0, stream, a);
-  hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
+  if (what & POS_POSITIONS) hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
+  fluxes();
   if (want_grad && m->lens_params)
     hipLaunchKernelGGL(gl_pos_p3_kernel, blocks((long long)B * a.J * m->lens_params), dim3(64), 0, stream, a,
                        m->lens_params);
@@ -180,6 +194,25 @@ int gl_multiplane_positions_fwd_bwd(const gl_model* m, const float* params, int 
   if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
   hipStream_t stream = (hipStream_t)hip_stream;
   if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream))) return rc;
+  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  if (grad_params_or_null)
+    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+
+int gl_position_fluxes_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2, float* grad_params_or_null,
+                               float* amplitude_or_null, float* model_flux_or_null, void* workspace, size_t workspace_bytes,
+                               void* hip_stream) {
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
+  if (rc) return rc;
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream, POS_FLUXES, amplitude_or_null, model_flux_or_null)))
+    return rc;
   GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
   GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
   if (grad_params_or_null)

@@ -71,8 +71,12 @@ GL_INTERNAL int post_fwd(const gl_model* m, int B, const float* S, float* out, h
 GL_INTERNAL int post_bwd(const gl_model* m, int B, const float* gP, float* gS, hipStream_t stream, float scale);
 
 // ---- gl_api_points.hip --------------------------------------------------------------------------------------------------
-// image-position likelihood on the packed parameter rows `params` [B,P] (already on the device)
-GL_INTERNAL int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream);
+// point-image likelihood on the packed parameter rows `params` [B,P] (already on the device): the image positions, the flux ratios
+// of a model that holds fluxes (gl_model_set_position_fluxes) or both, summed in w.pos_ll / pos_chi2 / pos_grad.  amp [B][F] and
+// model_flux [B][J]: the flux term's optional outputs (S_f, S_f m_j), or null
+enum PosTerms { POS_POSITIONS = 1, POS_FLUXES = 2, POS_BOTH = 3 };
+GL_INTERNAL int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream,
+                              int what = POS_POSITIONS, float* amp = nullptr, float* model_flux = nullptr);
 // the model's image of `parts` on its lens planes: into `img` [B][H][W] (x conversion factor), through the PSF + pooling launch of
 // the single-plane render where the model has one
 GL_INTERNAL int mp_render(const gl_model* m, const float* params, int B, unsigned parts, float* img, const Workspace& w,

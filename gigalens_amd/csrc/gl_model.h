@@ -169,6 +169,9 @@ struct gl_model {
   // image families behind lens planes (gl_model_set_position_targets): the couplings T_f of every image's family
   bool pos_targets = false;
   glk::DevBuf<float> d_pos_target;  // [J][4], zero-padded rows; allocated only while pos_targets
+  // measured fluxes of the images (gl_model_set_position_fluxes, gl_fluxes.hip.h): the flux-ratio term of the point-image likelihood
+  int pos_n_flux = 0;              // measured fluxes over all families; 0: the model holds none and every call runs as without them
+  glk::DevBuf<float> d_pos_flux;   // [2][J]: flux (NaN = not measured), flux error; allocated only while pos_n_flux
   bool has_epl = false;
   int epl_comp = -1;     // the model's only EPL component, or -1 (none / several)
   int fam = 0;  // family level of the interpreter variant (gl_main_kernel FAM): 1 dPIE family / catalogues / series, 2 gl_extra.h

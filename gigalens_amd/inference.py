@@ -274,7 +274,7 @@ class ModellingSequence:
         if pm.include_pixels:
             n += float(torch.count_nonzero(lens_sim.img_region))
         if pm.include_positions:
-            n += pm.n_position
+            n += pm.n_position + getattr(pm, "n_flux", 0.0)  # (the flux ratios of the families: part of the point-image term)
         return n
 
     def MAP(self, optimizer: Adam, start=None, n_samples=500, num_steps=350, seed=0, progress=None, graph=None):

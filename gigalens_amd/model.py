@@ -220,6 +220,68 @@ class _MpPositionsFn(torch.autograd.Function):
         return g_ll[:, None] * grad, None
 
 
+class _FluxesFn(torch.autograd.Function):
+    """autograd glue around gl_position_fluxes_fwd_bwd (flux-ratio likelihood of the image families, one plane or lens planes)."""
+
+    @staticmethod
+    def forward(ctx, packed, model):
+        want = packed.requires_grad
+        ll, chi2, grad = model.position_fluxes(packed.detach(), want)
+        if want:
+            ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(chi2)
+        return ll, chi2
+
+    @staticmethod
+    def backward(ctx, g_ll, g_chi2):
+        (grad,) = ctx.saved_tensors
+        return g_ll[:, None] * grad, None
+
+
+def _family_fluxes(fluxes, errors, centroids_x):
+    """``(fluxes, errors, n_flux)`` of ``ForwardProbModel(centroids_fluxes=..., centroids_fluxes_errors=...)``: one float32 array per
+    family shaped like its ``centroids_x``, NaN where an image has no measurement (its error is not looked at), errors broadcast as
+    the position errors are.  ``ValueError`` as the constructor documents."""
+    if (fluxes is None) != (errors is None):
+        raise ValueError("centroids_fluxes and centroids_fluxes_errors come together: give both or neither")
+    if fluxes is None:
+        return None, None, 0.0
+    if centroids_x is None:
+        raise ValueError("centroids_fluxes needs centroids_x/centroids_y (include_positions=True)")
+    if len(fluxes) != len(centroids_x) or len(errors) != len(centroids_x):
+        raise ValueError(f"centroids_fluxes / centroids_fluxes_errors: one entry per image family ({len(centroids_x)}), got "
+                         f"{len(fluxes)} / {len(errors)}")
+    out_f, out_s, n_flux = [], [], 0
+    for f, (F, s, x) in enumerate(zip(fluxes, errors, centroids_x)):
+        if F is None:  # a family without fluxes
+            out_f.append(np.full(x.shape, np.nan, dtype=np.float32))
+            out_s.append(np.full(x.shape, np.nan, dtype=np.float32))
+            continue
+        F = np.atleast_1d(np.asarray(F, dtype=np.float32))
+        if F.shape != x.shape:
+            raise ValueError(f"centroids_fluxes[{f}] has shape {F.shape}, the family's centroids_x {x.shape}")
+        if s is None:
+            raise ValueError(f"centroids_fluxes[{f}] without centroids_fluxes_errors[{f}]")
+        try:
+            s = np.broadcast_to(np.atleast_1d(np.asarray(s, dtype=np.float32)), x.shape).copy()
+        except ValueError:
+            raise ValueError(f"centroids_fluxes_errors[{f}] does not broadcast to the family's shape {x.shape}") from None
+        measured = ~np.isnan(F)
+        if not np.all(np.isfinite(F[measured])):
+            raise ValueError(f"centroids_fluxes[{f}]: a measured flux must be finite (NaN marks an image without one), got {F.tolist()}")
+        if not np.all(np.isfinite(s[measured])):
+            raise ValueError(f"centroids_fluxes_errors[{f}]: the error of a measured flux must be finite, got {s.tolist()}")
+        if np.any(s[measured] <= 0):
+            raise ValueError(f"centroids_fluxes_errors[{f}]: the error of a measured flux must be > 0, got {s.tolist()}")
+        if int(measured.sum()) == 1:
+            raise ValueError(f"centroids_fluxes[{f}]: one measured flux -- the term constrains flux ratios, a family takes two or more "
+                             "measured fluxes, or none")
+        n_flux += int(measured.sum())
+        out_f.append(F)
+        out_s.append(s)
+    return out_f, out_s, float(n_flux)
+
+
 class _PackBijector:
     """``pack_bij`` (tf/model.py:78-85): ``(B, d)`` <-> nested structure, column k = k-th nest leaf."""
 
@@ -256,7 +318,8 @@ class ForwardProbModel(ProbabilisticModel):
 
     def __init__(self, prior, observed_image=None, background_rms=None, exp_time=None, error_map=None,
                  centroids_x=None, centroids_y=None, centroids_errors_x=None, centroids_errors_y=None,
-                 include_pixels=True, include_positions=True, centroids_scales=None, centroids_redshifts=None):
+                 include_pixels=True, include_positions=True, centroids_scales=None, centroids_redshifts=None,
+                 centroids_fluxes=None, centroids_fluxes_errors=None):
         """``centroids_scales`` (beyond the reference): one deflection scale per image family of ``centroids_x`` -- a family at its
         own redshift is traced with ``beta = theta - c_f alpha`` and ``A = I - c_f H`` in the position likelihood, the predicted
         positions and the image-plane rms.  Default: all 1.
@@ -267,7 +330,17 @@ class ForwardProbModel(ProbabilisticModel):
         front of its family (``beta = theta - sum_i T_f,i a_i``, ``A = d beta / d theta``) in ``stats_positions`` and the fused
         ``log_prob`` / ``log_prob_and_grad`` / ``term_log_prob_and_grad``; on one plane they are the ``centroids_scales``.
         ``ValueError``: a redshift that is not finite, given together with ``centroids_scales`` or without centroids; at bind time, a
-        family at or in front of the first plane, or a model without a ``MultiPlane`` (use ``centroids_scales``)."""
+        family at or in front of the first plane, or a model without a ``MultiPlane`` (use ``centroids_scales``).
+
+        ``centroids_fluxes`` / ``centroids_fluxes_errors`` (beyond the reference): one array per image family, shaped like
+        ``centroids_x[f]`` -- the measured fluxes ``F_j`` of the images and their errors ``s_j`` (broadcast as the position errors are);
+        NaN marks an image without a measurement, ``None`` or an all-NaN array a family without fluxes.  With ``m_j = 1 / |det A_j|`` at
+        the observed positions the family's unlensed flux is profiled out, ``S_f = sum w F m / sum w m^2`` (``w = 1 / s^2``), and
+        ``log_like_f = -1/2 (sum w (F - S_f m)^2 + sum log(2 pi s^2))`` joins the image-position term of ``log_prob``,
+        ``log_prob_unfused``, ``log_like``, ``log_prob_and_grad`` and ``term_log_prob_and_grad(..., "positions")``, whose reduced chi^2
+        becomes ``(chi2_pos + chi2_flux) / (n_position + n_flux)``; ``stats_fluxes`` and ``predicted_fluxes`` give the term alone.  Only
+        flux ratios are constrained.  ``ValueError``: fluxes without centroids, fluxes without errors or the reverse, a shape mismatch,
+        exactly one measured flux in a family, a measured flux that is not finite or whose error is not finite and > 0."""
         super().__init__(prior)
         self.include_pixels = include_pixels
         self.include_positions = include_positions
@@ -312,6 +385,8 @@ class ForwardProbModel(ProbabilisticModel):
             if not np.all(np.isfinite(zf)):
                 raise ValueError(f"centroids_redshifts: every redshift must be finite, got {zf.tolist()}")
             self.centroids_redshifts = zf
+        self.centroids_fluxes, self.centroids_fluxes_errors, self.n_flux = _family_fluxes(centroids_fluxes, centroids_fluxes_errors,
+                                                                                          self.centroids_x)
         self._flat = prior.flat(self.device)
         example = prior.sample(seed=0)
         self.pack_bij = _PackBijector(example)
@@ -404,6 +479,8 @@ class ForwardProbModel(ProbabilisticModel):
                 model.set_position_targets(targets)
             elif given:
                 model.set_position_scales(scales)
+            if self.n_flux:  # (set_positions has cleared the fluxes of an earlier owner)
+                model.set_position_fluxes(np.concatenate(self.centroids_fluxes), np.concatenate(self.centroids_fluxes_errors))
             model._positions_owner = self
         return model
 
@@ -439,6 +516,38 @@ class ForwardProbModel(ProbabilisticModel):
         fn = _MpPositionsFn if self.centroids_x is not None and self._on_planes(simulator) else _PositionsFn
         ll, chi2 = fn.apply(packed, self._bind_positions(simulator))
         return ll, chi2 / self.n_position
+
+    def _need_fluxes(self, what):
+        if not self.n_flux:
+            raise ValueError(f"{what} needs a model built with centroids_fluxes / centroids_fluxes_errors")
+
+    def stats_fluxes(self, simulator, params):
+        """``(log_like, chi2 / n_flux)`` of the flux-ratio term alone (beyond the reference; see ``centroids_fluxes``), differentiable
+        in packed ``params``.  On lens planes the families need ``centroids_redshifts``, as in ``stats_positions``."""
+        self._need_fluxes("stats_fluxes")
+        packed = params if torch.is_tensor(params) else simulator.pack(params)
+        self._on_planes(simulator)  # (its refusals; one native entry serves one plane and lens planes)
+        ll, chi2 = _FluxesFn.apply(packed, self._bind_positions(simulator))
+        return ll, chi2 / self.n_flux
+
+    def predicted_fluxes(self, simulator, params):
+        """``(amplitude [B, F], model_flux [B, J])``: the profiled unlensed flux ``S_f`` of every family and the fluxes ``S_f |mu_j|`` the
+        model gives its images, in the concatenated image order; NaN for a family without fluxes.  Forward only."""
+        self._need_fluxes("predicted_fluxes")
+        packed = params if torch.is_tensor(params) else simulator.pack(params)
+        if packed.requires_grad:
+            raise NotImplementedError("predicted_fluxes is a forward-only diagnostic (no gradient)")
+        self._on_planes(simulator)
+        return self._bind_positions(simulator).position_fluxes(packed, False, want_model=True)[3:]
+
+    def _point_stats(self, simulator, packed):
+        """``(log_like, red_chi2)`` of the point-image term: the image positions and, when the model has fluxes, their flux ratios --
+        ``red_chi2 = (chi2_pos + chi2_flux) / (n_position + n_flux)``."""
+        ll, red = self.stats_positions(simulator, packed)
+        if self.n_flux:
+            ll_f, red_f = self.stats_fluxes(simulator, packed)
+            ll, red = ll + ll_f, (red * self.n_position + red_f * self.n_flux) / (self.n_position + self.n_flux)
+        return ll, red
 
     def predicted_positions(self, simulator, params, **solver_kwargs):
         """Images the model predicts for every family of ``centroids_x/y`` (beyond the reference).  The source of a family is
@@ -589,7 +698,7 @@ class ForwardProbModel(ProbabilisticModel):
         tensors are the graph's STATIC outputs, overwritten by the next call with ``graph=True`` on the same simulator; ``z`` is
         copied into the graph's static input unless it already IS that tensor (``graph_input(simulator, z)`` hands it out, for loops
         that update ``z`` in place).  The graph holds the device buffers the simulator's native model had when it was captured: its
-        image positions and, on lens planes, their families' couplings are uploaded again whenever ANOTHER ``ForwardProbModel`` with
+        image positions, their fluxes and, on lens planes, their families' couplings are uploaded again whenever ANOTHER ``ForwardProbModel`` with
         positions is bound to the same simulator, so keep one such model per simulator while its graph is in use."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
         on_planes = self._on_planes(simulator)
@@ -661,7 +770,7 @@ class ForwardProbModel(ProbabilisticModel):
             red_chi2 = red_chi2 + rc
             n_chi += 1
         if self.include_positions:
-            ll, rc = self.stats_positions(simulator, packed)
+            ll, rc = self._point_stats(simulator, packed)
             log_like = log_like + ll
             red_chi2 = red_chi2 + rc
             n_chi += 1
@@ -678,7 +787,7 @@ class ForwardProbModel(ProbabilisticModel):
         if self.include_pixels:
             ll = ll + self._pixel_stats_packed(simulator, packed)[0]
         if self.include_positions:
-            ll = ll + self.stats_positions(simulator, packed)[0]
+            ll = ll + self._point_stats(simulator, packed)[0]
         return ll
 
     def log_prior(self, z):

@@ -199,6 +199,30 @@ int gl_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* l
 int gl_model_set_source_scales(gl_model* m, const float* scales, int n_src);
 int gl_model_set_position_scales(gl_model* m, const float* scales, int n_families);
 
+/* Flux ratios of the image families (beyond the reference): the second observable of a lensed quasar or supernova.  With beta_j and
+ * A_j of the observed images as the position likelihood traces them, m_j = 1 / |det A_j|; an image with a measured flux F_j and error
+ * s_j enters with weight w_j = 1 / s_j^2.  The unlensed flux S_f of the family's source is profiled out in closed form:
+ *   S_f = sum w F m / sum w m^2 ,  chi2_f = sum w (F - S_f m)^2 ,  ll_f = -1/2 (chi2_f + sum log(2 pi s^2)) ,
+ * and, S_f minimising chi2_f, the gradient is the partial derivative at fixed S_f.  Only ratios are constrained: (F, s) -> (c F, c s)
+ * leaves chi2_f alone.
+ *   gl_model_set_position_fluxes  flux, flux_err [n_images] (HOST pointers, copied) in the concatenated image order of
+ *       gl_model_set_positions, which must have been called (and which clears the fluxes); a NaN flux marks an image without a
+ *       measurement, flux = NULL (or every flux NaN) clears them.  GL_EINVAL, the model left as it was: n_images that does not
+ *       match, a measured flux that is not finite or whose error is not finite and > 0, a family with exactly one measured flux.
+ *       While the model holds fluxes, GL_TERM_POSITIONS of gl_logprob_fwd_bwd / gl_multiplane_logprob_fwd_bwd is the sum of both
+ *       terms and its reduced chi2 divides by 2 J + n_flux (n_flux: the measured fluxes); gl_positions_fwd_bwd and
+ *       gl_multiplane_positions_fwd_bwd keep computing the positions alone, with unchanged bits.
+ *   gl_position_fluxes_fwd_bwd    the flux term alone, on one plane (with the scales of gl_model_set_position_scales) or on lens
+ *       planes (gl_model_set_position_targets) alike: loglike, chi2 [B] (summed over the families, not reduced), and when given
+ *       d loglike / d params [B][P], amplitude [B][n_families] = S_f and model_flux [B][n_images] = S_f m_j (NaN for a family without
+ *       fluxes).  Workspace of gl_workspace_bytes(m, B); enqueues on the caller's stream without allocation or synchronisation;
+ *       two calls give identical bits.  GL_EINVAL before gl_model_set_positions / gl_model_set_position_fluxes; GL_EUNSUPPORTED
+ *       for a GL_SERIES lens, as gl_positions_fwd_bwd. */
+int gl_model_set_position_fluxes(gl_model* m, const float* flux, const float* flux_err, int n_images);
+int gl_position_fluxes_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2, float* grad_params_or_null,
+                               float* amplitude_or_null, float* model_flux_or_null, void* workspace, size_t workspace_bytes,
+                               void* hip_stream);
+
 /* ScalingRelation.hessian on arbitrary points (scaling_relation.py:72-83): out [4][n_pts][B] = f_xx, f_xy, f_yx, f_yy
  * summed over the catalogue; other arguments as gl_scaled_eval. */
 int gl_scaled_hessian(int base_kind, int n_galaxies, const int32_t scale_col[3], const float* table_dev, const float* x,
