@@ -247,6 +247,7 @@ MainArgs base_args(const gl_model* m, const Workspace& w, int chunk) {
   a.neutral = m->d_nfw_tab ? m->d_nfw_tab + 2 * glh::kNfwNodes : nullptr;
   a.grid_rmax = m->shp_cull ? m->grid_rmax : -1.f;  // (negative: the culling test of the table-mode shapelet kernels is off)
   a.dbg = m->dbg_flags;
+  a.careful_tiles = m->careful_tiles;
   a.shp_stride = m->shp_stride;
   a.parts = 7u;
   a.cats = m->d_cats;
@@ -724,6 +725,7 @@ Knobs read_env_knobs(gl_model* m) {
   m->corr_wide = env_int("GIGALENS_HIP_CORR_WIDE", 1);           // 0: 8 outputs per thread in the stride-2 forward correlation as well
   k.corr_pair = env_int("GIGALENS_HIP_CORR_PAIR", 1);            // 0: the tap kernels for every PSF (no register-blocked pair kernel)
   m->wave_prep = env_int("GIGALENS_HIP_WAVE_PREP", 1) != 0;
+  m->careful_tiles = env_int("GIGALENS_HIP_CAREFUL_TILES", 0) != 0;  // tests: 1 = no select-free whole tiles in the pair kernels (read once)
   m->lstsq_wgs = std::max(1, env_int("GIGALENS_HIP_LSTSQ_WGS", 2048));
   m->lstsq_chol = env_int("GIGALENS_HIP_LSTSQ_CHOL", 1) != 0;    // tests: 0 = every system through the eigenvalue solve
   m->lstsq_fused = env_int("GIGALENS_HIP_LSTSQ_FUSED", 1) != 0;  // tests: 0 = the linear solve through the basis stack (read once)

@@ -126,6 +126,7 @@ struct gl_model {
   int shp_cull = 1;           // GIGALENS_HIP_SHP_CULL: wave-tiles provably outside the shapelet table skip the lens (gl_shp.hip.h)
   int corr_max_pairs = 0;     // GIGALENS_HIP_CORR_MAXPAIRS, read once at gl_model_create
   int corr_wide = 1;          // GIGALENS_HIP_CORR_WIDE, read once at gl_model_create
+  int careful_tiles = 0;      // GIGALENS_HIP_CAREFUL_TILES, read once at gl_model_create (MainArgs::careful_tiles)
   bool has_nfw = false;
   size_t nfw_lds = 0;          // bytes of that table in a main kernel's LDS
   int shp_stride = 0;

@@ -10,6 +10,8 @@
 // `m ? a : b` selects per lane.  Transcendentals (v_rcp/sqrt/log/exp) have no packed form and are applied
 // per lane.  Supported components: EPL, SIE, SHEAR, SIS lenses; SERSIC / SERSIC_ELLIPSE lights (K_SERSIC in a kind list
 // selects the spherical fast path: only for models whose light profiles are ALL spherical, else K_SERSIC_ELLIPSE serves both).
+// Whole unmasked tiles run the select-free flavour of the bodies behind one wave-uniform guard; a wave whose guard fires leaves
+// that loop and does the tile, and the rest of its chunk, with the careful body of the ragged tiles (same bits either way).
 #pragma once
 #include "gl_static.hip.h"
 #include "gl_vec.hip.h"
@@ -142,16 +144,31 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
 #pragma unroll
   for (int i = 0; i < NLIGHT; ++i) dC[i] = s_d + comps[NL + i].d_off;
   const bool has_err = a.err != nullptr, has_mask = a.mask != nullptr, has_pix = a.pix != nullptr;
+  // The observation and the error plane are read through raw buffer descriptors: a buffer load takes the 32-bit byte offset as it
+  // is, wherever the compiler places the load.  (As plain global loads they ended up behind the series loop, in another basic
+  // block than the offset's zero-extension, and instruction selection then formed a 64-bit address per load: two to four
+  // v_lshl_add_u64 per pixel pair and a register pair for each.)  No range check: the offsets are the ones the global loads used.
+  auto plane = [](const float* p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), (short)0, -1, 0x00020000); };
+  const auto r_obs = plane(a.obs), r_err = plane(a.err);
 
   // One tile = W*256 pixels.  CHECK=false is the steady state (whole tile inside the chunk, no pixel mask):
   // no validity selects, no weights.  CHECK=true handles the ragged last tile and img_region weights.
   // err_tag: 0 no error map, 1 error map (both compile the variance and the cotangent of their own case: as a run-time choice the
   // two were computed side by side and selected, 10 instructions per pixel pair), 2 decided at run time (the ragged-end tile)
+  // CHECK=false tiles are also SELECT-FREE (gl_vec.hip.h, FAST): the centre selects and the clamp of the EPL, the floors of the
+  // Sersic VJP, the R0 == 0 selects of the SIS and the NaN -> 0 rule on the image are not emitted -- each is an unpacked
+  // instruction per lane that every regular pixel passes unchanged.  Instead the forward bodies range-check what those selects
+  // look at into `worst`, and once the image m is known the tile asks whether ANY lane of the wave is out of range or has a NaN
+  // image: if so the tile returns false BEFORE it has added to st0, st1 or an accumulator, and the caller hands the same `base`
+  // to the careful (CHECK=true) body, which produces the same bits for a whole unmasked tile (w = 1).  8 instructions per pixel
+  // pair for the guard of EPL + Shear | Sersic against the 22 it replaces.
   // (requesting the NEXT whole tile's planes -- grid, observation, error map -- while a tile is worked on was tried in round 4, after
   // the shapelet kernel's dissection showed bare tile loads costing 1 400 cycles per wave-tile there: 147 VGPRs instead of 141 and
   // 0.0823 against 0.0819 ms per C2 step -- at three waves per SIMD the other waves already cover a tile's opening loads.)
-  auto tile = [&](int base, auto check_tag, auto err_tag) {
+  auto tile = [&](int base, auto check_tag, auto err_tag) -> bool {
     constexpr bool CHECK = decltype(check_tag)::value;
+    constexpr bool FAST = !CHECK;
+    unsigned worst = 0;  // FAST: the running maximum of the range checks (guard_range)
     constexpr int ERR = decltype(err_tag)::value;
     const bool herr = ERR == 2 ? has_err : ERR == 1;
     unsigned jj[W], pidx[W];
@@ -170,6 +187,10 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
 #pragma unroll
     for (int w = 0; w < W; ++w) { jo[w] = jj[w] << 2; po[w] = pidx[w] << 2; }
     auto ldf = [](const float* base, unsigned byte_off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
+    auto ldb = [](auto rsrc, const float* base, unsigned byte_off) {  // (the ragged-end tile keeps the global load: fewer scalar registers)
+      if constexpr (CHECK) return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
+      else return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, byte_off, 0, 0));
+    };
     if constexpr (W == 2) {
       x = V{ldf(a.gx, jo[0]), ldf(a.gx, jo[1])};
       y = V{ldf(a.gy, jo[0]), ldf(a.gy, jo[1])};
@@ -181,17 +202,18 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
     }
     V bx = x, by = y, m = V(0.f);
     EplStateV<V> est[NL > 0 ? NL : 1];
+    SieStateV<V> sie_st[NL > 0 ? NL : 1];  // FAST tiles only (gl_vec.hip.h)
     SerStateV<V> sst[NLIGHT > 0 ? NLIGHT : 1];
     static_for([&](auto I) {
       constexpr int i = decltype(I)::value;
       constexpr int kind = LK::kinds[i];
-      if constexpr (kind == K_EPL) epl_fwd_v<V, GRAD>(dL[i], gder + comps[i].d_off, x, y, bx, by, est[i]);
-      else if constexpr (kind == K_SIE) sie_fwd_v<V>(dL[i], x, y, bx, by);
+      if constexpr (kind == K_EPL) epl_fwd_v<V, GRAD, const float*, FAST>(dL[i], gder + comps[i].d_off, x, y, bx, by, est[i], &worst);
+      else if constexpr (kind == K_SIE) sie_fwd_v<V>(dL[i], x, y, bx, by, (FAST && GRAD) ? &sie_st[i] : nullptr);
       else if constexpr (kind == K_SHEAR) shear_fwd_v<V>(dL[i], x, y, bx, by);
 #ifdef GL_HAVE_USER
       else if constexpr (is_user_code(kind)) user_mass_fwd_v<V, kind>(dL[i], x, y, bx, by);
 #endif
-      else sis_fwd_v<V>(dL[i], x, y, bx, by);
+      else sis_fwd_v<V, FAST>(dL[i], x, y, bx, by, &worst);
     }, std::make_integer_sequence<int, NL>{});
     static_for([&](auto I) {
       constexpr int i = decltype(I)::value;
@@ -202,10 +224,15 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
       if constexpr (is_user_code(lkind)) m += user_light_fwd_v<V, lkind>(dC[i], src ? bx : x, src ? by : y);
       else
 #endif
-      m += sersic_fwd_v<V, ell>(dC[i], src ? bx : x, src ? by : y, sst[i]);
+      m += sersic_fwd_v<V, ell, FAST>(dC[i], src ? bx : x, src ? by : y, sst[i], GRAD ? &worst : nullptr);  // (the floors are the VJP's)
     }, std::make_integer_sequence<int, NLIGHT>{});
     auto nanp = m != m;
-    m = (nanp ? V(0.f) : m) * a.out_scale;  // NaN -> 0 (tf/simulator.py:140), then x det(T) (:156)
+    if constexpr (FAST) {  // the guard: nothing of this tile has been added anywhere yet
+      if ((__builtin_amdgcn_ballot_w64(worst > kGuardWidth) | __builtin_amdgcn_ballot_w64(any_nan(m))) != 0) return false;
+      m = m * a.out_scale;
+    } else {
+      m = (nanp ? V(0.f) : m) * a.out_scale;  // NaN -> 0 (tf/simulator.py:140), then x det(T) (:156)
+    }
     if (MODE == IMG_FWD) {
       float* row = a.img + (size_t)b * a.img_stride;
       if constexpr (W == 2) {
@@ -214,24 +241,24 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
       } else {
         if (valid[0]) row[pidx[0]] = m;
       }
-      return;
+      return true;
     }
     V gm;
     if (MODE == IMG_BWD) {
       const float* row = a.gimg + (size_t)b * a.img_stride;
       V g;
       if constexpr (W == 2) g = V{row[pidx[0]], row[pidx[1]]}; else g = row[pidx[0]];
-      gm = nanp ? V(0.f) : (CHECK ? g * vmask : g) * a.out_scale;
+      gm = FAST ? g * a.out_scale : (nanp ? V(0.f) : (CHECK ? g * vmask : g) * a.out_scale);
     } else {
       V o, w = vmask, e = V(1.f);
       if constexpr (W == 2) {
-        o = V{ldf(a.obs, po[0]), ldf(a.obs, po[1])};
+        o = V{ldb(r_obs, a.obs, po[0]), ldb(r_obs, a.obs, po[1])};
         if (CHECK && has_mask) w = w * V{ldf(a.mask, po[0]), ldf(a.mask, po[1])};
-        if (herr) e = V{ldf(a.err, po[0]), ldf(a.err, po[1])};
+        if (herr) e = V{ldb(r_err, a.err, po[0]), ldb(r_err, a.err, po[1])};
       } else {
-        o = ldf(a.obs, po[0]);
+        o = ldb(r_obs, a.obs, po[0]);
         if (CHECK && has_mask) w = w * ldf(a.mask, po[0]);
-        if (herr) e = ldf(a.err, po[0]);
+        if (herr) e = ldb(r_err, a.err, po[0]);
       }
       // tf/model.py:92-99; sigma^2 = bg^2 + m/t (no clip: negative -> NaN like sqrt of a negative)
       V dmo = m - o;
@@ -252,7 +279,7 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
       }
       if (MODE == LL_GRAD) {
         V g = herr ? -(dmo * is2) : (dmo * dmo * is2 - 1.f) * (is2 * (0.5f * a.inv_t)) - dmo * is2;
-        gm = nanp ? V(0.f) : (CHECK ? g * w : g) * a.out_scale;
+        gm = FAST ? g * a.out_scale : (nanp ? V(0.f) : (CHECK ? g * w : g) * a.out_scale);
       }
     }
     if constexpr (GRAD) {
@@ -271,7 +298,7 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
         if constexpr (is_user_code(lkind)) user_light_vjp_v<V, lkind, src>(dC[i], src ? bx : x, src ? by : y, gm, accC + off, gbx, gby);
         else
 #endif
-        sersic_vjp_v<V, src, ell>(dC[i], sst[i], gm, accC + off, gbx, gby);
+        sersic_vjp_v<V, src, ell, FAST>(dC[i], sst[i], gm, accC + off, gbx, gby);
       }, std::make_integer_sequence<int, NLIGHT>{});
       gbx = -gbx;
       gby = -gby;
@@ -280,24 +307,35 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
         constexpr int kind = LK::kinds[i];
         constexpr int off = [] { int n = 0; for (int j = 0; j < i; ++j) n += static_nacc(LK::kinds[j]); return n; }();
         if constexpr (kind == K_EPL) epl_vjp_v<V>(dL[i], gbx, gby, est[i], accL + off);
-        else if constexpr (kind == K_SIE) sie_vjp_v<V>(dL[i], x, y, gbx, gby, accL + off);
+        else if constexpr (kind == K_SIE) sie_vjp_v<V>(dL[i], x, y, gbx, gby, accL + off, FAST ? &sie_st[i] : nullptr);
         else if constexpr (kind == K_SHEAR) shear_vjp_v<V>(x, y, gbx, gby, accL + off);
 #ifdef GL_HAVE_USER
         else if constexpr (is_user_code(kind)) user_mass_vjp_v<V, kind>(dL[i], x, y, gbx, gby, accL + off);
 #endif
-        else sis_vjp_v<V>(dL[i], x, y, gbx, gby, accL + off);
+        else sis_vjp_v<V, FAST>(dL[i], x, y, gbx, gby, accL + off);
       }, std::make_integer_sequence<int, NL>{});
     }
+    return true;
   };
   {
-    const bool plain = !has_mask && !has_pix;
+    // the per-sample part of the guard (sersic_fast_ok), and the test knob that sends every whole tile to the careful body
+    bool sample_ok = !a.careful_tiles;
+    static_for([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      constexpr int lkind = i < NLL ? LLK::kinds[i < NLL ? i : 0] : SK::kinds[i >= NLL ? i - NLL : 0];
+      if constexpr (!is_user_code(lkind)) sample_ok = sample_ok && sersic_fast_ok(gder + comps[NL + i].d_off);
+    }, std::make_integer_sequence<int, NLIGHT>{});
+    const bool plain = !has_mask && !has_pix && sample_ok;
     int base = p0;
     if (GL_DBG(a.dbg, 1)) base = p1;
-    if (plain) {
-      if (has_err)
-        for (; base + WG * W <= p1; base += WG * W, ++n_whole) tile(base, std::false_type{}, std::integral_constant<int, 1>{});
-      else
-        for (; base + WG * W <= p1; base += WG * W, ++n_whole) tile(base, std::false_type{}, std::integral_constant<int, 0>{});
+    if (plain) {  // a tile whose guard fires is not counted in n_whole: the loop below takes over from that tile on
+      if (has_err) {
+        for (; base + WG * W <= p1; base += WG * W, ++n_whole)
+          if (!tile(base, std::false_type{}, std::integral_constant<int, 1>{})) break;
+      } else {
+        for (; base + WG * W <= p1; base += WG * W, ++n_whole)
+          if (!tile(base, std::false_type{}, std::integral_constant<int, 0>{})) break;
+      }
     }
     for (; base < p1; base += WG * W) tile(base, std::true_type{}, std::integral_constant<int, 2>{});
   }

@@ -52,6 +52,28 @@ template <class V> __device__ __forceinline__ V vmax(V a, V b) { return a > b ? 
 __device__ __forceinline__ float hsum(float a) { return a; }
 __device__ __forceinline__ float hsum(v2f a) { return a.x + a.y; }
 
+// ---- select-free bodies (FAST) and their guard --------------------------------------------------------------
+// The bodies below carry selects, clamps and floors that only act on singular inputs: a pixel exactly on a profile's centre,
+// a radius outside [1e-10, 1e10].  On a pixel pair each is an unpacked instruction per lane, and every regular pixel passes
+// through them unchanged.  With FAST they are not emitted; instead the value each of them looks at is range-checked into one
+// running word, and the caller (gl_pair.hip.h) abandons the tile for the careful body when any lane of the wave is out of range.
+// The check: positive floats order like their bit patterns, so  lo <= v <= hi  is  bits(v) - bits(lo) <= bits(hi) - bits(lo)
+// in unsigned arithmetic; zero, denormals below lo, negative numbers, inf and NaN all land above the width by themselves.  Every
+// check uses the SAME width (that of [1e-10, 1e10], about 66 octaves), so the checks of a tile fold into one running maximum
+// (v_max3_u32: two values per instruction) and one compare.
+constexpr unsigned kGuardWidth = __builtin_bit_cast(unsigned, 1e10f) - __builtin_bit_cast(unsigned, 1e-10f);
+// the range a squared radius / a radius is checked against: [1e-15, 1e-15 (+) width] = [1e-15, 1.0e5]
+constexpr float kGuardRadLo = 1e-15f;
+__device__ __forceinline__ void guard_range(unsigned& worst, float v, float lo) {
+  worst = max(worst, __float_as_uint(v) - __builtin_bit_cast(unsigned, lo));
+}
+__device__ __forceinline__ void guard_range(unsigned& worst, v2f v, float lo) {
+  const float v0 = v.x, v1 = v.y;  // (element copies first: see nfw_h_pair)
+  worst = max(max(worst, __float_as_uint(v0) - __builtin_bit_cast(unsigned, lo)), __float_as_uint(v1) - __builtin_bit_cast(unsigned, lo));
+}
+__device__ __forceinline__ bool any_nan(float a) { return a != a; }
+__device__ __forceinline__ bool any_nan(v2f a) { return __builtin_isunordered(a.x, a.y); }  // one v_cmp_u_f32 for the pair
+
 // ---- EPL ------------------------------------------------------------------------------------------------
 // The angular series  Omega = sum_n c_n e^{i(2n+1)theta}  (epl.py:39-54; c_n real, per sample) and its derivatives w.r.t.
 // f and t (same form with dc_n/df, dc_n/dt) are summed by CLENSHAW's backward recurrence: cos((2n+1)theta) and
@@ -78,9 +100,11 @@ template <class T, class P> struct gl_rebind;
 template <class T> struct gl_rebind<T, const float*> { using type = const T*; };
 template <class T> struct gl_rebind<T, gptr4> { using type = const T __attribute__((address_space(4)))*; };
 
-template <class V, bool GRAD, class P = const float*>
+// FAST: no centre selects and no clamp -- inv = invc = 1/clip(R0) = r, Cs = X r; `worst` takes the check 1e-10 <= r <= 1e10,
+// which implies r2 > 0 (r = rsq(r2) is finite and positive), clamp3(r) == r and with it the clamp's gradient mask.
+template <class V, bool GRAD, class P = const float*, bool FAST = false>
 __device__ __forceinline__ void epl_fwd_v(const float* d, const P gd, V x, V y, V& bx, V& by,
-                                          EplStateV<V>& st) {
+                                          EplStateV<V>& st, unsigned* worst = nullptr) {
   using PInt = typename gl_rebind<int, P>::type;
   using PRow = typename gl_rebind<vf4, P>::type;
   const float c = d[EPL_C], s = d[EPL_S], q = d[EPL_Q];
@@ -92,12 +116,21 @@ __device__ __forceinline__ void epl_fwd_v(const float* d, const P gd, V x, V y, 
   // one transcendental instead of sqrt + 2 rcp: r = 1/R0 (inf at R0 = 0), and 1/clip(R0, 1e-10, 1e10) is the
   // clip of 1/R0 to [1e-10, 1e10] (epl.py:31); R0 itself is only needed through 1/R0
   V r = rsq_(r2);
-  auto pos = r2 > V(0.f);
-  st.inv = pos ? r : V(0.f);
-  st.Cs = pos ? X * r : V(1.f);
+  V iRc;
+  if constexpr (FAST) {
+    guard_range(*worst, r, 1e-10f);
+    st.inv = r;
+    st.Cs = X * r;
+    iRc = r;
+    st.invc = r;
+  } else {
+    auto pos = r2 > V(0.f);
+    st.inv = pos ? r : V(0.f);
+    st.Cs = pos ? X * r : V(1.f);
+    iRc = clamp3(r, 1e-10f, 1e10f);  // one v_med3 per lane (a NaN gives the lower bound, like the two selects did)
+    st.invc = (iRc == r) ? r : V(0.f);  // clip_by_value passes gradient only inside the clamp
+  }
   st.Ss = st.yr * st.inv;
-  V iRc = clamp3(r, 1e-10f, 1e10f);  // one v_med3 per lane (a NaN gives the lower bound, like the two selects did)
-  st.invc = (iRc == r) ? r : V(0.f);  // clip_by_value passes gradient only inside the clamp
   V twoc = (st.Cs * st.Cs - st.Ss * st.Ss) * 2.f;
   // scalar-loaded trip count and coefficients (wave-uniform address): SGPR operands, scalar loop control
   const int K = ((PInt)gd)[EPL_KI];
@@ -203,22 +236,36 @@ __device__ __forceinline__ void epl_vjp_v(const float* d, V gx, V gy, const EplS
 }
 
 // ---- SIE / SHEAR / SIS (stateless: cheap to re-evaluate) ----------------------------------------------
-template <class V> __device__ __forceinline__ void sie_fwd_v(const float* d, V x, V y, V& bx, V& by) {
-  const float c = d[SIE_C], s = d[SIE_S], q = d[SIE_Q], sq = d[SIE_SQ], A = d[SIE_A];
+// The forward state the VJP needs.  sie_vjp_v recomputes it (stateless: the compiler merges the two evaluations inside one basic
+// block); the select-free tiles of gl_pair.hip.h hand it over instead (`keep` / `kept`), because the branch of their guard sits
+// between the forward and the VJP and the evaluations were no longer merged across it (SIE + Shear | Sersic | Sersic: 650 instead
+// of 410 instructions per pixel pair).
+template <class V> struct SieStateV { V xr, yr, ipsi, u, v, fu, fv; };
+template <class V> __device__ __forceinline__ SieStateV<V> sie_state_v(const float* d, V x, V y) {
+  const float c = d[SIE_C], s = d[SIE_S], q = d[SIE_Q], sq = d[SIE_SQ];
   V dx = x - d[SIE_CX], dy = y - d[SIE_CY];
-  V xr = dx * c + dy * s, yr = dy * c - dx * s;
-  V ipsi = rcp(sqrt_(xr * xr * (q * q) + yr * yr));
-  V arx = atan_(xr * ipsi * sq) * A, ary = atanh_(yr * ipsi * sq) * A;
+  SieStateV<V> st;
+  st.xr = dx * c + dy * s;
+  st.yr = dy * c - dx * s;
+  st.ipsi = rcp(sqrt_(st.xr * st.xr * (q * q) + st.yr * st.yr));
+  st.u = st.xr * st.ipsi * sq;
+  st.v = st.yr * st.ipsi * sq;
+  st.fu = atan_(st.u);
+  st.fv = atanh_(st.v);
+  return st;
+}
+template <class V> __device__ __forceinline__ void sie_fwd_v(const float* d, V x, V y, V& bx, V& by, SieStateV<V>* keep = nullptr) {
+  const float c = d[SIE_C], s = d[SIE_S], A = d[SIE_A];
+  const SieStateV<V> st = sie_state_v<V>(d, x, y);
+  V arx = st.fu * A, ary = st.fv * A;
   bx -= arx * c - ary * s;
   by -= arx * s + ary * c;
+  if (keep) *keep = st;
 }
-template <class V> __device__ __forceinline__ void sie_vjp_v(const float* d, V x, V y, V gx, V gy, V* acc) {
+template <class V> __device__ __forceinline__ void sie_vjp_v(const float* d, V x, V y, V gx, V gy, V* acc, const SieStateV<V>* kept = nullptr) {
   const float c = d[SIE_C], s = d[SIE_S], q = d[SIE_Q], sq = d[SIE_SQ], A = d[SIE_A];
-  V dx = x - d[SIE_CX], dy = y - d[SIE_CY];
-  V xr = dx * c + dy * s, yr = dy * c - dx * s;
-  V ipsi = rcp(sqrt_(xr * xr * (q * q) + yr * yr));
-  V u = xr * ipsi * sq, v = yr * ipsi * sq;
-  V fu = atan_(u), fv = atanh_(v);
+  const SieStateV<V> st = kept ? *kept : sie_state_v<V>(d, x, y);
+  const V xr = st.xr, yr = st.yr, ipsi = st.ipsi, u = st.u, v = st.v, fu = st.fu, fv = st.fv;
   V arx = fu * A, ary = fv * A;
   V ax = arx * c - ary * s, ay = arx * s + ary * c;
   V grx = gx * c + gy * s, gry = gy * c - gx * s;
@@ -244,17 +291,26 @@ template <class V> __device__ __forceinline__ void shear_vjp_v(V x, V y, V gx, V
   acc[0] += gx * x - gy * y;
   acc[1] += gx * y + gy * x;
 }
-template <class V> __device__ __forceinline__ void sis_fwd_v(const float* d, V x, V y, V& bx, V& by) {
+// FAST: no R0 == 0 selects; `worst` takes the check kGuardRadLo <= R0 <= 1e5 (sis_vjp_v recomputes the same R0)
+template <class V, bool FAST = false> __device__ __forceinline__ void sis_fwd_v(const float* d, V x, V y, V& bx, V& by, unsigned* worst = nullptr) {
   V dx = x - d[SIS_CX], dy = y - d[SIS_CY];
   V R0 = sqrt_(dx * dx + dy * dy);
-  V a = (R0 == V(0.f)) ? V(0.f) : rcp(R0) * d[SIS_TE];
+  V a;
+  if constexpr (FAST) {
+    guard_range(*worst, R0, kGuardRadLo);
+    a = rcp(R0) * d[SIS_TE];
+  } else {
+    a = (R0 == V(0.f)) ? V(0.f) : rcp(R0) * d[SIS_TE];
+  }
   bx -= a * dx;
   by -= a * dy;
 }
-template <class V> __device__ __forceinline__ void sis_vjp_v(const float* d, V x, V y, V gx, V gy, V* acc) {
+template <class V, bool FAST = false> __device__ __forceinline__ void sis_vjp_v(const float* d, V x, V y, V gx, V gy, V* acc) {
   V dx = x - d[SIS_CX], dy = y - d[SIS_CY];
   V R0 = sqrt_(dx * dx + dy * dy);
-  V iR = (R0 == V(0.f)) ? V(0.f) : rcp(R0);
+  V iR;
+  if constexpr (FAST) iR = rcp(R0);
+  else iR = (R0 == V(0.f)) ? V(0.f) : rcp(R0);
   V a = iR * d[SIS_TE];
   V ga = gx * dx + gy * dy;
   V gR0 = -(ga * a * iR);
@@ -268,7 +324,12 @@ template <class V> struct SerStateV { V a1, a2, r2, L2, u, E; };
 
 // ELL = false: the spherical profile (sersic.py:23-66 passes e1 = e2 = 0): no rotation, no axis-ratio stretch and no
 // ellipticity gradients -- 21 packed instructions per pixel pair less over forward + VJP
-template <class V, bool ELL = true> __device__ __forceinline__ V sersic_fwd_v(const float* d, V x, V y, SerStateV<V>& st) {
+// FAST: `worst` takes the check kGuardRadLo <= r2 <= 1e5, under which neither floor of sersic_vjp_v<.., FAST> acts: r2 >= 1e-37,
+// and log2(R / R_sersic) = log2(r2) / 2 + d[SER_L2IRS] lies within 25 of d[SER_L2IRS], which the caller checks once per sample
+// (sersic_fast_ok)
+__device__ __forceinline__ bool sersic_fast_ok(const float* d) { return d[SER_L2IRS] >= -1e29f; }  // (false for a NaN)
+template <class V, bool ELL = true, bool FAST = false>
+__device__ __forceinline__ V sersic_fwd_v(const float* d, V x, V y, SerStateV<V>& st, unsigned* worst = nullptr) {
   V dx = x - d[SER_CX], dy = y - d[SER_CY];
   if constexpr (ELL) {
     const float c = d[SER_C], s = d[SER_S];
@@ -281,12 +342,15 @@ template <class V, bool ELL = true> __device__ __forceinline__ V sersic_fwd_v(co
     st.a2 = dy;
     st.r2 = dx * dx + dy * dy;
   }
+  if constexpr (FAST) {
+    if (worst) guard_range(*worst, st.r2, kGuardRadLo);  // (null in the forward-only modes: no VJP, no floors)
+  }
   st.L2 = log2_(st.r2) * 0.5f + d[SER_L2IRS];  // log2(R / R_sersic) without the square root
   st.u = exp2_(st.L2 * d[SER_INVN]);
   st.E = vexp<V>((st.u - 1.f) * -d[SER_BN]);
   return st.E * d[SER_IE];
 }
-template <class V, bool SRC, bool ELL = true>
+template <class V, bool SRC, bool ELL = true, bool FAST = false>
 __device__ __forceinline__ void sersic_vjp_v(const float* d, const SerStateV<V>& st, V gI, V* acc, V& gpx, V& gpy) {
   // A pixel exactly on the centre (r2 = 0): u = 0 there, so g_u u and g_L are (signed) zeros and the reference's selects
   // (`where(x > 0, ...)` in TF's pow gradient) only keep 0 x inf from becoming NaN.  Flooring r2 and log2(R / Rs) does the same
@@ -295,7 +359,7 @@ __device__ __forceinline__ void sersic_vjp_v(const float* d, const SerStateV<V>&
   V tI = gE * d[SER_IE];
   V guu = -(tI * st.u) * d[SER_BN];
   V gL = guu * d[SER_INVN];
-  V k = gL * rcp(floor_at(st.r2, 1e-37f));
+  V k = gL * rcp(FAST ? st.r2 : floor_at(st.r2, 1e-37f));
   V gdx, gdy;
   if constexpr (ELL) {
     const float c = d[SER_C], s = d[SER_S], sq = d[SER_SQ], isq = d[SER_ISQ];
@@ -313,7 +377,7 @@ __device__ __forceinline__ void sersic_vjp_v(const float* d, const SerStateV<V>&
   acc[SERA_CX] -= gdx;
   acc[SERA_CY] -= gdy;
   acc[SERA_L] += gL;
-  acc[SERA_INVN] += guu * floor_at(st.L2, -1e30f);  // x ln2 in the epilogue
+  acc[SERA_INVN] += guu * (FAST ? st.L2 : floor_at(st.L2, -1e30f));  // x ln2 in the epilogue
   acc[SERA_BN] -= tI * (st.u - 1.f);
   acc[SERA_IE] += gE;
   if (SRC) { gpx += gdx; gpy += gdy; }

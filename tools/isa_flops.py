@@ -258,11 +258,19 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
         branch (register moves only) runs with the complementary probability,
       * the inner loop's preheader runs with probability 1 - `frac_short` (series of fewer than two terms skip the loop),
         the blocks of that bypass with probability `frac_short`,
-      * other conditional blocks (optional loads of the mask / error planes: <= 3 VALU, no flops) are counted as executed.
+      * other conditional blocks (optional loads of the mask / error planes: <= 3 VALU, no flops) are counted as executed,
+      * gl_pair_kernel's steady-state tiles are select-free behind a wave-uniform guard (gl_pair.hip.h): a wave whose guard fires
+        LEAVES the loop for the careful ragged-end loop, so the fallback is outside the tile loop and weighs 0 by itself; the
+        blocks of the loop behind the guard's branch -- the rest of the likelihood and the whole VJP -- no longer dominate the
+        latch in the structurised control flow, and run once per trip: weight 1.
     Returns per-lane flops and VALU wave-instructions per PIXEL, and the decomposition."""
-    # likelihood modes compile the steady-state tile twice, in address order: with an error map, without one (gl_pair.hip.h err_tag),
-    # then the ragged-end tile; image modes have the one steady-state loop and the ragged one
+    # likelihood modes compile the steady-state tile twice, in source (and address) order: with an error map, without one
+    # (gl_pair.hip.h err_tag), and the ragged-end tile once: the loop with the most instructions (validity selects, both variance
+    # forms), wherever the compiler lays it out; image modes have the one steady-state loop and the ragged one
     hot = _hot_loops(cfg)
+    if len(hot) >= 2:
+        ragged = max(hot, key=lambda l: cfg.tally(l.blocks - set().union(*[c.blocks for c in l.children]))["valu"])
+        hot = [l for l in hot if l is not ragged] + [ragged]
     tile = hot[0 if error_map or len(hot) < 3 else 1]
     inner = sorted(tile.children, key=lambda l: l.header)
     inner_blocks = set().union(*[c.blocks for c in inner]) if inner else set()
@@ -273,6 +281,7 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
         mandatory &= cfg.dom[lt]
     mandatory |= {tile.header} & own
     inner_headers = {c.header for c in inner}
+    guards = [b for b in mandatory if _is_tile_guard(cfg, b)]
     out = {k: float(v) for k, v in cfg.tally(mandatory).items()}
     detail = dict(tile_loop_header=hex(tile.header), n_blocks=len(tile.blocks), pixels_per_lane_per_trip=W,
                   mandatory=cfg.tally(mandatory), inner=[], conditional=[])
@@ -284,7 +293,9 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
     for b in sorted(own - mandatory):
         t = cfg.tally([b])
         after_loop = any(h in cfg.dom[b] for h in inner_headers)  # only reachable through the series loop
-        if after_loop and t["packed"] >= 4:
+        if any(g in cfg.dom[b] for g in guards):
+            prob, why = 1.0, "select-free tile behind its guard (the fallback leaves the loop: weight 0)"
+        elif after_loop and t["packed"] >= 4:
             prob, why = frac_odd, "series tail: the term left over by the two-term loop"
         elif after_loop and t["valu"] > 3:
             prob, why = 1.0 - frac_odd, "series tail: the other parity (register moves)"
@@ -300,6 +311,23 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
     per_pixel = {k: v / W for k, v in out.items()}
     detail["per_pixel"] = per_pixel
     return per_pixel, detail
+
+
+GUARD_WIDTH = 0x21391bfa  # csrc/gl_vec.hip.h kGuardWidth: bits(1e10f) - bits(1e-10f)
+
+
+def _is_tile_guard(cfg, b):
+    """The block that ends a select-free tile's forward part: it compares the folded range checks with kGuardWidth and tests the
+    image pair for NaN with ONE unordered compare of its two halves (the careful body compares each half with itself)."""
+    for k in cfg.blocks[b]:
+        addr, mnem, ops, tgt = cfg.ins[k]
+        if mnem.startswith("v_cmp_u_f32"):
+            srcs = [o.strip() for o in ops.split(",")][-2:]
+            if len(srcs) == 2 and srcs[0] != srcs[1]:
+                return True
+        if re.search(r"\b0x%x\b" % GUARD_WIDTH, ops):
+            return True
+    return False
 
 
 def _hot_loops(cfg, min_valu=100):
