@@ -39,6 +39,12 @@ class gl_zcolumn(ctypes.Structure):
                 ("lo", c_float), ("hi", c_float), ("log_norm", c_float)]
 
 
+class gl_workspace_layout(ctypes.Structure):
+    _fields_ = [("params_offset", c_size_t), ("derived_offset", c_size_t), ("order_offset", c_size_t), ("cost_offset", c_size_t),
+                ("params_count", c_size_t), ("derived_count", c_size_t), ("order_count", c_size_t), ("cost_count", c_size_t),
+                ("P", c_int), ("D", c_int), ("p_off", c_int), ("d_off", c_int)]
+
+
 class gl_grid(ctypes.Structure):
     _fields_ = [
         ("height", c_int32), ("width", c_int32), ("supersample", c_int32), ("n_region", c_int32),
@@ -166,6 +172,7 @@ SYMBOLS = {
     "gl_post_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "gl_model_last_post_kernel": (c_int, [c_void_p, c_int, ctypes.c_char_p, c_size_t]),
     "gl_model_launch_shape": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]),
+    "gl_model_workspace_layout": (c_int, [c_void_p, c_int, c_int, POINTER(gl_workspace_layout)]),
     "gl_last_error": (c_char_p, []),
     "gl_version": (c_char_p, []),
 }
@@ -1058,6 +1065,23 @@ class Model:
         ws = self._workspace(B)
         n = B * nc.value * row.value
         return ws[off.value:off.value + 4 * n].view(torch.float32).view(B, nc.value, row.value)
+
+    def workspace_layout(self, B, component=-1):
+        """``gl_model_workspace_layout``: byte offsets / element counts of the ``params``, ``derived``, ``order`` and ``cost`` regions of
+        the workspace of a call on ``B`` samples, the row lengths ``P`` / ``D`` and ``component``'s ``p_off`` / ``d_off`` (host only)."""
+        out = gl_workspace_layout()
+        _check(lib().gl_model_workspace_layout(self._h, int(B), int(component), ctypes.byref(out)))
+        return out
+
+    def workspace_rows(self, B):
+        """Views into the workspace of the most recent call on ``B`` samples (measurement aid): ``params [B, P]`` and ``derived
+        [B, D]`` float32, ``order [B]`` and ``cost [B]`` int32."""
+        lay, ws = self.workspace_layout(B), self._workspace(B)
+        view = lambda off, n, dt: ws[off:off + 4 * n].view(dt)
+        return {"params": view(lay.params_offset, lay.params_count, torch.float32).view(B, lay.P),
+                "derived": view(lay.derived_offset, lay.derived_count, torch.float32).view(B, lay.D),
+                "order": view(lay.order_offset, lay.order_count, torch.int32),
+                "cost": view(lay.cost_offset, lay.cost_count, torch.int32)}
 
     def last_main_ms(self):
         ms = c_float()

@@ -1126,6 +1126,28 @@ int gl_model_launch_shape(const gl_model* m, int B, int* chunk_px, int* n_chunks
   return GL_OK;
 }
 
+int gl_model_workspace_layout(const gl_model* m, int B, int component, gl_workspace_layout* out) {
+  if (!m || !out) return fail(GL_EINVAL, "null argument");
+  if (B < 1 || B > 65535) return fail(GL_EINVAL, "batch size %d outside [1, 65535]", B);
+  if (component < -1 || component >= (int)m->comps.size()) return fail(GL_EINVAL, "component index out of range");
+  const Workspace w = carve(m, B, nullptr, launch_plan(m, B));  // the carve of every call on B samples: nothing is launched
+  auto off = [](const void* p) { return (size_t)((const char*)p - (const char*)nullptr); };
+  *out = gl_workspace_layout{};
+  out->params_offset = off(w.params);
+  out->derived_offset = off(w.derived);
+  out->order_offset = off(w.order);
+  out->cost_offset = off(w.cost);
+  out->params_count = (size_t)B * m->P;
+  out->derived_count = (size_t)B * m->D;
+  out->order_count = (size_t)B;
+  out->cost_count = (size_t)B;
+  out->P = m->P;
+  out->D = m->D;
+  out->p_off = component >= 0 ? m->comps[component].p_off : -1;
+  out->d_off = component >= 0 ? m->comps[component].d_off : -1;
+  return GL_OK;
+}
+
 void gl_model_destroy(gl_model* m) {  // (the device buffers go with their owners: glk::DevBuf)
   if (!m) return;
   if (m->user_module) (void)hipModuleUnload(m->user_module);

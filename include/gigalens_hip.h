@@ -626,6 +626,19 @@ int gl_model_last_post_kernel(const gl_model* m, int transpose, char* buf, size_
  * workgroup's wave-tiles ran the shapelet chains and how many it saw -- what bench.py's instruction model weights the
  * conditional blocks with. */
 int gl_model_launch_shape(const gl_model* m, int B, int* chunk_px, int* n_chunks, int* row_floats, size_t* partial_offset_bytes);
+/* Measurement aid, host only (nothing is launched): where, inside a workspace of gl_workspace_bytes(m, B), a call on B samples
+ * keeps the constrained parameter rows [B][P] (float; written by the z entries, gl_logprob_fwd_bwd), the derived rows [B][D]
+ * (float; the front end's output: per-component constants, the EPL coefficient tables), the dispatch order [B] (int) and the
+ * per-sample cost [B] (int; the EPL trip count the order sorts on) -- byte offsets from the start of the workspace and element
+ * counts.  p_off / d_off: the first column of `component` inside a parameter row / a derived row (component == -1: not asked
+ * for, both -1).  GL_EINVAL: null arguments, B outside [1, 65535], component outside [-1, number of components). */
+typedef struct gl_workspace_layout {
+  size_t params_offset, derived_offset, order_offset, cost_offset;
+  size_t params_count, derived_count, order_count, cost_count;
+  int P, D;
+  int p_off, d_off;
+} gl_workspace_layout;
+int gl_model_workspace_layout(const gl_model* m, int B, int component, gl_workspace_layout* out);
 
 /* ---- Open plugin boundary: user-written profile bodies (csrc/gl_user.hip) -------------------------------------------------------
  * The reference's extension point is a Python subclass with a TensorFlow body: MassProfile.deriv / LightProfile.light are

@@ -47,8 +47,6 @@ def test_front_end_sort_changes_no_bit(gl, monkeypatch, batch):
 
 def test_the_extra_workgroup_sorts_by_the_same_trip_counts(gl):
     """The order the front end's extra workgroup writes is a permutation, sorted by the cost the sample workgroups wrote."""
-    import ctypes
-    from gigalens_amd import _native
     wl = gl.workloads.make("C2", num_pix=32, batch=257)
     obs, err, _ = gl.workloads.synthetic_observation(wl, gl.LensSimulator)
     sim = gl.LensSimulator(wl.phys_model, wl.sim_config, bs=wl.batch)
@@ -57,13 +55,8 @@ def test_the_extra_workgroup_sorts_by_the_same_trip_counts(gl):
     m.loglike(packed, obs, err, None, wl.background_rms, wl.exp_time, True)
     torch.cuda.synchronize()
     B = wl.batch
-    ws = m._workspace(B)
-    chunk, nc, row, off = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
-    _native._check(_native.lib().gl_model_launch_shape(m._h, B, ctypes.byref(chunk), ctypes.byref(nc), ctypes.byref(row), ctypes.byref(off)))
-    al = lambda n: (n + 255) // 256 * 256
-    o_order = off.value + al(B * nc.value * row.value * 4) + al(B * m.P * 4)   # carve(): partial | params | order | cost
-    order = ws[o_order:o_order + 4 * B].view(torch.int32).cpu().numpy()
-    cost = ws[o_order + al(4 * B):o_order + al(4 * B) + 4 * B].view(torch.int32).cpu().numpy()
+    rows = m.workspace_rows(B)  # gl_model_workspace_layout: carve()'s own offsets
+    order, cost = rows["order"].cpu().numpy(), rows["cost"].cpu().numpy()
     assert sorted(order.tolist()) == list(range(B))
     assert np.all(np.diff(cost[order]) <= 0), "not sorted heaviest first"
     assert cost.min() >= 0 and cost.max() > cost.min()
