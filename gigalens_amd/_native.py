@@ -127,6 +127,7 @@ SYMBOLS = {
     "gl_critical_curves": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_pixsrc_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "gl_pixsrc_layout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32)]),
     "gl_pixsrc_reconstruct": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                       c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
@@ -925,6 +926,13 @@ class Model:
                                                      _ptr(source), _ptr(image), _ptr(scalars), _ptr(ok), _ptr(ws), ws.numel(),
                                                      _stream()))
         return source, image, scalars, ok
+
+    def pixsrc_layout(self, B, n_strength, n_src, n_used):
+        """gl_pixsrc_layout: ``dict(cb, lch, pc, n_pad)`` -- samples per chunk, strengths per slice, basis planes per post-processing
+        launch and the padded row length of a ``pixsrc_reconstruct`` call of these sizes (host only)."""
+        out = (c_int32 * 4)()
+        _check(lib().gl_pixsrc_layout(self._h, int(B), int(n_strength), int(n_src[0]), int(n_src[1]), int(n_used), out))
+        return dict(zip(("cb", "lch", "pc", "n_pad"), (int(v) for v in out)))
 
     def _pix_tensor(self, t, dtype, shape, what):
         _require_cuda(t, what)

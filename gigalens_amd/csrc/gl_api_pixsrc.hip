@@ -48,6 +48,14 @@ size_t gl_pixsrc_workspace_bytes(const gl_model* m, int B, int n_strength, int n
   return pix_layout(m, B, n_strength, ny * nx, n_used).bytes;
 }
 
+int gl_pixsrc_layout(const gl_model* m, int B, int n_strength, int ny, int nx, int n_used, int32_t out[4]) {
+  if (!out) return fail(GL_EINVAL, "null argument");
+  if (!pix_sizes_ok(m, B, n_strength, ny, nx, n_used)) return fail(GL_EINVAL, "gl_pixsrc_layout: bad sizes");
+  const PixLayout lay = pix_layout(m, B, n_strength, ny * nx, n_used);
+  out[0] = lay.cb; out[1] = lay.lch; out[2] = lay.pc; out[3] = lay.n_pad;
+  return GL_OK;
+}
+
 int gl_pixsrc_reconstruct(const gl_model* m, const float* beta_x, const float* beta_y, int B, const float* obs, const float* sigma,
                           const float* lens_light, const int* pix, int n_used, int ny, int nx, const float* pose, int regularization,
                           const float* strength, int n_strength, float* source, float* model_image, double* scalars, int* ok,

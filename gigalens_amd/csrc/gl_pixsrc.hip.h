@@ -219,7 +219,8 @@ __global__ void __launch_bounds__(PIX_WG) gl_pix_solve_kernel(PixArgs a) {
     }
   }
   __syncthreads();
-  // (a thread owns row p: where an x and a y neighbour coincide -- nx = 2, p - 2 -- both terms are added, one after the other)
+  // (a thread owns row p, and no two of its additions meet: an x neighbour p - d' and a y neighbour p - d nx coincide only for
+  // d' = d nx, i.e. nx = 1 or nx = 2 with d' = 2, and there i - d' >= 0 never holds)
   bool ok = true;
   double logdet = 0.0;
   const int tr = tid >> 3, tc4 = (tid & 7) * 4;

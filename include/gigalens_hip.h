@@ -520,8 +520,12 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
  * others.  No host synchronisation, no allocation: everything lives in `workspace` (gl_pixsrc_workspace_bytes; 0 for invalid
  * sizes), which is bounded by a chunk of samples and a slice of strengths, not by B or n_strength.
  * GL_EINVAL: null arguments, sizes <= 0, B or n_strength > 65535, n_used > H W, unknown regularization;
- * GL_EUNSUPPORTED: S > 1024. */
+ * GL_EUNSUPPORTED: S > 1024.
+ * gl_pixsrc_layout (host only: no launch, no allocation) reports how a call of these sizes is cut up: out = samples per chunk,
+ * strengths per slice, basis planes per post-processing launch, and n_used rounded up to the tile of the normal matrix.
+ * GL_EINVAL where gl_pixsrc_workspace_bytes answers 0. */
 size_t gl_pixsrc_workspace_bytes(const gl_model* m, int B, int n_strength, int ny, int nx, int n_used);
+int gl_pixsrc_layout(const gl_model* m, int B, int n_strength, int ny, int nx, int n_used, int32_t out[4]);
 int gl_pixsrc_reconstruct(const gl_model* m, const float* beta_x, const float* beta_y, int B, const float* obs, const float* sigma,
                           const float* lens_light, const int* pix, int n_used, int ny, int nx, const float* pose, int regularization,
                           const float* strength, int n_strength, float* source, float* model_image, double* scalars, int* ok,

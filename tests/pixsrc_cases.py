@@ -108,30 +108,26 @@ def used_pixels(rs, mask):
     return np.flatnonzero(used.reshape(-1))
 
 
-def reconstruct(phys, cfg, psf, params, observed, err_map, *, n_src, pitch, center, regularization, strength, mask=None,
-                deflection_scale=1.0, dtype=F64, return_parts=False):
-    """The restatement of ``reconstruct_source``.  ``params``: nested dict of ``[B]`` arrays; ``observed``, ``err_map`` ``[H, W]`` or
-    ``[B, H, W]``; ``pitch``, ``center``: scalars or ``[B]``; ``strength``: ``[B]`` or ``[B, L]`` (taken as the float32 values the
-    library receives).  Returns numpy arrays in ``dtype``: the keys of the call, with the ``L`` axis where ``strength`` is 2-D,
-    plus ``cond`` (the 2-norm condition number of ``M``, float64 runs only).  ``return_parts``: also the per-sample ``(L, F, y, A0, b)``
-    (``"only"``: without solving).  A sample whose Cholesky fails has ``ok`` false and NaN outputs."""
-    from oracle import ref_torch as ref
+def reconstruct_from_rays(rs, fx, fy, lens_light, pix, obs_used, sig_used, *, n_src, pitch, center, regularization, strength,
+                          dtype=F64, return_parts=False):
+    """The restatement from the rays on: ``rs`` supplies the frame, the supersampling, the PSF and the flux scale only.  ``fx, fy``
+    ``[Hs Ws, B]`` (source-plane positions on the supersampled frame), ``lens_light`` ``[B, H W]`` or None, ``pix`` ``[n_used]``,
+    ``obs_used``, ``sig_used`` ``[B, n_used]`` (so they may differ per sample); ``pitch``, ``center``: scalars or ``[B]``; ``strength``:
+    ``[B]`` or ``[B, L]``.  Every input is taken as the float32 values the library receives and converted to ``dtype``.  Returns as
+    ``reconstruct`` does."""
     nd = _np_dtype(dtype)
     lam = np.asarray(strength, dtype=np.float32)
     B = lam.shape[0]
     scan = lam.ndim == 2
     lam = lam.reshape(B, -1).astype(nd)
-    tparams = {g: [{k: torch.as_tensor(np.asarray(v, dtype=np.float32)).to(dtype).reshape(-1).expand(B) for k, v in d.items()}
-                   for d in lst] for g, lst in params.items()}
-    rs = ref.RefSimulator(phys, cfg, B, dtype=dtype, supersampled_kernel=psf)
     ny, nx = n_src
     S, Lk = ny * nx, lam.shape[1]
     H, W = rs.wcs.n_x, rs.wcs.n_y
-    fx, fy = frame_beta(rs, tparams["lens_mass"], deflection_scale)
-    ll = lens_light_image(rs, tparams).numpy()
-    pix = used_pixels(rs, mask)
-    obs = np.broadcast_to(np.asarray(observed, dtype=np.float32).astype(nd).reshape(-1, H * W), (B, H * W))
-    sig = np.broadcast_to(np.asarray(err_map, dtype=np.float32).astype(nd).reshape(-1, H * W), (B, H * W))[:, pix]
+    fx, fy = torch.as_tensor(fx).to(dtype), torch.as_tensor(fy).to(dtype)
+    pix = np.asarray(pix, dtype=np.int64)
+    ll = np.zeros((B, H * W), dtype=nd) if lens_light is None else np.asarray(lens_light).astype(nd).reshape(B, H * W)
+    obs = np.broadcast_to(np.asarray(obs_used).astype(nd), (B, pix.size))
+    sig = np.broadcast_to(np.asarray(sig_used).astype(nd), (B, pix.size))
     pitch = np.broadcast_to(np.asarray(pitch, dtype=np.float32), (B,))
     cx = np.broadcast_to(np.asarray(center[0], dtype=np.float32), (B,))
     cy = np.broadcast_to(np.asarray(center[1], dtype=np.float32), (B,))
@@ -144,12 +140,13 @@ def reconstruct(phys, cfg, psf, params, observed, err_map, *, n_src, pitch, cent
     for b in range(B):
         Lm = mapping(fx[:, b], fy[:, b], n_src, pitch[b], cx[b], cy[b])
         F = operator(rs, Lm).numpy()[pix]
-        y = obs[b, pix] - ll[b].reshape(-1)[pix]
+        y = obs[b] - ll[b][pix]
         Fw, yw = F / sig[b][:, None], y / sig[b]
         with np.errstate(over="ignore", invalid="ignore"):
             A0, rhs = Fw.T @ Fw, Fw.T @ yw
         parts.append((Lm.numpy(), F, y, A0, rhs))
-        noise = np.sum(np.log(nd(2 * math.pi) * sig[b] ** 2), dtype=nd)
+        with np.errstate(divide="ignore"):  # (an rms whose square underflows: the broken-pivot cases)
+            noise = np.sum(np.log(nd(2 * math.pi) * sig[b] ** 2), dtype=nd)
         for l in range(0 if return_parts == "only" else Lk):
             with np.errstate(over="ignore", invalid="ignore"):
                 M = A0 + lam[b, l] * R
@@ -164,7 +161,7 @@ def reconstruct(phys, cfg, psf, params, observed, err_map, *, n_src, pitch, cent
             chi2 = np.sum(((y - fs) / sig[b]) ** 2, dtype=nd)
             reg = s @ (R @ s)
             log_det = 2 * np.sum(np.log(np.diag(C)), dtype=nd)
-            img = ll[b].reshape(-1).copy()
+            img = ll[b].copy()
             img[pix] += fs
             out["ok"][b, l] = True
             out["source"][b, l] = s.reshape(ny, nx)
@@ -178,6 +175,30 @@ def reconstruct(phys, cfg, psf, params, observed, err_map, *, n_src, pitch, cent
     if not scan:
         out = {k: v[:, 0] for k, v in out.items()}
     return (out, parts) if return_parts else out
+
+
+def reconstruct(phys, cfg, psf, params, observed, err_map, *, n_src, pitch, center, regularization, strength, mask=None,
+                deflection_scale=1.0, dtype=F64, return_parts=False):
+    """The restatement of ``reconstruct_source``.  ``params``: nested dict of ``[B]`` arrays; ``observed``, ``err_map`` ``[H, W]`` or
+    ``[B, H, W]``; ``pitch``, ``center``: scalars or ``[B]``; ``strength``: ``[B]`` or ``[B, L]`` (taken as the float32 values the
+    library receives).  Returns numpy arrays in ``dtype``: the keys of the call, with the ``L`` axis where ``strength`` is 2-D,
+    plus ``cond`` (the 2-norm condition number of ``M``, float64 runs only).  ``return_parts``: also the per-sample ``(L, F, y, A0, b)``
+    (``"only"``: without solving).  A sample whose Cholesky fails has ``ok`` false and NaN outputs.  The rays come from the lens of
+    ``params``; everything after them is ``reconstruct_from_rays``."""
+    from oracle import ref_torch as ref
+    nd = _np_dtype(dtype)
+    B = np.asarray(strength).shape[0]
+    tparams = {g: [{k: torch.as_tensor(np.asarray(v, dtype=np.float32)).to(dtype).reshape(-1).expand(B) for k, v in d.items()}
+                   for d in lst] for g, lst in params.items()}
+    rs = ref.RefSimulator(phys, cfg, B, dtype=dtype, supersampled_kernel=psf)
+    H, W = rs.wcs.n_x, rs.wcs.n_y
+    fx, fy = frame_beta(rs, tparams["lens_mass"], deflection_scale)
+    ll = lens_light_image(rs, tparams).numpy().reshape(B, H * W)
+    pix = used_pixels(rs, mask)
+    obs = np.broadcast_to(np.asarray(observed, dtype=np.float32).astype(nd).reshape(-1, H * W), (B, H * W))[:, pix]
+    sig = np.broadcast_to(np.asarray(err_map, dtype=np.float32).astype(nd).reshape(-1, H * W), (B, H * W))[:, pix]
+    return reconstruct_from_rays(rs, fx, fy, ll, pix, obs, sig, n_src=n_src, pitch=pitch, center=center,
+                                 regularization=regularization, strength=strength, dtype=dtype, return_parts=return_parts)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -311,3 +332,259 @@ def errors(got, ref, S):
     for k in SCALARS:
         out[k] = float((np.abs(np.asarray(got[k], dtype=np.float64) - ref[k]) / norm).max())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the case matrix of tests/test_gpu_pixsrc_matrix.py: rays of the tests' own handed to the native call, one case per block, chunk,
+# slice, stencil and range edge of csrc/gl_pixsrc.hip.h and csrc/gl_api_pixsrc.hip.  The simulator supplies the frame, the
+# supersampling and the PSF alone (pixel scale 1, so the flux scale of the operator is 1).
+# ---------------------------------------------------------------------------------------------------------------------
+MATRIX_DELTA_PIX = 1.0
+PIX_TK, PIX_MAX_L_SLICE, PIX_MAX_PLANES = 32, 4, 4096
+PIX_CHUNK_BUDGET, PIX_PLANE_BUDGET = 256 << 20, 32 << 20
+
+
+def layout(frame, supersample, psf, B, L, S, n_used):
+    """``dict(cb, lch, pc, n_pad)``: the host loops' split, restated from the budgets of csrc/gl_api_pixsrc.hip (float32 workspace:
+    per sample the operator ``S n_pad``, ``yw``, ``A0``, ``lch`` factors and ``b``; per basis plane the supersampled plane, where the
+    model post-processes, and the pooled one)."""
+    HW = frame[0] * frame[1]
+    HsWs = HW * supersample * supersample
+    n_pad = -(-n_used // PIX_TK) * PIX_TK
+    lch = min(L, PIX_MAX_L_SLICE)
+    per_sample = 4 * (S * n_pad + n_pad + S * S * (1 + lch) + S)
+    cb = max(1, min(B, PIX_CHUNK_BUDGET // per_sample))
+    per_plane = 4 * ((HsWs if (psf is not None or supersample != 1) else 0) + HW)
+    pc = max(1, min(cb * S, PIX_MAX_PLANES, PIX_PLANE_BUDGET // per_plane))
+    return dict(cb=cb, lch=lch, pc=pc, n_pad=n_pad)
+
+
+def splits(total, step):
+    """The lengths of the iterations of ``for i0 in range(0, total, step)``."""
+    return [min(step, total - i0) for i0 in range(0, total, step)]
+
+
+def _m(group, n_src, reg, *, frame=(16, 16), ss=1, psf=None, B=1, L=1, n_used=None, lens_light=False, pose="shared", lam=None,
+       sigma0=0.05, sits_on=""):
+    return dict(group=group, n_src=n_src, reg=reg, frame=frame, ss=ss, psf=psf, B=B, L=L, n_used=n_used, lens_light=lens_light,
+                pose=pose, lam=lam, sigma0=sigma0, sits_on=sits_on)
+
+
+def _matrix():
+    m = {}
+    # solve blocks: no PSF, supersample 1, all pixels used, B = 2, L = 1
+    for n_src, reg, frame, B, on in (((4, 8), "gradient", (16, 16), 2, "one full block, no panel"),
+                                     ((3, 11), "curvature", (16, 16), 2, "a panel of one row, a last block of one"),
+                                     ((8, 8), "identity", (16, 16), 2, "two full blocks"),
+                                     ((5, 13), "gradient", (16, 16), 2, "two full blocks and a last block of one"),
+                                     ((16, 18), "gradient", (32, 32), 2, "the last S with one stride of the 256-row loops"),
+                                     ((17, 17), "gradient", (32, 32), 2, "the first S with a second stride"),
+                                     ((32, 32), "curvature", (32, 32), 1, "the cap: 32 blocks, 528 normal tiles")):
+        m[f"solve_S{n_src[0] * n_src[1]}"] = _m("solve", n_src, reg, frame=frame, B=B, sits_on=on)
+    # the same 289 nodes under a 3 x 3 PSF: with the recipe's unrelated rays the PSF makes A0 dense (94 % of its entries), where the
+    # cases above have a banded M whose rows a second stride of the 256-row loops reaches hold zeros only
+    m["dense_S289"] = _m("solve", (17, 17), "gradient", frame=(32, 32), psf=gauss_psf((3, 3), 0.8), B=2,
+                         sits_on="the second stride of the 256-row loops on non-zero rows")
+    # stencil ends: every branch of pix_r1 (n = 1, 2, >= 3; corner and interior diagonals; |d| = 1 and 2 along either axis)
+    for reg in ("gradient", "curvature"):
+        for n_src in ((1, 1), (1, 2), (2, 1), (1, 33), (33, 1)):
+            m[f"stencil_{reg}_{n_src[0]}x{n_src[1]}"] = _m("stencil", n_src, reg)
+    for n_src in ((2, 16), (16, 2), (3, 3), (3, 11)):
+        m[f"stencil_curvature_{n_src[0]}x{n_src[1]}"] = _m("stencil", n_src, "curvature")
+    # pixel counts against the tile of 32: S = 40, 12 x 10 at supersample 2 with a 3 x 3 PSF; n_used < S leaves A0 singular
+    for n in (5, 31, 32, 33, 64, 95, 120):
+        m[f"pixels_{n}"] = _m("pixels", (5, 8), "gradient", frame=(12, 10), ss=2, psf=gauss_psf((3, 3), 0.8), B=2, n_used=n,
+                              lens_light=n != 33, sits_on="n_used < S" if n < 40 else f"n_used % 32 = {n % 32}")
+    m["frame_255"] = _m("pixels", (5, 8), "gradient", frame=(15, 17), B=2, sits_on="HsWs = 255: the q guard of the planes kernel")
+    # rays placed by hand (matrix_inputs), B = 3
+    for reg in ("identity", "curvature"):
+        m[f"hand_{reg}"] = _m("hand", (5, 9), reg, B=3, pose="hand")
+    # host loops
+    for L in (5, 8, 9):
+        m[f"slices_{L}"] = _m("loops", (3, 11), "gradient", B=3, L=L, sits_on="slices of " + " + ".join(map(str, splits(L, 4))))
+    m["planes_budget"] = _m("loops", (5, 9), "gradient", frame=(64, 64), ss=2, psf=gauss_psf((3, 3), 0.8), B=10,
+                            sigma0=0.5, sits_on="the 32 MB of planes: a launch ends inside a sample")
+    m["planes_cap"] = _m("loops", (10, 10), "gradient", frame=(10, 10), B=41, sits_on="4096 planes per launch")
+    cb = layout((32, 32), 1, None, 65535, 5, 1024, 1024)["cb"]
+    m["chunks"] = _m("loops", (32, 32), "gradient", frame=(32, 32), B=cb + 1, L=5, lens_light=True, pose="per_sample",
+                     sits_on="a second chunk of samples and a second slice together")
+    # a pivot failure after the first block (matrix_inputs); a harder system with a gate of its own
+    m["pivot"] = _m("pivot", (5, 8), "gradient", frame=(12, 10), B=2, sits_on="a pivot that is not finite in the second block")
+    m["hard"] = _m("hard", (17, 17), "gradient", B=2, lam=HARD_STRENGTH, sits_on="cond(M) in [1e3, 1e4]")
+    return m
+
+
+# planes_budget: at the recipe's rms of 0.05 the float32 sums over its 4096 used pixels put the yardstick of the source at 1.2e-5,
+# past the cap of the main gates; at 0.5 it is 1.2e-6.  hard: 256 rays on 289 nodes leave A0 singular, and the strength is lowered on
+# the float64 reference until cond(M) lies in [1e3, 1e4] (2e3 and 4e3; asserted by the tests).
+HARD_STRENGTH = 0.2
+PIVOT_NODE = 35
+MATRIX = _matrix()
+MAIN = tuple(n for n, c in MATRIX.items() if c["group"] not in ("pivot", "hard"))  # the cases that share the main gates
+LOOPS = tuple(n for n, c in MATRIX.items() if c["group"] == "loops")
+_MDATA = {}
+
+
+def matrix_sim_args(name):
+    """``(phys, cfg, psf)`` of the simulator of a case: any one-lens model does, its lens is not used."""
+    from gigalens_amd.model import PhysicalModel
+    from gigalens_amd.profiles.light.sersic import Sersic
+    from gigalens_amd.profiles.mass.sie import SIE
+    from gigalens_amd.simulator import SimulatorConfig
+    c = MATRIX[name]
+    return (PhysicalModel([SIE()], [], [Sersic()]), SimulatorConfig(delta_pix=MATRIX_DELTA_PIX, num_pix=c["frame"], supersample=c["ss"]),
+            c["psf"])
+
+
+def _hand_uv(n_src, Q, rng):
+    """Sample 0 of the hand-placed cases: ``u, v [Q]`` (float64; exact in float32 under the dyadic pose of these cases).  Node
+    ``(2, 4)`` is touched by no ray: no ray lies in its support ``(3, 5) x (1, 3)``."""
+    ny, nx = n_src
+    u, v = [], []
+    for j in range(ny):  # exactly on every node bar (2, 4): unit rows
+        for i in range(nx):
+            if (j, i) != (2, 4):
+                u.append(float(i)), v.append(float(j))
+    steps = []  # (ray, axis, edge, direction): matrix_inputs moves the ray's beta to the first float32 past the edge
+    for axis, n in ((0, nx), (1, ny)):
+        for e, d in ((-2.0, 0), (-1.0, 0), (float(n), 0), (n + 1.0, 0), (-2.0, -1), (-2.0, 1), (n + 1.0, -1), (n + 1.0, 1)):
+            if d:
+                steps.append((len(u), axis, e, d))
+            u.append(e if axis == 0 else 0.5), v.append(0.5 if axis == 0 else e)
+    for e in (-0.75, -0.25, nx - 0.75, nx - 0.25):  # inside (-1, 0) and (nx - 1, nx): half-supported border cells
+        u.append(e), v.append(1.25)
+    for e in (-0.75, -0.25, ny - 0.75, ny - 0.25):
+        u.append(0.25), v.append(e)
+    for bad in (float("nan"), float("inf"), float("-inf")):
+        u.append(bad), v.append(1.0)
+        u.append(1.0), v.append(bad)
+    n = Q - len(u)
+    assert n > 0
+    uu, vv = rng.uniform(-1, nx, size=4 * n), rng.uniform(-1, ny, size=4 * n)
+    keep = ~((uu > 3) & (uu < 5) & (vv > 1) & (vv < 3))
+    return np.concatenate([u, uu[keep][:n]]), np.concatenate([v, vv[keep][:n]]), steps
+
+
+def grid_coordinate(beta, pitch, c, n):
+    """``u`` (or ``v``) of a float32 ``beta`` in the float32 arithmetic of the planes kernel."""
+    return (np.float32(beta) - np.float32(c)) / np.float32(pitch) + np.float32(0.5) * np.float32(n - 1)
+
+
+def matrix_inputs(name):
+    """The float32 inputs of the native call for a case, as numpy: ``beta_x, beta_y [B, Hs Ws]``, ``obs, sigma [B, n_used]``,
+    ``lens_light [B, H W]`` or None, ``pix [n_used]`` int32, ``pose [B, 3]``, ``strength [B, L]``; plus the float64 ``u, v`` they
+    were made from.  The recipe: seeded uniform rays with ``u`` in ``[-1, nx]``, ``v`` in ``[-1, ny]``; ``sigma = 0.05 (1 + 0.1 b)``;
+    strengths between 10 and 100; ``obs = lens light + F s_true + noise`` formed in float64 (by ``matrix_data``)."""
+    import zlib
+    c = MATRIX[name]
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    (ny, nx), B, L = c["n_src"], c["B"], c["L"]
+    (H, W), ss = c["frame"], c["ss"]
+    HW, Q = H * W, H * W * ss * ss
+    u, v = rng.uniform(-1, nx, size=(B, Q)), rng.uniform(-1, ny, size=(B, Q))
+    bidx = np.arange(B)
+    if c["pose"] == "per_sample":
+        pose = np.stack([0.5 * (1 + 0.02 * bidx), 0.1 * bidx - 0.3, 0.2 - 0.05 * bidx], axis=1)
+    elif c["pose"] == "hand":  # dyadic: u and v of the hand-placed rays are exact in float32 and float64 alike
+        pose = np.stack([np.full(B, 0.5), np.full(B, 0.25), np.full(B, -0.5)], axis=1)
+    else:
+        pose = np.stack([np.full(B, 0.37), np.full(B, 0.11), np.full(B, -0.07)], axis=1)
+    pose = pose.astype(np.float32)
+    if c["group"] == "hand":
+        u[0], v[0], steps = _hand_uv(c["n_src"], Q, rng)
+        u[1] = np.where(rng.uniform(size=Q) < 0.5, rng.uniform(-40, -1, size=Q), rng.uniform(nx, nx + 40, size=Q))  # every ray misses
+    pix = np.arange(HW)
+    if c["n_used"] is not None and c["n_used"] < HW:  # scattered, keeping the first and the last pixel
+        pix = np.sort(np.concatenate([[0, HW - 1], 1 + rng.choice(HW - 2, size=c["n_used"] - 2, replace=False)]))
+    sigma = np.repeat((c["sigma0"] * (1 + 0.1 * bidx))[:, None], pix.size, axis=1)
+    if c["group"] == "pivot":  # sample 0: the ray of used pixel 7 sits exactly on node PIVOT_NODE, and that pixel's rms is 1e-25
+        u[0, 7], v[0, 7] = PIVOT_NODE % nx, PIVOT_NODE // nx
+        sigma[0, 7] = 1e-25
+    with np.errstate(invalid="ignore"):
+        bx = pose[:, 1:2].astype(np.float64) + (u - (nx - 1) / 2) * pose[:, 0:1].astype(np.float64)
+        by = pose[:, 2:3].astype(np.float64) + (v - (ny - 1) / 2) * pose[:, 0:1].astype(np.float64)
+    bx, by = bx.astype(np.float32), by.astype(np.float32)
+    if c["group"] == "hand":  # one float32 step either side of -2 and n + 1: the first beta whose float32 u lies past the edge
+        for q, axis, e, d in steps:
+            beta, n = (bx, nx) if axis == 0 else (by, ny)
+            while not (grid_coordinate(beta[0, q], pose[0, 0], pose[0, 1 + axis], n) - np.float32(e)) * d > 0:
+                beta[0, q] = np.nextafter(beta[0, q], np.float32(d * np.inf))
+    if c["lam"] is not None:
+        lam = np.full((B, L), c["lam"])
+    else:
+        lam = (np.geomspace(10, 90, L) if L > 1 else np.asarray([30.0]))[None, :] * (1 + 0.1 * bidx / max(B - 1, 1))[:, None]
+    ll = None
+    if c["lens_light"]:
+        jj, ii = np.mgrid[:H, :W]
+        ll = np.stack([(2.0 + 0.1 * b) * np.exp(-0.5 * (((jj - H / 2) / (0.3 * H)) ** 2 + ((ii - W / 2) / (0.3 * W)) ** 2))
+                       for b in range(B)]).reshape(B, HW).astype(np.float32)
+    noise = rng.normal(size=(B, pix.size))
+    return dict(beta_x=bx, beta_y=by, sigma=sigma.astype(np.float32), lens_light=ll,
+                pix=pix.astype(np.int32), pose=pose, strength=lam.astype(np.float32), u=u, v=v, noise=noise)
+
+
+def matrix_rs(name, B, dtype=F64):
+    from oracle import ref_torch as ref
+    phys, cfg, psf = matrix_sim_args(name)
+    return ref.RefSimulator(phys, cfg, B, dtype=dtype, supersampled_kernel=psf)
+
+
+def matrix_reference(name, inp, dtype=F64, samples=None, return_parts=False):
+    """``reconstruct_from_rays`` on the inputs of ``matrix_inputs`` (``inp["obs"]`` included), for all or some ``samples``."""
+    c = MATRIX[name]
+    sel = np.arange(c["B"]) if samples is None else np.asarray(samples)
+    rs = matrix_rs(name, len(sel), dtype)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a[sel].T))
+    return reconstruct_from_rays(rs, t(inp["beta_x"]), t(inp["beta_y"]), None if inp["lens_light"] is None else inp["lens_light"][sel],
+                                 inp["pix"], inp["obs"][sel], inp["sigma"][sel], n_src=c["n_src"], pitch=inp["pose"][sel, 0],
+                                 center=(inp["pose"][sel, 1], inp["pose"][sel, 2]), regularization=c["reg"],
+                                 strength=inp["strength"][sel], dtype=dtype, return_parts=return_parts)
+
+
+def matrix_data(name):
+    """``(case, inputs with obs, reference dict (float64), yardstick dict (float32))`` of a case of ``MATRIX``, computed once and left
+    unchanged.  Every output carries the ``L`` axis."""
+    if name not in _MDATA:
+        c = MATRIX[name]
+        inp = matrix_inputs(name)
+        B, n_used = c["B"], inp["pix"].size
+        inp["obs"] = np.zeros((B, n_used), dtype=np.float32)
+        _, parts = matrix_reference(name, {**inp, "sigma": np.ones_like(inp["sigma"])}, return_parts="only")
+        ll = np.zeros((B, n_used)) if inp["lens_light"] is None else inp["lens_light"].astype(np.float64)[:, inp["pix"]]
+        clean = np.stack([parts[b][1] @ smooth_source(c["n_src"], b % 3).reshape(-1) for b in range(B)])  # F s_true, float64
+        inp["obs"] = (ll + clean + inp["sigma"].astype(np.float64).clip(max=1.0) * inp["noise"]).astype(np.float32)
+        _MDATA[name] = (c, inp, matrix_reference(name, inp), matrix_reference(name, inp, dtype=torch.float32))
+    return _MDATA[name]
+
+
+def _case_layout(name):
+    c = MATRIX[name]
+    n_used = c["n_used"] or c["frame"][0] * c["frame"][1]
+    return layout(c["frame"], c["ss"], c["psf"], c["B"], c["L"], c["n_src"][0] * c["n_src"][1], n_used)
+
+
+def check_split(name, lay):
+    """Asserts on a layout (the library's ``pixsrc_layout`` or the restatement ``layout``) that the host loop a case of ``LOOPS`` is
+    named for makes at least two iterations, with the split the case states."""
+    c = MATRIX[name]
+    B, L, S = c["B"], c["L"], c["n_src"][0] * c["n_src"][1]
+    if name.startswith("slices_"):
+        assert splits(L, lay["lch"]) == {5: [4, 1], 8: [4, 4], 9: [4, 4, 1]}[L]
+    elif name == "planes_budget":
+        assert lay["cb"] == B and lay["pc"] < B * S and lay["pc"] % S != 0  # a launch ends inside a sample
+        assert len(splits(B * S, lay["pc"])) >= 2
+    elif name == "planes_cap":
+        assert lay["cb"] == B and lay["pc"] == PIX_MAX_PLANES and len(splits(B * S, lay["pc"])) == 2
+    elif name == "chunks":
+        assert lay["cb"] < B and lay["lch"] < L  # b0 and l0 are non-zero together
+        assert splits(B, lay["cb"]) == [B - 1, 1] and splits(L, lay["lch"]) == [4, 1]
+        assert len(splits(lay["cb"] * S, lay["pc"])) >= 2
+    else:
+        raise KeyError(name)
+
+
+def alone_samples(name):
+    """The samples of a host-loop case that are run again alone: the first, one in the middle, the last (for ``chunks`` the one in
+    the second chunk) and the one inside which the first launch of planes ends."""
+    c, lay = MATRIX[name], _case_layout(name)
+    return sorted({0, c["B"] // 2, c["B"] - 1, min(lay["pc"] // (c["n_src"][0] * c["n_src"][1]), c["B"] - 1)})
