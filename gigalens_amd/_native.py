@@ -652,8 +652,20 @@ class Model:
         self.offsets = [L.gl_model_param_offset(h, i) for i in range(n)]
         self.out_h, self.out_w = height // supersample, width // supersample
         self.ss_h, self.ss_w = int(height), int(width)
-        self._ws = {}
         self.n_planes = 1  # lens planes (set_lens_planes)
+        # what others bind to this model, and how they tell that it still holds
+        self.prior_owner = None  # the probabilistic model whose prior set_prior last took (the binder sets it)
+        self.positions_owner = None  # ... whose image positions set_positions last took
+        self.generation = 0  # bumped by every set_*: a HIP graph captured at another generation holds stale device pointers
+        self._ws = {}  # {B: workspace} of the latest batch size
+        self._scratch_bufs = {}  # {name: workspace} of the calls that size their own (_scratch)
+        self._timing_slots = 0
+
+    def _changed(self, layout):
+        """Every set_* ends here once the library has taken the new state.  ``layout``: the workspace layout follows it."""
+        self.generation += 1
+        if layout:
+            self._ws = {}
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -667,7 +679,7 @@ class Model:
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_catalogue(self._h, int(component), int(base_kind), int(t.shape[0]), col_arr,
                                                 t.ctypes.data_as(POINTER(c_float))))
-        self._ws = {}  # the workspace grows with the catalogue
+        self._changed(True)  # the workspace grows with the catalogue
 
     def set_light_image(self, component, image):
         """Attach the image of a GL_INTERPOL light (gl_model_set_light_image): ``image`` a 2-D float32 host array."""
@@ -675,6 +687,7 @@ class Model:
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_light_image(self._h, int(component), int(img.shape[0]), int(img.shape[1]),
                                                   img.ctypes.data_as(POINTER(c_float))))
+        self._changed(False)
 
     def _points(self, x, y, B):
         """``x, y`` broadcastable to ``(..., B)`` as contiguous ``[n_pts, B]`` tensors, and that shape."""
@@ -685,10 +698,9 @@ class Model:
 
     def _scratch(self, name, nbytes):
         """The scratch workspace ``name`` of at least ``nbytes`` bytes, grown on demand."""
-        ws = getattr(self, name, None)
+        ws = self._scratch_bufs.get(name)
         if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-            setattr(self, name, ws)
+            ws = self._scratch_bufs[name] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
         return ws
 
     def lens_maps(self, params, x, y):
@@ -725,7 +737,7 @@ class Model:
         s = np.ascontiguousarray(scales, dtype=np.float32)
         with torch.cuda.device(self.device):
             _check_potential(lib().gl_model_set_source_scales(self._h, s.ctypes.data_as(POINTER(c_float)), int(s.size)))
-        self._ws = {}  # the launch plan, and with it the workspace layout, follows the kernels that serve a scaled model
+        self._changed(True)  # the launch plan, and with it the workspace layout, follows the kernels that serve a scaled model
 
     def set_lens_planes(self, plane_of_lens, lens_scales, source_scales):
         """Lens planes at redshifts of their own (gl_model_set_lens_planes): ``plane_of_lens`` one int per lens, ``lens_scales``
@@ -743,7 +755,7 @@ class Model:
                                                             C.ctypes.data_as(POINTER(c_float)), S.ctypes.data_as(POINTER(c_float)),
                                                             int(S.shape[1])))
         self.n_planes = int(C.shape[0])
-        self._ws = {}  # the workspace holds the materialised image of the pixel statistics
+        self._changed(True)  # the workspace holds the materialised image of the pixel statistics
 
     def _single_plane(self, what):
         if self.n_planes >= 2:
@@ -803,6 +815,7 @@ class Model:
         with torch.cuda.device(self.device):
             _check_potential(lib().gl_model_set_position_targets(self._h, t.ctypes.data_as(POINTER(c_float)), int(t.shape[0]),
                                                                  int(t.shape[1])))
+        self._changed(False)
 
     def multiplane_positions(self, params, want_grad):
         """gl_multiplane_positions_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the image-position likelihood with
@@ -814,6 +827,7 @@ class Model:
         s = np.ascontiguousarray(scales, dtype=np.float32)
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_position_scales(self._h, s.ctypes.data_as(POINTER(c_float)), int(s.size)))
+        self._changed(False)
 
     def set_position_fluxes(self, fluxes, errors):
         """The measured fluxes of the images and their errors (gl_model_set_position_fluxes; after ``set_positions``, which clears
@@ -822,12 +836,13 @@ class Model:
         with torch.cuda.device(self.device):
             if fluxes is None:
                 _check(lib().gl_model_set_position_fluxes(self._h, None, None, 0))
-                return
-            F = np.ascontiguousarray(fluxes, dtype=np.float32).reshape(-1)
-            s = np.ascontiguousarray(errors, dtype=np.float32).reshape(-1)
-            if F.size != s.size:
-                raise NativeLibraryError("fluxes and their errors must have the same length")
-            _check(lib().gl_model_set_position_fluxes(self._h, fp(F), fp(s), int(F.size)))
+            else:
+                F = np.ascontiguousarray(fluxes, dtype=np.float32).reshape(-1)
+                s = np.ascontiguousarray(errors, dtype=np.float32).reshape(-1)
+                if F.size != s.size:
+                    raise NativeLibraryError("fluxes and their errors must have the same length")
+                _check(lib().gl_model_set_position_fluxes(self._h, fp(F), fp(s), int(F.size)))
+        self._changed(False)
 
     def position_fluxes(self, params, want_grad, want_model=False):
         """gl_position_fluxes_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the flux-ratio term on one plane or on
@@ -857,7 +872,7 @@ class Model:
             raise NativeLibraryError(f"source positions must be [B={B}, S], got {tuple(src_x.shape)} / {tuple(src_y.shape)}")
         S = src_x.shape[1]
         nbytes = lib().gl_image_positions_workspace_bytes(self._h, B, S, int(n_cells), int(max_images))
-        ws = self._scratch("_img_ws", nbytes)
+        ws = self._scratch("image_positions", nbytes)
         out = torch.empty((B, S, max(int(max_images), 1), 3), dtype=torch.float32, device=self.device)
         n_images = torch.empty((B, S), dtype=torch.int32, device=self.device)
         n_dropped = torch.empty_like(n_images)
@@ -882,7 +897,7 @@ class Model:
         params = self._params(params)
         B, M = params.shape[0], int(max_segments)
         nbytes = lib().gl_critical_curves_workspace_bytes(self._h, B, int(n_cells), M)
-        ws = self._scratch("_crit_ws", nbytes)
+        ws = self._scratch("critical_curves", nbytes)
         seg = torch.empty((B, max(M, 1), 2, 2), dtype=torch.float32, device=self.device)
         cau = torch.empty_like(seg)
         kind = torch.empty((B, max(M, 1)), dtype=torch.int32, device=self.device)
@@ -916,7 +931,7 @@ class Model:
         if lens_light is not None:
             lens_light = f32(lens_light, (B, self.out_h, self.out_w), "lens_light")
         nbytes = lib().gl_pixsrc_workspace_bytes(self._h, B, L, ny, nx, n_used)
-        ws = self._scratch("_pix_ws", nbytes)
+        ws = self._scratch("pixsrc", nbytes)
         source = torch.empty((B, L, ny, nx), dtype=torch.float32, device=self.device)
         image = torch.empty((B, L, self.out_h, self.out_w), dtype=torch.float32, device=self.device)
         scalars = torch.empty((B, L, 3), dtype=torch.float64, device=self.device)
@@ -949,7 +964,7 @@ class Model:
         params = self._params(params)
         B, D = params.shape[0], self.num_linear()
         nbytes = lib().gl_lstsq_workspace_bytes(self._h, B)
-        ws = self._scratch("_lstsq_ws", nbytes)
+        ws = self._scratch("lstsq", nbytes)
         dev = params.device
         coeffs = torch.empty((B, D), dtype=torch.float32, device=dev) if want == "coeffs" else None
         stacked = torch.empty((B, D, self.out_h, self.out_w), dtype=torch.float32, device=dev) if want == "stacked" else None
@@ -965,6 +980,11 @@ class Model:
         _check(lib().gl_lstsq_solve_flags(self._h, B, ctypes.byref(off)))
         return self._lstsq_ws[off.value:off.value + 4 * B].view(torch.int32)
 
+    @property
+    def _lstsq_ws(self):
+        """The workspace of the most recent ``lstsq`` (measurement aid: the dispatch tests pre-fill it)."""
+        return self._scratch_bufs["lstsq"]
+
     def set_series(self, component, r0, coeffs):
         """Attach the coefficient field of a GL_SERIES lens (gl_model_set_series)."""
         _require_cuda(coeffs, "series coefficients")
@@ -972,6 +992,7 @@ class Model:
             raise NativeLibraryError(f"series field has {coeffs.shape[-1]} points, the model grid {self.N}")
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_series(self._h, int(component), float(r0), _ptr(coeffs.contiguous())))
+        self._changed(False)
 
     def set_series_hessian(self, component, coeffs):
         """Attach the Hessian field of a GL_SERIES lens (gl_model_set_series_hessian)."""
@@ -980,6 +1001,7 @@ class Model:
             raise NativeLibraryError(f"series Hessian field is {tuple(coeffs.shape)}, expected (3, order+1, {self.N})")
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_series_hessian(self._h, int(component), _ptr(coeffs.contiguous())))
+        self._changed(False)
 
     def set_prior(self, columns, const_row):
         """columns: list of (param_col, bijector, prior, a, b, lo, hi, log_norm); const_row: [P] floats."""
@@ -988,6 +1010,8 @@ class Model:
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_prior(self._h, arr, len(columns), cr.ctypes.data_as(POINTER(c_float))))
         self.d_z = len(columns)
+        self.prior_owner = None
+        self._changed(False)
 
     def set_positions(self, xs, ys, exs, eys):
         """xs, ys, exs, eys: lists (one entry per image family) of 1-D arrays of equal length."""
@@ -1002,7 +1026,8 @@ class Model:
                                                 fp(ex), fp(ey)))
         self.n_images = int(sizes.sum())
         self.n_families = int(sizes.size)
-        self._ws = {}  # workspace layout changed
+        self.positions_owner = None
+        self._changed(True)  # the workspace layout follows the number of images
 
     def positions(self, params, want_grad):
         self._single_plane("positions")
@@ -1027,10 +1052,11 @@ class Model:
         _check(lib().gl_model_set_timing(self._h, int(slots)))
         _check(lib().gl_model_set_timing_stride(self._h, max(int(stride), 1)))
         self._timing_slots = int(slots)
+        self._changed(False)
 
     def timing_drain(self):
         """Durations [ms] of the main launches recorded since the last drain (oldest first)."""
-        cap = max(int(getattr(self, "_timing_slots", 0)), 1)
+        cap = max(self._timing_slots, 1)
         buf = (c_float * cap)()
         n = c_int()
         _check(lib().gl_model_timing_drain(self._h, buf, cap, ctypes.byref(n)))

@@ -149,12 +149,13 @@ class _LogLikeFn(torch.autograd.Function):
 
 
 class _LogProbFn(torch.autograd.Function):
-    """autograd glue around gl_logprob_fwd_bwd (bijector + kernels + prior in one native launch sequence)."""
+    """autograd glue around ``ForwardProbModel._fused`` (bijector + kernels + prior in one native launch sequence, on one plane or
+    on lens planes)."""
 
     @staticmethod
-    def forward(ctx, z, model, obs, err, mask, bg_rms, exp_time, n_eff, terms):
+    def forward(ctx, z, prob_model, simulator, terms):
         want = z.requires_grad
-        lp, ll, chi2, grad = model.logprob(z.detach(), obs, err, mask, bg_rms, exp_time, want, n_eff, terms)
+        lp, ll, chi2, grad = prob_model._fused(simulator, z, want, terms)
         if want:
             ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(ll, chi2)
@@ -163,34 +164,17 @@ class _LogProbFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_lp, g_ll, g_chi2):
         (grad,) = ctx.saved_tensors
-        return g_lp[:, None] * grad, None, None, None, None, None, None, None, None
+        return g_lp[:, None] * grad, None, None, None
 
 
-class _MpLogProbFn(torch.autograd.Function):
-    """autograd glue around gl_multiplane_logprob_fwd_bwd (lens planes at redshifts of their own)."""
-
-    @staticmethod
-    def forward(ctx, z, model, obs, err, mask, bg_rms, exp_time, n_eff, terms):
-        want = z.requires_grad
-        lp, ll, chi2, grad = model.multiplane_logprob(z.detach(), obs, err, mask, bg_rms, exp_time, want, n_eff, terms)
-        if want:
-            ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(ll, chi2)
-        return lp, ll, chi2
+class _PointTermFn(torch.autograd.Function):
+    """autograd glue around a point-image term of the native model: ``entry`` is its bound ``positions`` (gl_positions_fwd_bwd),
+    ``multiplane_positions`` (gl_multiplane_positions_fwd_bwd) or ``position_fluxes`` (gl_position_fluxes_fwd_bwd)."""
 
     @staticmethod
-    def backward(ctx, g_lp, g_ll, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_lp[:, None] * grad, None, None, None, None, None, None, None, None
-
-
-class _PositionsFn(torch.autograd.Function):
-    """autograd glue around gl_positions_fwd_bwd (image-position likelihood)."""
-
-    @staticmethod
-    def forward(ctx, packed, model):
+    def forward(ctx, packed, entry):
         want = packed.requires_grad
-        ll, chi2, grad = model.positions(packed.detach(), want)
+        ll, chi2, grad = entry(packed.detach(), want)
         if want:
             ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(chi2)
@@ -202,40 +186,27 @@ class _PositionsFn(torch.autograd.Function):
         return g_ll[:, None] * grad, None
 
 
-class _MpPositionsFn(torch.autograd.Function):
-    """autograd glue around gl_multiplane_positions_fwd_bwd (image-position likelihood behind lens planes)."""
+class _GraphEntry:
+    """One captured ``log_prob_and_grad`` launch sequence with what its device pointers refer to: the static input and outputs, the
+    workspace (held here, so the caching allocator cannot hand it out while the graph lives) and, to tell whether the rest still
+    stands, the native model's generation at capture and the image tensors of the owning ``ForwardProbModel``."""
+    __slots__ = ("graph", "z_static", "outs", "owner", "terms", "workspace", "generation", "inputs")
 
-    @staticmethod
-    def forward(ctx, packed, model):
-        want = packed.requires_grad
-        ll, chi2, grad = model.multiplane_positions(packed.detach(), want)
-        if want:
-            ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(chi2)
-        return ll, chi2
+    def __init__(self, graph, z_static, outs, owner, simulator, terms):
+        model = simulator._model
+        self.graph, self.z_static, self.outs, self.owner, self.terms = graph, z_static, outs, owner, terms
+        self.workspace = model._workspace(z_static.shape[0])
+        self.generation = model.generation
+        self.inputs = (owner.observed_image, owner.error_map, owner._mask(simulator))
 
-    @staticmethod
-    def backward(ctx, g_ll, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_ll[:, None] * grad, None
-
-
-class _FluxesFn(torch.autograd.Function):
-    """autograd glue around gl_position_fluxes_fwd_bwd (flux-ratio likelihood of the image families, one plane or lens planes)."""
-
-    @staticmethod
-    def forward(ctx, packed, model):
-        want = packed.requires_grad
-        ll, chi2, grad = model.position_fluxes(packed.detach(), want)
-        if want:
-            ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(chi2)
-        return ll, chi2
-
-    @staticmethod
-    def backward(ctx, g_ll, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_ll[:, None] * grad, None
+    def valid(self, simulator):
+        """False once anything was handed to the native model after the capture (every ``set_*`` frees or re-sizes device buffers the
+        graph points into), another model was bound, or the owner's image tensors were replaced."""
+        model, owner = simulator._model, self.owner
+        obs, err, mask = self.inputs
+        return (model.generation == self.generation and model.prior_owner is owner
+                and (model.positions_owner is owner or not self.terms & 2)
+                and owner.observed_image is obs and owner.error_map is err and owner._mask(simulator) is mask)
 
 
 def _family_fluxes(fluxes, errors, centroids_x):
@@ -424,7 +395,7 @@ class ForwardProbModel(ProbabilisticModel):
     def _bind_prior(self, simulator):
         """Hand the prior / bijector column table to the simulator's native model (once per pairing)."""
         model = simulator._model
-        if getattr(model, "_prior_owner", None) is not self:
+        if model.prior_owner is not self:
             slot_of = {(g, i, n): p for p, (g, i, n, _) in enumerate(simulator._layout.slots)}
             columns = []
             for k, (path, leaf) in enumerate(zip(self._paths, self._flat.leaves)):
@@ -440,11 +411,8 @@ class ForwardProbModel(ProbabilisticModel):
                         raise KeyError(f"{g}[{i}]['{n}'] has neither a prior nor a constant")
                     const_row[p] = float(np.asarray(const, dtype=np.float32).reshape(-1)[0])
             model.set_prior(columns, const_row)
-            model._prior_owner = self
+            model.prior_owner = self
         return model
-
-    def _fused_ok(self, simulator):
-        return self.include_pixels or self.include_positions
 
     def position_targets(self, multiplane):
         """``[F, K]`` couplings of the image families on the planes of ``multiplane``: row f = ``multiplane.target_scales(z_f)``, 0 for
@@ -458,7 +426,7 @@ class ForwardProbModel(ProbabilisticModel):
         ``centroids_redshifts`` through the one-plane ``MultiPlane`` the physical model was built with."""
         if self.centroids_redshifts is None:
             return self.centroids_scales, self._centroids_scales_given
-        if getattr(simulator, "_mp", None) is not None:
+        if simulator._mp is not None:
             raise _native.UnsupportedLensError(f"a model with {simulator._mp.K} lens planes: one deflection scale per family exists on a "
                                                "single plane alone (the solver, the predicted positions and their users)")
         mp = getattr(simulator.phys_model, "_multiplane_single", None)
@@ -469,8 +437,8 @@ class ForwardProbModel(ProbabilisticModel):
 
     def _bind_positions(self, simulator):
         model = simulator._model
-        if getattr(model, "_positions_owner", None) is not self:
-            mp = getattr(simulator, "_mp", None)
+        if model.positions_owner is not self:
+            mp = simulator._mp
             # (validated before anything is handed over: a refusal leaves the native model as it was)
             targets = self.position_targets(mp) if mp is not None and self.centroids_redshifts is not None else None
             scales, given = self._family_scales(simulator) if mp is None else (None, False)
@@ -481,14 +449,14 @@ class ForwardProbModel(ProbabilisticModel):
                 model.set_position_scales(scales)
             if self.n_flux:  # (set_positions has cleared the fluxes of an earlier owner)
                 model.set_position_fluxes(np.concatenate(self.centroids_fluxes), np.concatenate(self.centroids_fluxes_errors))
-            model._positions_owner = self
+            model.positions_owner = self
         return model
 
     def _on_planes(self, simulator):
         """True for a simulator with several lens planes, whose fused log-probability comes from the multi-plane entries.  A model
         that carries image positions is served there when its families have redshifts (``centroids_redshifts``); without them it is
         refused -- a family names no plane."""
-        mp = getattr(simulator, "_mp", None)
+        mp = simulator._mp
         if mp is None:
             return False
         if not (self.include_pixels or self.include_positions):
@@ -499,22 +467,31 @@ class ForwardProbModel(ProbabilisticModel):
                                                "family without a redshift names no plane")
         return True
 
-    def _mp_logprob(self, simulator, z, want_grad, terms):
+    def _fused(self, simulator, z, want_grad, terms):
+        """``(log_prob, log_like, red_chi2, d log_prob / d z or None)`` of ``terms`` (1 pixels, 2 image positions, 3 both): bijector ->
+        prep -> fused render/chi2/VJP -> finalize + prior, all inside the native library.  The one place that binds this model to
+        the simulator's native model and calls its fused entry; the reduced chi^2 of the pixels divides by the region's pixel count
+        (the library does not look at the divisor without the pixel term)."""
+        on_planes = self._on_planes(simulator)
         model = self._bind_prior(simulator)
         if terms & 2:
             self._bind_positions(simulator)
-        return model.multiplane_logprob(z.detach(), self.observed_image, self.error_map, self._mask(simulator),
-                                        self.background_rms or 0.0, self.exp_time or 1.0, want_grad,
-                                        self._n_eff(simulator) if terms & 1 else 1.0, terms)
+        entry = model.multiplane_logprob if on_planes else model.logprob
+        return entry(z.detach(), self.observed_image, self.error_map, self._mask(simulator), self.background_rms or 0.0,
+                     self.exp_time or 1.0, want_grad, self._n_eff(simulator) if terms & 1 else 1.0, terms)
 
     def _terms(self):
         return (1 if self.include_pixels else 0) | (2 if self.include_positions else 0)
 
+    def _mask(self, simulator):
+        return simulator.img_region if simulator.sim_config.pix_region is not None else None
+
     def stats_positions(self, simulator, params):
         """tf/model.py:103-124: ``(log_like, red_chi2)`` of the image-position term."""
         packed = params if torch.is_tensor(params) else simulator.pack(params)
-        fn = _MpPositionsFn if self.centroids_x is not None and self._on_planes(simulator) else _PositionsFn
-        ll, chi2 = fn.apply(packed, self._bind_positions(simulator))
+        on_planes = self.centroids_x is not None and self._on_planes(simulator)
+        model = self._bind_positions(simulator)
+        ll, chi2 = _PointTermFn.apply(packed, model.multiplane_positions if on_planes else model.positions)
         return ll, chi2 / self.n_position
 
     def _need_fluxes(self, what):
@@ -527,7 +504,7 @@ class ForwardProbModel(ProbabilisticModel):
         self._need_fluxes("stats_fluxes")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         self._on_planes(simulator)  # (its refusals; one native entry serves one plane and lens planes)
-        ll, chi2 = _FluxesFn.apply(packed, self._bind_positions(simulator))
+        ll, chi2 = _PointTermFn.apply(packed, self._bind_positions(simulator).position_fluxes)
         return ll, chi2 / self.n_flux
 
     def predicted_fluxes(self, simulator, params):
@@ -627,65 +604,42 @@ class ForwardProbModel(ProbabilisticModel):
         return x.index_select(1, cols)
 
     def _pixel_stats_packed(self, simulator, packed):
-        if getattr(simulator, "_mp", None) is not None:  # lens planes: the forward image through the image-statistics launch
+        inputs = (self.observed_image, self.error_map, self._mask(simulator), self.background_rms or 0.0, self.exp_time or 1.0)
+        if simulator._mp is not None:  # lens planes: the forward image through the image-statistics launch
             if packed.requires_grad:
                 raise NotImplementedError("the pixel statistics of a model with several lens planes carry no autograd graph: the "
                                           "gradient entries are log_prob / log_prob_and_grad and _model.multiplane_loglike_grad")
-            ll, chi2 = simulator._model.multiplane_loglike(packed, self.observed_image, self.error_map, self._mask(simulator),
-                                                           self.background_rms or 0.0, self.exp_time or 1.0)
-            return ll, chi2 / self._n_eff(simulator)
-        ll, chi2 = _LogLikeFn.apply(packed, simulator._model, self.observed_image, self.error_map,
-                                    simulator.img_region if simulator.sim_config.pix_region is not None else None,
-                                    self.background_rms or 0.0, self.exp_time or 1.0)
+            ll, chi2 = simulator._model.multiplane_loglike(packed, *inputs)
+        else:
+            ll, chi2 = _LogLikeFn.apply(packed, simulator._model, *inputs)
         return ll, chi2 / self._n_eff(simulator)  # tf/model.py:100
 
     def stats_pixels(self, simulator, params):
         """tf/model.py:89-101: ``params`` is the nested constrained structure."""
         return self._pixel_stats_packed(simulator, simulator.pack(params))
 
+    def _fused_ok(self, simulator):
+        """False for a model with neither likelihood term: the prior alone comes from torch ops (``log_prob_unfused``)."""
+        return self.include_pixels or self.include_positions
+
     def log_prob(self, simulator, z):
         """tf/model.py:126-167: ``z`` is ``(bs, d)`` unconstrained; returns ``(log_prob, red_chi2)``."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        if self._on_planes(simulator):
-            model = self._bind_prior(simulator)
-            if self.include_positions:
-                self._bind_positions(simulator)
-            lp, _, red_chi2 = _MpLogProbFn.apply(z, model, self.observed_image, self.error_map,
-                                                 self._mask(simulator), self.background_rms or 0.0, self.exp_time or 1.0,
-                                                 self._n_eff(simulator) if self.include_pixels else 1.0, self._terms())
-            return lp, red_chi2
-        if self._fused_ok(simulator):
-            # bijector -> prep -> fused render/chi2/VJP -> finalize + prior, all inside the native library
-            model = self._bind_prior(simulator)
-            if self.include_positions:
-                self._bind_positions(simulator)
-            lp, _, red_chi2 = _LogProbFn.apply(z, model, self.observed_image, self.error_map, self._mask(simulator),
-                                               self.background_rms or 0.0, self.exp_time or 1.0, self._n_eff(simulator),
-                                               self._terms())
-            return lp, red_chi2
-        return self.log_prob_unfused(simulator, z)
-
-    def _mask(self, simulator):
-        return simulator.img_region if simulator.sim_config.pix_region is not None else None
+        terms = self._terms()
+        if not terms and not self._on_planes(simulator):  # (lens planes refuse a model without a term)
+            return self.log_prob_unfused(simulator, z)
+        lp, _, red_chi2 = _LogProbFn.apply(z, self, simulator, terms)
+        return lp, red_chi2
 
     def term_log_prob_and_grad(self, simulator, z, term):
         """``(log_prior + log_like_term, log_like_term, gradient of the former w.r.t. z)`` for ONE likelihood term
         (``"pixels"`` or ``"positions"``) -- the pieces the tempered SMC target is assembled from
         (tf/inference.py:213-238,292-303)."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        if self._on_planes(simulator):
-            if term == "positions" and not self.include_positions:
-                raise _native.UnsupportedLensError("the model carries no image positions: on lens planes the position term needs "
-                                                   "centroids_x/centroids_y with centroids_redshifts")
-            lp, ll, _, grad = self._mp_logprob(simulator, z, True, {"pixels": 1, "positions": 2}[term])
-            return lp, ll, grad
-        model = self._bind_prior(simulator)
-        bit = {"pixels": 1, "positions": 2}[term]
-        if bit == 2:
-            self._bind_positions(simulator)
-        lp, ll, _, grad = model.logprob(z.detach(), self.observed_image, self.error_map, self._mask(simulator),
-                                        self.background_rms or 0.0, self.exp_time or 1.0, True,
-                                        self._n_eff(simulator) if bit == 1 else 1.0, bit)
+        if self._on_planes(simulator) and term == "positions" and not self.include_positions:
+            raise _native.UnsupportedLensError("the model carries no image positions: on lens planes the position term needs "
+                                               "centroids_x/centroids_y with centroids_redshifts")
+        lp, ll, _, grad = self._fused(simulator, z, True, {"pixels": 1, "positions": 2}[term])
         return lp, ll, grad
 
     def log_prob_and_grad(self, simulator, z, graph=False):
@@ -697,60 +651,54 @@ class ForwardProbModel(ProbabilisticModel):
         (simulator, shape of ``z``) in a HIP graph and replayed.  The contract is that of torch's CUDA graphs: the three returned
         tensors are the graph's STATIC outputs, overwritten by the next call with ``graph=True`` on the same simulator; ``z`` is
         copied into the graph's static input unless it already IS that tensor (``graph_input(simulator, z)`` hands it out, for loops
-        that update ``z`` in place).  The graph holds the device buffers the simulator's native model had when it was captured: its
-        image positions, their fluxes and, on lens planes, their families' couplings are uploaded again whenever ANOTHER ``ForwardProbModel`` with
-        positions is bound to the same simulator, so keep one such model per simulator while its graph is in use."""
+        that update ``z`` in place).  Anything that re-binds the simulator's native model (another ``ForwardProbModel``, any of its
+        ``set_*``) makes the next call capture again, so two models alternating on one simulator with ``graph=True`` capture on
+        every call."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        on_planes = self._on_planes(simulator)
-        if graph and z.is_cuda and self._fused_ok(simulator):
-            return self._log_prob_and_grad_graph(simulator, z)
-        if on_planes:
-            lp, _, red, grad = self._mp_logprob(simulator, z, True, self._terms())
-            return lp, red, grad
-        if self._fused_ok(simulator):
-            model = self._bind_prior(simulator)
-            if self.include_positions:
-                self._bind_positions(simulator)
-            lp, _, red, grad = model.logprob(z.detach(), self.observed_image, self.error_map, self._mask(simulator),
-                                             self.background_rms or 0.0, self.exp_time or 1.0, True,
-                                             self._n_eff(simulator), self._terms())
-            return lp, red, grad
-        zz = z.detach().requires_grad_(True)
-        lp, red = self.log_prob_unfused(simulator, zz)
-        (g,) = torch.autograd.grad(lp.sum(), zz)
-        return lp.detach(), red.detach(), g
+        terms = self._terms()
+        if not terms and not self._on_planes(simulator):
+            zz = z.detach().requires_grad_(True)
+            lp, red = self.log_prob_unfused(simulator, zz)
+            (g,) = torch.autograd.grad(lp.sum(), zz)
+            return lp.detach(), red.detach(), g
+        if graph and z.is_cuda:
+            return self._log_prob_and_grad_graph(simulator, z).outs
+        lp, _, red, grad = self._fused(simulator, z, True, terms)
+        return lp, red, grad
 
     def _log_prob_and_grad_graph(self, simulator, z):
-        key = (id(self), tuple(z.shape))
-        cache = simulator.__dict__.setdefault("_lp_graphs", {})
-        ent = cache.get(key)
-        if ent is None:
-            z_static = z.detach().clone().contiguous()
+        """The graph of this shape of ``z``, replayed on ``z``: captured on first use, and again when its entry no longer holds."""
+        key = (id(self), z.shape)  # (the entry keeps self, so its id is not reused while the entry lives)
+        ent = simulator._lp_graphs.get(key)
+        if ent is None or not ent.valid(simulator):
+            z_static = z.detach().clone().contiguous() if ent is None else ent.z_static  # (graph_input's tensor stays the input)
+            if z is not z_static and z.data_ptr() != z_static.data_ptr():
+                z_static.copy_(z.detach())
+            terms = self._terms()
             side = torch.cuda.Stream(device=z.device)
             side.wait_stream(torch.cuda.current_stream(z.device))
             with torch.cuda.stream(side):  # warm-up off the default stream: binds the prior, sizes the workspaces
                 for _ in range(2):
-                    self.log_prob_and_grad(simulator, z_static)
+                    self._fused(simulator, z_static, True, terms)
             torch.cuda.current_stream(z.device).wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                outs = self.log_prob_and_grad(simulator, z_static)
-            ent = cache[key] = (g, z_static, outs, self)  # (self: keeps id(self) from being reused while the entry lives)
-        g, z_static, outs, _ = ent
-        if z.data_ptr() != z_static.data_ptr():
-            z_static.copy_(z.detach())
-        g.replay()
-        return outs
+                lp, _, red, grad = self._fused(simulator, z_static, True, terms)
+            ent = simulator._lp_graphs[key] = _GraphEntry(g, z_static, (lp, red, grad), self, simulator, terms)
+            simulator._lp_captures += 1
+        elif z is not ent.z_static and z.data_ptr() != ent.z_static.data_ptr():
+            ent.z_static.copy_(z.detach())
+        ent.graph.replay()
+        return ent
 
     def graph_input(self, simulator, z):
         """The static input tensor of ``log_prob_and_grad(..., graph=True)`` for this shape of ``z`` (created, and the graph
         captured, on first use), initialised with ``z``: update it in place and pass it back to skip the copy."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        self._log_prob_and_grad_graph(simulator, z)
-        return simulator._lp_graphs[(id(self), tuple(z.shape))][1]
+        return self._log_prob_and_grad_graph(simulator, z).z_static
 
     def _n_eff(self, simulator):
-        n = getattr(simulator, "_n_eff", None)
+        n = simulator._n_eff
         if n is None:
             n = simulator._n_eff = float(torch.count_nonzero(simulator.img_region))
         return n
@@ -830,7 +778,7 @@ class BackwardProbModel(ProbabilisticModel):
         log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
         packed = simulator.pack(self.pack_bij.forward(x))
         coeffs = simulator._model.lstsq(packed.detach(), self.observed_image, self.err_map, 7, want="coeffs")[0]
-        lin = getattr(simulator, "_linear_cols_dev", None)  # uploaded once per simulator, not per call
+        lin = simulator._linear_cols_dev  # uploaded once per simulator, not per call
         if lin is None or lin.device != packed.device:
             lin = simulator._linear_cols_dev = torch.tensor(simulator._layout.linear, dtype=torch.int64, device=packed.device)
         full = packed.index_copy(1, lin, coeffs / simulator.conversion_factor)  # amplitude = coeff / det(T)

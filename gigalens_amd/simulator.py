@@ -153,7 +153,12 @@ class LensSimulator(LensSimulatorInterface):
             from gigalens_amd.kernel_util import subgrid_kernel
             psf = np.asarray(subgrid_kernel(np.asarray(sim_config.kernel), ss, odd=True), dtype=np.float32)
         self.kernel = psf
-        self._mp = getattr(phys_model, "multiplane", None)  # lenses on planes of their own (PhysicalModel multiplane, K >= 2)
+        # what the probabilistic models keep per simulator
+        self._n_eff = None  # pixels of the region (ForwardProbModel._n_eff)
+        self._linear_cols_dev = None  # the linear columns of the layout on the device (BackwardProbModel.log_prob)
+        self._lp_graphs = {}  # {(id(prob_model), shape of z): model._GraphEntry} of log_prob_and_grad(graph=True)
+        self._lp_captures = 0  # how many of them were captured so far
+        self._mp =getattr(phys_model, "multiplane", None)  # lenses on planes of their own (PhysicalModel multiplane, K >= 2)
         if self._mp is not None:
             self._refuse_on_planes_profiles()
         bodies = []  # user-written profile bodies (profile.py `hip_body`): compiled into this model's kernels

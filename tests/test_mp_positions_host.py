@@ -157,13 +157,13 @@ def test_one_plane_multiplane_is_retained_for_the_redshifts():
     phys1 = PhysicalModel(c["phys"].lenses, [], [], multiplane=mp1)
     assert phys1.multiplane is None and phys1._multiplane_single is mp1
     pm = _prob_model(c)
-    scales, given = pm._family_scales(types.SimpleNamespace(phys_model=phys1))
+    scales, given = pm._family_scales(types.SimpleNamespace(phys_model=phys1, _mp=None))
     assert given and scales.dtype == np.float32
     assert np.array_equal(scales, np.asarray([mp1.target_scales(fm["z"])[0] for fm in c["fams"]], dtype=np.float32))
     with pytest.raises(ValueError, match="centroids_scales"):
-        pm._family_scales(types.SimpleNamespace(phys_model=c["phys"]))
+        pm._family_scales(types.SimpleNamespace(phys_model=c["phys"], _mp=None))
     plain = _prob_model(c, centroids_redshifts=None, centroids_scales=[0.8, 1.2])
-    s2, g2 = plain._family_scales(types.SimpleNamespace(phys_model=c["phys"]))
+    s2, g2 = plain._family_scales(types.SimpleNamespace(phys_model=c["phys"], _mp=None))
     assert g2 and np.array_equal(s2, np.asarray([0.8, 1.2], np.float32))
 
 
