@@ -79,6 +79,9 @@ SYMBOLS = {
     "gl_model_set_position_fluxes": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_int]),
     "gl_position_fluxes_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_size_t, c_void_p]),
+    "gl_model_set_position_delays": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_int, POINTER(c_float), c_int]),
+    "gl_position_delays_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]),
     "gl_image_positions_scaled": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_float), c_float, c_float,
                                           c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),
@@ -858,6 +861,40 @@ class Model:
         _check_potential(lib().gl_position_fluxes_fwd_bwd(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(amp), _ptr(mf),
                                                           _ptr(ws), ws.numel(), _stream()))
         return (ll, chi2, grad, amp, mf) if want_model else (ll, chi2, grad)
+
+    def set_position_delays(self, delays, errors, scales):
+        """The measured arrival times of the images (days) and their errors (gl_model_set_position_delays; after ``set_positions``,
+        which clears them): ``[J]`` arrays in the concatenated image order, NaN for an image without a measurement; ``scales`` ``[F]``:
+        ``lambda_f`` in days / arcsec^2, NaN to profile it out.  ``delays`` None: no delays.  Lens planes, a scaled family, series
+        and user-written lenses raise ``UnsupportedLensError`` and leave the model as it was."""
+        fp = lambda a: a.ctypes.data_as(POINTER(c_float))
+        with torch.cuda.device(self.device):
+            if delays is None:
+                _check(lib().gl_model_set_position_delays(self._h, None, None, 0, None, 0))
+            else:
+                t = np.ascontiguousarray(delays, dtype=np.float32).reshape(-1)
+                s = np.ascontiguousarray(errors, dtype=np.float32).reshape(-1)
+                lam = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+                if t.size != s.size:
+                    raise NativeLibraryError("arrival times and their errors must have the same length")
+                _check_potential(lib().gl_model_set_position_delays(self._h, fp(t), fp(s), int(t.size), fp(lam), int(lam.size)))
+        self._changed(False)
+
+    def position_delays(self, params, want_grad, want_model=False):
+        """gl_position_delays_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the time-delay term; with ``want_model``
+        also ``(scale [B, F], offset [B, F], model_delay [B, J])`` = ``lambda_f``, ``T_f`` and ``lambda_f phi_j + T_f`` in days."""
+        params = self._params(params)
+        B = params.shape[0]
+        ws = self._workspace(B)
+        ll = torch.empty(B, dtype=torch.float32, device=params.device)
+        chi2 = torch.empty_like(ll)
+        grad = torch.empty_like(params) if want_grad else None
+        lam = torch.empty((B, self.n_families), dtype=torch.float32, device=params.device) if want_model else None
+        off = torch.empty_like(lam) if want_model else None
+        md = torch.empty((B, self.n_images), dtype=torch.float32, device=params.device) if want_model else None
+        _check_potential(lib().gl_position_delays_fwd_bwd(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(lam), _ptr(off),
+                                                          _ptr(md), _ptr(ws), ws.numel(), _stream()))
+        return (ll, chi2, grad, lam, off, md) if want_model else (ll, chi2, grad)
 
     def image_positions(self, params, src_x, src_y, window, n_cells, max_images, tol, max_iter, scales=None):
         """gl_image_positions[_scaled]: ``src_x, src_y`` [B, S] on the device, ``window`` = (x_lo, x_hi, y_lo, y_hi), ``scales``

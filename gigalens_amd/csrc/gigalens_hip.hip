@@ -205,6 +205,7 @@ Workspace carve(const gl_model* m, int B, void* base, const LaunchPlan& plan) {
     w.pos_ll = take(B);
     w.pos_chi2 = take(B);
     w.pos_grad = take((size_t)B * std::max(m->P, 1));
+    w.pos_dadj = take((size_t)B * m->pos_J);  // (with or without delays: gl_model_set_position_delays leaves the layout alone)
   }
   if (m->has_post) {
     w.img_ss = (float*)(p + off);
@@ -575,9 +576,12 @@ int logprob_grad(const gl_model* m, const float* z, const float* obs, const floa
     return rc;
   // a model that holds fluxes (gl_model_set_position_fluxes): the flux ratios are part of the point-image term, whose reduced chi2
   // then divides by 2 J + n_flux
-  const bool flux = pos && m->pos_n_flux > 0;
-  if (pos && (rc = run_positions(m, w.params, B, w, want_grad, stream, flux ? POS_BOTH : POS_POSITIONS))) return rc;
-  const float n_point = flux ? 2.0f * (float)m->pos_J + (float)m->pos_n_flux : 2.0f * (float)m->pos_J;
+  // ... and likewise the time delays of a model that holds arrival times (gl_model_set_position_delays): 2 J + n_flux + n_delay
+  const bool flux = pos && m->pos_n_flux > 0, delays = pos && m->pos_n_delay > 0;
+  if (pos && (rc = run_positions(m, w.params, B, w, want_grad, stream, (flux ? POS_BOTH : POS_POSITIONS) | (delays ? POS_DELAYS : 0))))
+    return rc;
+  float n_point = flux ? 2.0f * (float)m->pos_J + (float)m->pos_n_flux : 2.0f * (float)m->pos_J;
+  if (delays) n_point += (float)m->pos_n_delay;
   return run_finalize(m, w.params, B, fin_rows, w, loglike, chi2, nullptr, stream, z, logprob, grad_z,
                       pix ? 1.0f / (chi2_divisor * n_chi) : 0.f, extra, use_partial, pos,
                       pos ? 1.0f / (n_point * n_chi) : 0.f);
@@ -1386,6 +1390,10 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
   m->d_pos_target.reset();
   m->pos_n_flux = 0;  // ... and without fluxes until gl_model_set_position_fluxes
   m->d_pos_flux.reset();
+  m->pos_n_delay = 0;  // ... and without arrival times until gl_model_set_position_delays
+  m->d_pos_delay.reset();
+  m->pos_fam_delay.clear();
+  m->pos_fam_scale.clear();
   return GL_OK;
 }
 
@@ -1453,6 +1461,10 @@ int gl_model_set_position_scales(gl_model* m, const float* scales, int n_familie
                            "couplings from gl_model_set_position_targets");
   bool any;
   if (int rc = check_scales(scales, n_families, m->pos_F, "image famil(ies)", &any)) return rc;
+  for (int f = 0; f < (int)m->pos_fam_delay.size(); ++f)
+    if (m->pos_fam_delay[f] && scales[f] != 1.f)
+      return fail(GL_EUNSUPPORTED, "image family %d holds arrival times (gl_model_set_position_delays): the Fermat potential of a "
+                                   "scaled source plane (scale %g) is not served", f, scales[f]);
   if (any) {
     std::vector<float> per_image((size_t)m->pos_J);
     for (int f = 0; f < m->pos_F; ++f)
@@ -1462,6 +1474,7 @@ int gl_model_set_position_scales(gl_model* m, const float* scales, int n_familie
     m->d_pos_scale.reset();
   }
   m->pos_scaled = any;
+  m->pos_fam_scale.assign(scales, scales + n_families);  // (the host copy the delay setter reads: after the upload has succeeded)
   return GL_OK;
 }
 

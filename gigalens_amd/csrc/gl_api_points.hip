@@ -9,6 +9,7 @@
 #include "gl_host.hip.h"
 #include "gl_positions.hip.h"
 #include "gl_fluxes.hip.h"
+#include "gl_tdelays.hip.h"
 #include "gl_images.hip.h"
 #include "gl_critical.hip.h"
 #include "gl_potential.hip.h"
@@ -90,9 +91,14 @@ MpArgs mp_args(const gl_model* m) {
 namespace glk {
 
 int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream, int what,
-                  float* amp, float* model_flux) {
+                  float* amp, float* model_flux, const DelayOut* delay_out) {
   if (m->n_series) return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image-position likelihood");
   if ((what & POS_FLUXES) && !m->pos_n_flux) return fail(GL_EINVAL, "gl_model_set_position_fluxes has not been called on this model");
+  if ((what & POS_DELAYS) && !m->pos_n_delay) return fail(GL_EINVAL, "gl_model_set_position_delays has not been called on this model");
+  // (gl_model_set_position_delays, gl_model_set_position_scales and gl_model_set_lens_planes see to it that a model with delays is
+  // one plane of built-in lenses whose families with delays lie on the reference plane)
+  if ((what & POS_DELAYS) && (m->mp_K >= 2 || m->has_user))
+    return fail(GL_EUNSUPPORTED, "the time-delay term serves one lens plane of built-in lenses");
   if (m->has_user)  // the four kernels below, compiled at run time with the user's bodies on the nested duals (once per model text)
     if (int rc = compile_user_points(m)) return rc;
   PosArgs a = point_args(m, params, B);  // + the position tables and the likelihood's workspace
@@ -153,9 +159,22 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
   hipLaunchKernelGGL(gl_pos_p1_kernel, blocks((long long)B * a.J), dim3(64), 0, stream, a);
   if (what & POS_POSITIONS) hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
   fluxes();
-  if (want_grad && m->lens_params)
+  // the time delays (gl_tdelays.hip.h): statistics and beta adjoints by the thread that owns the family's elements, the direct
+  // d psi / d params part added to what P3 wrote, before P4 sums it
+  if (what & POS_DELAYS) {
+    const float* tab = m->d_pos_delay.get();
+    const DelayOut none{nullptr, nullptr, nullptr};
+    const DelayOut& o = delay_out ? *delay_out : none;
+    hipLaunchKernelGGL(gl_pos_tdelay_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a, tab, tab + m->pos_J, tab + 2 * m->pos_J,
+                       (what & (POS_POSITIONS | POS_FLUXES)) ? 1 : 0, w.pos_dadj, o.scale, o.offset, o.model_delay);
+  }
+  if (want_grad && m->lens_params) {
     hipLaunchKernelGGL(gl_pos_p3_kernel, blocks((long long)B * a.J * m->lens_params), dim3(64), 0, stream, a,
                        m->lens_params);
+    if (what & POS_DELAYS)
+      hipLaunchKernelGGL(gl_pos_tdelay_grad_kernel, blocks((long long)B * a.J * m->lens_params), dim3(64), 0, stream, a,
+                         (const float*)w.pos_dadj, m->lens_params);
+  }
   hipLaunchKernelGGL(gl_pos_p4_kernel, blocks((long long)B * (a.P + 1)), dim3(64), 0, stream, a, m->lens_params);
   GL_HIP(hipGetLastError());
   return GL_OK;
@@ -213,6 +232,88 @@ int gl_position_fluxes_fwd_bwd(const gl_model* m, const float* params, int B, fl
   hipStream_t stream = (hipStream_t)hip_stream;
   if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream, POS_FLUXES, amplitude_or_null, model_flux_or_null)))
     return rc;
+  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  if (grad_params_or_null)
+    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+
+// ---- time delays of the image families (gl_tdelays.hip.h) ---------------------------------------------------------------
+int gl_model_set_position_delays(gl_model* m, const float* delay, const float* delay_err, int n_images, const float* scale_per_family,
+                                 int n_families) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  auto clear = [&]() {
+    m->pos_n_delay = 0;
+    m->d_pos_delay.reset();
+    m->pos_fam_delay.clear();
+    return GL_OK;
+  };
+  if (!delay) return clear();  // no delays: the model as gl_model_set_positions left it
+  if (!delay_err || !scale_per_family) return fail(GL_EINVAL, "delay_err / scale_per_family is null");
+  if (n_images != m->pos_J) return fail(GL_EINVAL, "%d arrival times for %d image(s)", n_images, m->pos_J);
+  if (n_families != m->pos_F) return fail(GL_EINVAL, "%d delay scales for %d image famil(ies)", n_families, m->pos_F);
+  int n_delay = 0;
+  std::vector<char> has(m->pos_F, 0);
+  for (int f = 0; f < m->pos_F; ++f) {
+    int n = 0;
+    for (int j = m->pos_fam_off[f]; j < m->pos_fam_off[f + 1]; ++j) {
+      if (std::isnan(delay[j])) continue;  // not measured
+      if (!std::isfinite(delay[j])) return fail(GL_EINVAL, "arrival time %d (%g) is not finite", j, delay[j]);
+      if (!(std::isfinite(delay_err[j]) && delay_err[j] > 0.f))
+        return fail(GL_EINVAL, "arrival-time error %d (%g) is not finite and > 0", j, delay_err[j]);
+      ++n;
+    }
+    if (n == 1)
+      return fail(GL_EINVAL, "image family %d has one measured arrival time: the term constrains delay differences, a family takes two "
+                             "or more, or none", f);
+    if (n && std::isinf(scale_per_family[f])) return fail(GL_EINVAL, "delay scale %d (%g) is not finite (NaN: profiled out)", f, scale_per_family[f]);
+    if (n == 2 && std::isnan(scale_per_family[f]))
+      return fail(GL_EINVAL, "image family %d has two measured arrival times and a profiled delay scale: the fit is exact and "
+                             "constrains nothing, a profiled scale takes three or more", f);
+    has[f] = n > 0;
+    n_delay += n;
+  }
+  if (!n_delay) return clear();  // every time is NaN: none
+  if (m->mp_K >= 2) return fail(GL_EUNSUPPORTED, "the time-delay term is not served on lens planes (gl_model_set_lens_planes)");
+  for (int f = 0; f < m->pos_F; ++f)
+    if (has[f] && f < (int)m->pos_fam_scale.size() && m->pos_fam_scale[f] != 1.f)
+      return fail(GL_EUNSUPPORTED, "image family %d has a deflection scale of %g (gl_model_set_position_scales): the Fermat potential "
+                                   "of a scaled source plane is not served", f, m->pos_fam_scale[f]);
+  for (int l = 0; l < m->n_lens; ++l) {  // the set gl_lens_potential refuses
+    const int kind = m->comps[l].kind;
+    if (kind == GL_SERIES)
+      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its precomputed field holds the deflection, no potential", l);
+    if (kind == GL_USER_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
+                                   "a body defines the deflection only, no potential", l);
+    if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
+  }
+  std::vector<float> tab((size_t)2 * m->pos_J + m->pos_F);
+  std::copy(delay, delay + m->pos_J, tab.begin());
+  std::copy(delay_err, delay_err + m->pos_J, tab.begin() + m->pos_J);
+  std::copy(scale_per_family, scale_per_family + m->pos_F, tab.begin() + 2 * (size_t)m->pos_J);
+  glk::DevBuf<float> fresh;  // (a failed upload leaves the model as it was)
+  GL_HIP(fresh.upload(tab.data(), tab.size()));
+  m->d_pos_delay = std::move(fresh);
+  m->pos_fam_delay = has;
+  m->pos_n_delay = n_delay;
+  return GL_OK;
+}
+
+int gl_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2, float* grad_params_or_null,
+                               float* scale_or_null, float* offset_or_null, float* model_delay_or_null, void* workspace,
+                               size_t workspace_bytes, void* hip_stream) {
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
+  if (rc) return rc;
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const DelayOut out{scale_or_null, offset_or_null, model_delay_or_null};
+  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream, POS_DELAYS, nullptr, nullptr, &out))) return rc;
   GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
   GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
   if (grad_params_or_null)
@@ -556,6 +657,9 @@ int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, 
   if (m->n_series)
     return fail(GL_EUNSUPPORTED, "a series-expansion lens stores its field on the image-plane grid theta, not on the ray's position "
                                  "theta_j on its own plane: not served on lens planes");
+  if (m->pos_n_delay)
+    return fail(GL_EUNSUPPORTED, "the model holds arrival times (gl_model_set_position_delays): the time-delay term is not served on "
+                                 "lens planes");
   if (m->src_scaled) return fail(GL_EINVAL, "the model carries per-source deflection scales (gl_model_set_source_scales): the source couplings of the planes replace them");
   for (int l = 0; l < m->n_lens; ++l)
     if (m->comps[l].kind == K_SCALED)

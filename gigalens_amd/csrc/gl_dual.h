@@ -107,6 +107,7 @@ GLD_T Dual<T, N> fabs_(const Dual<T, N>& a) { return val(a) < 0 ? -a : a; }
 GLD_T Dual<T, N> fmin_(const Dual<T, N>& a, const Dual<T, N>& b) { return a < b ? a : b; }
 GLD_T Dual<T, N> fmax_(const Dual<T, N>& a, const Dual<T, N>& b) { return a > b ? a : b; }
 GLD_T bool isnan_(const Dual<T, N>& a) { auto x = val(a); return x != x; }
+GLD_T auto floor_(const Dual<T, N>& a) { return glm::floor_(val(a)); }  // (a count taken on the value: piecewise constant, a plain scalar)
 GLD_T Dual<T, N> p_sqrt(const Dual<T, N>& a) { return l_sqrt(a); }
 GLD_T Dual<T, N> p_log(const Dual<T, N>& a) { return l_log(a); }
 GLD_T Dual<T, N> p_sin(const Dual<T, N>& a) { return l_sin(a); }

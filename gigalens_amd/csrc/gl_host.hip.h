@@ -29,6 +29,7 @@ struct Workspace {
   int* cost;      // [B] per-sample dispatch cost written by prep (single-EPL models)
   float* gal_dyn;  // [B][G][DP_ND] catalogue members' per-sample constants
   float *pos_w, *pos_adj, *pos_g, *pos_fam, *pos_ll, *pos_chi2, *pos_grad;  // image-position likelihood
+  float* pos_dadj;  // [B][J] d loglike / d Fermat potential of the time-delay term (gl_tdelays.hip.h)
   float* img_ss;   // supersampled / pre-PSF image or its cotangent (PSF path only)
   float* img_tmp;  // final-resolution image / its cotangent (PSF path only)
   float* stats;    // [B][2] chi2, normalisation of the materialised image (PSF path only)
@@ -72,11 +73,14 @@ GL_INTERNAL int post_bwd(const gl_model* m, int B, const float* gP, float* gS, h
 
 // ---- gl_api_points.hip --------------------------------------------------------------------------------------------------
 // point-image likelihood on the packed parameter rows `params` [B,P] (already on the device): the image positions, the flux ratios
-// of a model that holds fluxes (gl_model_set_position_fluxes) or both, summed in w.pos_ll / pos_chi2 / pos_grad.  amp [B][F] and
-// model_flux [B][J]: the flux term's optional outputs (S_f, S_f m_j), or null
-enum PosTerms { POS_POSITIONS = 1, POS_FLUXES = 2, POS_BOTH = 3 };
+// of a model that holds fluxes (gl_model_set_position_fluxes), the time delays of one that holds arrival times
+// (gl_model_set_position_delays) or any sum of them, in w.pos_ll / pos_chi2 / pos_grad.  amp [B][F] and model_flux [B][J]: the flux
+// term's optional outputs (S_f, S_f m_j), or null; delay_out: those of the delay term (lambda_f, T_f [B][F], model delays [B][J])
+enum PosTerms { POS_POSITIONS = 1, POS_FLUXES = 2, POS_BOTH = 3, POS_DELAYS = 4 };
+struct DelayOut { float *scale, *offset, *model_delay; };
 GL_INTERNAL int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream,
-                              int what = POS_POSITIONS, float* amp = nullptr, float* model_flux = nullptr);
+                              int what = POS_POSITIONS, float* amp = nullptr, float* model_flux = nullptr,
+                              const DelayOut* delay_out = nullptr);
 // the model's image of `parts` on its lens planes: into `img` [B][H][W] (x conversion factor), through the PSF + pooling launch of
 // the single-plane render where the model has one
 GL_INTERNAL int mp_render(const gl_model* m, const float* params, int B, unsigned parts, float* img, const Workspace& w,

@@ -173,6 +173,11 @@ struct gl_model {
   // measured fluxes of the images (gl_model_set_position_fluxes, gl_fluxes.hip.h): the flux-ratio term of the point-image likelihood
   int pos_n_flux = 0;              // measured fluxes over all families; 0: the model holds none and every call runs as without them
   glk::DevBuf<float> d_pos_flux;   // [2][J]: flux (NaN = not measured), flux error; allocated only while pos_n_flux
+  // measured arrival times of the images (gl_model_set_position_delays, gl_tdelays.hip.h): the time-delay term of the same likelihood
+  int pos_n_delay = 0;             // measured times over all families; 0: the model holds none and every call runs as without them
+  glk::DevBuf<float> d_pos_delay;  // [2][J] time (NaN = not measured), error, then [F] lambda_f (NaN = profiled); only while pos_n_delay
+  std::vector<char> pos_fam_delay;   // [F] on the host: the family has measured times (empty without delays)
+  std::vector<float> pos_fam_scale;  // [F] on the host: the scales of gl_model_set_position_scales (empty: all 1)
   bool has_epl = false;
   int epl_comp = -1;     // the model's only EPL component, or -1 (none / several)
   int fam = 0;  // family level of the interpreter variant (gl_main_kernel FAM): 1 dPIE family / catalogues / series, 2 gl_extra.h

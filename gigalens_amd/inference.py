@@ -274,7 +274,8 @@ class ModellingSequence:
         if pm.include_pixels:
             n += float(torch.count_nonzero(lens_sim.img_region))
         if pm.include_positions:
-            n += pm.n_position + getattr(pm, "n_flux", 0.0)  # (the flux ratios of the families: part of the point-image term)
+            # (the flux ratios and the time delays of the families: part of the point-image term)
+            n += pm.n_position + getattr(pm, "n_flux", 0.0) + getattr(pm, "n_delay", 0.0)
         return n
 
     def MAP(self, optimizer: Adam, start=None, n_samples=500, num_steps=350, seed=0, progress=None, graph=None):

@@ -253,6 +253,68 @@ def _family_fluxes(fluxes, errors, centroids_x):
     return out_f, out_s, float(n_flux)
 
 
+def _family_delays(delays, errors, distances, centroids_x):
+    """``(delays, errors, distances [F] float64 with NaN = profiled, n_delay)`` of ``ForwardProbModel(centroids_time_delays=...,
+    centroids_time_delays_errors=..., time_delay_distances=...)``: one float32 array per family shaped like its ``centroids_x``, NaN
+    where an image has no measured arrival time (its error is not looked at), errors broadcast as the flux errors are.
+    ``ValueError`` as the constructor documents."""
+    if (delays is None) != (errors is None):
+        raise ValueError("centroids_time_delays and centroids_time_delays_errors come together: give both or neither")
+    if delays is None:
+        if distances is not None:
+            raise ValueError("time_delay_distances needs centroids_time_delays / centroids_time_delays_errors")
+        return None, None, None, 0.0
+    if centroids_x is None:
+        raise ValueError("centroids_time_delays needs centroids_x/centroids_y (include_positions=True)")
+    n_fam = len(centroids_x)
+    if len(delays) != n_fam or len(errors) != n_fam:
+        raise ValueError(f"centroids_time_delays / centroids_time_delays_errors: one entry per image family ({n_fam}), got "
+                         f"{len(delays)} / {len(errors)}")
+    if distances is None:
+        distances = [None] * n_fam
+    elif np.ndim(distances) == 0:
+        raise ValueError(f"time_delay_distances: one float (Mpc) or None per image family ({n_fam}), or a single None; got {distances!r}")
+    if len(distances) != n_fam:
+        raise ValueError(f"time_delay_distances: one entry per image family ({n_fam}), got {len(distances)}")
+    dist = np.asarray([np.nan if d is None else float(d) for d in distances], dtype=np.float64)
+    out_t, out_s, n_delay = [], [], 0
+    for f, (t, s, x) in enumerate(zip(delays, errors, centroids_x)):
+        if t is None:  # a family without delays
+            out_t.append(np.full(x.shape, np.nan, dtype=np.float32))
+            out_s.append(np.full(x.shape, np.nan, dtype=np.float32))
+            continue
+        t = np.atleast_1d(np.asarray(t, dtype=np.float32))
+        if t.shape != x.shape:
+            raise ValueError(f"centroids_time_delays[{f}] has shape {t.shape}, the family's centroids_x {x.shape}")
+        if s is None:
+            raise ValueError(f"centroids_time_delays[{f}] without centroids_time_delays_errors[{f}]")
+        try:
+            s = np.broadcast_to(np.atleast_1d(np.asarray(s, dtype=np.float32)), x.shape).copy()
+        except ValueError:
+            raise ValueError(f"centroids_time_delays_errors[{f}] does not broadcast to the family's shape {x.shape}") from None
+        measured = ~np.isnan(t)
+        if not np.all(np.isfinite(t[measured])):
+            raise ValueError(f"centroids_time_delays[{f}]: a measured arrival time must be finite (NaN marks an image without one), got "
+                             f"{t.tolist()}")
+        if not np.all(np.isfinite(s[measured])):
+            raise ValueError(f"centroids_time_delays_errors[{f}]: the error of a measured arrival time must be finite, got {s.tolist()}")
+        if np.any(s[measured] <= 0):
+            raise ValueError(f"centroids_time_delays_errors[{f}]: the error of a measured arrival time must be > 0, got {s.tolist()}")
+        n = int(measured.sum())
+        if n == 1:
+            raise ValueError(f"centroids_time_delays[{f}]: one measured arrival time -- the term constrains delay differences, a family "
+                             "takes two or more measured times, or none")
+        if n and np.isinf(dist[f]):
+            raise ValueError(f"time_delay_distances[{f}] must be finite (None: profiled out), got {dist[f]}")
+        if n == 2 and np.isnan(dist[f]):
+            raise ValueError(f"centroids_time_delays[{f}]: two measured arrival times with a profiled time-delay distance -- the fit is "
+                             "exact and constrains nothing; give time_delay_distances or three or more measured times")
+        n_delay += n
+        out_t.append(t)
+        out_s.append(s)
+    return out_t, out_s, dist, float(n_delay)
+
+
 class _PackBijector:
     """``pack_bij`` (tf/model.py:78-85): ``(B, d)`` <-> nested structure, column k = k-th nest leaf."""
 
@@ -290,7 +352,8 @@ class ForwardProbModel(ProbabilisticModel):
     def __init__(self, prior, observed_image=None, background_rms=None, exp_time=None, error_map=None,
                  centroids_x=None, centroids_y=None, centroids_errors_x=None, centroids_errors_y=None,
                  include_pixels=True, include_positions=True, centroids_scales=None, centroids_redshifts=None,
-                 centroids_fluxes=None, centroids_fluxes_errors=None):
+                 centroids_fluxes=None, centroids_fluxes_errors=None, centroids_time_delays=None,
+                 centroids_time_delays_errors=None, time_delay_distances=None):
         """``centroids_scales`` (beyond the reference): one deflection scale per image family of ``centroids_x`` -- a family at its
         own redshift is traced with ``beta = theta - c_f alpha`` and ``A = I - c_f H`` in the position likelihood, the predicted
         positions and the image-plane rms.  Default: all 1.
@@ -311,7 +374,23 @@ class ForwardProbModel(ProbabilisticModel):
         ``log_prob_unfused``, ``log_like``, ``log_prob_and_grad`` and ``term_log_prob_and_grad(..., "positions")``, whose reduced chi^2
         becomes ``(chi2_pos + chi2_flux) / (n_position + n_flux)``; ``stats_fluxes`` and ``predicted_fluxes`` give the term alone.  Only
         flux ratios are constrained.  ``ValueError``: fluxes without centroids, fluxes without errors or the reverse, a shape mismatch,
-        exactly one measured flux in a family, a measured flux that is not finite or whose error is not finite and > 0."""
+        exactly one measured flux in a family, a measured flux that is not finite or whose error is not finite and > 0.
+
+        ``centroids_time_delays`` / ``centroids_time_delays_errors`` (beyond the reference): one array per image family, shaped like
+        ``centroids_x[f]`` -- the measured arrival times ``t_j`` of the images in days, relative to any zero, and their errors ``s_j``
+        (broadcast as the flux errors are); NaN marks an image without a measurement, ``None`` or an all-NaN array a family without
+        delays.  ``time_delay_distances``: ``D_dt`` of every family in Mpc, or ``None`` to profile it out (a single ``None``: all).
+        With the Fermat potential ``phi_j = |theta_j - mean beta|^2 / 2 - psi(theta_j)`` of the family's barycentre source,
+        ``lambda_f = D_dt DAYS_PER_MPC_ARCSEC2`` (or ``sum w t~ phi~ / sum w phi~^2``, ``~``: minus the ``w = 1 / s^2`` weighted mean)
+        and ``log_like_f = -1/2 (sum w (t~ - lambda_f phi~)^2 + sum log(2 pi s^2))`` joins the image-position term of ``log_prob``,
+        ``log_prob_unfused``, ``log_like``, ``log_prob_and_grad`` and ``term_log_prob_and_grad(..., "positions")``, whose reduced chi^2
+        becomes ``(chi2_pos + chi2_flux + chi2_delay) / (n_position + n_flux + n_delay)``; ``stats_time_delays`` and
+        ``fitted_time_delays`` give the term alone.  The zero of every family's clock is profiled out: only delay differences are
+        constrained.  ``ValueError``: delays without centroids, delays without errors or the reverse, a shape mismatch, exactly one
+        measured time in a family, two with a profiled distance (the fit is exact), a measured time that is not finite or whose error
+        is not finite and > 0, a distance that is not finite.  At bind time: ``UnsupportedLensError`` on lens planes and for lenses
+        without a potential (series expansions, user-written bodies), ``NotImplementedError`` for a family with delays whose
+        ``centroids_scales`` differs from 1."""
         super().__init__(prior)
         self.include_pixels = include_pixels
         self.include_positions = include_positions
@@ -358,6 +437,8 @@ class ForwardProbModel(ProbabilisticModel):
             self.centroids_redshifts = zf
         self.centroids_fluxes, self.centroids_fluxes_errors, self.n_flux = _family_fluxes(centroids_fluxes, centroids_fluxes_errors,
                                                                                           self.centroids_x)
+        (self.centroids_time_delays, self.centroids_time_delays_errors, self.time_delay_distances,
+         self.n_delay) = _family_delays(centroids_time_delays, centroids_time_delays_errors, time_delay_distances, self.centroids_x)
         self._flat = prior.flat(self.device)
         example = prior.sample(seed=0)
         self.pack_bij = _PackBijector(example)
@@ -442,6 +523,7 @@ class ForwardProbModel(ProbabilisticModel):
             # (validated before anything is handed over: a refusal leaves the native model as it was)
             targets = self.position_targets(mp) if mp is not None and self.centroids_redshifts is not None else None
             scales, given = self._family_scales(simulator) if mp is None else (None, False)
+            delay_scales = self._delay_scales(simulator, scales) if self.n_delay else None
             model.set_positions(self.centroids_x, self.centroids_y, self.centroids_errors_x, self.centroids_errors_y)
             if targets is not None:
                 model.set_position_targets(targets)
@@ -449,8 +531,25 @@ class ForwardProbModel(ProbabilisticModel):
                 model.set_position_scales(scales)
             if self.n_flux:  # (set_positions has cleared the fluxes of an earlier owner)
                 model.set_position_fluxes(np.concatenate(self.centroids_fluxes), np.concatenate(self.centroids_fluxes_errors))
+            if self.n_delay:  # (... and the arrival times)
+                model.set_position_delays(np.concatenate(self.centroids_time_delays), np.concatenate(self.centroids_time_delays_errors),
+                                          delay_scales)
             model.positions_owner = self
         return model
+
+    def _delay_scales(self, simulator, scales):
+        """``lambda_f [F]`` in days / arcsec^2 (NaN: profiled out) for a simulator the time-delay term is served on; its refusals, as
+        ``predicted_time_delays`` words them, before anything is handed to the native model."""
+        if simulator._mp is not None:
+            raise _native.UnsupportedLensError(f"a model with {simulator._mp.K} lens planes: the time-delay term (centroids_time_delays) "
+                                               "stays single-plane")
+        from gigalens_amd.simulator import LensSimulator
+        LensSimulator._potential_lenses(simulator)
+        has = np.asarray([bool(np.any(~np.isnan(t))) for t in self.centroids_time_delays])
+        if np.any(has & (np.asarray(scales) != 1.0)):
+            raise NotImplementedError("centroids_time_delays: the Fermat potential of a scaled source plane (centroids_scales != 1) "
+                                      "is not served; time delays stay single-plane")
+        return (self.time_delay_distances * LensSimulator.DAYS_PER_MPC_ARCSEC2).astype(np.float32)
 
     def _on_planes(self, simulator):
         """True for a simulator with several lens planes, whose fused log-probability comes from the multi-plane entries.  A model
@@ -517,14 +616,46 @@ class ForwardProbModel(ProbabilisticModel):
         self._on_planes(simulator)
         return self._bind_positions(simulator).position_fluxes(packed, False, want_model=True)[3:]
 
+    def _need_delays(self, what):
+        if not self.n_delay:
+            raise ValueError(f"{what} needs a model built with centroids_time_delays / centroids_time_delays_errors")
+
+    def stats_time_delays(self, simulator, params):
+        """``(log_like, chi2 / n_delay)`` of the time-delay term alone (beyond the reference; see ``centroids_time_delays``),
+        differentiable in packed ``params``.  One lens plane, lenses with a potential, families with delays on the reference plane."""
+        self._need_delays("stats_time_delays")
+        packed = params if torch.is_tensor(params) else simulator.pack(params)
+        ll, chi2 = _PointTermFn.apply(packed, self._bind_positions(simulator).position_delays)
+        return ll, chi2 / self.n_delay
+
+    def fitted_time_delays(self, simulator, params):
+        """``(D_dt [B, F], offset [B, F], model_delay [B, J])``: the time-delay distance of every family in Mpc -- the one given, or
+        the profiled ``lambda_f / DAYS_PER_MPC_ARCSEC2`` --, the fitted zero ``T_f`` of its clock in days and the arrival times
+        ``lambda_f phi_j + T_f`` the model gives its images, in the concatenated image order; NaN for a family without delays.
+        Forward only."""
+        self._need_delays("fitted_time_delays")
+        packed = params if torch.is_tensor(params) else simulator.pack(params)
+        if packed.requires_grad:
+            raise NotImplementedError("fitted_time_delays is a forward-only diagnostic (no gradient)")
+        lam, off, md = self._bind_positions(simulator).position_delays(packed, False, want_model=True)[3:]
+        from gigalens_amd.simulator import LensSimulator
+        return lam / LensSimulator.DAYS_PER_MPC_ARCSEC2, off, md
+
     def _point_stats(self, simulator, packed):
-        """``(log_like, red_chi2)`` of the point-image term: the image positions and, when the model has fluxes, their flux ratios --
-        ``red_chi2 = (chi2_pos + chi2_flux) / (n_position + n_flux)``."""
+        """``(log_like, red_chi2)`` of the point-image term: the image positions and, when the model has them, the flux ratios and
+        the time delays -- ``red_chi2 = (chi2_pos + chi2_flux + chi2_delay) / (n_position + n_flux + n_delay)``."""
         ll, red = self.stats_positions(simulator, packed)
+        if not (self.n_flux or self.n_delay):  # the positions alone: the reference's expression, bit for bit
+            return ll, red
+        # (with fluxes alone this is (red n_position + red_flux n_flux) / (n_position + n_flux), operation for operation)
+        chi2, n = red * self.n_position, self.n_position
         if self.n_flux:
             ll_f, red_f = self.stats_fluxes(simulator, packed)
-            ll, red = ll + ll_f, (red * self.n_position + red_f * self.n_flux) / (self.n_position + self.n_flux)
-        return ll, red
+            ll, chi2, n = ll + ll_f, chi2 + red_f * self.n_flux, n + self.n_flux
+        if self.n_delay:
+            ll_d, red_d = self.stats_time_delays(simulator, packed)
+            ll, chi2, n = ll + ll_d, chi2 + red_d * self.n_delay, n + self.n_delay
+        return ll, chi2 / n
 
     def predicted_positions(self, simulator, params, **solver_kwargs):
         """Images the model predicts for every family of ``centroids_x/y`` (beyond the reference).  The source of a family is

@@ -223,6 +223,39 @@ int gl_position_fluxes_fwd_bwd(const gl_model* m, const float* params, int B, fl
                                float* amplitude_or_null, float* model_flux_or_null, void* workspace, size_t workspace_bytes,
                                void* hip_stream);
 
+/* Time delays of the image families (beyond the reference): the third observable of a lensed quasar or supernova.  Family f has
+ * images theta_j with beta_j as the position likelihood traces them and the source  mean beta  over ALL its images.  An image with a
+ * measured arrival time t_j (days, relative to any zero) and error s_j enters with weight w_j = 1 / s_j^2.  With
+ *   phi_j = 1/2 |theta_j - mean beta|^2 - psi(theta_j)   (arcsec^2; psi as gl_lens_potential),  phi~, t~: minus their w-weighted means,
+ *   lambda_f = the family's given scale, or profiled out:  sum w t~ phi~ / sum w phi~^2 ,
+ *   chi2_f = sum w (t~ - lambda_f phi~)^2 ,  ll_f = -1/2 (chi2_f + sum log(2 pi s^2)) ,  T_f = t_bar - lambda_f phi_bar ,
+ * the zero T_f of the family's clock is always profiled out: only delay differences are constrained.  T_f, and lambda_f where it is
+ * profiled, minimise chi2_f, so the gradient is the partial derivative at fixed (lambda_f, T_f).  lambda_f is D_dt / c in
+ * days / arcsec^2: D_dt [Mpc] x 0.0280 (LensSimulator.DAYS_PER_MPC_ARCSEC2).
+ *   gl_model_set_position_delays  delay, delay_err [n_images] (HOST pointers, copied) in the concatenated image order of
+ *       gl_model_set_positions, which must have been called (and which clears the delays); a NaN time marks an image without a
+ *       measurement, delay = NULL (or every time NaN) clears them.  scale_per_family [n_families]: lambda_f, or NaN to profile it.
+ *       GL_EINVAL, the model left as it was: counts that do not match, a measured time that is not finite or whose error is not
+ *       finite and > 0, a family with exactly one measured time, a family with two measured times and a NaN scale (the fit would be
+ *       exact).  GL_EUNSUPPORTED, the model left as it was: lens planes (gl_model_set_lens_planes, which in turn refuses a model that
+ *       holds delays), a family with delays whose deflection scale differs from 1 (gl_model_set_position_scales, which in turn
+ *       refuses such a scale), a GL_SERIES or GL_USER_MASS lens -- the set gl_lens_potential refuses.  A negative or huge profiled
+ *       lambda_f is data, not an error.  The workspace layout does not change.  The checks run in this order: the tables (GL_EINVAL),
+ *       then -- only if some time is measured; a table of NaN clears and returns GL_OK like delay = NULL -- planes, scales, lens kinds.
+ *       While the model holds delays, GL_TERM_POSITIONS of gl_logprob_fwd_bwd is the sum of the point terms and its reduced chi2
+ *       divides by 2 J + n_flux + n_delay (n_delay: the measured times); gl_positions_fwd_bwd and gl_position_fluxes_fwd_bwd keep
+ *       their bits.
+ *   gl_position_delays_fwd_bwd    the delay term alone: loglike, chi2 [B] (summed over the families, not reduced), and when given
+ *       d loglike / d params [B][P], scale [B][n_families] = lambda_f, offset [B][n_families] = T_f and model_delay [B][n_images] =
+ *       lambda_f phi_j + T_f in days (NaN for a family without delays).  Workspace of gl_workspace_bytes(m, B); enqueues on the
+ *       caller's stream without allocation or synchronisation; no atomics: two calls give identical bits.  GL_EINVAL before
+ *       gl_model_set_positions / gl_model_set_position_delays. */
+int gl_model_set_position_delays(gl_model* m, const float* delay, const float* delay_err, int n_images, const float* scale_per_family,
+                                 int n_families);
+int gl_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2, float* grad_params_or_null,
+                               float* scale_or_null, float* offset_or_null, float* model_delay_or_null, void* workspace,
+                               size_t workspace_bytes, void* hip_stream);
+
 /* ScalingRelation.hessian on arbitrary points (scaling_relation.py:72-83): out [4][n_pts][B] = f_xx, f_xy, f_yx, f_yy
  * summed over the catalogue; other arguments as gl_scaled_eval. */
 int gl_scaled_hessian(int base_kind, int n_galaxies, const int32_t scale_col[3], const float* table_dev, const float* x,
