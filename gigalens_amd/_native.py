@@ -110,6 +110,9 @@ SYMBOLS = {
     "gl_series_hessian_eval": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "gl_model_set_series_hessian": (c_int, [c_void_p, c_int, c_void_p]),
     "gl_lens_maps": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "gl_lens_maps_vjp_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int64]),
+    "gl_lens_maps_vjp": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
     "gl_model_set_lens_planes": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_float), POINTER(c_float), c_int]),
     "gl_multiplane_maps": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, POINTER(c_float), c_int, c_void_p,
                                    c_void_p]),
@@ -134,6 +137,11 @@ SYMBOLS = {
     "gl_pixsrc_reconstruct": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                       c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    "gl_pixsrc_grad_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "gl_pixsrc_grad_layout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32)]),
+    "gl_pixsrc_evidence_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_size_t, c_void_p]),
     "gl_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
                                    c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_model_num_linear": (c_int, [c_void_p]),
@@ -720,6 +728,23 @@ class Model:
         _check(lib().gl_lens_maps(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), xb.shape[0], 1, _ptr(out), _stream()))
         return out.reshape((6,) + tuple(shape))
 
+    def lens_maps_vjp(self, params, x, y, cot_x, cot_y):
+        """gl_lens_maps_vjp: the cotangents ``cot_x, cot_y`` on ``lens_maps``' beta_x, beta_y (with ``x, y`` broadcastable to
+        ``(..., B)``) -> the gradient on the packed rows ``[B, P]``; columns of no lens are 0.  Points whose cotangents are both
+        exactly 0, or not finite, are skipped.  ``UnsupportedLensError``: series and user-written lenses, lens planes."""
+        self._single_plane("lens_maps_vjp")
+        params = self._params(params)
+        B = params.shape[0]
+        xb, yb, shape = self._points(x, y, B)
+        cot = torch.stack([torch.as_tensor(c, dtype=torch.float32, device=self.device).expand(shape).reshape(-1, B)
+                           for c in (cot_x, cot_y)]).contiguous()
+        n_pts = xb.shape[0]
+        ws = self._scratch("lens_maps_vjp", lib().gl_lens_maps_vjp_workspace_bytes(self._h, B, n_pts))
+        out = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
+        _check_potential(lib().gl_lens_maps_vjp(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), n_pts, 1, _ptr(cot), _ptr(out), _ptr(ws),
+                                                ws.numel(), _stream()))
+        return out
+
     def lens_potential(self, params, x, y):
         """gl_lens_potential: ``x, y`` broadcastable to ``(..., B)`` (or both None: the model's own grid, ``(N, B)``); returns psi."""
         self._single_plane("lens_potential")
@@ -978,6 +1003,41 @@ class Model:
                                                      _ptr(source), _ptr(image), _ptr(scalars), _ptr(ok), _ptr(ws), ws.numel(),
                                                      _stream()))
         return source, image, scalars, ok
+
+    def pixsrc_evidence_grad(self, beta_x, beta_y, obs, sigma, lens_light, pix, n_src, pose, regularization, strength):
+        """gl_pixsrc_evidence_grad: the arguments of ``pixsrc_reconstruct`` with ``strength`` [B].  Returns ``source`` [B, ny, nx],
+        ``model_image`` [B, H, W], ``scalars`` [B, 3] and ``ok`` [B] (the bits of ``pixsrc_reconstruct``), ``grad_beta``
+        [2, B, Hs Ws] (d E / d beta_x, beta_y) and ``grad_image`` [B, H, W] (d E / d lens-light image)."""
+        self._single_plane("pixsrc_evidence_grad")
+        ny, nx = (int(v) for v in n_src)
+        B, n_used = int(beta_x.shape[0]), int(pix.numel())
+        f32 = lambda t, shape, what: self._pix_tensor(t, torch.float32, shape, what)
+        beta_x, beta_y = f32(beta_x, (B, self.ss_h * self.ss_w), "beta_x"), f32(beta_y, (B, self.ss_h * self.ss_w), "beta_y")
+        obs, sigma = f32(obs, (B, n_used), "obs"), f32(sigma, (B, n_used), "sigma")
+        pose, strength = f32(pose, (B, 3), "pose"), f32(strength, (B,), "strength")
+        pix = self._pix_tensor(pix, torch.int32, (n_used,), "pix")
+        if lens_light is not None:
+            lens_light = f32(lens_light, (B, self.out_h, self.out_w), "lens_light")
+        ws = self._scratch("pixsrc_grad", lib().gl_pixsrc_grad_workspace_bytes(self._h, B, ny, nx, n_used))
+        dev = self.device
+        source = torch.empty((B, ny, nx), dtype=torch.float32, device=dev)
+        image = torch.empty((B, self.out_h, self.out_w), dtype=torch.float32, device=dev)
+        scalars = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        ok = torch.empty((B,), dtype=torch.int32, device=dev)
+        grad_beta = torch.empty((2, B, self.ss_h * self.ss_w), dtype=torch.float32, device=dev)
+        grad_image = torch.empty((B, self.out_h, self.out_w), dtype=torch.float32, device=dev)
+        _check(lib().gl_pixsrc_evidence_grad(self._h, _ptr(beta_x), _ptr(beta_y), B, _ptr(obs), _ptr(sigma), _ptr(lens_light), _ptr(pix),
+                                             n_used, ny, nx, _ptr(pose), int(regularization), _ptr(strength), _ptr(source), _ptr(image),
+                                             _ptr(scalars), _ptr(ok), _ptr(grad_beta), _ptr(grad_image), _ptr(ws), ws.numel(),
+                                             _stream()))
+        return source, image, scalars, ok, grad_beta, grad_image
+
+    def pixsrc_grad_layout(self, B, n_src, n_used):
+        """gl_pixsrc_grad_layout: ``dict(cb, pc, n_pad)`` -- samples per chunk, planes per post-processing launch and the padded row
+        length of a ``pixsrc_evidence_grad`` call of these sizes (host only)."""
+        out = (c_int32 * 3)()
+        _check(lib().gl_pixsrc_grad_layout(self._h, int(B), int(n_src[0]), int(n_src[1]), int(n_used), out))
+        return dict(zip(("cb", "pc", "n_pad"), (int(v) for v in out)))
 
     def pixsrc_layout(self, B, n_strength, n_src, n_used):
         """gl_pixsrc_layout: ``dict(cb, lch, pc, n_pad)`` -- samples per chunk, strengths per slice, basis planes per post-processing

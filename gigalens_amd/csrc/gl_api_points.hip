@@ -16,6 +16,7 @@
 #include "gl_multiplane.hip.h"
 #include "gl_multiplane_bwd.hip.h"
 #include "gl_multiplane_pos.hip.h"
+#include "gl_lens_vjp.hip.h"
 
 using namespace glk;
 
@@ -377,6 +378,52 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
   }
   hipLaunchKernelGGL(gl_lens_maps_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, a,
                      x, y, (long long)n_pts, xy_batched, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- VJP of the ray-shoot (gl_lens_vjp.hip.h) ------------------------------------------------------------------
+namespace {
+// blocks of VJP_PTS points per (sample, lens column); 0: a size the call refuses
+long long vjp_blocks(const gl_model* m, int B, int64_t n_pts) {
+  if (!m || B <= 0 || n_pts <= 0) return 0;
+  const long long n_blocks = ((long long)n_pts + VJP_PTS - 1) / VJP_PTS;
+  const long long rows = (long long)B * std::max(m->lens_params, 1);
+  return n_blocks <= 0x7fffffffLL / rows && (long long)B * std::max(m->P, 1) <= 0x7fffffffLL ? n_blocks : 0;
+}
+}  // namespace
+
+size_t gl_lens_maps_vjp_workspace_bytes(const gl_model* m, int B, int64_t n_pts) {
+  const long long n_blocks = vjp_blocks(m, B, n_pts);
+  if (!n_blocks) return 0;
+  return align_up((size_t)B * (size_t)std::max(m->lens_params, 1) * (size_t)n_blocks * sizeof(float), 256);
+}
+
+int gl_lens_maps_vjp(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
+                     const float* cot, float* grad_params, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !x || !y || !cot || !grad_params || !workspace) return fail(GL_EINVAL, "null argument");
+  if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
+  if (int rp = refuse_planes(m, "gl_lens_maps_vjp")) return rp;
+  for (int l = 0; l < m->n_lens; ++l) {
+    const int kind = m->comps[l].kind;
+    if (kind == GL_SERIES)
+      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its field lives on the model grid and has no parameter derivative here", l);
+    if (kind == GL_USER_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
+                                   "not served by the ray-shoot VJP", l);
+  }
+  if (int rc = check_ready(m, false, false)) return rc;
+  const long long n_blocks = vjp_blocks(m, B, n_pts);
+  if (!n_blocks) return fail(GL_EINVAL, "too many points x samples for one call");
+  const size_t need = gl_lens_maps_vjp_workspace_bytes(m, B, n_pts);
+  if (workspace_bytes < need) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  float* partial = (float*)workspace;
+  if (m->lens_params)
+    hipLaunchKernelGGL(gl_lens_vjp_kernel, dim3((unsigned)((long long)B * m->lens_params * n_blocks)), dim3(VJP_WG), 0, stream,
+                       point_args(m, params, B), x, y, (long long)n_pts, xy_batched, cot, m->lens_params, (int)n_blocks, partial);
+  hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
+                     m->P, m->lens_params, (int)n_blocks, grad_params);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

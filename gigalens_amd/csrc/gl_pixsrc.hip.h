@@ -419,4 +419,147 @@ __global__ void __launch_bounds__(PIX_WG) gl_pix_combine_kernel(PixArgs a) {
   }
 }
 
+// ---- gradient of the evidence with respect to the rays (gl_pixsrc_evidence_grad) ---------------------------------------------
+// With Fw = D P L, rw = yw - Fw s and E = -1/2 |rw|^2 - 1/2 lambda s^T R s - 1/2 log det M (s stationary for the first two terms,
+// d log det M = 2 tr(M^-1 Fw^T dFw)):   dE/dF = D (rw s^T - Fw M^-1)  [n_used x S],   G = P^T (dE/dF scattered to the H x W image)
+// [Hs Ws x S]  (P^T: the model's own post_bwd), and with u = (beta_x - cx) / pitch + (nx-1)/2, v likewise,
+//   dE/dbeta_x[q] = (1/pitch) sum_(j,i) G[q,(j,i)] hat(v_q - j) hat'(u_q - i),   dE/dbeta_y[q] = (1/pitch) sum G hat'(v_q - j) hat(u_q - i),
+// hat'(t) = -sign(t) for 0 < |t| < 1, else 0: at most the four nodes around (u_q, v_q) contribute, and a ray with a row of exact
+// zeros in L (not finite, out of range) has a cotangent of exactly zero.  After the forward launches of a chunk of samples:
+//   resid    (b, used pixel):     rw = yw - Fw s, the sum in float64 as combine has it
+//   inv      (pooled pixel):      the inverse of `pix`: index of the used pixel, -1 elsewhere (once per call)
+//   gimage   (b, pooled pixel):   grad_image = rw / sigma on the used pixels, 0 elsewhere
+//   zsolve   (b, column of Fw):   Z = M^-1 Fw from the factor solve left in the workspace: one thread a right-hand side, forward and
+//                                 back substitution in float32 in ascending / descending node order (columns past n_used are zero)
+//   scatter  (plane, pooled px):  column (b, s) of dE/dF as a pooled plane: every element WRITTEN, no atomics, nothing to clear
+//   post_bwd                      the model's own transpose of PSF + pooling over a chunk of planes
+//   contract (b, subpixel):       one thread owns a supersampled pixel and adds the nodes of this chunk that are among its four,
+//                                 in ascending node order; chunks arrive in launch order on one stream, so the order is fixed
+struct PixGradArgs {
+  const float* Z;     // [B][S][n_pad]  M^-1 Fw
+  const float* rw;    // [B][n_pad]
+  const int* inv;     // [HW] used-pixel index of a pooled pixel, or -1
+  float* gbx;         // [B][HsWs] of this chunk
+  float* gby;
+  float* gimg;        // [B][HW] of this chunk
+};
+
+__global__ void __launch_bounds__(PIX_WG) gl_pix_resid_kernel(PixArgs a, float* __restrict__ rw) {
+  const int n = blockIdx.x * PIX_WG + threadIdx.x, b = blockIdx.y;
+  if (n >= a.n_pad) return;
+  float r = 0.f;
+  if (n < a.n_used) {
+    const float* F = a.Fw + (size_t)b * a.S * a.n_pad;
+    const float* s = a.source + (size_t)b * a.L_total * a.S;
+    double acc = 0.0;
+    for (int p = 0; p < a.S; ++p) acc = fma((double)F[(size_t)p * a.n_pad + n], (double)s[p], acc);
+    r = (float)((double)a.yw[(size_t)b * a.n_pad + n] - acc);
+  }
+  rw[(size_t)b * a.n_pad + n] = r;
+}
+
+__global__ void __launch_bounds__(PIX_WG) gl_pix_inv_fill_kernel(int HW, int* __restrict__ inv) {
+  const int k = blockIdx.x * PIX_WG + threadIdx.x;
+  if (k < HW) inv[k] = -1;
+}
+__global__ void __launch_bounds__(PIX_WG) gl_pix_inv_set_kernel(const int* __restrict__ pix, int n_used, int HW, int* __restrict__ inv) {
+  const int n = blockIdx.x * PIX_WG + threadIdx.x;
+  if (n < n_used && pix[n] >= 0 && pix[n] < HW) inv[pix[n]] = n;
+}
+
+__global__ void __launch_bounds__(PIX_WG) gl_pix_gimage_kernel(PixArgs a, PixGradArgs g) {
+  const int k = blockIdx.x * PIX_WG + threadIdx.x, b = blockIdx.y;
+  if (k >= a.HW) return;
+  const int n = g.inv[k];
+  float v = 0.f;
+  if (!a.ok[(size_t)b * a.L_total]) v = __builtin_nanf("");
+  else if (n >= 0) v = g.rw[(size_t)b * a.n_pad + n] / a.sigma[(size_t)b * a.n_used + n];
+  g.gimg[(size_t)b * a.HW + k] = v;
+}
+
+// Z [S][n_pad] of sample b: column n of Fw through L w = f, L^T z = w with the lower-triangle factor in a.M (one strength per sample).
+// One wave per workgroup (the columns of a sample spread over many CUs); a row's dot product runs in four interleaved partial sums,
+// added as (t0 + t1) + (t2 + t3): a fixed order that keeps four loads in flight instead of one.
+constexpr int PIX_ZS_WG = 64;
+__global__ void __launch_bounds__(PIX_ZS_WG) gl_pix_zsolve_kernel(PixArgs a, float* Zall) {
+  const int n = blockIdx.x * PIX_ZS_WG + threadIdx.x, b = blockIdx.y, S = a.S;
+  if (n >= a.n_pad || !a.ok[(size_t)b * a.L_total]) return;
+  const float* Lf = a.M + (size_t)b * S * S;
+  const float* F = a.Fw + (size_t)b * S * a.n_pad + n;
+  float* Z = Zall + (size_t)b * S * a.n_pad + n;
+  const size_t st = (size_t)a.n_pad;
+  for (int i = 0; i < S; ++i) {
+    const float* row = Lf + (size_t)i * S;
+    float t0 = F[(size_t)i * st], t1 = 0.f, t2 = 0.f, t3 = 0.f;
+    int k = 0;
+    for (; k + 4 <= i; k += 4) {
+      t0 = fmaf(-row[k], Z[(size_t)k * st], t0);
+      t1 = fmaf(-row[k + 1], Z[(size_t)(k + 1) * st], t1);
+      t2 = fmaf(-row[k + 2], Z[(size_t)(k + 2) * st], t2);
+      t3 = fmaf(-row[k + 3], Z[(size_t)(k + 3) * st], t3);
+    }
+    for (; k < i; ++k) t0 = fmaf(-row[k], Z[(size_t)k * st], t0);
+    Z[(size_t)i * st] = ((t0 + t1) + (t2 + t3)) / row[i];
+  }
+  for (int i = S - 1; i >= 0; --i) {
+    float t0 = Z[(size_t)i * st], t1 = 0.f, t2 = 0.f, t3 = 0.f;
+    int k = S - 1;
+    for (; k - 4 >= i; k -= 4) {
+      t0 = fmaf(-Lf[(size_t)k * S + i], Z[(size_t)k * st], t0);
+      t1 = fmaf(-Lf[(size_t)(k - 1) * S + i], Z[(size_t)(k - 1) * st], t1);
+      t2 = fmaf(-Lf[(size_t)(k - 2) * S + i], Z[(size_t)(k - 2) * st], t2);
+      t3 = fmaf(-Lf[(size_t)(k - 3) * S + i], Z[(size_t)(k - 3) * st], t3);
+    }
+    for (; k > i; --k) t0 = fmaf(-Lf[(size_t)k * S + i], Z[(size_t)k * st], t0);
+    Z[(size_t)i * st] = ((t0 + t1) + (t2 + t3)) / Lf[(size_t)i * S + i];
+  }
+}
+
+// planes p0 .. p0 + gridDim.y - 1 of the chunk's flat (sample, node) list -> out[plane][k] = out_scale dE/dF[n(k), node] (0 off the used pixels)
+__global__ void __launch_bounds__(PIX_WG) gl_pix_scatter_kernel(PixArgs a, PixGradArgs g, int p0, float out_scale, float* __restrict__ out) {
+  const int k = blockIdx.x * PIX_WG + threadIdx.x;
+  if (k >= a.HW) return;
+  const int p = p0 + blockIdx.y, b = p / a.S, s = p - b * a.S;
+  const int n = g.inv[k];
+  float v = 0.f;
+  if (n >= 0 && a.ok[(size_t)b * a.L_total]) {
+    const float src = a.source[(size_t)b * a.L_total * a.S + s];
+    v = out_scale * (g.rw[(size_t)b * a.n_pad + n] * src - g.Z[((size_t)b * a.S + s) * a.n_pad + n]) / a.sigma[(size_t)b * a.n_used + n];
+  }
+  out[(size_t)blockIdx.y * a.HW + k] = v;
+}
+
+__device__ inline float pix_dhat(float t) { return (t > 0.f && t < 1.f) ? -1.f : ((t < 0.f && t > -1.f) ? 1.f : 0.f); }
+
+// samples b_lo .. b_lo + gridDim.y - 1 of the chunk, planes p0 .. p0 + np - 1 in G [np][HsWs]
+__global__ void __launch_bounds__(PIX_WG) gl_pix_contract_kernel(PixArgs a, PixGradArgs g, int b_lo, int p0, int np, const float* __restrict__ G) {
+  const int q = blockIdx.x * PIX_WG + threadIdx.x;
+  if (q >= a.HsWs) return;
+  const int b = b_lo + blockIdx.y;
+  const size_t o = (size_t)b * a.HsWs + q;
+  const bool first = b * a.S >= p0, last = (b + 1) * a.S <= p0 + np;  // this launch holds the sample's first / last plane
+  float gx = first ? 0.f : g.gbx[o], gy = first ? 0.f : g.gby[o];
+  const float pitch = a.pose[3 * b], cx = a.pose[3 * b + 1], cy = a.pose[3 * b + 2];
+  const float u = (a.beta_x[o] - cx) / pitch + 0.5f * (float)(a.nx - 1);
+  const float v = (a.beta_y[o] - cy) / pitch + 0.5f * (float)(a.ny - 1);
+  const bool in = u >= -2.f && u <= (float)(a.nx + 1) && v >= -2.f && v <= (float)(a.ny + 1);
+  if (in) {
+    const int j0 = (int)floorf(v), i0 = (int)floorf(u);
+    for (int dj = 0; dj < 2; ++dj)
+      for (int di = 0; di < 2; ++di) {
+        const int j = j0 + dj, i = i0 + di;
+        if (j < 0 || j >= a.ny || i < 0 || i >= a.nx) continue;
+        const int p = b * a.S + j * a.nx + i;
+        if (p < p0 || p >= p0 + np) continue;
+        const float w = G[(size_t)(p - p0) * a.HsWs + q];
+        const float tu = u - (float)i, tv = v - (float)j;
+        gx += w * pix_hat(tv) * pix_dhat(tu) / pitch;
+        gy += w * pix_dhat(tv) * pix_hat(tu) / pitch;
+      }
+  }
+  if (last && !a.ok[(size_t)b * a.L_total]) gx = gy = __builtin_nanf("");
+  g.gbx[o] = gx;
+  g.gby[o] = gy;
+}
+
 }  // namespace glk

@@ -931,3 +931,75 @@ class BackwardProbModel(ProbabilisticModel):
 
     def init_centroids(self, bs):
         return None
+
+
+class _SourceEvidenceFn(torch.autograd.Function):
+    """log evidence of the pixelated source (``LensSimulator.source_evidence_and_grad``) with its hand-written gradient with
+    respect to the packed rows."""
+
+    @staticmethod
+    def forward(ctx, packed, prob_model, simulator):
+        pm = prob_model
+        res = simulator.source_evidence_and_grad(packed.detach(), pm.observed_image, pm.err_map, n_src=pm.n_src, pitch=pm.pitch,
+                                                 center=pm.center, regularization=pm.regularization, strength=pm.strength,
+                                                 mask=pm.mask)
+        ctx.save_for_backward(res["grad"])
+        ctx.mark_non_differentiable(res["chi2"])
+        return res["log_evidence"].float(), res["chi2"].float()
+
+    @staticmethod
+    def backward(ctx, g_ev, g_chi2):
+        (grad,) = ctx.saved_tensors
+        return g_ev[:, None] * grad, None, None
+
+
+class SourceEvidenceProbModel(ProbabilisticModel):
+    """The Bayesian evidence of a pixelated source as the target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the reference):
+    ``log_prob = log_evidence + log_prior`` of ``LensSimulator.reconstruct_source`` at one regularisation strength, with the
+    hand-written gradient of ``LensSimulator.source_evidence_and_grad``.  The prior is over ``lens_mass``, and over ``lens_light``
+    where the model has lens light; the model's ``source_light`` is replaced by the source grid (``n_src``, ``pitch``, ``center``,
+    as in ``reconstruct_source``).  The evidence is continuous but only piecewise smooth in the lens (a kink wherever a ray crosses
+    a source-grid line); its gradient is taken with the set of finite rays held fixed.  Runs on the stream path."""
+
+    include_pixels, include_positions, n_position = True, False, 0.0
+
+    def __init__(self, prior, observed_image, err_map, *, n_src, pitch, center=(0.0, 0.0), regularization="gradient", strength=1.0,
+                 mask=None):
+        super().__init__(prior)
+        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
+        self.observed_image = torch.as_tensor(np.asarray(observed_image, dtype=np.float32), device=self.device).contiguous()
+        self.err_map = torch.as_tensor(np.asarray(err_map, dtype=np.float32), device=self.device).contiguous()
+        self.n_src, self.pitch, self.center = (int(n_src[0]), int(n_src[1])), pitch, tuple(center)
+        self.regularization, self.strength = regularization, strength
+        self.mask = None if mask is None else np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).astype(bool)
+        self._flat = prior.flat(self.device)
+        example = prior.sample(seed=0)
+        self.pack_bij = _PackBijector(example)
+        self.unconstraining_bij = _prior.JointBijector(self._flat)
+        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+
+    def _n_used(self, simulator):
+        used = np.asarray(simulator.img_region.cpu()) != 0
+        return int((used & self.mask).sum() if self.mask is not None else used.sum())
+
+    def log_prob(self, simulator, z):
+        """``(log_evidence + log_prior, chi2 / n_used)``; differentiable with respect to ``z``."""
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        x = self._flat.forward(z)
+        log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+        packed = simulator._pack_partial(self.pack_bij.forward(x))  # missing groups filled; torch.stack keeps the graph
+        ev, chi2 = _SourceEvidenceFn.apply(packed, self, simulator)
+        return ev + log_prior, chi2 / float(self._n_used(simulator))
+
+    def log_prob_and_grad(self, simulator, z):
+        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
+        lp, red = self.log_prob(simulator, zz)
+        (g,) = torch.autograd.grad(lp.sum(), zz)
+        return lp.detach(), red.detach(), g
+
+    def log_prior(self, z):
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
+
+    def init_centroids(self, bs):
+        return None

@@ -272,6 +272,21 @@ class LensSimulator(LensSimulatorInterface):
                 lens._hessian_bound = lens._hcoefs
         return self._model.lens_maps(packed, None, None)
 
+    def beta_vjp(self, x, y, lens_params, cot_x, cot_y, deflection_scale=1.0):
+        """The VJP of ``beta`` with respect to the lens parameters (beyond the reference, whose tape does this): the cotangents
+        ``cot_x, cot_y`` on ``beta_x, beta_y`` at ``(x, y)`` (point layout as the lens maps: broadcastable to ``(..., B)``) -> the
+        gradient ``[B, P]`` in packed order, zero outside the lens-mass columns.  ``beta = theta - c sum alpha``, so the cotangent is
+        scaled by ``c = deflection_scale``.  A point whose two cotangents are both exactly 0, or not finite, is skipped (its
+        deflection is never formed).  Deterministic.  ``UnsupportedLensError``: lens planes, series and user-written lenses."""
+        self._single_plane("beta_vjp")
+        cs = self._scale(deflection_scale)
+        packed = self._pack_partial({"lens_mass": lens_params}) if not torch.is_tensor(lens_params) else lens_params
+        cot_x = torch.as_tensor(cot_x, dtype=torch.float32, device=self.device)
+        cot_y = torch.as_tensor(cot_y, dtype=torch.float32, device=self.device)
+        if cs != 1.0:
+            cot_x, cot_y = cs * cot_x, cs * cot_y
+        return self._model.lens_maps_vjp(packed, x, y, cot_x, cot_y)
+
     def _hessian(self, x, y, lens_params, deflection_scale):
         """``f_xx, f_xy, f_yx, f_yy`` of ``_lens_maps`` on the plane of ``deflection_scale`` (linear in it: ``c H``).  With lens
         planes: ``I - A_t`` of the target plane, which is not symmetric."""
@@ -605,14 +620,37 @@ class LensSimulator(LensSimulatorInterface):
         finite or not positive, and the sample's other outputs are then NaN.  ``ValueError`` for ``ny nx > 1024``, a ``strength`` or
         ``pitch`` that is not finite or not > 0, an ``err_map`` that is not finite or not > 0 on a used pixel, an unknown
         ``regularization`` and shapes that do not match; lens kinds ``lens_maps`` refuses stay refused with its error.  Forward only."""
-        self._single_plane("reconstruct_source")
+        p = self._pixsrc_prepare("reconstruct_source", params, observed_image, err_map, n_src, pitch, center, regularization, strength,
+                                 mask, deflection_scale)
+        source, image, scal, ok = self._model.pixsrc_reconstruct(p["bx"], p["by"], p["obs_u"], p["sig_u"], p["lens_light"], p["pix"],
+                                                                 p["n_src"], p["pose"], self.REGULARIZATIONS[regularization], p["lam_t"])
+        out = self._pixsrc_outputs(p, regularization, source, image, scal, ok)
+        return out if p["scan"] else {k: v[:, 0] for k, v in out.items()}
+
+    def _pixsrc_outputs(self, p, regularization, source, image, scal, ok):
+        """The result dict of the pixelated-source calls from the native outputs (an ``L`` axis after ``B`` on every entry)."""
+        ny, nx = p["n_src"]
+        S = ny * nx
+        chi2, reg, log_det = scal[..., 0], scal[..., 1], scal[..., 2]
+        lam64 = p["lam_t"].double()
+        noise = torch.log(2.0 * math.pi * p["sig_u"].double() ** 2).sum(dim=1, keepdim=True)
+        log_ev = (-0.5 * chi2 - 0.5 * lam64 * reg - 0.5 * log_det + 0.5 * S * torch.log(lam64)
+                  + 0.5 * self.log_det_regularization(regularization, (ny, nx)) - 0.5 * noise)
+        return {"source": source, "model_image": image, "chi2": chi2, "reg": reg, "log_det": log_det, "log_evidence": log_ev,
+                "ok": ok != 0}
+
+    def _pixsrc_prepare(self, what, params, observed_image, err_map, n_src, pitch, center, regularization, strength, mask,
+                        deflection_scale):
+        """Validation and input preparation the pixelated-source calls share: the used pixels, data and rms on them, the rays of
+        the whole supersampled frame, the lens-light image, pose and strengths, all on the device."""
+        self._single_plane(what)
         if regularization not in self.REGULARIZATIONS:
             raise ValueError(f"regularization must be one of {sorted(self.REGULARIZATIONS)}, got {regularization!r}")
         ny, nx = (int(v) for v in n_src)
         if ny < 1 or nx < 1 or ny * nx > self.MAX_SOURCE_NODES:
             raise ValueError(f"n_src = ({ny}, {nx}): the source grid must have 1 .. {self.MAX_SOURCE_NODES} nodes")
         packed = self._pack_partial(params)
-        self._forward_only("reconstruct_source", packed, observed_image, err_map, strength)
+        self._forward_only(what, packed, observed_image, err_map, strength)
         B = packed.shape[0]
         H, W = self._model.out_h, self._model.out_w
         ss, dev = self.supersample, self.device
@@ -665,17 +703,49 @@ class LensSimulator(LensSimulatorInterface):
         lens_light = self._model.simulate_parts(packed, 2) if len(self.phys_model.lens_light) else None
         pose = torch.from_numpy(np.stack([pitch_h, cx_h, cy_h], axis=1)).to(dev)
         lam_t = torch.from_numpy(np.ascontiguousarray(lam)).to(dev)
-        source, image, scal, ok = self._model.pixsrc_reconstruct(bx, by, obs_u, sig_u, lens_light, torch.from_numpy(pix).to(dev),
-                                                                 (ny, nx), pose, self.REGULARIZATIONS[regularization], lam_t)
-        S = ny * nx
-        chi2, reg, log_det = scal[..., 0], scal[..., 1], scal[..., 2]
-        lam64 = lam_t.double()
-        noise = torch.log(2.0 * math.pi * sig_u.double() ** 2).sum(dim=1, keepdim=True)
-        log_ev = (-0.5 * chi2 - 0.5 * lam64 * reg - 0.5 * log_det + 0.5 * S * torch.log(lam64)
-                  + 0.5 * self.log_det_regularization(regularization, (ny, nx)) - 0.5 * noise)
-        out = {"source": source, "model_image": image, "chi2": chi2, "reg": reg, "log_det": log_det, "log_evidence": log_ev,
-               "ok": ok != 0}
-        return out if scan else {k: v[:, 0] for k, v in out.items()}
+        return {"packed": packed, "B": B, "n_src": (ny, nx), "scan": scan, "cs": cs, "pix": torch.from_numpy(pix).to(dev), "obs_u": obs_u,
+                "sig_u": sig_u, "gx": gx_t, "gy": gy_t, "bx": bx, "by": by, "lens_light": lens_light, "pose": pose, "lam_t": lam_t}
+
+    def source_evidence_and_grad(self, params, observed_image, err_map, *, n_src, pitch, center=(0.0, 0.0), regularization="gradient",
+                                 strength=1.0, mask=None, deflection_scale=1.0):
+        """``reconstruct_source`` for one strength per sample (``strength``: a scalar or ``[B]``; 2-D raises ``ValueError``) with the
+        gradient of the evidence.  Returns the dict of ``reconstruct_source`` plus ``grad`` ``[B, P]`` (float32, packed order:
+        d log_evidence / d lens-mass parameters through the rays, d / d lens-light parameters through the lens-light image, 0 in
+        the source-light columns), ``grad_pose`` ``[B, 3]`` = d / d(pitch, cx, cy) and ``grad_beta`` ``[2, B, Hs Ws]`` (d / d beta_x,
+        beta_y of every supersampled pixel).  The gradient is that of the evidence with the set of finite rays held fixed; the
+        evidence is continuous but only piecewise smooth in the lens: it has a kink wherever a ray crosses a source-grid line.
+        Rows with ``ok == False`` are NaN.  Deterministic.  Inputs must not require a gradient (``model.SourceEvidenceProbModel``
+        is the autograd entry); lens planes, series and user-written lenses raise ``UnsupportedLensError``."""
+        if np.ndim(strength.detach().cpu() if torch.is_tensor(strength) else strength) > 1:
+            raise ValueError("source_evidence_and_grad: strength must be a scalar or [B] (one strength per sample, no scan)")
+        p = self._pixsrc_prepare("source_evidence_and_grad", params, observed_image, err_map, n_src, pitch, center, regularization,
+                                 strength, mask, deflection_scale)
+        packed, B = p["packed"], p["B"]
+        source, image, scal, ok, gb, gimg = self._model.pixsrc_evidence_grad(
+            p["bx"], p["by"], p["obs_u"], p["sig_u"], p["lens_light"], p["pix"], p["n_src"], p["pose"],
+            self.REGULARIZATIONS[regularization], p["lam_t"][:, 0].contiguous())
+        out = self._pixsrc_outputs(p, regularization, source[:, None], image[:, None], scal[:, None], ok[:, None])
+        out = {k: v[:, 0] for k, v in out.items()}
+        good = out["ok"]
+        # lens mass: the VJP of the ray-shoot with the ray cotangents (rays with a row of zeros carry an exact 0 and are skipped)
+        grad = self.beta_vjp(p["gx"].reshape(-1, 1), p["gy"].reshape(-1, 1), packed, gb[0].t(), gb[1].t(), deflection_scale=p["cs"])
+        if p["lens_light"] is not None:  # lens light: the VJP of the render, its lens-light columns alone
+            g_img = self._model.simulate_bwd(packed, torch.where(good[:, None, None], gimg, torch.zeros_like(gimg)))
+            cols = torch.tensor([k for k, slot in enumerate(self._layout.slots) if slot[0] == "lens_light"], dtype=torch.long,
+                                device=self.device)
+            grad[:, cols] = g_img[:, cols]
+        # pose: u = (beta_x - cx) / pitch + const, so d/dcx = -sum g_x, d/dpitch = -sum (g_x (beta_x - cx) + g_y (beta_y - cy)) / pitch
+        gx64, gy64 = gb[0].double(), gb[1].double()
+        pitch64, cx64, cy64 = (p["pose"][:, k:k + 1].double() for k in range(3))
+        zero = torch.zeros((), dtype=torch.float64, device=self.device)
+        tx = torch.where(gx64 != 0, gx64 * (p["bx"].double() - cx64), zero)
+        ty = torch.where(gy64 != 0, gy64 * (p["by"].double() - cy64), zero)
+        grad_pose = torch.stack([-(tx + ty).sum(dim=1) / pitch64[:, 0], -gx64.sum(dim=1), -gy64.sum(dim=1)], dim=1)
+        nan = float("nan")
+        out["grad"] = torch.where(good[:, None], grad, torch.full_like(grad, nan))
+        out["grad_pose"] = torch.where(good[:, None], grad_pose, torch.full_like(grad_pose, nan))
+        out["grad_beta"] = gb
+        return out
 
     def simulate(self, params, no_deflection=False):
         """tf/simulator.py:109-156.  Returns ``(bs, H, W)`` squeezed like ``tf.squeeze``."""

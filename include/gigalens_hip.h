@@ -381,6 +381,20 @@ int gl_scaled_eval(int base_kind, int n_galaxies, const int32_t scale_col[3], co
 int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts,
                  int xy_batched, float* out, void* hip_stream);
 
+/* The VJP of gl_lens_maps' ray-shoot beta = theta - sum alpha with respect to the lens parameters (beyond the reference, whose
+ * tape does this): cot [2][n_pts][B] = the cotangents on beta_x, beta_y (DEVICE), x, y as in gl_lens_maps but never NULL;
+ *   grad_params[b][p_off + k] = - sum_pt ( cot_x d alpha_x / d p_k + cot_y d alpha_y / d p_k )    [B][P], DEVICE,
+ * columns that belong to no lens written as 0.  A point whose two cotangents are both exactly 0, or one of whose cotangents is not
+ * finite, is skipped and its deflection never formed (an SIE at e = 0 or a ray at a centre has NaN derivatives there).  The sum
+ * over the points has a fixed order (one partial per workgroup of 64 points in the workspace, then a second pass; no atomics):
+ * two calls give identical bits and a sample does not depend on the others.  Served: the built-in mass kinds and GL_SCALED
+ * catalogues.  GL_EUNSUPPORTED: GL_SERIES and GL_USER_MASS lenses, models with lens planes.  GL_EINVAL: null arguments, sizes
+ * <= 0.  GL_ENOMEM: a workspace under gl_lens_maps_vjp_workspace_bytes(m, B, n_pts) (0 for a null model or sizes <= 0).  No host
+ * synchronisation, no allocation. */
+size_t gl_lens_maps_vjp_workspace_bytes(const gl_model* m, int B, int64_t n_pts);
+int gl_lens_maps_vjp(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
+                     const float* cot, float* grad_params, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Lens planes at redshifts of their own: multi-plane ray tracing (beyond the reference, which bends every ray at one plane).
  * Planes are numbered 0 .. n_planes - 1 by ascending redshift; every lens keeps its parameters as the reduced deflection for the
  * model's reference plane.  With theta_0 = theta the ray meets plane j at
@@ -563,6 +577,29 @@ int gl_pixsrc_reconstruct(const gl_model* m, const float* beta_x, const float* b
                           const float* lens_light, const int* pix, int n_used, int ny, int nx, const float* pose, int regularization,
                           const float* strength, int n_strength, float* source, float* model_image, double* scalars, int* ok,
                           void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* The evidence of gl_pixsrc_reconstruct with its gradient with respect to the rays and the lens-light image.  The arguments of
+ * gl_pixsrc_reconstruct with strength [B] (one strength per sample, no scan); source [B][S], model_image [B][H W], scalars [B][3] and
+ * ok [B] come from the same kernels and carry exactly the bits gl_pixsrc_reconstruct gives for the same inputs.  With
+ * E = -1/2 chi2 - 1/2 lambda s^T R s - 1/2 log det M (the terms of the evidence that depend on the lens), Fw = D P L, rw = yw - Fw s:
+ *   dE/dF = D (rw s^T - Fw M^-1),  G = P^T (dE/dF on the H x W image),
+ *   grad_beta [2][B][Hs Ws] = dE/dbeta_x, dE/dbeta_y = (1/pitch) sum over the at most four nodes around the ray of G x the hat
+ *       product with one factor differentiated (hat'(t) = -sign(t) for 0 < |t| < 1, else 0); exactly 0 for a ray with a row of
+ *       zeros (not finite, out of range): the gradient of the evidence with the set of finite rays held fixed,
+ *   grad_image [B][H W] = dE/d(lens light image) = rw / sigma on the used pixels, 0 elsewhere.
+ * A sample whose ok is 0 has NaN in grad_beta and grad_image.  Kernels (csrc/gl_pixsrc.hip.h): Z = M^-1 Fw by forward and back
+ * substitution with the factor the solve left in the workspace (float32, fixed order), the scatter of dE/dF columns to pooled
+ * planes (every element written), the model's own transpose of PSF + pooling on a chunk of planes, and a contraction in which one
+ * thread owns a supersampled pixel; samples and planes are chunked under the budgets of the forward call.  No atomics: two calls
+ * give identical bits, a sample does not depend on the others.  No allocation, no host synchronisation.  Errors as
+ * gl_pixsrc_reconstruct.  gl_pixsrc_grad_workspace_bytes: the workspace (0 for sizes the call refuses); gl_pixsrc_grad_layout:
+ * out[3] = samples per chunk, planes per post-processing launch, n_pad (host only). */
+size_t gl_pixsrc_grad_workspace_bytes(const gl_model* m, int B, int ny, int nx, int n_used);
+int gl_pixsrc_grad_layout(const gl_model* m, int B, int ny, int nx, int n_used, int32_t out[3]);
+int gl_pixsrc_evidence_grad(const gl_model* m, const float* beta_x, const float* beta_y, int B, const float* obs, const float* sigma,
+                            const float* lens_light, const int* pix, int n_used, int ny, int nx, const float* pose, int regularization,
+                            const float* strength, float* source, float* model_image, double* scalars, int* ok, float* grad_beta,
+                            float* grad_image, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Plugin-level point evaluation, the reference's MassProfile.deriv / LightProfile.light called on
  * arbitrary coordinates (tests/test_profiles.py calls exactly these):
