@@ -129,6 +129,7 @@ SYMBOLS = {
                                                 c_void_p]),
     "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "gl_image_positions_stage_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "gl_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "gl_critical_curves": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -950,6 +951,18 @@ class Model:
                                                    int(max_images), float(tol), int(max_iter), _ptr(out), _ptr(n_images),
                                                    _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
         return out, n_images, n_dropped
+
+    def image_positions_stage_counts(self, B, n_src, n_cells):
+        """gl_image_positions_stage_counts: ``n_cand``, ``n_over`` [B, n_src] (int32) of the scan stage, out of the workspace the
+        last ``image_positions`` call of these sizes filled (read-only; for tests and diagnostics)."""
+        ws = self._scratch_bufs.get("image_positions")
+        if ws is None:
+            raise NativeLibraryError("image_positions_stage_counts: no image_positions call has filled a workspace yet")
+        n_cand = torch.empty((int(B), int(n_src)), dtype=torch.int32, device=self.device)
+        n_over = torch.empty_like(n_cand)
+        _check(lib().gl_image_positions_stage_counts(self._h, int(B), int(n_src), int(n_cells), _ptr(ws), ws.numel(), _ptr(n_cand),
+                                                     _ptr(n_over), _stream()))
+        return n_cand, n_over
 
     def critical_curves(self, params, window, n_cells, max_segments, scale=None):
         """gl_critical_curves[_scaled]: ``scale`` the deflection scale of the source plane or None; ``window`` = (x_lo, x_hi, y_lo, y_hi).  Returns ``seg``, ``cau`` [B, max_segments, 2, 2] (NaN-padded),

@@ -558,6 +558,22 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
   return GL_OK;
 }
 
+// read-only: the scan stage's two planes out of a workspace the solver has just filled (same layout arguments, same stream)
+int gl_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_cells, const void* workspace, size_t workspace_bytes,
+                                    int* n_cand, int* n_over, void* hip_stream) {
+  if (!m || !workspace || !n_cand || !n_over) return fail(GL_EINVAL, "null argument");
+  if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  const ImgLayout lay = img_layout(B, n_src, n_cells);
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  const size_t bytes = sizeof(int) * (size_t)B * (size_t)n_src;
+  const char* base = (const char*)workspace;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  GL_HIP(hipMemcpyAsync(n_cand, base + lay.n_cand, bytes, hipMemcpyDeviceToDevice, stream));
+  GL_HIP(hipMemcpyAsync(n_over, base + lay.n_over, bytes, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+
 // ---- critical curves and caustics (gl_critical.hip.h) ----------------------------------------------------------
 size_t gl_critical_curves_workspace_bytes(const gl_model* m, int B, int n_cells, int max_segments) {
   if (!m || B <= 0 || n_cells <= 0 || n_cells > IMG_MAX_CELLS || max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS) return 0;

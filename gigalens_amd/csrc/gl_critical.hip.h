@@ -99,6 +99,7 @@ __device__ inline float crit_eval_impl(const PosArgs& a, int b, float px, float 
     bx -= ax.v;
     by -= ay.v;
     h[0] += ax.d[0] + ex; h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1] + ex;
+    if (lens_singular_at(cd, pf, px, py)) h[0] = __builtin_nanf("");  // exactly on an SIS centre: D is not finite (the vertex is flagged)
   }
   if (c != 1.f) {  // (c == 1: every value as the sum formed it)
     bx = px + c * (bx - px);

@@ -45,6 +45,13 @@ struct ImgArgs {
   int* n_dropped;  // [B][S]
 };
 
+// The SIS deflection is DEFINED as 0 at its own centre (sis_fwd, as the reference has it), so a grid vertex that coincides bit for bit
+// with the centre would see alpha = 0, H = 0 (beta = theta, D = 1) where the lens is singular (D -> -inf).  The map kernels of the
+// solver and of the critical curves flag such a vertex instead (no other built-in kind defines a value at a singular centre).
+__device__ inline bool lens_singular_at(const CompDesc& cd, const float* p, float x, float y) {
+  return cd.kind == glp::K_SIS && x == p[1] && y == p[2];
+}
+
 __device__ inline float img_vx(const ImgArgs& g, int c) { return g.x_lo + (float)c * g.hx; }
 __device__ inline float img_vy(const ImgArgs& g, int r) { return g.y_lo + (float)r * g.hy; }
 
@@ -63,7 +70,7 @@ __global__ void __launch_bounds__(256) gl_img_map_kernel(PosArgs a, ImgArgs g) {
     for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)b * a.P + cd.p_off + k];
     float ax, ay;
     lens_point<float>(a, cd, p, x, y, ax, ay);
-    bx -= ax;
+    bx -= lens_singular_at(cd, p, x, y) ? __builtin_nanf("") : ax;
     by -= ay;
   }
   if (!(isfinite(bx) && isfinite(by))) bx = by = __builtin_nanf("");

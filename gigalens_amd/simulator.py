@@ -351,7 +351,13 @@ class LensSimulator(LensSimulatorInterface):
         magnification, the quantity ``magnification`` returns) and ``n`` ``[B, S]``.  Images that were found but could not be
         stored or refined (``max_images`` exceeded, Newton not converged, converged outside the window) warn, or raise
         ``RuntimeError`` with ``strict=True``.  ``deflection_scale``: a scalar, or one value per source ``[S]`` -- source s is solved
-        on its own plane ``beta_s(theta) = theta - c_s sum alpha`` (``mu`` is that plane's magnification).  Forward only (no gradient)."""
+        on its own plane ``beta_s(theta) = theta - c_s sum alpha`` (``mu`` is that plane's magnification).  Forward only (no gradient).
+
+        The window is half-open for an image exactly ON its boundary: two of the four sides count, one of ``y_lo`` / ``y_hi`` and
+        one of ``x_lo`` / ``x_hi`` -- those whose counter-clockwise direction, mapped by ``sign(det A) A`` (``A = I - H``), points
+        upwards or exactly to the right; without a lens ``y = y_lo`` and ``x = x_hi``, the corner ``(x_hi, y_lo)`` included.  An
+        image on the other two sides is neither returned nor counted.  Strictly inside, an image on a shared cell edge or
+        vertex is found once."""
         self._single_plane("image_positions")
         if torch.is_tensor(lens_params):
             packed = lens_params

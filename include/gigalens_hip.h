@@ -477,7 +477,8 @@ int gl_lens_potential(const gl_model* m, const float* params, int B, const float
 /* Lens-equation solver (beyond the reference, which maps image plane -> source plane only): the images theta of source
  * positions beta_s, beta(theta) = beta_s, for every sample.  params [B,P] (DEVICE); src_x, src_y [B][n_src] (DEVICE).
  * The window [x_lo, x_hi] x [y_lo, y_hi] is cut into n_cells x n_cells cells, two triangles each; beta is mapped at the vertices
- * (vertices where it is not finite are flagged and their triangles skipped); every triangle whose image in the source plane
+ * (vertices where it is not finite, or that coincide bit for bit with the centre of a GL_SIS lens -- whose deflection is defined as 0
+ * there --, are flagged and their triangles skipped); every triangle whose image in the source plane
  * contains beta_s (edge-function sign test, a point on a shared edge counted once) seeds Newton at the preimage of beta_s under
  * the triangle's affine map: theta <- theta + (I - H)^-1 (beta_s - beta(theta)), |step| <= one cell diagonal, until
  * |beta(theta) - beta_s| <= tol (then one polishing step) or max_iter steps.  Converged candidates closer than 0.05 of a cell
@@ -507,11 +508,25 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
                               const float* src_scale, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_images,
                               float tol, int max_iter, float* out, int* n_images, int* n_dropped, void* workspace,
                               size_t workspace_bytes, void* hip_stream);
+/* Read-only view of the scan stage, for tests and diagnostics: copies the planes n_cand and n_over [B][n_src] (int32, DEVICE) --
+ * triangle hits stored as Newton seeds (at most 64) and hits beyond them -- out of a workspace that gl_image_positions[_scaled] has
+ * just filled with the same B, n_src, n_cells, on hip_stream (device-to-device; no host synchronisation).  A source that lies
+ * exactly on a shared triangle edge or vertex is one hit; the final outputs cannot show a double claim (Newton merges duplicates).
+ * The scan's window is half-open: an image exactly ON the window's boundary is found on two of the four sides only.  A side is
+ * walked counter-clockwise around the window (bottom +x, right +y, top -x, left -y) by the one triangle that holds it, and is
+ * claimed when that triangle owns the edge under the tie rule: with u that direction and A = I - H the Jacobian of the map there,
+ * d = sign(det A) A u has d.y > 0, or d.y == 0 and d.x > 0.  So one of bottom / top and one of left / right is claimed, a corner
+ * when both of its sides are; for the identity map: y = y_lo and x = x_hi with the corner (x_hi, y_lo).  An image on an unclaimed
+ * side is not seeded and not counted in n_dropped.  Newton's own window test x_lo <= x <= x_hi, y_lo <= y <= y_hi is inclusive.
+ * GL_EINVAL: null arguments, sizes out of range; GL_ENOMEM: workspace smaller than gl_image_positions_workspace_bytes. */
+int gl_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_cells, const void* workspace,
+                                    size_t workspace_bytes, int32_t* n_cand, int32_t* n_over, void* hip_stream);
 
 /* Critical curves and caustics (beyond the reference): the image-plane locus D = det(I - H) = 0 (the Hessian as gl_lens_maps has
  * it) of every sample, contoured by marching squares on n_cells x n_cells cells over the window [x_lo, x_hi] x [y_lo, y_hi], and
  * its image in the source plane.  params [B,P] (DEVICE).  D is mapped at the vertices (one float each; a D that is not finite is
- * flagged); every grid edge whose two finite endpoint values differ in sign (sign = D < 0) carries one crossing point, bisected ON
+ * flagged, and so is a vertex that coincides bit for bit with the centre of a GL_SIS lens, whose Hessian is defined as 0 there);
+ * every grid edge whose two finite endpoint values differ in sign (sign = D < 0) carries one crossing point, bisected ON
  * the edge until the bracket is 4 float32 spacings of the window's largest |coordinate| (at most 32 halvings), so the cells on both
  * sides of an edge see the same bits and segments join exactly.  Every cell yields 0, 1 or 2 segments; in the ambiguous case
  * (diagonal signs equal, neighbours different) the D < 0 corners are joined when the mean of the four vertex values is < 0.

@@ -6,9 +6,11 @@ per cell in row-major order with D < 0 on the left of every segment; the ambiguo
 values is < 0; a segment is tangential when the mean of 1 - kappa at its endpoints is > 0.
 
 The 16-case table below is, by design, the table the kernel uses: the restatement is independent of the kernel in its numerics
-(float64 fields from the oracle), its edge listing, bisection and ordering, not in the table.  The table's orientation and the
-loop topology are pinned independently by the closed-form tests (SIS: one loop of positive area pi theta_E^2; NFW: a radial loop
-inside the tangential one).
+(float64 fields from the oracle), its edge listing, bisection and ordering, not in the table.  The table is pinned independently,
+row by row: `orientation_violations` checks D < 0 on the left of every segment from the vertex plane alone, `physical_loops`
+counts the closed curves without contouring (the joined rows 16 and 17 against the separated rows 5 and 10, on the AMBIGUOUS
+cases), and the closed-form tests fix the overall sign (SIS: one loop of positive area pi theta_E^2; NFW: a radial loop inside
+the tangential one).  `with_capacity` restates the overflow accounting of a call with too few segment or edge slots.
 
 The module also holds the small helpers the critical-curve GPU tests share (simulator, packed rows, the oracle's view of them)."""
 import numpy as np
@@ -55,7 +57,7 @@ JOINED = {5: [(0, 1), (2, 3)], 10: [(3, 0), (1, 2)]}
 
 def contour64(fields, window, n, tol=1e-13):
     """``fields(x, y) -> (D, beta_x, beta_y, 1 - kappa)`` on float64 arrays.  Returns a dict: ``seg``, ``cau`` [K, 2, 2], ``kind``
-    [K], ``edges`` (crossing edge id -> refined (x, y, beta_x, beta_y, 1 - kappa)), ``D`` (vertex plane), ``open``, ``n_flagged``,
+    [K], ``seg_edges`` [K, 2] (the grid edges that carry the two endpoints), ``edges`` (crossing edge id -> refined (x, y, beta_x, beta_y, 1 - kappa)), ``D`` (vertex plane), ``open``, ``n_flagged``,
     ``n_ambiguous`` and ``area`` (tangential, radial in the image plane, then in the source plane; signed as the native call)."""
     x_lo, x_hi, y_lo, y_hi = (float(v) for v in window)
     hx, hy = (x_hi - x_lo) / n, (y_hi - y_lo) / n
@@ -86,7 +88,7 @@ def contour64(fields, window, n, tol=1e-13):
         _, bx, by, omk = fields(px, py)
         edges = {int(e): (px[k], py[k], bx[k], by[k], omk[k]) for k, e in enumerate(ids)}
     is_open = bool(hz[0].any() or hz[n].any() or vt[:, 0].any() or vt[:, n].any())
-    seg, cau, kind = [], [], []
+    seg, cau, kind, seg_edges = [], [], [], []
     n_flagged = n_ambiguous = 0
     area = np.zeros(4)
     cx = 0.5 * (x_lo + x_hi)
@@ -110,10 +112,11 @@ def contour64(fields, window, n, tol=1e-13):
             cau.append([[p1[2], p1[3]], [p2[2], p2[3]]])
             kd = 0 if p1[4] + p2[4] > 0 else 1
             kind.append(kd)
+            seg_edges.append((cell_edge[a], cell_edge[b]))
             area[kd] += 0.5 * ((p1[0] - cx) + (p2[0] - cx)) * (p2[1] - p1[1])
             area[2 + kd] += 0.5 * ((p1[2] - cx) + (p2[2] - cx)) * (p2[3] - p1[3])
     return {"seg": np.array(seg).reshape(-1, 2, 2), "cau": np.array(cau).reshape(-1, 2, 2), "kind": np.array(kind, dtype=np.int64),
-            "edges": edges, "D": D, "open": is_open, "n_flagged": n_flagged, "n_ambiguous": n_ambiguous, "area": area}
+            "seg_edges": np.array(seg_edges, dtype=np.int64).reshape(-1, 2), "edges": edges, "D": D, "open": is_open, "n_flagged": n_flagged, "n_ambiguous": n_ambiguous, "area": area}
 
 
 def sis_fields(theta_E, cx, cy):
@@ -124,6 +127,158 @@ def sis_fields(theta_E, cx, cy):
             r = np.hypot(dx, dy)
             return 1 - theta_E / r, x - theta_E * dx / r, y - theta_E * dy / r, 1 - 0.5 * theta_E / r
     return fields
+
+
+def multi_sis_fields(lenses, scale=1.0):
+    """Closed form of a sum of SIS lenses ``[(theta_E, cx, cy), ...]`` on the plane of deflection scale ``scale``:
+    alpha = theta_E r_hat, H = theta_E / r^3 [[dy^2, -dx dy], [-dx dy, dx^2]], kappa = theta_E / (2 r), each times ``scale``."""
+    def fields(x, y):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        ax = ay = fxx = fxy = fyy = kap = 0.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for te, cx, cy in lenses:
+                dx, dy = x - cx, y - cy
+                r = np.hypot(dx, dy)
+                ax, ay = ax + te * dx / r, ay + te * dy / r
+                fxx, fxy, fyy = fxx + te * dy * dy / r ** 3, fxy - te * dx * dy / r ** 3, fyy + te * dx * dx / r ** 3
+                kap = kap + 0.5 * te / r
+            fxx, fxy, fyy, kap = scale * fxx, scale * fxy, scale * fyy, scale * kap
+            return (1 - fxx) * (1 - fyy) - fxy * fxy, x - scale * ax, y - scale * ay, 1 - kap
+    return fields
+
+
+def scaled_fields(fields, scale):
+    """The fields of the source plane with deflection scale c from oracle fields that carry ``hessian``: D = det(I - c H),
+    beta = theta - c sum alpha, 1 - c kappa."""
+    def out(x, y):
+        bx, by, fxx, fxy, fyx, fyy = fields.hessian(x, y)
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return ((1 - scale * fxx) * (1 - scale * fyy) - scale * scale * fxy * fyx, x + scale * (bx - x), y + scale * (by - y),
+                1 - 0.5 * scale * (fxx + fyy))
+
+    def hessian(x, y):
+        bx, by, fxx, fxy, fyx, fyy = fields.hessian(x, y)
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return x + scale * (bx - x), y + scale * (by - y), scale * fxx, scale * fxy, scale * fyx, scale * fyy
+    out.hessian = hessian
+    return out
+
+
+def cell_codes(D):
+    """Marching-squares code of every cell of a vertex plane (corner bits as CASES has them); -1 where a vertex is not finite."""
+    fin, neg = np.isfinite(D), np.nan_to_num(D, nan=1.0) < 0
+    code = neg[:-1, :-1] * 1 + neg[:-1, 1:] * 2 + neg[1:, 1:] * 4 + neg[1:, :-1] * 8
+    return np.where(fin[:-1, :-1] & fin[:-1, 1:] & fin[1:, 1:] & fin[1:, :-1], code, -1)
+
+
+def ambiguous_cells(D):
+    """[(row, col, code, joined, margin)] of the cells with code 5 or 10: ``joined`` = mean of the four vertex values < 0, ``margin``
+    = the smallest of |mean| and the four |vertex value|."""
+    out = []
+    code = cell_codes(D)
+    for r, c in zip(*np.nonzero((code == 5) | (code == 10))):
+        d = np.array([D[r, c], D[r, c + 1], D[r + 1, c + 1], D[r + 1, c]])
+        out.append((int(r), int(c), int(code[r, c]), bool(d.mean() < 0), float(min(abs(d.mean()), np.abs(d).min()))))
+    return out
+
+
+def edge_of(p, window, n):
+    """Id of the grid edge that carries the point p: the coordinate that sits on a grid line (to 2e-5 of a cell: the float32 grid of
+    the kernel is off the float64 one by a few 1e-6 of a cell at 127 cells) says which; horizontal edges first, row by row."""
+    x_lo, x_hi, y_lo, y_hi = window
+    fx, fy = (p[0] - x_lo) / ((x_hi - x_lo) / n), (p[1] - y_lo) / ((y_hi - y_lo) / n)
+    ox, oy = abs(fx - round(fx)), abs(fy - round(fy))
+    assert min(ox, oy) < 2e-5, p
+    if oy <= ox:  # y on a grid line: a horizontal edge
+        return int(round(fy)) * n + min(max(int(np.floor(fx)), 0), n - 1)
+    return (n + 1) * n + min(max(int(np.floor(fy)), 0), n - 1) * (n + 1) + int(round(fx))
+
+
+def orientation_violations(seg, D, window, n):
+    """Independently of the table: D < 0 lies on the LEFT of every directed segment.  For each endpoint take the D < 0 vertex of the
+    grid edge that carries it (from the float64 vertex plane ``D``); cross(p2 - p1, v_neg - p1) must be > 0.  Returns the offenders."""
+    x_lo, x_hi, y_lo, y_hi = window
+    hx, hy = (x_hi - x_lo) / n, (y_hi - y_lo) / n
+    H, bad = (n + 1) * n, []
+    for s, (p1, p2) in enumerate(np.asarray(seg, np.float64)):
+        for p in (p1, p2):
+            e = edge_of(p, window, n)
+            if e < H:
+                r, c = divmod(e, n)
+                ends = [(r, c), (r, c + 1)]
+            else:
+                r, c = divmod(e - H, n + 1)
+                ends = [(r, c), (r + 1, c)]
+            neg = [v for v in ends if D[v] < 0]
+            assert len(neg) == 1, (s, e, [D[v] for v in ends])
+            vx, vy = x_lo + neg[0][1] * hx, y_lo + neg[0][0] * hy
+            cross = (p2[0] - p1[0]) * (vy - p1[1]) - (p2[1] - p1[1]) * (vx - p1[0])
+            if not cross > 0:
+                bad.append((s, e, cross))
+    return bad
+
+
+def _components(mask):
+    """Number of 4-connected regions of a boolean plane."""
+    n_r, n_c = mask.shape
+    seen, regions = np.zeros_like(mask), 0
+    for r0, c0 in zip(*np.nonzero(mask)):
+        if seen[r0, c0]:
+            continue
+        regions += 1
+        stack = [(r0, c0)]
+        seen[r0, c0] = True
+        while stack:
+            r, c = stack.pop()
+            for rr, cc in ((r + 1, c), (r - 1, c), (r, c + 1), (r, c - 1)):
+                if 0 <= rr < n_r and 0 <= cc < n_c and mask[rr, cc] and not seen[rr, cc]:
+                    seen[rr, cc] = True
+                    stack.append((rr, cc))
+    return regions
+
+
+def physical_loops(fields, window, n_fine=256):
+    """The number of closed critical curves inside the window, found without contouring: the regions of D < 0 and of D >= 0 on a
+    fine grid of cell centres (4-connectivity) are the nodes of a tree whose links are the curves between them (closed curves nest),
+    so their number is regions - 1.  Returns (curves, regions of D < 0)."""
+    x_lo, x_hi, y_lo, y_hi = window
+    xs = x_lo + (np.arange(n_fine) + 0.5) * (x_hi - x_lo) / n_fine
+    ys = y_lo + (np.arange(n_fine) + 0.5) * (y_hi - y_lo) / n_fine
+    X, Y = np.meshgrid(xs, ys)
+    neg = np.nan_to_num(fields(X.ravel(), Y.ravel())[0].reshape(n_fine, n_fine), nan=-1.0) < 0
+    n_neg = _components(neg)
+    return n_neg + _components(~neg) - 1, n_neg
+
+
+# Two SIS lenses whose critical curves nearly touch along the (1, 1) diagonal (code 5) or the (1, -1) diagonal (code 10), one sample
+# per variant of the ambiguous cell, found by a random search with hill climbing on the margin (window (-3, 3)^2, 12 cells, i.e.
+# cells of 0.5): name -> (lenses [(theta_E, cx, cy)] as float32 values, code, joined, closed curves).  Separated: the mean of the
+# four vertex values is > 0 and the two D < 0 regions stay apart (two curves); joined: it is < 0 and they are one region (one curve).
+AMBIGUOUS_WINDOW, AMBIGUOUS_N, AMBIGUOUS_MARGIN = (-3.0, 3.0, -3.0, 3.0), 12, 5e-3
+AMBIGUOUS = {
+    "code5_separated": ([(0.5378, -1.0550, -1.0400), (0.5381, 0.5871, 0.5170)], 5, False, 2),
+    "code5_joined": ([(0.5, -0.5200, -0.5266), (0.5, 0.8072, 0.8104)], 5, True, 1),
+    "code10_separated": ([(0.5009, -0.9036, 1.0759), (0.5028, 0.5240, -0.4852)], 10, False, 2),
+    "code10_joined": ([(0.5, -0.8155, 0.8259), (0.5, 0.4905, -0.5028)], 10, True, 1),
+}
+
+
+def ambiguous_case(name):
+    """(lenses as the float64 values of their float32 parameters, code, joined, curves) of AMBIGUOUS[name]."""
+    lenses, code, joined, curves = AMBIGUOUS[name]
+    return [tuple(float(np.float32(v)) for v in lens) for lens in lenses], code, joined, curves
+
+
+def with_capacity(ref, max_segments):
+    """What the native call returns of the contour ``ref`` (contour64) with room for ``max_segments`` segments and 2 max_segments
+    crossing edges: the edge list keeps the smallest ids; the first min(T, max_segments) segments in cell order take their slots,
+    a slot whose endpoint's edge was not kept is padding and counts as dropped, as does every segment beyond the slots.
+    Returns (n, keep [n] bool: the slot holds its segment, n_dropped)."""
+    kept = set(sorted(ref["edges"])[:2 * max_segments])
+    T = len(ref["seg"])
+    n = min(T, max_segments)
+    keep = np.array([a in kept and b in kept for a, b in ref["seg_edges"][:n].tolist()], dtype=bool).reshape(n)
+    return n, keep, (T - n) + int((~keep).sum())
 
 
 def oracle_fields(phys, lens_rows, b):

@@ -83,3 +83,96 @@ def test_float64_restatement_on_the_sis():
     assert (1 - h * h / (3 * theta_E ** 2)) * exact <= out["area"][0] <= exact
     assert out["area"][1] == 0.0 and abs(out["area"][2]) < 1e-12
     assert CC.count_loops(out["seg"]) == (1, 0)
+    # D < 0 (inside the ring) on the left of every segment, from the vertex plane alone
+    assert CC.orientation_violations(out["seg"], out["D"], (-half, half, -half, half), n) == []
+    assert CC.physical_loops(CC.sis_fields(theta_E, cx, cy), (-half, half, -half, half)) == (1, 1)
+
+
+@pytest.mark.parametrize("name", sorted(CC.AMBIGUOUS))
+def test_ambiguous_variants_have_their_margin_topology_and_orientation(name):
+    lenses, code, joined, curves = CC.ambiguous_case(name)
+    fields = CC.multi_sis_fields(lenses)
+    out = CC.contour64(fields, CC.AMBIGUOUS_WINDOW, CC.AMBIGUOUS_N)
+    amb = CC.ambiguous_cells(out["D"])
+    assert len(amb) == 1 == out["n_ambiguous"] and amb[0][2:4] == (code, joined), amb
+    assert amb[0][4] >= CC.AMBIGUOUS_MARGIN and np.abs(out["D"]).min() >= CC.AMBIGUOUS_MARGIN
+    assert not out["open"] and out["n_flagged"] == 0
+    # topology, independently of the table: closed loops only, as many as the regions of D < 0 and D > 0 imply on a fine grid
+    # (two resolutions agree), and that is the variant's: separated = two curves, joined = one
+    assert CC.physical_loops(fields, CC.AMBIGUOUS_WINDOW, 256) == CC.physical_loops(fields, CC.AMBIGUOUS_WINDOW, 512) == (curves, curves)
+    assert CC.count_loops(out["seg"]) == (curves, 0)
+    # orientation, independently of the table
+    assert CC.orientation_violations(out["seg"], out["D"], CC.AMBIGUOUS_WINDOW, CC.AMBIGUOUS_N) == []
+    # the other variant of the same cell has the wrong number of curves: the mean rule decides the topology here
+    wrong = dict(CC.JOINED) if not joined else {5: CC.CASES[5], 10: CC.CASES[10]}
+    segs = []
+    H = (CC.AMBIGUOUS_N + 1) * CC.AMBIGUOUS_N
+    r, c = amb[0][:2]
+    cell_edge = [r * CC.AMBIGUOUS_N + c, H + r * (CC.AMBIGUOUS_N + 1) + c + 1, (r + 1) * CC.AMBIGUOUS_N + c, H + r * (CC.AMBIGUOUS_N + 1) + c]
+    mine = {tuple(e) for e in out["seg_edges"].tolist()}
+    theirs = (mine - {(cell_edge[a], cell_edge[b]) for a, b in (CC.JOINED if joined else CC.CASES)[code]}) | \
+             {(cell_edge[a], cell_edge[b]) for a, b in wrong[code]}
+    for a, b in theirs:
+        segs.append([out["edges"][a][:2], out["edges"][b][:2]])
+    assert CC.count_loops(np.array(segs)) == (3 - curves, 0)
+
+
+def test_ambiguous_cases_cover_every_nontrivial_code():
+    seen = set()
+    for name in CC.AMBIGUOUS:
+        out = CC.contour64(CC.multi_sis_fields(CC.ambiguous_case(name)[0]), CC.AMBIGUOUS_WINDOW, CC.AMBIGUOUS_N)
+        seen |= set(CC.cell_codes(out["D"]).ravel().tolist())
+    assert seen >= set(range(1, 15)), sorted(seen)
+
+
+def test_orientation_check_bites_on_a_swapped_table_row():
+    """The invariant is independent of the table: a restatement whose rows 5 and 16 are swapped (separated <-> joined) still has
+    D < 0 on the left, but the wrong number of curves; one whose row is reversed has the right curves and the wrong side."""
+    lenses, code, joined, curves = CC.ambiguous_case("code5_joined")
+    fields = CC.multi_sis_fields(lenses)
+    saved = CC.JOINED[5]
+    try:
+        CC.JOINED[5] = CC.CASES[5]
+        out = CC.contour64(fields, CC.AMBIGUOUS_WINDOW, CC.AMBIGUOUS_N)
+        assert CC.count_loops(out["seg"]) == (2, 0) != (curves, 0)
+        CC.JOINED[5] = [(b, a) for a, b in saved]
+        out = CC.contour64(fields, CC.AMBIGUOUS_WINDOW, CC.AMBIGUOUS_N)
+        assert len(CC.orientation_violations(out["seg"], out["D"], CC.AMBIGUOUS_WINDOW, CC.AMBIGUOUS_N)) == 4
+    finally:
+        CC.JOINED[5] = saved
+
+
+def test_flagged_cells_of_an_sis_centred_on_a_vertex():
+    window, n = (-2.0, 2.0, -2.0, 2.0), 16  # h = 0.25; the centre on the interior vertex (row 10, column 7)
+    cx, cy, h = -0.25, 0.5, 0.25
+    small = CC.contour64(CC.sis_fields(0.3, cx, cy), window, n)  # h < theta_E < h sqrt(2): axial neighbours D < 0, diagonal D > 0
+    assert np.isnan(small["D"][10, 7]) and int(np.isnan(small["D"]).sum()) == 1
+    # the four cells around the centre are skipped and counted; the cells beyond the axial neighbours still cut their corner off:
+    # eight segments, four open arcs
+    assert small["n_flagged"] == 4 and not small["open"] and len(small["edges"]) == 12
+    assert len(small["seg"]) == 8 and CC.count_loops(small["seg"]) == (0, 4)
+    mid = small["seg"].mean(1)
+    assert np.all(np.maximum(np.abs(mid[:, 0] - cx), np.abs(mid[:, 1] - cy)) > h)  # none inside the four flagged cells
+    big = CC.contour64(CC.sis_fields(0.7, cx, cy), window, n)  # theta_E > 2 h: the finite vertices of the four cells agree
+    assert big["n_flagged"] == 0 and len(big["seg"]) > 0 and CC.count_loops(big["seg"]) == (1, 0)
+    assert CC.orientation_violations(big["seg"], big["D"], window, n) == []
+
+
+def test_capacity_restatement():
+    ref = CC.contour64(CC.sis_fields(1.3, 0.11, -0.23), (-2.0, 2.0, -2.0, 2.0), 32)
+    T = len(ref["seg"])
+    assert T == len(ref["edges"])  # a closed curve: as many crossing edges as segments
+    for M in (T, T + 1):
+        n, keep, dropped = CC.with_capacity(ref, M)
+        assert (n, dropped) == (T, 0) and keep.all()
+    n, keep, dropped = CC.with_capacity(ref, T - 1)
+    assert (n, dropped) == (T - 1, 1) and keep.all()  # 2 (T - 1) >= T: every edge kept, one segment beyond the slots
+    # 2 (T / 2 - 1) < T: the edge list overflows, by the two largest ids (vertical edges of the top row), which none of the first
+    # T / 2 - 1 segments touches
+    n, keep, dropped = CC.with_capacity(ref, T // 2 - 1)
+    assert n == T // 2 - 1 and keep.all() and dropped == T - n
+    # fewer edges: slots whose endpoint fell off the list are padding and count as dropped, the others hold their segment
+    n, keep, dropped = CC.with_capacity(ref, 3 * T // 10)
+    assert n == 3 * T // 10 and 0 < keep.sum() < n and dropped == (T - n) + int((~keep).sum())
+    n, keep, dropped = CC.with_capacity(ref, 1)  # two horizontal edges kept; the first segment ends on a vertical one
+    assert n == 1 and not keep[0] and dropped == T

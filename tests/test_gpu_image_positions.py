@@ -1,7 +1,6 @@
 """Lens-equation solver (LensSimulator.image_positions, gl_image_positions): the images of a source for every sample, against the
-closed form of the SIS and a float64 Newton solver written here on the oracle's deflections (Hessians from torch.autograd),
-plus the family-level diagnostics of ForwardProbModel (predicted_positions, image_plane_rms) and the refusals."""
-import math
+closed form of the SIS and the float64 Newton solver of tests/images_cases.py on the oracle's deflections (Hessians from
+torch.autograd), plus the family-level diagnostics of ForwardProbModel (predicted_positions, image_plane_rms) and the refusals."""
 import warnings
 
 import numpy as np
@@ -9,6 +8,8 @@ import pytest
 import torch
 
 from tests import helpers as H
+# the float64 Newton reference lives in tests/images_cases.py (shared with tests/test_gpu_images_edges.py)
+from tests.images_cases import _check_against_f64, _default_tol, _deriv64, _lens_rows, _residual64, _solve64  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -29,130 +30,6 @@ def _rows(sim, lens_cols):
     B = lens_cols.shape[0]
     src = np.tile(np.array([[0.2, 2.0, 0.0, 0.0, 1.0]], np.float32), (B, 1))
     return torch.tensor(np.concatenate([np.asarray(lens_cols, np.float32), src], 1), device=sim.device)
-
-
-def _lens_rows(sim, packed):
-    """Per-lens dicts of float64 CPU columns (the oracle's view of the packed rows)."""
-    struct = H.struct_from_packed(sim.phys_model, packed.detach().double().cpu())
-    return struct["lens_mass"]
-
-
-def _deriv64(sim, lens_rows, b):
-    """float64 deflection (sum over the lenses) of sample b, on the oracle's restatement of every profile."""
-    from oracle import ref_torch as ref
-    phys = sim.phys_model
-
-    def f(x, y):
-        ax = ay = 0
-        for prof, p, c in zip(phys.lenses, lens_rows, phys.lenses_constants):
-            kw = {k: v[b] for k, v in p.items()}
-            kw.update({k: torch.as_tensor(np.asarray(v, dtype=np.float32)).to(F64) for k, v in c.items()})
-            fx, fy = ref.mass_deriv(prof, x, y, **kw)
-            ax, ay = ax + fx, ay + fy
-        return ax, ay
-    return f
-
-
-def _beta_jac(deriv, x, y):
-    x = x.detach().clone().requires_grad_(True)
-    y = y.detach().clone().requires_grad_(True)
-    ax, ay = deriv(x, y)
-    gxx, gxy = torch.autograd.grad(ax.sum(), (x, y), retain_graph=True)
-    gyx, gyy = torch.autograd.grad(ay.sum(), (x, y))
-    return (x - ax).detach(), (y - ay).detach(), gxx, gxy, gyx, gyy
-
-
-def _solve64(deriv, sx, sy, window, n):
-    """float64 reference: seeds = centroids of the triangles of an n x n grid whose source-plane image contains the source,
-    then Newton to 1e-11; duplicates (1e-6) merged; images outside the window dropped.  Returns [K, 3] (x, y, mu) sorted by x."""
-    x_lo, x_hi, y_lo, y_hi = window
-    xs = torch.linspace(x_lo, x_hi, n + 1, dtype=F64)
-    ys = torch.linspace(y_lo, y_hi, n + 1, dtype=F64)
-    Y, X = torch.meshgrid(ys, xs, indexing="ij")
-    with torch.no_grad():
-        ax, ay = deriv(X.reshape(-1), Y.reshape(-1))
-    bx, by = (X.reshape(-1) - ax).reshape(n + 1, n + 1), (Y.reshape(-1) - ay).reshape(n + 1, n + 1)
-    v = lambda t, dj, di: t[dj:dj + n, di:di + n].reshape(-1)
-    pos = lambda t, dj, di: t[dj:dj + n, di:di + n].reshape(-1)
-    tris = [((0, 0), (0, 1), (1, 1)), ((0, 0), (1, 1), (1, 0))]
-    seeds_x, seeds_y = [], []
-    for tri in tris:
-        P = [(v(bx, *o), v(by, *o)) for o in tri]
-        cross = []
-        for e in range(3):
-            (px, py), (qx, qy) = P[e], P[(e + 1) % 3]
-            cross.append((qx - px) * (sy - py) - (qy - py) * (sx - px))
-        inside = ((cross[0] > 0) & (cross[1] > 0) & (cross[2] > 0)) | ((cross[0] < 0) & (cross[1] < 0) & (cross[2] < 0))
-        inside &= torch.isfinite(cross[0] + cross[1] + cross[2])
-        seeds_x.append(sum(pos(X, *o) for o in tri)[inside] / 3)
-        seeds_y.append(sum(pos(Y, *o) for o in tri)[inside] / 3)
-    x, y = torch.cat(seeds_x), torch.cat(seeds_y)
-    for _ in range(60):
-        b_x, b_y, fxx, fxy, fyx, fyy = _beta_jac(deriv, x, y)
-        rx, ry = sx - b_x, sy - b_y
-        a00, a01, a10, a11 = 1 - fxx, -fxy, -fyx, 1 - fyy
-        det = a00 * a11 - a01 * a10
-        dx, dy = (a11 * rx - a01 * ry) / det, (a00 * ry - a10 * rx) / det
-        step = torch.hypot(dx, dy).clamp(min=1e-300)
-        lim = torch.clamp(0.2 / step, max=1.0)
-        x, y = x + dx * lim, y + dy * lim
-    b_x, b_y, fxx, fxy, fyx, fyy = _beta_jac(deriv, x, y)
-    ok = (torch.hypot(sx - b_x, sy - b_y) < 1e-11) & (x >= x_lo) & (x <= x_hi) & (y >= y_lo) & (y <= y_hi)
-    mu = 1 / ((1 - fxx) * (1 - fyy) - fxy * fyx)
-    found = []
-    for xi, yi, mi in zip(x[ok].tolist(), y[ok].tolist(), mu[ok].tolist()):
-        if all(math.hypot(xi - a, yi - b) > 1e-6 for a, b, _ in found):
-            found.append((xi, yi, mi))
-    return np.array(sorted(found), dtype=np.float64).reshape(-1, 3)
-
-
-def _default_tol(window):
-    from gigalens_amd.simulator import LensSimulator
-    return LensSimulator.IMAGE_TOL_EPS * EPS32 * max(abs(v) for v in window)
-
-
-def _residual64(deriv, x, y, sx, sy):
-    with torch.no_grad():
-        ax, ay = deriv(torch.as_tensor(x, dtype=F64), torch.as_tensor(y, dtype=F64))
-    return np.hypot(np.asarray(x, np.float64) - ax.numpy() - sx, np.asarray(y, np.float64) - ay.numpy() - sy)
-
-
-def _check_against_f64(sim, packed, srcx, srcy, window, n_cells, mu_min=0.02, fold_cells=2.0):
-    """Compare the solver's images with the float64 solver; returns (number of (sample, source) pairs compared, counts seen)."""
-    x, y, mu, n = sim.image_positions(packed, srcx, srcy, window=window, num_cells=n_cells)
-    x, y, mu, n = (t.cpu().numpy() for t in (x, y, mu, n))
-    rows = _lens_rows(sim, packed)
-    tol = _default_tol(window)
-    cell = (window[1] - window[0]) / n_cells
-    compared, counts = 0, []
-    for b in range(packed.shape[0]):
-        deriv = _deriv64(sim, rows, b)
-        for s in range(srcx.shape[1]):
-            sx, sy = float(srcx[b, s]), float(srcy[b, s])
-            ref = _solve64(deriv, sx, sy, window, 2 * n_cells)
-            k = int(n[b, s])
-            got = np.stack([x[b, s, :k], y[b, s, :k], mu[b, s, :k]], axis=1)
-            assert np.all(np.isfinite(got)) and np.all(np.isnan(x[b, s, k:]))
-            # lens-equation residual of every returned image, in float64
-            res = _residual64(deriv, got[:, 0], got[:, 1], sx, sy)
-            assert np.all(res <= 2 * tol), (b, s, res, tol)
-            # what the solver does not promise: two images closer than ~a cell at a fold
-            if len(ref) > 1:
-                d = np.hypot(ref[:, None, 0] - ref[None, :, 0], ref[:, None, 1] - ref[None, :, 1]) + np.eye(len(ref)) * 1e9
-                if d.min() < fold_cells * cell:
-                    continue
-            # highly demagnified central images sit within a cell of a cusp or singularity: compared above mu_min
-            ref_m, got_m = ref[np.abs(ref[:, 2]) >= mu_min], got[np.abs(got[:, 2]) >= mu_min]
-            assert len(ref_m) == len(got_m), (b, s, ref, got)
-            for r in ref_m:
-                j = np.argmin(np.hypot(got_m[:, 0] - r[0], got_m[:, 1] - r[1]))
-                # (beyond |mu| = 30 the root itself is conditioned by mu: float32 rounding of beta times |mu|)
-                assert math.hypot(got_m[j, 0] - r[0], got_m[j, 1] - r[1]) <= max(5e-5, 2e-6 * abs(r[2])), (b, s, r, got_m[j])
-                if abs(r[2]) < 30:
-                    assert abs(got_m[j, 2] - r[2]) <= 1e-3 * abs(r[2]), (b, s, r, got_m[j])
-            compared += 1
-            counts.append(len(ref_m))
-    return compared, counts
 
 
 def test_sis_closed_form():

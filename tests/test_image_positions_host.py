@@ -22,3 +22,10 @@ def test_image_positions_refuses_bad_arguments(native):
                                 null)
     assert rc == -1  # GL_EINVAL
     assert b"null" in lib.gl_last_error()
+
+
+def test_stage_counts_refuses_bad_arguments(native):
+    lib = native.lib()
+    null = ctypes.c_void_p(0)
+    assert lib.gl_image_positions_stage_counts(None, 4, 2, 64, null, 0, null, null, null) == -1  # GL_EINVAL
+    assert b"null" in lib.gl_last_error()
