@@ -143,6 +143,14 @@ SYMBOLS = {
     "gl_pixsrc_evidence_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),
+    "gl_ptimg_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "gl_ptimg_render": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(ctypes.c_double), c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "gl_ptimg_render_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(ctypes.c_double), c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gl_ptimg_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(ctypes.c_double), c_void_p, c_void_p, c_int, c_void_p, c_int,
+                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                             c_void_p]),
     "gl_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float,
                                    c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_model_num_linear": (c_int, [c_void_p]),
@@ -1044,6 +1052,78 @@ class Model:
                                              _ptr(scalars), _ptr(ok), _ptr(grad_beta), _ptr(grad_image), _ptr(ws), ws.numel(),
                                              _stream()))
         return source, image, scalars, ok, grad_beta, grad_image
+
+    # -- point images in the pixel likelihood (gl_ptimg_*) -------------------------------------------------------------
+    def _ptimg_inputs(self, what, transform, *rows):
+        """``rows``: ``[B, J]`` float32 device tensors of one shape; returns them contiguous with ``B``, ``J``, the transform as six
+        C doubles and the call's workspace."""
+        self._single_plane(what)
+        shape = tuple(rows[0].shape)
+        out = []
+        for t in rows:
+            _require_cuda(t, what)
+            if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != shape:
+                raise NativeLibraryError(f"{what}: positions and amplitudes must be float32 [B, J] of one shape, got {t.dtype} "
+                                         f"{tuple(t.shape)} against {shape}")
+            out.append(t.contiguous())
+        B, J = shape
+        xf = (ctypes.c_double * 6)(*[float(v) for v in transform])
+        nbytes = lib().gl_ptimg_workspace_bytes(self._h, B, J)
+        return out, B, J, xf, self._scratch("ptimg", nbytes)
+
+    def _ptimg_image(self, t, B, what, name):
+        """``[H, W]`` or ``[B, H, W]`` float32 on the device -> (contiguous tensor, batched flag)"""
+        _require_cuda(t, name)
+        if t.dtype != torch.float32 or tuple(t.shape) not in ((self.out_h, self.out_w), (B, self.out_h, self.out_w)):
+            raise NativeLibraryError(f"{what}: {name} must be float32 [{self.out_h}, {self.out_w}] or [{B}, {self.out_h}, "
+                                     f"{self.out_w}], got {t.dtype} {tuple(t.shape)}")
+        return t.contiguous(), int(t.dim() == 3)
+
+    def ptimg_render(self, x, y, amplitude, transform):
+        """gl_ptimg_render: ``x, y, amplitude`` [B, J] on the device, ``transform`` = (x0, y0, m00, m01, m10, m11) on the host
+        -> the image ``sum_j amplitude_j D_j`` [B, H, W]."""
+        (x, y, amplitude), B, J, xf, ws = self._ptimg_inputs("ptimg_render", transform, x, y, amplitude)
+        image = torch.empty((B, self.out_h, self.out_w), dtype=torch.float32, device=self.device)
+        _check_potential(lib().gl_ptimg_render(self._h, _ptr(x), _ptr(y), _ptr(amplitude), B, J, xf, _ptr(image), _ptr(ws), ws.numel(),
+                                               _stream()))
+        return image
+
+    def ptimg_render_bwd(self, x, y, amplitude, transform, grad_image):
+        """gl_ptimg_render_bwd: the transpose of ``ptimg_render``; ``grad_image`` [B, H, W] -> ``grad_x, grad_y, grad_amplitude``
+        [B, J]."""
+        (x, y, amplitude), B, J, xf, ws = self._ptimg_inputs("ptimg_render_bwd", transform, x, y, amplitude)
+        _require_cuda(grad_image, "grad_image")
+        if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (B, self.out_h, self.out_w):
+            raise NativeLibraryError(f"ptimg_render_bwd: grad_image must be float32 [{B}, {self.out_h}, {self.out_w}], got "
+                                     f"{grad_image.dtype} {tuple(grad_image.shape)}")
+        grad_image = grad_image.contiguous()
+        gx, gy, ga = (torch.empty((B, J), dtype=torch.float32, device=self.device) for _ in range(3))
+        _check_potential(lib().gl_ptimg_render_bwd(self._h, _ptr(x), _ptr(y), _ptr(amplitude), B, J, xf, _ptr(grad_image), _ptr(gx),
+                                                   _ptr(gy), _ptr(ga), _ptr(ws), ws.numel(), _stream()))
+        return gx, gy, ga
+
+    def ptimg_fit(self, x, y, transform, extended, observed, weight, want_grad):
+        """gl_ptimg_fit: ``x, y`` [B, J], ``extended`` [B, H, W], ``observed`` and ``weight`` [H, W] or [B, H, W] (``weight`` = 1 / err^2
+        on the used pixels, 0 elsewhere).  Returns ``amplitude`` [B, J], ``model_image``, ``cotangent_image`` [B, H, W], ``chi2`` [B]
+        (float64), ``ok`` [B] (int32) and, with ``want_grad``, ``grad_x, grad_y`` [B, J] (else None twice)."""
+        (x, y), B, J, xf, ws = self._ptimg_inputs("ptimg_fit", transform, x, y)
+        extended, _ = self._ptimg_image(extended, B, "ptimg_fit", "extended")
+        if extended.dim() != 3:
+            raise NativeLibraryError(f"ptimg_fit: extended must be [{B}, {self.out_h}, {self.out_w}], got {tuple(extended.shape)}")
+        observed, obs_b = self._ptimg_image(observed, B, "ptimg_fit", "observed")
+        weight, w_b = self._ptimg_image(weight, B, "ptimg_fit", "weight")
+        dev = self.device
+        amp = torch.empty((B, J), dtype=torch.float32, device=dev)
+        model = torch.empty((B, self.out_h, self.out_w), dtype=torch.float32, device=dev)
+        cot = torch.empty((B, self.out_h, self.out_w), dtype=torch.float32, device=dev)
+        chi2 = torch.empty((B,), dtype=torch.float64, device=dev)
+        ok = torch.empty((B,), dtype=torch.int32, device=dev)
+        gx = torch.empty((B, J), dtype=torch.float32, device=dev) if want_grad else None
+        gy = torch.empty((B, J), dtype=torch.float32, device=dev) if want_grad else None
+        _check_potential(lib().gl_ptimg_fit(self._h, _ptr(x), _ptr(y), B, J, xf, _ptr(extended), _ptr(observed), obs_b, _ptr(weight), w_b,
+                                            int(bool(want_grad)), _ptr(amp), _ptr(model), _ptr(cot), _ptr(chi2), _ptr(ok), _ptr(gx),
+                                            _ptr(gy), _ptr(ws), ws.numel(), _stream()))
+        return amp, model, cot, chi2, ok, gx, gy
 
     def pixsrc_grad_layout(self, B, n_src, n_used):
         """gl_pixsrc_grad_layout: ``dict(cb, pc, n_pad)`` -- samples per chunk, planes per post-processing launch and the padded row

@@ -946,11 +946,17 @@ void plan_corr_bwd(gl_model* m, const std::vector<double>& keff, std::vector<flo
 // PSF and pooling: the effective kernel flip(psf) (*) box(ss)/ss^2 of the tap kernels and, where it serves, the pair kernel's plans
 int build_post(gl_model* m, const gl_grid* grid, const Knobs& k) {
   m->has_post = grid->psf != nullptr || grid->supersample != 1;
-  if (!m->has_post) return GL_OK;
-  // flat = flip(psf) cross-correlated with SAME padding (tf/simulator.py:62-70,145-147), then box(ss)/ss^2 pooling
   const int kh = grid->psf ? grid->psf_h : 1, kw = grid->psf ? grid->psf_w : 1, ss = grid->supersample;
   m->psf_h = kh;
   m->psf_w = kw;
+  {  // the PSF as given inside a two-node zero apron: the table of the point-image kernels (gl_ptimg.hip.h)
+    std::vector<float> tab((size_t)(kh + 4) * (kw + 4), 0.f);
+    for (int u = 0; u < kh; ++u)
+      for (int v = 0; v < kw; ++v) tab[(size_t)(u + 2) * (kw + 4) + v + 2] = grid->psf ? grid->psf[(size_t)u * kw + v] : 1.f;
+    if (int rc = put(m->d_ptimg_tab, tab.data(), tab.size())) return rc;
+  }
+  if (!m->has_post) return GL_OK;
+  // flat = flip(psf) cross-correlated with SAME padding (tf/simulator.py:62-70,145-147), then box(ss)/ss^2 pooling
   m->KH = kh + ss - 1;
   m->KW = kw + ss - 1;
   m->pad_t = (kh - 1) / 2;

@@ -1,6 +1,6 @@
 // gl_model.h -- the library-internal model descriptor, the owner type of its device buffers (DevBuf) and the error helper shared
 // by the translation units of libgigalens_hip.so (gigalens_hip.hip: models, launch plan, front end / finalize / PSF launchers, the
-// render, likelihood and log-prob entries; gl_api_points.hip, gl_api_lstsq.hip, gl_api_pixsrc.hip, gl_api_plugin.hip: the entry
+// render, likelihood and log-prob entries; gl_api_points.hip, gl_api_lstsq.hip, gl_api_pixsrc.hip, gl_api_ptimg.hip, gl_api_plugin.hip: the entry
 // points of one feature family each, sharing gl_host.hip.h; gl_launch_mode*.hip / gl_generic_noslp_mode*.hip: one instantiation of
 // a main-kernel launcher per mode; gl_user.hip: the run-time compiler of user-written profiles -- all compiled in parallel).  The
 // model owns every device allocation it holds: destroying it frees them.
@@ -136,6 +136,9 @@ struct gl_model {
   CorrPlan corr_fwd, corr_bwd;
   glk::DevBuf<float> d_corr_k;
   int psf_h = 0, psf_w = 0;
+  // the PSF as given (not flipped, not pooled; [[1]] without one) with a two-node zero apron, [(psf_h + 4)][(psf_w + 4)]: the table
+  // the point-image kernels interpolate (gl_ptimg.hip.h)
+  glk::DevBuf<float> d_ptimg_tab;
   int KH = 1, KW = 1, pad_t = 0, pad_l = 0;
   bool has_post = false;
   // unconstrained-space front end (gl_model_set_prior)

@@ -6,6 +6,8 @@ the pixel log-likelihood and its gradient w.r.t. every profile parameter come fr
 sequence (prep -> main -> finalize, see csrc/gl_kernels.hip.h); prior densities and bijectors are a few
 elementwise torch ops on ``(B, d)``.
 """
+import math
+import weakref
 from typing import Dict, List
 
 import numpy as np
@@ -992,6 +994,125 @@ class SourceEvidenceProbModel(ProbabilisticModel):
         return ev + log_prior, chi2 / float(self._n_used(simulator))
 
     def log_prob_and_grad(self, simulator, z):
+        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
+        lp, red = self.log_prob(simulator, zz)
+        (g,) = torch.autograd.grad(lp.sum(), zz)
+        return lp.detach(), red.detach(), g
+
+    def log_prior(self, z):
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
+
+    def init_centroids(self, bs):
+        return None
+
+
+class _PointImageFn(torch.autograd.Function):
+    """log-likelihood of the extended model plus point images with solved amplitudes
+    (``LensSimulator.point_image_log_like_and_grad``) with its hand-written gradient: packed rows and image positions."""
+
+    @staticmethod
+    def forward(ctx, packed, x, y, prob_model, simulator):
+        pm = prob_model
+        res = simulator.point_image_log_like_and_grad(packed.detach(), x.detach(), y.detach(), pm.observed_image, pm.err_map,
+                                                      mask=pm.mask)
+        ctx.save_for_backward(res["grad"], res["grad_x"], res["grad_y"])
+        ctx.mark_non_differentiable(res["chi2"])
+        return res["log_like"].float(), res["chi2"].float()
+
+    @staticmethod
+    def backward(ctx, g_ll, g_chi2):
+        grad, gx, gy = ctx.saved_tensors
+        return g_ll[:, None] * grad, g_ll[:, None] * gx, g_ll[:, None] * gy, None, None
+
+
+class _SourcePlaneTieFn(torch.autograd.Function):
+    """``-1/2 sum_j |beta_j - mean beta|^2 / sigma^2`` of the images' source-plane positions ``beta_j`` (``lens_maps`` at
+    ``(x_j, y_j)``).  Gradient from existing entries: the cotangent ``-(beta_j - mean beta) / sigma^2`` goes through
+    ``lens_maps_vjp`` to the lens columns and through ``(I - H_j)^T`` (``H_j`` the Hessian ``lens_maps`` returns) to the positions."""
+
+    @staticmethod
+    def forward(ctx, packed, x, y, simulator, sigma):
+        xp, yp = x.detach().t().contiguous(), y.detach().t().contiguous()  # [J, B]: the point layout of the lens maps
+        maps = simulator._lens_maps(xp, yp, packed.detach())
+        bx, by = maps[0].double(), maps[1].double()
+        cx, cy = -(bx - bx.mean(dim=0, keepdim=True)) / sigma ** 2, -(by - by.mean(dim=0, keepdim=True)) / sigma ** 2
+        ctx.simulator = simulator
+        ctx.save_for_backward(packed.detach(), xp, yp, cx.float(), cy.float(), maps[2:])
+        return (-0.5 * sigma ** 2 * (cx * cx + cy * cy).sum(dim=0)).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        packed, xp, yp, cx, cy, h = ctx.saved_tensors
+        g_packed = ctx.simulator.beta_vjp(xp, yp, packed, cx, cy)
+        gx = (1.0 - h[0]) * cx - h[2] * cy  # (I - H)^T (cx, cy), H = [[f_xx, f_xy], [f_yx, f_yy]]
+        gy = -h[1] * cx + (1.0 - h[3]) * cy
+        return g[:, None] * g_packed, g[:, None] * gx.t(), g[:, None] * gy.t(), None, None
+
+
+class PointImageProbModel(ProbabilisticModel):
+    """The pixel likelihood of an extended model plus the PSF-rendered images of a lensed point source (quasar, supernova) as the
+    target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the reference): ``log_prob = log_like + log_prior`` of
+    ``LensSimulator.fit_point_images``, where the amplitudes of the images are solved per sample, with the hand-written gradient
+    of ``LensSimulator.point_image_log_like_and_grad``.
+
+    The prior's structure carries one group beside the model's own: ``"point_images": [{"x": ..., "y": ...}] * J`` (``J <= 8``), the
+    image positions in arcsec.  ``source_plane_sigma`` (arcsec, optional) ties the images to one source and so lets them constrain
+    the lens: with ``beta_j`` the source-plane position of image ``j`` and ``mean beta`` their plain mean it adds
+    ``-1/2 sum_j |beta_j - mean beta|^2 / sigma^2 - (J - 1) log(2 pi sigma^2)``.  Lenses ``lens_maps`` / ``lens_maps_vjp`` refuse
+    stay refused with their error.  A sample whose fit is singular (``ok == False``) has a NaN ``log_prob``.  Runs on the stream
+    path (``MAP(graph=True)`` falls back to it)."""
+
+    include_pixels, include_positions, n_position = True, False, 0.0
+
+    def __init__(self, prior, observed_image, err_map, *, mask=None, source_plane_sigma=None):
+        super().__init__(prior)
+        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
+        self.observed_image = torch.as_tensor(np.asarray(observed_image, dtype=np.float32), device=self.device).contiguous()
+        self.err_map = torch.as_tensor(np.asarray(err_map, dtype=np.float32), device=self.device).contiguous()
+        self.mask = None if mask is None else torch.as_tensor(np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).astype(bool),
+                                                              device=self.device)
+        self._n_used_of = weakref.WeakKeyDictionary()  # per simulator: the number of used pixels
+        if source_plane_sigma is not None:
+            source_plane_sigma = float(source_plane_sigma)
+            if not (np.isfinite(source_plane_sigma) and source_plane_sigma > 0):
+                raise ValueError(f"source_plane_sigma must be finite and > 0, got {source_plane_sigma}")
+        self.source_plane_sigma = source_plane_sigma
+        self._flat = prior.flat(self.device)
+        example = prior.sample(seed=0)
+        images = example.get("point_images") if isinstance(example, dict) else None
+        if not images or any(set(d) != {"x", "y"} for d in images):
+            raise ValueError('the prior needs a group "point_images": a list of {"x": ..., "y": ...}, one per image')
+        if len(images) > 8:
+            raise ValueError(f"{len(images)} point images: at most 8 are served")
+        self.n_images = len(images)
+        self.pack_bij = _PackBijector(example)
+        self.unconstraining_bij = _prior.JointBijector(self._flat)
+        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+
+    def _n_used(self, simulator):
+        if simulator not in self._n_used_of:
+            used = simulator.img_region != 0
+            self._n_used_of[simulator] = int((used & self.mask.to(used.device)).sum() if self.mask is not None else used.sum())
+        return self._n_used_of[simulator]
+
+    def log_prob(self, simulator, z):
+        """``(log_like + source-plane tie + log_prior, chi2 / n_used)``; differentiable with respect to ``z``."""
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        x = self._flat.forward(z)
+        log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+        struct = self.pack_bij.forward(x)
+        packed = simulator._pack_partial(struct)  # groups outside the layout are ignored; torch.stack keeps the graph
+        px = torch.stack([d["x"] for d in struct["point_images"]], dim=1)
+        py = torch.stack([d["y"] for d in struct["point_images"]], dim=1)
+        ll, chi2 = _PointImageFn.apply(packed, px, py, self, simulator)
+        lp = ll + log_prior
+        if self.source_plane_sigma is not None:
+            s = self.source_plane_sigma
+            lp = lp + _SourcePlaneTieFn.apply(packed, px, py, simulator, s) - (self.n_images - 1) * math.log(2.0 * math.pi * s * s)
+        return lp, chi2 / float(self._n_used(simulator))
+
+    def log_prob_and_grad(self, simulator, z, graph=False):
         zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
         lp, red = self.log_prob(simulator, zz)
         (g,) = torch.autograd.grad(lp.sum(), zz)

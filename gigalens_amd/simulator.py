@@ -109,6 +109,22 @@ class _SimulateFn(torch.autograd.Function):
         return ctx.model.simulate_bwd(params, grad_img), None
 
 
+class _PointImagesFn(torch.autograd.Function):
+    """autograd glue: forward = gl_ptimg_render, backward = gl_ptimg_render_bwd (both HIP)."""
+
+    @staticmethod
+    def forward(ctx, x, y, amplitude, model, transform):
+        ctx.model, ctx.transform = model, transform
+        ctx.save_for_backward(x, y, amplitude)
+        return model.ptimg_render(x, y, amplitude, transform)
+
+    @staticmethod
+    def backward(ctx, grad_img):
+        x, y, amplitude = ctx.saved_tensors
+        gx, gy, ga = ctx.model.ptimg_render_bwd(x, y, amplitude, ctx.transform, grad_img.contiguous())
+        return gx, gy, ga, None, None
+
+
 class LensSimulator(LensSimulatorInterface):
     """Drop-in for ``gigalens.tf.simulator.LensSimulator`` (tf/simulator.py:13-156).
 
@@ -158,6 +174,7 @@ class LensSimulator(LensSimulatorInterface):
         self._linear_cols_dev = None  # the linear columns of the layout on the device (BackwardProbModel.log_prob)
         self._lp_graphs = {}  # {(id(prob_model), shape of z): model._GraphEntry} of log_prob_and_grad(graph=True)
         self._lp_captures = 0  # how many of them were captured so far
+        self._point_cache = None  # (key, inputs, checked data) of the last point-image fit on device tensors (_point_data)
         self._mp =getattr(phys_model, "multiplane", None)  # lenses on planes of their own (PhysicalModel multiplane, K >= 2)
         if self._mp is not None:
             self._refuse_on_planes_profiles()
@@ -751,6 +768,133 @@ class LensSimulator(LensSimulatorInterface):
         out["grad"] = torch.where(good[:, None], grad, torch.full_like(grad, nan))
         out["grad_pose"] = torch.where(good[:, None], grad_pose, torch.full_like(grad_pose, nan))
         out["grad_beta"] = gb
+        return out
+
+    # -- point images in the pixel likelihood (gl_ptimg_*; beyond the reference) ---------------------------------------
+    MAX_POINT_IMAGES = 8
+
+    def _point_transform(self):
+        """``(x0, y0, m00, m01, m10, m11)``: a position in arcsec -> supersampled pixel coordinates, ``(u, v) = M (x - x0, y - y0)``
+        with ``u`` along the columns: ``supersample * wcs.angle2pix``, the inverse of ``wcs.pix2angle`` on the supersampled grid
+        (``M = supersample inv(T^T)``, the ``T`` / ``T^T`` quirk of ``LensWCS`` kept)."""
+        m = self.supersample * self.wcs.transform_angle2pix.T
+        x0, y0 = self.wcs.radec_at_xy_0
+        return (float(x0), float(y0), float(m[0, 0]), float(m[0, 1]), float(m[1, 0]), float(m[1, 1]))
+
+    def _point_rows(self, what, *rows):
+        """``[B, J]`` float32 device tensors of one shape (``ValueError`` otherwise, or for ``J`` outside ``1..MAX_POINT_IMAGES``)."""
+        out = [torch.as_tensor(r, dtype=torch.float32, device=self.device) for r in rows]
+        shape = tuple(out[0].shape)
+        if len(shape) != 2 or any(tuple(t.shape) != shape for t in out):
+            raise ValueError(f"{what}: x, y (and amplitude) must be [B, J] of one shape, got {[tuple(t.shape) for t in out]}")
+        if not 1 <= shape[1] <= self.MAX_POINT_IMAGES:
+            raise ValueError(f"{what}: {shape[1]} images per sample (1..{self.MAX_POINT_IMAGES})")
+        if shape[0] < 1:
+            raise ValueError(f"{what}: an empty batch")
+        return out
+
+    def point_images(self, x, y, amplitude):
+        """The image of ``J`` point sources per sample seen through the PSF (beyond the reference): ``x, y`` in arcsec and
+        ``amplitude`` (flux in image counts), ``[B, J]`` each -> ``[B, H, W]`` = ``sum_j amplitude_j D(x_j, y_j)``.
+
+        The unit point image ``D(x, y)``: with ``(u, v) = supersample * wcs.angle2pix(x, y)`` the position on the supersampled grid,
+        Keys' cubic weights (``a = -1/2``) of the 4 x 4 nodes around it on a zero supersampled frame (nodes outside the frame are
+        dropped), the PSF applied as ``simulate`` applies it (``[[1]]`` without one), then the **sum** over ``supersample`` x
+        ``supersample`` sub-pixels, without the ``det T`` factor.  ``sum(D) = sum(psf)`` while the footprint lies inside the frame;
+        ``D`` is C1 in ``(x, y)`` and, the cubic weights being negative between one and two nodes from the position, has negative
+        lobes: 5e-3 of its peak behind a PSF with sigma = 1.6 nodes, more behind a narrower one, up to 1/9 with none.  A position that is not finite, or whose footprint misses the frame, gives ``D = 0`` and a
+        zero gradient.  ``pix_region`` does not apply (the fit uses it).  Differentiable in all three arguments (HIP kernels both
+        ways); lens planes raise ``UnsupportedLensError``."""
+        self._single_plane("point_images")
+        x, y, amplitude = self._point_rows("point_images", x, y, amplitude)
+        return _PointImagesFn.apply(x, y, amplitude, self._model, self._point_transform())
+
+    def _point_prepare(self, what, params, x, y, observed_image, err_map, mask):
+        """Validation and inputs the point-image fits share: positions, the extended image, data and weights on the device."""
+        self._single_plane(what)
+        packed = params if torch.is_tensor(params) else self.pack(params)
+        x, y = self._point_rows(what, x, y)
+        self._forward_only(what, packed, x, y, observed_image, err_map)
+        B = packed.shape[0]
+        if x.shape[0] != B:
+            raise ValueError(f"{what}: x, y must be [B={B}, J], got {tuple(x.shape)}")
+        data = self._point_data(B, observed_image, err_map, mask)
+        return {"packed": packed, "x": x, "y": y, "extended": self._model.simulate_fwd(packed), **data}
+
+    def _point_data(self, B, observed_image, err_map, mask):
+        """The data side of a point-image fit, checked: ``obs``, ``weight`` (``1 / err_map^2`` on the used pixels, 0 elsewhere) and
+        ``noise`` (``sum_U log(2 pi err^2)``, float64).  The checks read the device; for device tensors that were not written to since
+        the last call (a probabilistic model's data, step after step) the result of that call is handed back."""
+        given = (observed_image, err_map, mask)
+        key = None
+        if all(t is None or (torch.is_tensor(t) and t.device == self.device) for t in given):
+            key = (B,) + tuple(None if t is None else (id(t), t._version) for t in given)
+            if self._point_cache is not None and self._point_cache[0] == key:
+                return self._point_cache[2]
+        H, W = self._model.out_h, self._model.out_w
+        dev = self.device
+        used = self.img_region != 0
+        if mask is not None:
+            mk = torch.as_tensor(mask, device=dev)
+            if tuple(mk.shape) != (H, W):
+                raise ValueError(f"mask must be [{H}, {W}], got {tuple(mk.shape)}")
+            used = used & mk.bool()
+        if not bool(used.any()):
+            raise ValueError("no pixel is left to fit (mask and pix_region)")
+
+        def per_pixel(a, name):
+            t = torch.as_tensor(a, dtype=torch.float32, device=dev)
+            if tuple(t.shape) not in ((H, W), (B, H, W)):
+                raise ValueError(f"{name} must be [{H}, {W}] or [{B}, {H}, {W}], got {tuple(t.shape)}")
+            return t.contiguous()
+        obs, err = per_pixel(observed_image, "observed_image"), per_pixel(err_map, "err_map")
+        good = torch.isfinite(err) & (err > 0)
+        if not bool((good | ~used).all()):
+            raise ValueError("err_map must be finite and > 0 on every used pixel")
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        weight = torch.where(used & good, 1.0 / (err * err), zero).contiguous()
+        noise = torch.where(used & good, torch.log(2.0 * math.pi * err.double() ** 2), zero.double()).reshape(-1, H * W).sum(dim=1)
+        data = {"obs": obs, "weight": weight, "noise": noise}
+        if key is not None:  # (the tensors are kept alongside: their ids stay theirs)
+            self._point_cache = (key, given, data)
+        return data
+
+    def _point_outputs(self, p, amp, model, chi2, ok):
+        good = ok != 0
+        return {"amplitudes": amp, "model_image": model, "extended_image": p["extended"], "chi2": chi2,
+                "log_like": -0.5 * chi2 - 0.5 * p["noise"], "ok": good}
+
+    def fit_point_images(self, params, x, y, observed_image, err_map, *, mask=None):
+        """The extended model plus ``J`` point images at ``(x, y)`` ``[B, J]`` whose amplitudes are solved per sample (beyond the
+        reference; the linear amplitudes of lenstronomy's point sources): ``m = E + sum_j a_j D_j`` with ``E = simulate(params)`` and
+        ``D_j`` the unit point images of ``point_images``.  On the used pixels ``U`` (``pix_region`` and ``mask`` ``[H, W]`` bool), with
+        ``w = 1 / err_map^2``: ``N_jk = sum_U w D_j D_k``, ``r_j = sum_U w D_j (obs - E)``, ``a = N^-1 r`` by Cholesky (sums and solve
+        in float64), ``chi2 = sum_U w (obs - m)^2``, ``log_like = -chi2 / 2 - sum_U log(2 pi err^2) / 2``.  The amplitudes are not
+        constrained in sign.
+
+        ``observed_image``, ``err_map``: ``[H, W]`` or ``[B, H, W]``.  Returns a dict: ``amplitudes`` ``[B, J]``, ``model_image`` and
+        ``extended_image`` ``[B, H, W]``, ``chi2`` and ``log_like`` ``[B]`` (float64), ``ok`` ``[B]`` bool -- false where a Cholesky
+        pivot is not finite or not above 1e-6 of its diagonal entry (coincident images, an image on unused pixels alone, an image
+        outside the frame); that sample's other outputs (``extended_image`` aside) are then NaN.  ``ValueError``: shapes, more than
+        ``MAX_POINT_IMAGES`` images, an ``err_map`` that is not finite or not > 0 on a used pixel, no used pixel.  Forward only."""
+        p = self._point_prepare("fit_point_images", params, x, y, observed_image, err_map, mask)
+        amp, model, _, chi2, ok, _, _ = self._model.ptimg_fit(p["x"], p["y"], self._point_transform(), p["extended"], p["obs"],
+                                                              p["weight"], False)
+        return self._point_outputs(p, amp, model, chi2, ok)
+
+    def point_image_log_like_and_grad(self, params, x, y, observed_image, err_map, *, mask=None):
+        """``fit_point_images`` with the gradient of ``log_like``: the dict gains ``grad`` ``[B, P]`` (packed order) and ``grad_x``,
+        ``grad_y`` ``[B, J]``.  The amplitudes maximise ``log_like``, so no term goes through them (envelope theorem):
+        ``d log_like / dE = w (obs - m)`` on the used pixels -- handed to the render's VJP for ``grad`` -- and
+        ``d log_like / d(x_j, y_j) = a_j sum_U w (obs - m) dD_j / d(x_j, y_j)``.  Rows with ``ok == False`` are NaN.  Deterministic."""
+        p = self._point_prepare("point_image_log_like_and_grad", params, x, y, observed_image, err_map, mask)
+        amp, model, cot, chi2, ok, gx, gy = self._model.ptimg_fit(p["x"], p["y"], self._point_transform(), p["extended"], p["obs"],
+                                                                  p["weight"], True)
+        out = self._point_outputs(p, amp, model, chi2, ok)
+        good = out["ok"]
+        grad = self._model.simulate_bwd(p["packed"], torch.where(good[:, None, None], cot, torch.zeros_like(cot)))
+        out["grad"] = torch.where(good[:, None], grad, torch.full_like(grad, float("nan")))
+        out["grad_x"], out["grad_y"] = gx, gy
         return out
 
     def simulate(self, params, no_deflection=False):

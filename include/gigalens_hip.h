@@ -616,6 +616,40 @@ int gl_pixsrc_evidence_grad(const gl_model* m, const float* beta_x, const float*
                             const float* strength, float* source, float* model_image, double* scalars, int* ok, float* grad_beta,
                             float* grad_image, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Point images in the pixel likelihood: PSF-rendered images of a lensed point source with linear amplitudes (beyond the reference;
+ * csrc/gl_ptimg.hip.h).  x, y, amplitude [B][n_images] (DEVICE; 1 <= n_images <= 8): positions in arcsec and fluxes in image counts.
+ * transform (HOST, 6 doubles) = x0, y0, m00, m01, m10, m11 maps a position to supersampled pixel coordinates, u along the columns and
+ * v along the rows: (u, v) = M (x - x0, y - y0), the inverse of the camera's pix2angle on the supersampled grid (formed in float64, rounded once).
+ * The unit image D(x, y) [H W] on final pixels: Keys' cubic weights (a = -1/2) of the 4 x 4 supersampled nodes around (u, v) on a
+ * zero frame, nodes outside the frame dropped; the model's PSF applied as the render applies it (flipped, cross-correlated with
+ * SAME padding; [[1]] without one); then the SUM over ss x ss sub-pixels, without the conversion factor.  D is C1 in (x, y), has
+ * negative lobes (5e-3 of its peak behind a PSF with sigma = 1.6 nodes, up to 1/9 with none), and is 0 with a zero gradient for a position that is not finite or whose footprint
+ * misses the frame.  sum(D) = sum(psf) when the footprint lies inside the frame.
+ *   gl_ptimg_render:      image [B][H W] = sum_j amplitude_j D_j
+ *   gl_ptimg_render_bwd:  its transpose: grad_image [B][H W] -> grad_amplitude_j = <grad_image, D_j>, grad_x, grad_y [B][n_images]
+ *   gl_ptimg_fit:         the amplitudes that maximise the likelihood of observed = extended_image + sum_j a_j D_j:
+ *       N_jk = sum w D_j D_k,  r_j = sum w D_j (observed - extended_image),  a = N^-1 r by Cholesky (float64; sums in float64),
+ *       weight [H W] (or [B][H W], weight_batched) = 1 / err^2 on the used pixels and 0 elsewhere, observed likewise [H W] or
+ *       [B][H W]; amplitude [B][n_images], model_image [B][H W], cotangent_image [B][H W] = weight (observed - model_image) (the
+ *       gradient of -chi2 / 2 with respect to extended_image), chi2 [B] (float64), ok [B] = 0 where a pivot is not finite or not
+ *       above 1e-6 of its diagonal entry (coincident images, an image on unused pixels alone) -- that sample's other outputs are
+ *       then NaN; with want_grad, grad_x, grad_y [B][n_images] = d(-chi2 / 2)/d(x_j, y_j) at the fitted amplitudes (which
+ *       maximise it: no term through them).
+ * No atomics: two calls give identical bits; a sample does not depend on the others.  No allocation, no host synchronisation.
+ * GL_EINVAL (before the model is read): null arguments, n_images outside 1..8, B outside 1..65535; a workspace smaller than
+ * gl_ptimg_workspace_bytes (0 for sizes the calls refuse).  GL_EUNSUPPORTED: lens planes, a PSF of more than 12288 nodes with
+ * its apron. */
+size_t gl_ptimg_workspace_bytes(const gl_model* m, int B, int n_images);
+int gl_ptimg_render(const gl_model* m, const float* x, const float* y, const float* amplitude, int B, int n_images,
+                    const double* transform, float* image, void* workspace, size_t workspace_bytes, void* hip_stream);
+int gl_ptimg_render_bwd(const gl_model* m, const float* x, const float* y, const float* amplitude, int B, int n_images,
+                        const double* transform, const float* grad_image, float* grad_x, float* grad_y, float* grad_amplitude,
+                        void* workspace, size_t workspace_bytes, void* hip_stream);
+int gl_ptimg_fit(const gl_model* m, const float* x, const float* y, int B, int n_images, const double* transform,
+                 const float* extended_image, const float* observed, int observed_batched, const float* weight, int weight_batched,
+                 int want_grad, float* amplitude, float* model_image, float* cotangent_image, double* chi2, int* ok, float* grad_x,
+                 float* grad_y, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Plugin-level point evaluation, the reference's MassProfile.deriv / LightProfile.light called on
  * arbitrary coordinates (tests/test_profiles.py calls exactly these):
  *   x, y [n_pts, B] when xy_batched, else [n_pts] shared by every sample (pixel-major, batch-minor
