@@ -113,6 +113,12 @@ SYMBOLS = {
     "gl_lens_maps_vjp_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int64]),
     "gl_lens_maps_vjp": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
+    "gl_lens_hessian_vjp_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int64]),
+    "gl_lens_hessian_vjp": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "gl_shear_loglike_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "gl_shear_loglike": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_model_set_lens_planes": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_float), POINTER(c_float), c_int]),
     "gl_multiplane_maps": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, POINTER(c_float), c_int, c_void_p,
                                    c_void_p]),
@@ -753,6 +759,46 @@ class Model:
         _check_potential(lib().gl_lens_maps_vjp(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), n_pts, 1, _ptr(cot), _ptr(out), _ptr(ws),
                                                 ws.numel(), _stream()))
         return out
+
+    def lens_hessian_vjp(self, params, x, y, cot_xx, cot_xy, cot_yx, cot_yy):
+        """gl_lens_hessian_vjp: the cotangents on ``lens_maps``' f_xx, f_xy, f_yx, f_yy (with ``x, y`` broadcastable to
+        ``(..., B)``) -> the gradient on the packed rows ``[B, P]``; columns of no lens are 0.  Points whose four cotangents are all
+        exactly 0, or one of which is not finite, are skipped.  ``UnsupportedLensError``: series and user-written lenses, lens
+        planes."""
+        self._single_plane("lens_hessian_vjp")
+        params = self._params(params)
+        B = params.shape[0]
+        xb, yb, shape = self._points(x, y, B)
+        cot = torch.stack([torch.as_tensor(c, dtype=torch.float32, device=self.device).expand(shape).reshape(-1, B)
+                           for c in (cot_xx, cot_xy, cot_yx, cot_yy)]).contiguous()
+        n_pts = xb.shape[0]
+        ws = self._scratch("lens_hessian_vjp", lib().gl_lens_hessian_vjp_workspace_bytes(self._h, B, n_pts))
+        out = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
+        _check_potential(lib().gl_lens_hessian_vjp(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), n_pts, 1, _ptr(cot), _ptr(out), _ptr(ws),
+                                                   ws.numel(), _stream()))
+        return out
+
+    def shear_loglike(self, params, x, y, e1, e2, sigma, scales=None, want_grad=True, want_model=True):
+        """gl_shear_loglike: the reduced-shear likelihood of the galaxies ``x, y, e1, e2, sigma`` (and ``scales`` or None: all 1),
+        float32 ``[n_gal]`` device tensors.  Returns ``(log_like [B], chi2 [B], model_g [2, n_gal, B] or None, grad [B, P] or
+        None)``.  ``UnsupportedLensError`` as ``lens_hessian_vjp``."""
+        self._single_plane("shear_loglike")
+        params = self._params(params)
+        B = params.shape[0]
+        tabs = [None if t is None else torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
+                for t in (x, y, scales, e1, e2, sigma)]
+        n_gal = int(tabs[0].numel())
+        if any(t is not None and (t.dim() != 1 or t.numel() != n_gal) for t in tabs):
+            raise ValueError(f"shear_loglike: x, y, e1, e2, sigma and scales must be 1-D arrays of one length ({n_gal})")
+        ll = torch.empty(B, dtype=torch.float32, device=self.device)
+        chi2 = torch.empty(B, dtype=torch.float32, device=self.device)
+        model = torch.empty((2, n_gal, B), dtype=torch.float32, device=self.device) if want_model else None
+        grad = torch.empty((B, self.P), dtype=torch.float32, device=self.device) if want_grad else None
+        ws = self._scratch("shear_loglike", lib().gl_shear_loglike_workspace_bytes(self._h, B, n_gal, 1 if want_grad else 0))
+        _check_potential(lib().gl_shear_loglike(self._h, _ptr(params), B, _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]),
+                                                _ptr(tabs[4]), _ptr(tabs[5]), n_gal, _ptr(ll), _ptr(chi2), _ptr(model), _ptr(grad),
+                                                _ptr(ws), ws.numel(), _stream()))
+        return ll, chi2, model, grad
 
     def lens_potential(self, params, x, y):
         """gl_lens_potential: ``x, y`` broadcastable to ``(..., B)`` (or both None: the model's own grid, ``(N, B)``); returns psi."""

@@ -1,6 +1,6 @@
 // gl_api_points.hip -- the entry points of the point family: everything that evaluates the lenses of a model (or one free-standing
 // profile) at points through gl_positions.hip.h -- image-position likelihood, lens maps, Hessians, potential, the lens-equation
-// solver, critical curves, and the lens planes (maps, render and its VJP).
+// solver, critical curves, the Hessian VJP with the weak-lensing shear likelihood, and the lens planes (maps, render and its VJP).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -17,6 +17,7 @@
 #include "gl_multiplane_bwd.hip.h"
 #include "gl_multiplane_pos.hip.h"
 #include "gl_lens_vjp.hip.h"
+#include "gl_hessian_vjp.hip.h"
 
 using namespace glk;
 
@@ -424,6 +425,108 @@ int gl_lens_maps_vjp(const gl_model* m, const float* params, int B, const float*
                        point_args(m, params, B), x, y, (long long)n_pts, xy_batched, cot, m->lens_params, (int)n_blocks, partial);
   hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
                      m->P, m->lens_params, (int)n_blocks, grad_params);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- VJP of the Hessian, reduced-shear likelihood (gl_hessian_vjp.hip.h) ------------------------------------------
+namespace {
+// the lenses gl_lens_maps_vjp refuses, in its order and words
+int refuse_vjp_lenses(const gl_model* m, const char* fn, const char* what) {
+  if (int rp = refuse_planes(m, fn)) return rp;
+  for (int l = 0; l < m->n_lens; ++l) {
+    const int kind = m->comps[l].kind;
+    if (kind == GL_SERIES)
+      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its field lives on the model grid and has no parameter derivative here", l);
+    if (kind == GL_USER_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
+                                   "not served by %s", l, what);
+  }
+  return GL_OK;
+}
+
+// the parts of the shear likelihood's workspace: block partials, cotangents [4][n_gal][B], the partials of the Hessian VJP
+struct ShearLayout { size_t part, cot, vjp, bytes; long long n_blocks; };
+bool shear_layout(const gl_model* m, int B, int n_gal, bool want_grad, ShearLayout* l) {
+  if (!m || B <= 0 || n_gal <= 0) return false;
+  l->n_blocks = ((long long)n_gal + VJP_PTS - 1) / VJP_PTS;
+  if (l->n_blocks > 0x7fffffffLL / B) return false;
+  l->part = 0;
+  l->cot = l->part + align_up((size_t)B * (size_t)l->n_blocks * 2 * sizeof(float), 256);
+  l->vjp = l->cot;
+  l->bytes = l->cot;
+  if (want_grad) {
+    const size_t vjp = gl_lens_hessian_vjp_workspace_bytes(m, B, n_gal);
+    if (!vjp) return false;
+    l->vjp = l->cot + align_up((size_t)4 * (size_t)n_gal * (size_t)B * sizeof(float), 256);
+    l->bytes = l->vjp + vjp;
+  }
+  return true;
+}
+
+void launch_hessian_vjp(const gl_model* m, const float* params, int B, const float* x, const float* y, long long n_pts, int xy_batched,
+                        const float* cot, float* grad_params, float* partial, long long n_blocks, hipStream_t stream) {
+  if (m->lens_params)
+    hipLaunchKernelGGL(gl_hessian_vjp_kernel, dim3((unsigned)((long long)B * m->lens_params * n_blocks)), dim3(VJP_WG), 0, stream,
+                       point_args(m, params, B), x, y, n_pts, xy_batched, cot, m->lens_params, (int)n_blocks, partial);
+  hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
+                     m->P, m->lens_params, (int)n_blocks, grad_params);
+}
+}  // namespace
+
+size_t gl_lens_hessian_vjp_workspace_bytes(const gl_model* m, int B, int64_t n_pts) {
+  return gl_lens_maps_vjp_workspace_bytes(m, B, n_pts);  // one partial per (sample, lens column, block of points), as the ray-shoot VJP
+}
+
+int gl_lens_hessian_vjp(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
+                        const float* cot, float* grad_params, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !x || !y || !cot || !grad_params || !workspace) return fail(GL_EINVAL, "null argument");
+  if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
+  if (int rc = refuse_vjp_lenses(m, "gl_lens_hessian_vjp", "the Hessian VJP")) return rc;
+  if (int rc = check_ready(m, false, false)) return rc;
+  const long long n_blocks = vjp_blocks(m, B, n_pts);
+  if (!n_blocks) return fail(GL_EINVAL, "too many points x samples for one call");
+  const size_t need = gl_lens_hessian_vjp_workspace_bytes(m, B, n_pts);
+  if (workspace_bytes < need) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  launch_hessian_vjp(m, params, B, x, y, (long long)n_pts, xy_batched, cot, grad_params, (float*)workspace, n_blocks, (hipStream_t)hip_stream);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+size_t gl_shear_loglike_workspace_bytes(const gl_model* m, int B, int n_gal, int want_grad) {
+  ShearLayout lay;
+  return shear_layout(m, B, n_gal, want_grad != 0, &lay) ? lay.bytes : 0;
+}
+
+int gl_shear_loglike(const gl_model* m, const float* params, int B, const float* x, const float* y, const float* scale_or_null,
+                     const float* e1, const float* e2, const float* sigma, int n_gal, float* ll, float* chi2, float* model_g_or_null,
+                     float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !x || !y || !e1 || !e2 || !sigma || !ll || !chi2 || !workspace) return fail(GL_EINVAL, "null argument");
+  if (B <= 0 || n_gal <= 0) return fail(GL_EINVAL, "B and n_gal must be positive");
+  if (int rc = refuse_vjp_lenses(m, "gl_shear_loglike", "the shear likelihood")) return rc;
+  if (int rc = check_ready(m, false, false)) return rc;
+  const bool want_grad = grad_params_or_null != nullptr;
+  ShearLayout lay;
+  if (!shear_layout(m, B, n_gal, want_grad, &lay)) return fail(GL_EINVAL, "too many galaxies x samples for one call");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  char* base = (char*)workspace;
+  ShearArgs s{};
+  s.x = x;
+  s.y = y;
+  s.scale = scale_or_null;
+  s.e1 = e1;
+  s.e2 = e2;
+  s.sigma = sigma;
+  s.n_gal = n_gal;
+  s.n_blocks = (int)lay.n_blocks;
+  s.part = (float*)(base + lay.part);
+  s.model_g = model_g_or_null;
+  s.cot = want_grad ? (float*)(base + lay.cot) : nullptr;
+  hipLaunchKernelGGL(gl_shear_fwd_kernel, dim3((unsigned)((long long)B * lay.n_blocks)), dim3(VJP_WG), 0, stream, point_args(m, params, B), s);
+  hipLaunchKernelGGL(gl_shear_sum_kernel, dim3((unsigned)B), dim3(VJP_WG), 0, stream, (const float*)s.part, s.n_blocks, ll, chi2);
+  if (want_grad)
+    launch_hessian_vjp(m, params, B, x, y, (long long)n_gal, 0, s.cot, grad_params_or_null, (float*)(base + lay.vjp), lay.n_blocks, stream);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

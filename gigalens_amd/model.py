@@ -1124,3 +1124,128 @@ class PointImageProbModel(ProbabilisticModel):
 
     def init_centroids(self, bs):
         return None
+
+
+class ShearCatalogue:
+    """The weak-lensing catalogue of ``WeakLensingProbModel`` and ``LensSimulator.shear_log_like_and_grad``: ``N`` background
+    galaxies at ``(x, y)`` (arcsec) with measured ellipticity components ``(e1, e2)``, their error ``sigma`` per component and the
+    deflection scale of every galaxy's own redshift (``gigalens_amd.cosmology.deflection_scale``; default 1: the model's reference
+    plane).  Everything is held as float32 ``[N]``; ``sigma`` and ``scales`` broadcast.  ``ValueError``: a shape mismatch, an
+    entry that is not finite, a ``sigma`` or a scale that is not finite and > 0."""
+
+    def __init__(self, x, y, e1, e2, sigma, scales=None):
+        x = np.atleast_1d(np.asarray(x, dtype=np.float32))
+        if x.ndim != 1 or x.size == 0:
+            raise ValueError(f"ShearCatalogue: x must be a non-empty 1-D array, got shape {tuple(x.shape)}")
+        n = x.size
+        tabs = {"x": x}
+        for name, v in (("y", y), ("e1", e1), ("e2", e2)):
+            v = np.atleast_1d(np.asarray(v, dtype=np.float32))
+            if v.shape != (n,):
+                raise ValueError(f"ShearCatalogue: {name} has shape {tuple(v.shape)}, x has {(n,)}")
+            tabs[name] = v
+        for name, v in (("sigma", sigma), ("scales", scales)):
+            if v is None and name == "scales":
+                tabs[name] = None
+                continue
+            v = np.asarray(v, dtype=np.float32)
+            if v.ndim > 1 or (v.ndim == 1 and v.size not in (1, n)):
+                raise ValueError(f"ShearCatalogue: {name} has shape {tuple(v.shape)}: a scalar or {(n,)}")
+            v = np.broadcast_to(v.reshape(-1) if v.ndim else v, (n,)).copy()
+            if not (np.all(np.isfinite(v)) and np.all(v > 0)):
+                raise ValueError(f"ShearCatalogue: every entry of {name} must be finite and > 0")
+            tabs[name] = v
+        for name in ("x", "y", "e1", "e2"):
+            if not np.all(np.isfinite(tabs[name])):
+                raise ValueError(f"ShearCatalogue: {name} holds an entry that is not finite")
+        self.n = n
+        self.x, self.y, self.e1, self.e2, self.sigma, self.scales = (tabs[k] for k in ("x", "y", "e1", "e2", "sigma", "scales"))
+        self._dev = {}
+
+    def __len__(self):
+        return self.n
+
+    def device_tables(self, device):
+        """The arrays as device tensors (uploaded once per device); ``scales`` stays None when it was not given."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = {k: None if v is None else torch.as_tensor(v, device=device).contiguous()
+                              for k, v in (("x", self.x), ("y", self.y), ("e1", self.e1), ("e2", self.e2), ("sigma", self.sigma),
+                                           ("scales", self.scales))}
+        return self._dev[key]
+
+
+class _ShearFn(torch.autograd.Function):
+    """log-likelihood of the reduced shear (``LensSimulator.shear_log_like_and_grad``) with its hand-written gradient with respect
+    to the packed rows."""
+
+    @staticmethod
+    def forward(ctx, packed, catalogue, simulator):
+        res = simulator.shear_log_like_and_grad(packed.detach(), catalogue, want_grad=True)
+        ctx.save_for_backward(res["grad"])
+        ctx.mark_non_differentiable(res["chi2"])
+        return res["log_like"], res["chi2"]
+
+    @staticmethod
+    def backward(ctx, g_ll, g_chi2):
+        (grad,) = ctx.saved_tensors
+        return g_ll[:, None] * grad, None, None
+
+
+class WeakLensingProbModel(ProbabilisticModel):
+    """The weak-lensing shear of a ``ShearCatalogue`` as the target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the reference):
+    ``log_prob = log_like + log_prior`` of ``LensSimulator.shear_log_like_and_grad`` with its hand-written gradient.  The prior is
+    over ``lens_mass`` (groups the physical model has beside it are packed from the prior when it carries them).
+
+    ``strong``: a ``ForwardProbModel`` over the SAME prior -- pixels, image positions, flux ratios, time delays -- whose ``log_prob``
+    is added for a joint strong + weak fit; the prior is counted once (inside ``strong``'s term).  The reduced chi^2 is then
+    ``(chi2_shear + red_strong n_strong) / (2 N + n_strong)`` with ``n_strong = strong._n_eff(simulator)``; without ``strong`` it is
+    ``chi2_shear / (2 N)``.  Lenses ``hessian_vjp`` refuses stay refused with their error.  Runs on the stream path
+    (``MAP(graph=True)`` falls back to it)."""
+
+    def __init__(self, prior, catalogue, strong=None):
+        super().__init__(prior)
+        if not isinstance(catalogue, ShearCatalogue):
+            raise TypeError("catalogue must be a ShearCatalogue")
+        if strong is not None and not isinstance(strong, ForwardProbModel):
+            raise TypeError("strong must be a ForwardProbModel over the same prior")
+        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
+        self.catalogue, self.strong = catalogue, strong
+        # what ModellingSequence sizes its loss with: the 2 N ellipticity components count with the point terms
+        self.include_pixels = bool(strong is not None and strong.include_pixels)
+        self.include_positions = True
+        self.n_position = 2.0 * catalogue.n
+        if strong is not None and strong.include_positions:
+            self.n_position += strong.n_position + getattr(strong, "n_flux", 0.0) + getattr(strong, "n_delay", 0.0)
+        self._flat = prior.flat(self.device)
+        example = prior.sample(seed=0)
+        self.pack_bij = _PackBijector(example)
+        self.unconstraining_bij = _prior.JointBijector(self._flat)
+        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+
+    def log_prob(self, simulator, z):
+        """``(log_like + log_prior [+ strong's log_like], reduced chi^2)``; differentiable with respect to ``z``."""
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        x = self._flat.forward(z)
+        packed = simulator._pack_partial(self.pack_bij.forward(x))  # missing groups filled; torch.stack keeps the graph
+        ll, chi2 = _ShearFn.apply(packed, self.catalogue, simulator)
+        n_shear = 2.0 * self.catalogue.n
+        if self.strong is None:
+            log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+            return ll + log_prior, chi2 / n_shear
+        lp_strong, red_strong = self.strong.log_prob(simulator, z)  # (carries the prior)
+        n_strong = float(self.strong._n_eff(simulator))
+        return ll + lp_strong, (chi2 + red_strong * n_strong) / (n_shear + n_strong)
+
+    def log_prob_and_grad(self, simulator, z, graph=False):
+        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
+        lp, red = self.log_prob(simulator, zz)
+        (g,) = torch.autograd.grad(lp.sum(), zz)
+        return lp.detach(), red.detach(), g
+
+    def log_prior(self, z):
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
+
+    def init_centroids(self, bs):
+        return None

@@ -304,6 +304,47 @@ class LensSimulator(LensSimulatorInterface):
             cot_x, cot_y = cs * cot_x, cs * cot_y
         return self._model.lens_maps_vjp(packed, x, y, cot_x, cot_y)
 
+    def hessian_vjp(self, x, y, lens_params, cot_xx, cot_xy, cot_yx, cot_yy, deflection_scale=1.0):
+        """The VJP of the summed Hessian ``f_xx, f_xy, f_yx, f_yy`` of the lens maps (what ``convergence``, ``shear`` and
+        ``magnification`` are made of) with respect to the lens parameters (beyond the reference, whose tape does this): the four
+        cotangents at ``(x, y)`` (point layout as the lens maps: broadcastable to ``(..., B)``) -> the gradient ``[B, P]`` in packed
+        order, zero outside the lens-mass columns.  The Hessian of a plane at ``c = deflection_scale`` is ``c H``, so the
+        cotangents are scaled by ``c``.  A point whose four cotangents are all exactly 0, or one of which is not finite, is
+        skipped (its lens is never evaluated).  Deterministic.  ``UnsupportedLensError``: lens planes, series and user-written
+        lenses."""
+        self._single_plane("hessian_vjp")
+        cs = self._scale(deflection_scale)
+        packed = self._pack_partial({"lens_mass": lens_params}) if not torch.is_tensor(lens_params) else lens_params
+        cots = [torch.as_tensor(c, dtype=torch.float32, device=self.device) for c in (cot_xx, cot_xy, cot_yx, cot_yy)]
+        if cs != 1.0:
+            cots = [cs * c for c in cots]
+        return self._model.lens_hessian_vjp(packed, x, y, *cots)
+
+    def reduced_shear(self, x, y, lens_params, deflection_scale=1.0):
+        """Reduced shear ``(g1, g2)`` as a weak-lensing ellipticity estimates it (beyond the reference): ``g = gamma / (1 - kappa)``
+        from ``shear`` and ``convergence`` where ``|g| <= 1``, and ``1 / g* = g / |g|^2`` where ``|g| > 1`` (continuous at
+        ``|g| = 1``).  Forward only."""
+        fxx, fxy, _, fyy = self._hessian(x, y, lens_params, deflection_scale)
+        omk = 1.0 - 0.5 * (fxx + fyy)
+        g1, g2 = 0.5 * (fxx - fyy) / omk, fxy / omk
+        n2 = g1 * g1 + g2 * g2
+        weak = n2 <= 1.0
+        return torch.where(weak, g1, g1 / n2), torch.where(weak, g2, g2 / n2)
+
+    def shear_log_like_and_grad(self, lens_params, catalogue, want_grad=True):
+        """The weak-lensing likelihood of a ``model.ShearCatalogue`` (beyond the reference): with the reduced shear ``g^`` of
+        ``reduced_shear`` at every galaxy, on the plane of the galaxy's own deflection scale,
+        ``chi2 = sum [(e1 - g^1)^2 + (e2 - g^2)^2] / sigma^2`` and ``log_like = -1/2 (chi2 + 2 sum log(2 pi sigma^2))``.  Returns
+        ``dict(log_like [B], chi2 [B], model_g [2, N, B], grad)``: ``grad`` is ``d log_like / d`` packed rows ``[B, P]`` (zero outside
+        the lens-mass columns) through the kernels of ``hessian_vjp``, or None without ``want_grad``.  Deterministic; no host
+        synchronisation.  ``UnsupportedLensError``: lens planes, series and user-written lenses."""
+        self._single_plane("shear_log_like_and_grad")
+        packed = self._lens_rows(lens_params)
+        tabs = catalogue.device_tables(self.device)
+        ll, chi2, model_g, grad = self._model.shear_loglike(packed.detach(), tabs["x"], tabs["y"], tabs["e1"], tabs["e2"], tabs["sigma"],
+                                                            scales=tabs["scales"], want_grad=want_grad)
+        return dict(log_like=ll, chi2=chi2, model_g=model_g, grad=grad)
+
     def _hessian(self, x, y, lens_params, deflection_scale):
         """``f_xx, f_xy, f_yx, f_yy`` of ``_lens_maps`` on the plane of ``deflection_scale`` (linear in it: ``c H``).  With lens
         planes: ``I - A_t`` of the target plane, which is not symmetric."""

@@ -395,6 +395,33 @@ size_t gl_lens_maps_vjp_workspace_bytes(const gl_model* m, int B, int64_t n_pts)
 int gl_lens_maps_vjp(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
                      const float* cot, float* grad_params, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* The VJP of gl_lens_maps' summed Hessian with respect to the lens parameters (beyond the reference): cot [4][n_pts][B] = the
+ * cotangents on f_xx, f_xy, f_yx, f_yy (DEVICE), x, y as in gl_lens_maps_vjp;
+ *   grad_params[b][p_off + k] = sum_pt ( cot_xx d f_xx / d p_k + cot_xy d f_xy / d p_k + cot_yx d f_yx / d p_k + cot_yy d f_yy / d p_k ),
+ * [B][P], DEVICE, columns that belong to no lens written as 0; f includes the dPIS convergence excess on f_xx and f_yy, as
+ * gl_lens_maps returns it.  A point whose four cotangents are all exactly 0, or one of whose cotangents is not finite, is skipped
+ * and its lens never evaluated.  Sum order, determinism, batch independence, the lenses served, the refusals, the error codes and
+ * the workspace size are those of gl_lens_maps_vjp.  No host synchronisation, no allocation. */
+size_t gl_lens_hessian_vjp_workspace_bytes(const gl_model* m, int B, int64_t n_pts);
+int gl_lens_hessian_vjp(const gl_model* m, const float* params, int B, const float* x, const float* y, int64_t n_pts, int xy_batched,
+                        const float* cot, float* grad_params, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* Weak-lensing reduced-shear likelihood of a catalogue of n_gal background galaxies (beyond the reference).  x, y, e1, e2, sigma
+ * and scale_or_null: [n_gal], DEVICE -- positions (arcsec), measured ellipticity components, their error per component (> 0) and
+ * the deflection scale c of every galaxy's own redshift (NULL: every scale 1).  With f the Hessian of gl_lens_maps,
+ *   kappa = c (f_xx + f_yy)/2, gamma1 = c (f_xx - f_yy)/2, gamma2 = c f_xy, g = (gamma1 + i gamma2)/(1 - kappa),
+ *   g^ = g where |g|^2 <= 1, g/|g|^2 (= 1/g*) otherwise,
+ *   chi2[b] = sum_i [(e1_i - g^1_i)^2 + (e2_i - g^2_i)^2]/sigma_i^2,   ll[b] = -1/2 (chi2[b] + 2 sum_i log(2 pi sigma_i^2)).
+ * model_g_or_null [2][n_gal][B] receives g^; grad_params_or_null [B][P] receives d ll / d params through gl_lens_hessian_vjp's
+ * kernels (columns of no lens 0).  Every sum has a fixed order: two calls give identical bits and a sample does not depend on the
+ * others.  Refusals and error codes as gl_lens_hessian_vjp (GL_EINVAL: a null x, y, e1, e2, sigma, ll, chi2 or workspace, sizes
+ * <= 0; GL_ENOMEM: a workspace under gl_shear_loglike_workspace_bytes(m, B, n_gal, want_grad), which is 0 for a null model or
+ * sizes <= 0; want_grad = whether grad_params_or_null is given).  No host synchronisation, no allocation. */
+size_t gl_shear_loglike_workspace_bytes(const gl_model* m, int B, int n_gal, int want_grad);
+int gl_shear_loglike(const gl_model* m, const float* params, int B, const float* x, const float* y, const float* scale_or_null,
+                     const float* e1, const float* e2, const float* sigma, int n_gal, float* ll, float* chi2, float* model_g_or_null,
+                     float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Lens planes at redshifts of their own: multi-plane ray tracing (beyond the reference, which bends every ray at one plane).
  * Planes are numbered 0 .. n_planes - 1 by ascending redshift; every lens keeps its parameters as the reduced deflection for the
  * model's reference plane.  With theta_0 = theta the ray meets plane j at
