@@ -30,7 +30,8 @@ __global__ void __launch_bounds__(256) gl_adam_kernel(float* __restrict__ x, con
     const float vi = v[i] * b2 + (g * g) * (1.0f - b2);
     m[i] = mi;
     v[i] = vi;
-    x[i] -= lr * (mi / c1) / (sqrtf(vi / c2) + eps);
+    const float upd = lr * (mi / c1) / (sqrtf(vi / c2) + eps);
+    if (upd != 0.f) x[i] -= upd;  // a zero update (lr == 0) leaves the bits of x alone: -0.0f - (-0.0f) is +0.0f; a NaN still lands
   }
   if (t_dev) {  // advance the device counter once per launch, after the last reader
     __syncthreads();

@@ -510,8 +510,9 @@ class ModellingSequence:
         step-size scalings follow ``simple_heuristic_tuning(optimal_accept=0.651)``.  ``num_ensembles`` independent
         populations run side by side.  Returns ``(samples, info)``; with ``post_sampling_steps > 0`` the samples are
         the HMC chain continued at ``beta = 1`` (:270-281), shape ``(steps, particles * ensembles, d)``.
-        The stochastic driver cannot be pinned bit-for-bit against TFP (different random streams): tests check the
-        evidence and posterior moments on a conjugate toy problem and against HMC.
+        The stochastic driver cannot be pinned bit-for-bit against TFP (different random streams):
+        ``tests/test_inference_host.py::test_smc_evidence_and_posterior_on_a_conjugate_problem`` checks the evidence and the
+        posterior moments where both are known in closed form.
         """
         del ess_threshold_ratio  # as in the reference (:243 passes 0.8)
         pm = self.prob_model
