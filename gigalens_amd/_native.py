@@ -119,6 +119,9 @@ SYMBOLS = {
     "gl_shear_loglike_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "gl_shear_loglike": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gl_imgplane_loglike_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "gl_imgplane_loglike": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_void_p, c_float,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_model_set_lens_planes": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_float), POINTER(c_float), c_int]),
     "gl_multiplane_maps": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, POINTER(c_float), c_int, c_void_p,
                                    c_void_p]),
@@ -799,6 +802,38 @@ class Model:
                                                 _ptr(tabs[4]), _ptr(tabs[5]), n_gal, _ptr(ll), _ptr(chi2), _ptr(model), _ptr(grad),
                                                 _ptr(ws), ws.numel(), _stream()))
         return ll, chi2, model, grad
+
+    def imgplane_loglike(self, params, image_table, family_table, family_offsets, source=None, tol=1e-6, max_iter=30, want_grad=True):
+        """gl_imgplane_loglike: the image-plane position likelihood of the families whose tables are ``image_table`` (float32
+        ``[5, J]`` device: x, y, sigma, cap, scale), ``family_table`` (int32 ``[3, J]`` device: family, first image, count) and
+        ``family_offsets`` (int32 ``[F + 1]`` host); ``source`` None (the barycentre of every family) or ``[2, B, F]``.  Returns
+        ``(log_like [B], chi2 [B], n_lost [B] int32, predicted [2, J, B], grad [B, P] or None, grad_source [2, B, F] or None)``.
+        ``UnsupportedLensError`` as ``lens_maps_vjp``."""
+        self._single_plane("imgplane_loglike")
+        params = self._params(params)
+        B = params.shape[0]
+        off = np.ascontiguousarray(family_offsets, dtype=np.int32)
+        J, F = int(image_table.shape[1]), int(off.size) - 1
+        if tuple(image_table.shape) != (5, J) or tuple(family_table.shape) != (3, J) or image_table.dtype != torch.float32 or \
+                family_table.dtype != torch.int32 or F < 1:
+            raise ValueError("imgplane_loglike: image_table is float32 [5, J], family_table int32 [3, J], family_offsets [F + 1]")
+        if source is not None:
+            source = torch.as_tensor(source, dtype=torch.float32, device=self.device).contiguous()
+            if tuple(source.shape) != (2, B, F):
+                raise ValueError(f"imgplane_loglike: source has shape {tuple(source.shape)}, expected {(2, B, F)}")
+        ll = torch.empty(B, dtype=torch.float32, device=self.device)
+        chi2 = torch.empty(B, dtype=torch.float32, device=self.device)
+        n_lost = torch.empty(B, dtype=torch.int32, device=self.device)
+        pred = torch.empty((2, J, B), dtype=torch.float32, device=self.device)
+        grad = torch.empty((B, self.P), dtype=torch.float32, device=self.device) if want_grad else None
+        grad_src = torch.empty((2, B, F), dtype=torch.float32, device=self.device) if want_grad and source is not None else None
+        ws = self._scratch("imgplane_loglike", lib().gl_imgplane_loglike_workspace_bytes(self._h, B, J, 0 if source is None else 1,
+                                                                                        1 if want_grad else 0))
+        _check_potential(lib().gl_imgplane_loglike(self._h, _ptr(params), B, _ptr(image_table.contiguous()), _ptr(family_table.contiguous()),
+                                                   off.ctypes.data_as(POINTER(c_int32)), J, F, _ptr(source), float(tol), int(max_iter),
+                                                   _ptr(ll), _ptr(chi2), _ptr(n_lost), _ptr(pred), _ptr(grad), _ptr(grad_src), _ptr(ws),
+                                                   ws.numel(), _stream()))
+        return ll, chi2, n_lost, pred, grad, grad_src
 
     def lens_potential(self, params, x, y):
         """gl_lens_potential: ``x, y`` broadcastable to ``(..., B)`` (or both None: the model's own grid, ``(N, B)``); returns psi."""

@@ -1,6 +1,7 @@
 // gl_api_points.hip -- the entry points of the point family: everything that evaluates the lenses of a model (or one free-standing
 // profile) at points through gl_positions.hip.h -- image-position likelihood, lens maps, Hessians, potential, the lens-equation
-// solver, critical curves, the Hessian VJP with the weak-lensing shear likelihood, and the lens planes (maps, render and its VJP).
+// solver, critical curves, the Hessian VJP with the weak-lensing shear likelihood, the image-plane position likelihood, and the lens
+// planes (maps, render and its VJP).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -18,6 +19,7 @@
 #include "gl_multiplane_pos.hip.h"
 #include "gl_lens_vjp.hip.h"
 #include "gl_hessian_vjp.hip.h"
+#include "gl_imgplane.hip.h"
 
 using namespace glk;
 
@@ -527,6 +529,103 @@ int gl_shear_loglike(const gl_model* m, const float* params, int B, const float*
   hipLaunchKernelGGL(gl_shear_sum_kernel, dim3((unsigned)B), dim3(VJP_WG), 0, stream, (const float*)s.part, s.n_blocks, ll, chi2);
   if (want_grad)
     launch_hessian_vjp(m, params, B, x, y, (long long)n_gal, 0, s.cot, grad_params_or_null, (float*)(base + lay.vjp), lay.n_blocks, stream);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- image-plane position likelihood of image families (gl_imgplane.hip.h) ------------------------------------------
+namespace {
+// the parts of the workspace: the point list [2][n_pts][B], u [2][J][B], chi2_j and the lost flags [J][B], the cotangents
+// [2][n_pts][B] and the partials of the ray-shoot VJP (the last two with a gradient only)
+struct ImgPlaneLayout { size_t pts, u, chi2_j, lost, cot, vjp, bytes; long long n_pts, n_blocks; };
+bool imgplane_layout(const gl_model* m, int B, int J, bool with_source, bool want_grad, ImgPlaneLayout* l) {
+  if (!m || B <= 0 || J <= 0) return false;
+  l->n_pts = with_source ? (long long)J : 2LL * J;
+  if ((l->n_pts * B + VJP_WG - 1) / VJP_WG > 0x7fffffffLL) return false;
+  const size_t JB = (size_t)J * (size_t)B, NB = (size_t)l->n_pts * (size_t)B;
+  l->pts = 0;
+  l->u = l->pts + align_up(2 * NB * sizeof(float), 256);
+  l->chi2_j = l->u + align_up(2 * JB * sizeof(float), 256);
+  l->lost = l->chi2_j + align_up(JB * sizeof(float), 256);
+  l->cot = l->lost + align_up(JB * sizeof(int), 256);
+  l->vjp = l->cot;
+  l->bytes = l->cot;
+  l->n_blocks = 0;
+  if (want_grad) {
+    l->n_blocks = vjp_blocks(m, B, l->n_pts);
+    if (!l->n_blocks) return false;
+    l->vjp = l->cot + align_up(2 * NB * sizeof(float), 256);
+    l->bytes = l->vjp + gl_lens_maps_vjp_workspace_bytes(m, B, l->n_pts);
+  }
+  return true;
+}
+}  // namespace
+
+size_t gl_imgplane_loglike_workspace_bytes(const gl_model* m, int B, int n_images, int with_source, int want_grad) {
+  ImgPlaneLayout lay;
+  return imgplane_layout(m, B, n_images, with_source != 0, want_grad != 0, &lay) ? lay.bytes : 0;
+}
+
+int gl_imgplane_loglike(const gl_model* m, const float* params, int B, const float* image_table, const int32_t* family_table,
+                        const int32_t* family_offsets_host, int n_images, int n_families, const float* source_or_null, float tol,
+                        int max_iter, float* ll, float* chi2, int32_t* n_lost, float* pred_or_null, float* grad_params_or_null,
+                        float* grad_source_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !image_table || !family_table || !family_offsets_host || !ll || !chi2 || !n_lost || !workspace)
+    return fail(GL_EINVAL, "null argument");
+  const int J = n_images, F = n_families;
+  if (B <= 0 || J <= 0 || F <= 0) return fail(GL_EINVAL, "B, n_images and n_families must be positive");
+  if (grad_source_or_null && !source_or_null) return fail(GL_EINVAL, "grad_source without explicit sources");
+  if (family_offsets_host[0] != 0 || family_offsets_host[F] != J)
+    return fail(GL_EINVAL, "family offsets run from %d to %d for %d image(s)", family_offsets_host[0], family_offsets_host[F], J);
+  for (int f = 0; f < F; ++f) {
+    const int n = family_offsets_host[f + 1] - family_offsets_host[f];
+    if (n < 1) return fail(GL_EINVAL, "image family %d holds no image", f);
+    if (n > IMGP_MAX_FAMILY) return fail(GL_EINVAL, "image family %d holds %d images: at most %d", f, n, IMGP_MAX_FAMILY);
+    if (n == 1 && !source_or_null)
+      return fail(GL_EINVAL, "image family %d holds one image: the barycentre source takes two or more (or give the sources)", f);
+  }
+  if (!(tol > 0.f) || max_iter < 1) return fail(GL_EINVAL, "tol must be > 0 and max_iter >= 1 (got %g, %d)", tol, max_iter);
+  if (int rc = refuse_vjp_lenses(m, "gl_imgplane_loglike", "the image-plane position likelihood")) return rc;
+  if (int rc = check_ready(m, false, false)) return rc;
+  const bool want_grad = grad_params_or_null != nullptr;
+  ImgPlaneLayout lay;
+  if (!imgplane_layout(m, B, J, source_or_null != nullptr, want_grad, &lay)) return fail(GL_EINVAL, "too many images x samples for one call");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  char* base = (char*)workspace;
+  ImgPlaneArgs g{};
+  g.tab = image_table;
+  g.fam = family_table;
+  g.source = source_or_null;
+  g.J = J;
+  g.F = F;
+  g.max_iter = max_iter;
+  g.tol = tol;
+  g.pts = (float*)(base + lay.pts);
+  g.u = (float*)(base + lay.u);
+  g.chi2_j = (float*)(base + lay.chi2_j);
+  g.lost = (int*)(base + lay.lost);
+  g.cot = want_grad ? (float*)(base + lay.cot) : nullptr;
+  g.n_pts = lay.n_pts;
+  const PosArgs a = point_args(m, params, B);
+  const size_t JB = (size_t)J * (size_t)B, NB = (size_t)lay.n_pts * (size_t)B;
+  const dim3 newton_grid((unsigned)((JB + VJP_WG - 1) / VJP_WG));
+  hipLaunchKernelGGL(gl_imgp_newton_kernel, newton_grid, dim3(VJP_WG), 0, stream, a, g);
+  hipLaunchKernelGGL(gl_imgp_sum_kernel, dim3((unsigned)B), dim3(VJP_WG), 0, stream, g, B, ll, chi2, (int*)n_lost, grad_source_or_null);
+  if (pred_or_null) {  // [2][J][B]: the first J points of the list, x then y
+    GL_HIP(hipMemcpyAsync(pred_or_null, g.pts, JB * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    GL_HIP(hipMemcpyAsync(pred_or_null + JB, g.pts + NB, JB * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  }
+  if (want_grad) {
+    hipLaunchKernelGGL(gl_imgp_cot_kernel, dim3((unsigned)((NB + VJP_WG - 1) / VJP_WG)), dim3(VJP_WG), 0, stream, g, B);
+    float* partial = (float*)(base + lay.vjp);
+    if (m->lens_params)
+      hipLaunchKernelGGL(gl_lens_vjp_kernel, dim3((unsigned)((long long)B * m->lens_params * lay.n_blocks)), dim3(VJP_WG), 0, stream, a,
+                         (const float*)g.pts, (const float*)(g.pts + NB), lay.n_pts, 1, (const float*)g.cot, m->lens_params,
+                         (int)lay.n_blocks, partial);
+    hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
+                       m->P, m->lens_params, (int)lay.n_blocks, grad_params_or_null);
+  }
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

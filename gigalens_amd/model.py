@@ -1249,3 +1249,188 @@ class WeakLensingProbModel(ProbabilisticModel):
 
     def init_centroids(self, bs):
         return None
+
+
+class ImageFamilies:
+    """The image families of ``ImagePlaneProbModel`` and ``LensSimulator.image_plane_log_like_and_grad``: ``x, y`` are lists with one
+    array of observed image positions (arcsec) per family, shaped like ``centroids_x / centroids_y`` of ``ForwardProbModel``;
+    ``sigma`` the isotropic position error -- a scalar, one value per family, or one array per family; ``scales`` one deflection
+    scale per family (``gigalens_amd.cosmology.deflection_scale``; default 1: the model's reference plane).
+
+    ``max_shift``: the cap of every image -- the furthest its predicted image may lie from it, and the longest Newton step towards it.
+    Default: half the distance to the nearest sibling of its family (float64 on the host, stored as float32), so the balls of two
+    siblings at most touch and two observed images never claim the same predicted one.  A scalar, or one array per family (a flat
+    array over all images is taken too), overrides it; a family of one image needs it.
+
+    Everything is held concatenated family by family as float32 ``[J]``.  ``ValueError``: a shape mismatch, an entry that is not
+    finite, a ``sigma``, scale or ``max_shift`` that is not finite and > 0, two coincident images in a family, a family of more than
+    64 images, a family of one image without ``max_shift``."""
+
+    MAX_FAMILY = 64
+
+    def __init__(self, x, y, sigma, scales=None, max_shift=None):
+        if isinstance(x, np.ndarray) and x.ndim == 1 or not len(x):
+            raise ValueError("ImageFamilies: x and y are lists with one array per family")
+        xs = [np.atleast_1d(np.asarray(v, dtype=np.float32)) for v in x]
+        ys = [np.atleast_1d(np.asarray(v, dtype=np.float32)) for v in y]
+        if len(ys) != len(xs):
+            raise ValueError(f"ImageFamilies: {len(xs)} families in x, {len(ys)} in y")
+        F = len(xs)
+        for f, (a, b) in enumerate(zip(xs, ys)):
+            if a.ndim != 1 or a.size == 0 or a.shape != b.shape:
+                raise ValueError(f"ImageFamilies: family {f}: x has shape {tuple(a.shape)}, y has {tuple(b.shape)}")
+            if a.size > self.MAX_FAMILY:
+                raise ValueError(f"ImageFamilies: family {f} holds {a.size} images: at most {self.MAX_FAMILY}")
+            if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b))):
+                raise ValueError(f"ImageFamilies: family {f} holds a position that is not finite")
+        counts = np.array([a.size for a in xs], dtype=np.int32)
+        J = int(counts.sum())
+
+        def per_image(name, v):
+            """A scalar, one value per family or one array per family (or a flat ``[J]`` array) as float32 ``[J]``, finite and > 0."""
+            if isinstance(v, (list, tuple)) and len(v) == F and any(np.ndim(e) > 0 for e in v):
+                parts = [np.asarray(e, dtype=np.float32) for e in v]
+                for f, e in enumerate(parts):
+                    if e.ndim > 1 or (e.ndim == 1 and e.size not in (1, counts[f])):
+                        raise ValueError(f"ImageFamilies: {name} of family {f} has shape {tuple(e.shape)}: a scalar or {(int(counts[f]),)}")
+                out = np.concatenate([np.broadcast_to(e.reshape(-1) if e.ndim else e, (counts[f],)) for f, e in enumerate(parts)])
+            else:
+                a = np.asarray(v, dtype=np.float32)
+                if a.ndim == 0:
+                    out = np.full(J, a, dtype=np.float32)
+                elif a.ndim == 1 and a.size == F:
+                    out = np.repeat(a, counts)
+                elif a.ndim == 1 and a.size == J:
+                    out = a.copy()
+                else:
+                    raise ValueError(f"ImageFamilies: {name} has shape {tuple(a.shape)}: a scalar, one value per family ({F}) or one "
+                                     f"array per family")
+            out = np.ascontiguousarray(out, dtype=np.float32)
+            if not (np.all(np.isfinite(out)) and np.all(out > 0)):
+                raise ValueError(f"ImageFamilies: every entry of {name} must be finite and > 0")
+            return out
+
+        self.F, self.J = F, J
+        self.counts = counts
+        self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        self.x, self.y = np.concatenate(xs), np.concatenate(ys)
+        self.sigma = per_image("sigma", sigma)
+        self.family_scales = _native.deflection_scales(scales, F, "ImageFamilies: scales")
+        self.scales = np.repeat(self.family_scales, counts).astype(np.float32)
+        half = np.full(J, np.inf)
+        for f in range(F):
+            a, b = xs[f].astype(np.float64), ys[f].astype(np.float64)
+            if a.size < 2:
+                continue
+            d = np.hypot(a[:, None] - a[None, :], b[:, None] - b[None, :])
+            np.fill_diagonal(d, np.inf)
+            if not d.min() > 0:
+                raise ValueError(f"ImageFamilies: family {f} holds two coincident images")
+            half[self.offsets[f]:self.offsets[f + 1]] = 0.5 * d.min(axis=1)
+        if max_shift is None:
+            if counts.min() < 2:
+                raise ValueError(f"ImageFamilies: family {int(np.argmin(counts))} holds one image: it has no sibling to take the "
+                                 f"default max_shift from, give max_shift")
+            self.max_shift = half.astype(np.float32)
+        else:
+            self.max_shift = per_image("max_shift", max_shift)
+        self.min_count = int(counts.min())
+        self.max_coordinate = float(max(np.abs(self.x).max(), np.abs(self.y).max()))
+        self.norm = float(np.log(2.0 * np.pi * self.sigma.astype(np.float64) ** 2).sum())
+        self._dev = {}
+
+    def __len__(self):
+        return self.J
+
+    def device_tables(self, device):
+        """The static per-image tables as device tensors (uploaded once per device): ``image`` float32 ``[5, J]`` = x, y, sigma,
+        max_shift, scale; ``family`` int32 ``[3, J]`` = family, first image and count of the family of every image."""
+        key = str(device)
+        if key not in self._dev:
+            fam = np.repeat(np.arange(self.F, dtype=np.int32), self.counts)
+            image = np.stack([self.x, self.y, self.sigma, self.max_shift, self.scales]).astype(np.float32)
+            family = np.stack([fam, self.offsets[:-1][fam], self.counts[fam]]).astype(np.int32)
+            self._dev[key] = {"image": torch.as_tensor(image, device=device).contiguous(),
+                              "family": torch.as_tensor(family, device=device).contiguous()}
+        return self._dev[key]
+
+
+class _ImagePlaneFn(torch.autograd.Function):
+    """log-likelihood of the image-plane positions (``LensSimulator.image_plane_log_like_and_grad``) with its hand-written gradient
+    with respect to the packed rows."""
+
+    @staticmethod
+    def forward(ctx, packed, families, simulator):
+        res = simulator.image_plane_log_like_and_grad(packed.detach(), families, want_grad=True)
+        ctx.save_for_backward(res["grad"])
+        ctx.mark_non_differentiable(res["chi2"], res["n_lost"])
+        return res["log_like"], res["chi2"], res["n_lost"]
+
+    @staticmethod
+    def backward(ctx, g_ll, g_chi2, g_lost):
+        (grad,) = ctx.saved_tensors
+        return g_ll[:, None] * grad, None, None
+
+
+class ImagePlaneProbModel(ProbabilisticModel):
+    """The image-plane position likelihood of ``ImageFamilies`` as the target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the
+    reference): ``log_prob = log_like + log_prior`` of ``LensSimulator.image_plane_log_like_and_grad`` with the barycentre source
+    of every family and its hand-written gradient -- the stage after a source-plane fit (``ForwardProbModel``'s position term is its
+    linearisation at the observed positions), started from that fit's samples.  A sample with a lost image keeps a finite
+    ``log_prob``: the image sits at its cap and adds nothing to the gradient.  The prior is over ``lens_mass`` (groups the physical
+    model has beside it are packed from the prior when it carries them).
+
+    ``strong``: a ``ForwardProbModel`` over the SAME prior -- pixels, flux ratios, time delays, source-plane positions -- whose
+    ``log_prob`` is added; the prior is counted once (inside ``strong``'s term).  The reduced chi^2 is then
+    ``(chi2 + red_strong n_strong) / (2 J + n_strong)`` with ``n_strong = strong._n_eff(simulator)``; without ``strong`` it is
+    ``chi2 / (2 J)``.  Lenses ``beta_vjp`` refuses stay refused with their error.  Runs on the stream path (``MAP(graph=True)``
+    falls back to it)."""
+
+    def __init__(self, prior, families, strong=None):
+        super().__init__(prior)
+        if not isinstance(families, ImageFamilies):
+            raise TypeError("families must be an ImageFamilies")
+        if families.min_count < 2:
+            raise ValueError("ImagePlaneProbModel takes the barycentre source of every family: two or more images per family")
+        if strong is not None and not isinstance(strong, ForwardProbModel):
+            raise TypeError("strong must be a ForwardProbModel over the same prior")
+        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
+        self.families, self.strong = families, strong
+        # what ModellingSequence sizes its loss with: the 2 J image coordinates count with the point terms
+        self.include_pixels = bool(strong is not None and strong.include_pixels)
+        self.include_positions = True
+        self.n_position = 2.0 * families.J
+        if strong is not None and strong.include_positions:
+            self.n_position += strong.n_position + getattr(strong, "n_flux", 0.0) + getattr(strong, "n_delay", 0.0)
+        self._flat = prior.flat(self.device)
+        example = prior.sample(seed=0)
+        self.pack_bij = _PackBijector(example)
+        self.unconstraining_bij = _prior.JointBijector(self._flat)
+        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+
+    def log_prob(self, simulator, z):
+        """``(log_like + log_prior [+ strong's log_like], reduced chi^2)``; differentiable with respect to ``z``."""
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        x = self._flat.forward(z)
+        packed = simulator._pack_partial(self.pack_bij.forward(x))  # missing groups filled; torch.stack keeps the graph
+        ll, chi2, _ = _ImagePlaneFn.apply(packed, self.families, simulator)
+        n_img = 2.0 * self.families.J
+        if self.strong is None:
+            log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+            return ll + log_prior, chi2 / n_img
+        lp_strong, red_strong = self.strong.log_prob(simulator, z)  # (carries the prior)
+        n_strong = float(self.strong._n_eff(simulator))
+        return ll + lp_strong, (chi2 + red_strong * n_strong) / (n_img + n_strong)
+
+    def log_prob_and_grad(self, simulator, z, graph=False):
+        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
+        lp, red = self.log_prob(simulator, zz)
+        (g,) = torch.autograd.grad(lp.sum(), zz)
+        return lp.detach(), red.detach(), g
+
+    def log_prior(self, z):
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
+
+    def init_centroids(self, bs):
+        return None

@@ -345,6 +345,50 @@ class LensSimulator(LensSimulatorInterface):
                                                             scales=tabs["scales"], want_grad=want_grad)
         return dict(log_like=ll, chi2=chi2, model_g=model_g, grad=grad)
 
+    def image_plane_log_like_and_grad(self, lens_params, families, *, source_x=None, source_y=None, tol=None, max_iter=30,
+                                      want_grad=True):
+        """The image-plane position likelihood of a ``model.ImageFamilies`` (beyond the reference, whose position term is the
+        source-plane linearisation; the refinement stage after a source-plane fit).  The source of family f is ``source_x/_y``
+        ``[B, F]`` or, by default, the barycentre of its back-traced observed images (the source ``predicted_positions`` solves
+        for; two or more images per family).  The predicted image of observed image j is the root of ``beta(theta) = beta_f`` that
+        Newton reaches from ``theta_obs_j`` (the iteration of ``image_positions``; ``tol`` defaults to ``IMAGE_TOL_EPS eps32 max
+        |coordinate|``), every step at most ``cap_j = families.max_shift[j]`` long.  It is LOST when Newton has not converged after
+        ``max_iter`` steps, the point is not finite, it lies further than ``cap_j`` from ``theta_obs_j``, or the Jacobian of ``beta`` is singular there.
+        ``chi2 = sum_j min(|theta_pred_j - theta_obs_j|^2, cap_j^2) / sigma_j^2`` (a lost image sits at the cap) and
+        ``log_like = -chi2 / 2 - sum_j log(2 pi sigma_j^2)``: finite for every sample.
+
+        Returns ``dict(log_like [B], chi2 [B], n_lost [B], predicted_x, predicted_y [B, J] (NaN where lost), lost [B, J], grad,
+        grad_source_x, grad_source_y)``: ``grad`` is ``d log_like / d`` packed rows ``[B, P]`` (zero outside the lens-mass columns) by
+        the implicit function theorem through the kernels of ``beta_vjp`` -- exact, a lost image contributes nothing -- and
+        ``grad_source_x/_y`` ``[B, F]`` the gradient on explicit sources; None without ``want_grad`` (or without sources).
+        Deterministic; no host synchronisation.  ``UnsupportedLensError``: lens planes, series and user-written lenses;
+        ``NotImplementedError``: an input that requires a gradient (wrap the entry as ``model.ImagePlaneProbModel`` does)."""
+        self._single_plane("image_plane_log_like_and_grad")
+        packed = self._lens_rows(lens_params)
+        if any(torch.is_tensor(t) and t.requires_grad for t in (packed, source_x, source_y)):
+            raise NotImplementedError("image_plane_log_like_and_grad carries no autograd graph: its gradient is the returned grad")
+        B = int(packed.shape[0])
+        if (source_x is None) != (source_y is None):
+            raise ValueError("source_x and source_y must both be given or both be None")
+        source = None
+        if source_x is None:
+            if families.min_count < 2:
+                raise ValueError("a family of one image has no barycentre source: give source_x / source_y")
+        else:
+            sx, sy = (torch.as_tensor(s, dtype=torch.float32, device=self.device) for s in (source_x, source_y))
+            if tuple(sx.shape) != (B, families.F) or tuple(sy.shape) != (B, families.F):
+                raise ValueError(f"source_x / source_y must have shape {(B, families.F)}, got {tuple(sx.shape)} and {tuple(sy.shape)}")
+            source = torch.stack([sx, sy])
+        if tol is None:
+            tol = self.IMAGE_TOL_EPS * float(np.finfo(np.float32).eps) * families.max_coordinate
+        tabs = families.device_tables(self.device)
+        ll, chi2, n_lost, pred, grad, grad_src = self._model.imgplane_loglike(packed, tabs["image"], tabs["family"], families.offsets,
+                                                                              source=source, tol=tol, max_iter=max_iter,
+                                                                              want_grad=want_grad)
+        px, py = pred[0].t(), pred[1].t()
+        return dict(log_like=ll, chi2=chi2, n_lost=n_lost, predicted_x=px, predicted_y=py, lost=torch.isnan(px), grad=grad,
+                    grad_source_x=None if grad_src is None else grad_src[0], grad_source_y=None if grad_src is None else grad_src[1])
+
     def _hessian(self, x, y, lens_params, deflection_scale):
         """``f_xx, f_xy, f_yx, f_yy`` of ``_lens_maps`` on the plane of ``deflection_scale`` (linear in it: ``c H``).  With lens
         planes: ``I - A_t`` of the target plane, which is not symmetric."""

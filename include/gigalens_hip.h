@@ -422,6 +422,37 @@ int gl_shear_loglike(const gl_model* m, const float* params, int B, const float*
                      const float* e1, const float* e2, const float* sigma, int n_gal, float* ll, float* chi2, float* model_g_or_null,
                      float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Image-plane position likelihood of image families with its exact gradient (beyond the reference, whose position term is the
+ * source-plane linearisation).  The n_images observed images of the n_families families are concatenated family by family:
+ *   image_table  [5][n_images] DEVICE: x, y (arcsec), the isotropic error sigma (> 0), the cap (> 0) and the deflection scale c of
+ *                the image's family (beta = theta - c sum alpha, A = I - c H, H the Hessian of gl_lens_maps);
+ *   family_table [3][n_images] DEVICE: family, first image and image count of the family of every image;
+ *   family_offsets_host [n_families + 1] HOST: the first image of every family, then n_images (read by the call's checks only);
+ *   source_or_null [2][B][n_families] DEVICE: the source of every family, x then y; NULL: the barycentre of the family's back-traced
+ *                observed images, (1/J_f) sum_k beta(theta_obs_k), which needs two or more images in every family.
+ * The predicted image of observed image j is the root of beta(theta) = beta_f that Newton reaches from theta_obs_j (the iteration
+ * of gl_image_positions with its polishing step, tol and max_iter as there, every step at most cap_j long).  It is LOST when
+ * Newton has not converged, the point is not finite, |theta_pred - theta_obs_j| > cap_j or u_j below is not finite.  With
+ * r_j = theta_pred_j - theta_obs_j,
+ *   chi2[b] = sum_j min(|r_j|^2, cap_j^2)/sigma_j^2 (a lost image sits at the cap),  ll[b] = -chi2[b]/2 - sum_j log(2 pi sigma_j^2),
+ * n_lost[b] the lost images of sample b; pred_or_null [2][n_images][B] receives theta_pred, x then y, NaN where lost.
+ * Gradient by the implicit function theorem, u_j = J(theta_pred_j)^-T r_j / sigma_j^2 (0 where lost), J = I - c d alpha / d theta the
+ * derivative of the deflection alone (A steers the Newton steps; the dPIS convergence excess in H belongs to no deflection):
+ *   d ll / d p = sum_j u_j . d beta / d p at theta_pred_j - (sum_{j in f} u_j) . d beta_f / d p
+ * into grad_params_or_null [B][P] through gl_lens_maps_vjp's kernels (columns of no lens 0), and grad_source_or_null
+ * [2][B][n_families] = -sum_{j in f} u_j (explicit sources only).  Every sum has a fixed order: two calls give identical bits and a
+ * sample does not depend on the others.  Lenses served and refusals as gl_lens_maps_vjp (GL_EUNSUPPORTED: lens planes, series
+ * expansions, user-written bodies).  GL_EINVAL: a null table, ll, chi2, n_lost or workspace, sizes <= 0, offsets that do not run
+ * from 0 to n_images, an empty family or one of more than 64 images, a one-image family without sources, grad_source without
+ * sources, tol <= 0, max_iter < 1.  GL_ENOMEM: a workspace under gl_imgplane_loglike_workspace_bytes(m, B, n_images, with_source,
+ * want_grad), which is 0 for a null model or sizes <= 0 (with_source: source_or_null given; want_grad: grad_params_or_null given).
+ * All work on the caller's stream; no host synchronisation, no allocation. */
+size_t gl_imgplane_loglike_workspace_bytes(const gl_model* m, int B, int n_images, int with_source, int want_grad);
+int gl_imgplane_loglike(const gl_model* m, const float* params, int B, const float* image_table, const int32_t* family_table,
+                        const int32_t* family_offsets_host, int n_images, int n_families, const float* source_or_null, float tol,
+                        int max_iter, float* ll, float* chi2, int32_t* n_lost, float* pred_or_null, float* grad_params_or_null,
+                        float* grad_source_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Lens planes at redshifts of their own: multi-plane ray tracing (beyond the reference, which bends every ray at one plane).
  * Planes are numbered 0 .. n_planes - 1 by ascending redshift; every lens keeps its parameters as the reduced deflection for the
  * model's reference plane.  With theta_0 = theta the ray meets plane j at
