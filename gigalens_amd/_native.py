@@ -82,6 +82,7 @@ SYMBOLS = {
     "gl_model_set_position_delays": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_int, POINTER(c_float), c_int]),
     "gl_position_delays_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_size_t, c_void_p]),
+    "gl_position_family_terms": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     "gl_image_positions_scaled": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_float), c_float, c_float,
                                           c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),
@@ -1010,6 +1011,15 @@ class Model:
         _check_potential(lib().gl_position_delays_fwd_bwd(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(lam), _ptr(off),
                                                           _ptr(md), _ptr(ws), ws.numel(), _stream()))
         return (ll, chi2, grad, lam, off, md) if want_model else (ll, chi2, grad)
+
+    def position_family_terms(self, B):
+        """gl_position_family_terms: ``[B, F, 2]`` = (log_like, chi2) of every (sample, family) as the most recent point-likelihood call
+        on ``B`` samples (any of the position / flux / delay entries, or the fused log-prob with its position term) left them in the
+        workspace.  A copy, no launch."""
+        ws = self._workspace(B)
+        out = torch.empty((B, self.n_families, 2), dtype=torch.float32, device=self.device)
+        _check(lib().gl_position_family_terms(self._h, _ptr(ws), ws.numel(), B, _ptr(out), _stream()))
+        return out
 
     def image_positions(self, params, src_x, src_y, window, n_cells, max_images, tol, max_iter, scales=None):
         """gl_image_positions[_scaled]: ``src_x, src_y`` [B, S] on the device, ``window`` = (x_lo, x_hi, y_lo, y_hi), ``scales``

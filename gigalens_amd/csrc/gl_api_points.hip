@@ -325,6 +325,18 @@ int gl_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, fl
   return GL_OK;
 }
 
+// ---- per-family read-back: w_fam of the most recent point-likelihood call on this workspace -----------------------------
+int gl_position_family_terms(const gl_model* m, void* workspace, size_t workspace_bytes, int B, float* out, void* hip_stream) {
+  if (!out) return fail(GL_EINVAL, "out is null");
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, out, B, workspace, workspace_bytes, &plan, &w);  // (no packed rows here: `out` stands in for the null check)
+  if (rc) return rc;
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  GL_HIP(hipMemcpyAsync(out, w.pos_fam, sizeof(float) * (size_t)B * m->pos_F * 2, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+  return GL_OK;
+}
+
 int gl_profile_hessian(const gl_component* comp, const float* x, const float* y, int64_t n_pts, int B, int xy_batched,
                        const float* params, float* out, void* hip_stream) {
   if (!comp || !x || !y || !params || !out) return fail(GL_EINVAL, "null argument");

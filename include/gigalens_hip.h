@@ -256,6 +256,13 @@ int gl_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, fl
                                float* scale_or_null, float* offset_or_null, float* model_delay_or_null, void* workspace,
                                size_t workspace_bytes, void* hip_stream);
 
+/* Per-family read-back of the point likelihood (a test and diagnostic aid): copies w_fam [B][n_families][2] = (log_like, chi2) of
+ * every (sample, family) -- as the most recent gl_positions_fwd_bwd / gl_multiplane_positions_fwd_bwd / gl_position_fluxes_fwd_bwd /
+ * gl_position_delays_fwd_bwd / GL_TERM_POSITIONS call with the same B left it in `workspace` -- to out (DEVICE) on the caller's
+ * stream.  One device-to-device copy: no launch, and no store is added to any of those calls.  The per-sample outputs of those
+ * calls are the sums of these elements over the families in family order.  GL_EINVAL before gl_model_set_positions. */
+int gl_position_family_terms(const gl_model* m, void* workspace, size_t workspace_bytes, int B, float* out, void* hip_stream);
+
 /* ScalingRelation.hessian on arbitrary points (scaling_relation.py:72-83): out [4][n_pts][B] = f_xx, f_xy, f_yx, f_yy
  * summed over the catalogue; other arguments as gl_scaled_eval. */
 int gl_scaled_hessian(int base_kind, int n_galaxies, const int32_t scale_col[3], const float* table_dev, const float* x,
