@@ -751,35 +751,29 @@ class Model:
         """gl_lens_maps_vjp: the cotangents ``cot_x, cot_y`` on ``lens_maps``' beta_x, beta_y (with ``x, y`` broadcastable to
         ``(..., B)``) -> the gradient on the packed rows ``[B, P]``; columns of no lens are 0.  Points whose cotangents are both
         exactly 0, or not finite, are skipped.  ``UnsupportedLensError``: series and user-written lenses, lens planes."""
-        self._single_plane("lens_maps_vjp")
-        params = self._params(params)
-        B = params.shape[0]
-        xb, yb, shape = self._points(x, y, B)
-        cot = torch.stack([torch.as_tensor(c, dtype=torch.float32, device=self.device).expand(shape).reshape(-1, B)
-                           for c in (cot_x, cot_y)]).contiguous()
-        n_pts = xb.shape[0]
-        ws = self._scratch("lens_maps_vjp", lib().gl_lens_maps_vjp_workspace_bytes(self._h, B, n_pts))
-        out = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
-        _check_potential(lib().gl_lens_maps_vjp(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), n_pts, 1, _ptr(cot), _ptr(out), _ptr(ws),
-                                                ws.numel(), _stream()))
-        return out
+        return self._vjp("gl_lens_maps_vjp", "lens_maps_vjp", params, x, y, (cot_x, cot_y))
 
     def lens_hessian_vjp(self, params, x, y, cot_xx, cot_xy, cot_yx, cot_yy):
         """gl_lens_hessian_vjp: the cotangents on ``lens_maps``' f_xx, f_xy, f_yx, f_yy (with ``x, y`` broadcastable to
         ``(..., B)``) -> the gradient on the packed rows ``[B, P]``; columns of no lens are 0.  Points whose four cotangents are all
         exactly 0, or one of which is not finite, are skipped.  ``UnsupportedLensError``: series and user-written lenses, lens
         planes."""
-        self._single_plane("lens_hessian_vjp")
+        return self._vjp("gl_lens_hessian_vjp", "lens_hessian_vjp", params, x, y, (cot_xx, cot_xy, cot_yx, cot_yy))
+
+    def _vjp(self, symbol, name, params, x, y, cots):
+        """The library's ``symbol`` (and its ``symbol_workspace_bytes``) on the cotangents ``cots``, each broadcastable to the points
+        ``x, y``, with the scratch workspace ``name`` -> ``[B, P]``."""
+        self._single_plane(name)
         params = self._params(params)
         B = params.shape[0]
         xb, yb, shape = self._points(x, y, B)
         cot = torch.stack([torch.as_tensor(c, dtype=torch.float32, device=self.device).expand(shape).reshape(-1, B)
-                           for c in (cot_xx, cot_xy, cot_yx, cot_yy)]).contiguous()
+                           for c in cots]).contiguous()
         n_pts = xb.shape[0]
-        ws = self._scratch("lens_hessian_vjp", lib().gl_lens_hessian_vjp_workspace_bytes(self._h, B, n_pts))
+        ws = self._scratch(name, getattr(lib(), symbol + "_workspace_bytes")(self._h, B, n_pts))
         out = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
-        _check_potential(lib().gl_lens_hessian_vjp(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), n_pts, 1, _ptr(cot), _ptr(out), _ptr(ws),
-                                                   ws.numel(), _stream()))
+        _check_potential(getattr(lib(), symbol)(self._h, _ptr(params), B, _ptr(xb), _ptr(yb), n_pts, 1, _ptr(cot), _ptr(out), _ptr(ws),
+                                                ws.numel(), _stream()))
         return out
 
     def shear_loglike(self, params, x, y, e1, e2, sigma, scales=None, want_grad=True, want_model=True):
@@ -966,17 +960,8 @@ class Model:
     def position_fluxes(self, params, want_grad, want_model=False):
         """gl_position_fluxes_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the flux-ratio term on one plane or on
         lens planes; with ``want_model`` also ``(amplitude [B, F], model_flux [B, J])``."""
-        params = self._params(params)
-        B = params.shape[0]
-        ws = self._workspace(B)
-        ll = torch.empty(B, dtype=torch.float32, device=params.device)
-        chi2 = torch.empty_like(ll)
-        grad = torch.empty_like(params) if want_grad else None
-        amp = torch.empty((B, self.n_families), dtype=torch.float32, device=params.device) if want_model else None
-        mf = torch.empty((B, self.n_images), dtype=torch.float32, device=params.device) if want_model else None
-        _check_potential(lib().gl_position_fluxes_fwd_bwd(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(amp), _ptr(mf),
-                                                          _ptr(ws), ws.numel(), _stream()))
-        return (ll, chi2, grad, amp, mf) if want_model else (ll, chi2, grad)
+        return self._positions(lib().gl_position_fluxes_fwd_bwd, _check_potential, params, want_grad,
+                               (self.n_families, self.n_images), want_model)
 
     def set_position_delays(self, delays, errors, scales):
         """The measured arrival times of the images (days) and their errors (gl_model_set_position_delays; after ``set_positions``,
@@ -999,18 +984,8 @@ class Model:
     def position_delays(self, params, want_grad, want_model=False):
         """gl_position_delays_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the time-delay term; with ``want_model``
         also ``(scale [B, F], offset [B, F], model_delay [B, J])`` = ``lambda_f``, ``T_f`` and ``lambda_f phi_j + T_f`` in days."""
-        params = self._params(params)
-        B = params.shape[0]
-        ws = self._workspace(B)
-        ll = torch.empty(B, dtype=torch.float32, device=params.device)
-        chi2 = torch.empty_like(ll)
-        grad = torch.empty_like(params) if want_grad else None
-        lam = torch.empty((B, self.n_families), dtype=torch.float32, device=params.device) if want_model else None
-        off = torch.empty_like(lam) if want_model else None
-        md = torch.empty((B, self.n_images), dtype=torch.float32, device=params.device) if want_model else None
-        _check_potential(lib().gl_position_delays_fwd_bwd(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(lam), _ptr(off),
-                                                          _ptr(md), _ptr(ws), ws.numel(), _stream()))
-        return (ll, chi2, grad, lam, off, md) if want_model else (ll, chi2, grad)
+        return self._positions(lib().gl_position_delays_fwd_bwd, _check_potential, params, want_grad,
+                               (self.n_families, self.n_families, self.n_images), want_model)
 
     def position_family_terms(self, B):
         """gl_position_family_terms: ``[B, F, 2]`` = (log_like, chi2) of every (sample, family) as the most recent point-likelihood call
@@ -1314,15 +1289,19 @@ class Model:
         self._single_plane("positions")
         return self._positions(lib().gl_positions_fwd_bwd, _check, params, want_grad)
 
-    def _positions(self, fn, check, params, want_grad):
+    def _positions(self, fn, check, params, want_grad, extra=(), want_extra=False):
+        """One point-likelihood entry ``fn`` -> ``(loglike, chi2, grad or None)``.  ``extra``: the width of every further output the
+        entry takes between ``grad`` and the workspace; with ``want_extra`` they are allocated ``[B, width]`` and appended to the
+        result, without they are null pointers."""
         params = self._params(params)
         B = params.shape[0]
         ws = self._workspace(B)
         ll = torch.empty(B, dtype=torch.float32, device=params.device)
         chi2 = torch.empty_like(ll)
         grad = torch.empty_like(params) if want_grad else None
-        check(fn(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), _ptr(ws), ws.numel(), _stream()))
-        return ll, chi2, grad
+        more = [torch.empty((B, n), dtype=torch.float32, device=params.device) if want_extra else None for n in extra]
+        check(fn(self._h, _ptr(params), B, _ptr(ll), _ptr(chi2), _ptr(grad), *map(_ptr, more), _ptr(ws), ws.numel(), _stream()))
+        return (ll, chi2, grad, *more) if want_extra else (ll, chi2, grad)
 
     def logprob(self, z, obs, err, mask, bg_rms, exp_time, want_grad, chi2_divisor=1.0, terms=1):
         self._single_plane("logprob")

@@ -53,6 +53,34 @@ bool potential_kind(int kind) {
   return (kind >= GL_EPL && kind <= GL_DPIEP) || kind == GL_NFW_ELLIPSE || kind == GL_TNFW;
 }
 
+// the lenses without a potential: what gl_lens_potential and the time-delay term (gl_model_set_position_delays) refuse
+int refuse_potential_lenses(const gl_model* m) {
+  for (int l = 0; l < m->n_lens; ++l) {
+    const int kind = m->comps[l].kind;
+    if (kind == GL_SERIES)
+      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its precomputed field holds the deflection, no potential", l);
+    if (kind == GL_USER_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
+                                   "a body defines the deflection only, no potential", l);
+    if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
+  }
+  return GL_OK;
+}
+
+// the lenses the ray-shoot VJP (gl_lens_maps_vjp) and what is built on it or on its Hessian twin refuse, after the lens planes
+int refuse_vjp_lenses(const gl_model* m, const char* fn, const char* what) {
+  if (int rp = refuse_planes(m, fn)) return rp;
+  for (int l = 0; l < m->n_lens; ++l) {
+    const int kind = m->comps[l].kind;
+    if (kind == GL_SERIES)
+      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its field lives on the model grid and has no parameter derivative here", l);
+    if (kind == GL_USER_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
+                                   "not served by %s", l, what);
+  }
+  return GL_OK;
+}
+
 struct ImgLayout { size_t map, cand, n_cand, n_over, scale, bytes; };
 ImgLayout img_layout(int B, int n_src, int n_cells) {
   ImgLayout l{};
@@ -186,61 +214,47 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
 
 }  // namespace glk
 
+namespace {
+// What the four point-likelihood entries share after their own refusals: the call checks (then the lens planes, where the entry
+// needs them), the terms `what` through run_positions, and the results copied out of the workspace.
+int point_term_call(const gl_model* m, const float* params, int B, float* loglike, float* chi2, float* grad_params_or_null,
+                    void* workspace, size_t workspace_bytes, void* hip_stream, bool need_planes = false, int what = POS_POSITIONS,
+                    float* amp = nullptr, float* model_flux = nullptr, const DelayOut* delay_out = nullptr) {
+  LaunchPlan plan;
+  Workspace w;
+  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
+  if (rc) return rc;
+  if (need_planes && (rc = check_planes_set(m))) return rc;
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream, what, amp, model_flux, delay_out))) return rc;
+  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
+  if (grad_params_or_null)
+    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int gl_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
                          float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (int rp = refuse_planes(m, "gl_positions_fwd_bwd")) return rp;
-  LaunchPlan plan;
-  Workspace w;
-  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
-  if (rc) return rc;
-  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
-  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream))) return rc;
-  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  if (grad_params_or_null)
-    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
-  return GL_OK;
+  return point_term_call(m, params, B, loglike, chi2, grad_params_or_null, workspace, workspace_bytes, hip_stream);
 }
 
 int gl_multiplane_positions_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
                                     float* grad_params_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  LaunchPlan plan;
-  Workspace w;
-  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
-  if (rc) return rc;
-  if ((rc = check_planes_set(m))) return rc;
-  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
-  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream))) return rc;
-  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  if (grad_params_or_null)
-    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
-  return GL_OK;
+  return point_term_call(m, params, B, loglike, chi2, grad_params_or_null, workspace, workspace_bytes, hip_stream, true);
 }
 
 int gl_position_fluxes_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2, float* grad_params_or_null,
                                float* amplitude_or_null, float* model_flux_or_null, void* workspace, size_t workspace_bytes,
                                void* hip_stream) {
-  LaunchPlan plan;
-  Workspace w;
-  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
-  if (rc) return rc;
-  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
-  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
-  hipStream_t stream = (hipStream_t)hip_stream;
-  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream, POS_FLUXES, amplitude_or_null, model_flux_or_null)))
-    return rc;
-  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  if (grad_params_or_null)
-    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
-  return GL_OK;
+  return point_term_call(m, params, B, loglike, chi2, grad_params_or_null, workspace, workspace_bytes, hip_stream, false, POS_FLUXES,
+                         amplitude_or_null, model_flux_or_null);
 }
 
 // ---- time delays of the image families (gl_tdelays.hip.h) ---------------------------------------------------------------
@@ -285,15 +299,7 @@ int gl_model_set_position_delays(gl_model* m, const float* delay, const float* d
     if (has[f] && f < (int)m->pos_fam_scale.size() && m->pos_fam_scale[f] != 1.f)
       return fail(GL_EUNSUPPORTED, "image family %d has a deflection scale of %g (gl_model_set_position_scales): the Fermat potential "
                                    "of a scaled source plane is not served", f, m->pos_fam_scale[f]);
-  for (int l = 0; l < m->n_lens; ++l) {  // the set gl_lens_potential refuses
-    const int kind = m->comps[l].kind;
-    if (kind == GL_SERIES)
-      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its precomputed field holds the deflection, no potential", l);
-    if (kind == GL_USER_MASS)
-      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
-                                   "a body defines the deflection only, no potential", l);
-    if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
-  }
+  if (int rc = refuse_potential_lenses(m)) return rc;
   std::vector<float> tab((size_t)2 * m->pos_J + m->pos_F);
   std::copy(delay, delay + m->pos_J, tab.begin());
   std::copy(delay_err, delay_err + m->pos_J, tab.begin() + m->pos_J);
@@ -309,20 +315,9 @@ int gl_model_set_position_delays(gl_model* m, const float* delay, const float* d
 int gl_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2, float* grad_params_or_null,
                                float* scale_or_null, float* offset_or_null, float* model_delay_or_null, void* workspace,
                                size_t workspace_bytes, void* hip_stream) {
-  LaunchPlan plan;
-  Workspace w;
-  int rc = check_call(m, params, B, workspace, workspace_bytes, &plan, &w);
-  if (rc) return rc;
-  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
-  if (!loglike || !chi2) return fail(GL_EINVAL, "loglike / chi2 is null");
-  hipStream_t stream = (hipStream_t)hip_stream;
   const DelayOut out{scale_or_null, offset_or_null, model_delay_or_null};
-  if ((rc = run_positions(m, params, B, w, grad_params_or_null != nullptr, stream, POS_DELAYS, nullptr, nullptr, &out))) return rc;
-  GL_HIP(hipMemcpyAsync(loglike, w.pos_ll, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  GL_HIP(hipMemcpyAsync(chi2, w.pos_chi2, sizeof(float) * B, hipMemcpyDeviceToDevice, stream));
-  if (grad_params_or_null)
-    GL_HIP(hipMemcpyAsync(grad_params_or_null, w.pos_grad, sizeof(float) * (size_t)B * m->P, hipMemcpyDeviceToDevice, stream));
-  return GL_OK;
+  return point_term_call(m, params, B, loglike, chi2, grad_params_or_null, workspace, workspace_bytes, hip_stream, false, POS_DELAYS,
+                         nullptr, nullptr, &out);
 }
 
 // ---- per-family read-back: w_fam of the most recent point-likelihood call on this workspace -----------------------------
@@ -341,7 +336,7 @@ int gl_profile_hessian(const gl_component* comp, const float* x, const float* y,
                        const float* params, float* out, void* hip_stream) {
   if (!comp || !x || !y || !params || !out) return fail(GL_EINVAL, "null argument");
   if (n_pts <= 0 || B <= 0) return fail(GL_EINVAL, "n_pts and B must be positive");
-  if (!((comp->kind >= GL_EPL && comp->kind <= GL_DPIEP) || comp->kind == GL_NFW_ELLIPSE || comp->kind == GL_TNFW))
+  if (!potential_kind(comp->kind))
     return fail(GL_EINVAL, "kind %d is not a free-standing mass profile", comp->kind);
   const CompDesc cd = point_comp(comp);
   const long long total = (long long)n_pts * B;
@@ -406,6 +401,18 @@ long long vjp_blocks(const gl_model* m, int B, int64_t n_pts) {
   const long long rows = (long long)B * std::max(m->lens_params, 1);
   return n_blocks <= 0x7fffffffLL / rows && (long long)B * std::max(m->P, 1) <= 0x7fffffffLL ? n_blocks : 0;
 }
+
+// The launch pair of a lens VJP: `kernel` -- gl_lens_vjp_kernel (the ray-shoot) or gl_hessian_vjp_kernel, one signature -- writes
+// one partial per (sample, lens column, block of points), gl_lens_vjp_sum_kernel sums them into grad_params.
+using VjpKernel = void (*)(PosArgs, const float*, const float*, long long, int, const float*, int, int, float*);
+void launch_vjp(VjpKernel kernel, const gl_model* m, const float* params, int B, const float* x, const float* y, long long n_pts,
+                int xy_batched, const float* cot, float* grad_params, float* partial, long long n_blocks, hipStream_t stream) {
+  if (m->lens_params)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)B * m->lens_params * n_blocks)), dim3(VJP_WG), 0, stream,
+                       point_args(m, params, B), x, y, n_pts, xy_batched, cot, m->lens_params, (int)n_blocks, partial);
+  hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
+                     m->P, m->lens_params, (int)n_blocks, grad_params);
+}
 }  // namespace
 
 size_t gl_lens_maps_vjp_workspace_bytes(const gl_model* m, int B, int64_t n_pts) {
@@ -418,47 +425,20 @@ int gl_lens_maps_vjp(const gl_model* m, const float* params, int B, const float*
                      const float* cot, float* grad_params, void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!m || !params || !x || !y || !cot || !grad_params || !workspace) return fail(GL_EINVAL, "null argument");
   if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
-  if (int rp = refuse_planes(m, "gl_lens_maps_vjp")) return rp;
-  for (int l = 0; l < m->n_lens; ++l) {
-    const int kind = m->comps[l].kind;
-    if (kind == GL_SERIES)
-      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its field lives on the model grid and has no parameter derivative here", l);
-    if (kind == GL_USER_MASS)
-      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
-                                   "not served by the ray-shoot VJP", l);
-  }
+  if (int rc = refuse_vjp_lenses(m, "gl_lens_maps_vjp", "the ray-shoot VJP")) return rc;
   if (int rc = check_ready(m, false, false)) return rc;
   const long long n_blocks = vjp_blocks(m, B, n_pts);
   if (!n_blocks) return fail(GL_EINVAL, "too many points x samples for one call");
   const size_t need = gl_lens_maps_vjp_workspace_bytes(m, B, n_pts);
   if (workspace_bytes < need) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  hipStream_t stream = (hipStream_t)hip_stream;
-  float* partial = (float*)workspace;
-  if (m->lens_params)
-    hipLaunchKernelGGL(gl_lens_vjp_kernel, dim3((unsigned)((long long)B * m->lens_params * n_blocks)), dim3(VJP_WG), 0, stream,
-                       point_args(m, params, B), x, y, (long long)n_pts, xy_batched, cot, m->lens_params, (int)n_blocks, partial);
-  hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
-                     m->P, m->lens_params, (int)n_blocks, grad_params);
+  launch_vjp(gl_lens_vjp_kernel, m, params, B, x, y, (long long)n_pts, xy_batched, cot, grad_params, (float*)workspace, n_blocks,
+             (hipStream_t)hip_stream);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
 
 // ---- VJP of the Hessian, reduced-shear likelihood (gl_hessian_vjp.hip.h) ------------------------------------------
 namespace {
-// the lenses gl_lens_maps_vjp refuses, in its order and words
-int refuse_vjp_lenses(const gl_model* m, const char* fn, const char* what) {
-  if (int rp = refuse_planes(m, fn)) return rp;
-  for (int l = 0; l < m->n_lens; ++l) {
-    const int kind = m->comps[l].kind;
-    if (kind == GL_SERIES)
-      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its field lives on the model grid and has no parameter derivative here", l);
-    if (kind == GL_USER_MASS)
-      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
-                                   "not served by %s", l, what);
-  }
-  return GL_OK;
-}
-
 // the parts of the shear likelihood's workspace: block partials, cotangents [4][n_gal][B], the partials of the Hessian VJP
 struct ShearLayout { size_t part, cot, vjp, bytes; long long n_blocks; };
 bool shear_layout(const gl_model* m, int B, int n_gal, bool want_grad, ShearLayout* l) {
@@ -477,15 +457,6 @@ bool shear_layout(const gl_model* m, int B, int n_gal, bool want_grad, ShearLayo
   }
   return true;
 }
-
-void launch_hessian_vjp(const gl_model* m, const float* params, int B, const float* x, const float* y, long long n_pts, int xy_batched,
-                        const float* cot, float* grad_params, float* partial, long long n_blocks, hipStream_t stream) {
-  if (m->lens_params)
-    hipLaunchKernelGGL(gl_hessian_vjp_kernel, dim3((unsigned)((long long)B * m->lens_params * n_blocks)), dim3(VJP_WG), 0, stream,
-                       point_args(m, params, B), x, y, n_pts, xy_batched, cot, m->lens_params, (int)n_blocks, partial);
-  hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
-                     m->P, m->lens_params, (int)n_blocks, grad_params);
-}
 }  // namespace
 
 size_t gl_lens_hessian_vjp_workspace_bytes(const gl_model* m, int B, int64_t n_pts) {
@@ -502,7 +473,8 @@ int gl_lens_hessian_vjp(const gl_model* m, const float* params, int B, const flo
   if (!n_blocks) return fail(GL_EINVAL, "too many points x samples for one call");
   const size_t need = gl_lens_hessian_vjp_workspace_bytes(m, B, n_pts);
   if (workspace_bytes < need) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  launch_hessian_vjp(m, params, B, x, y, (long long)n_pts, xy_batched, cot, grad_params, (float*)workspace, n_blocks, (hipStream_t)hip_stream);
+  launch_vjp(gl_hessian_vjp_kernel, m, params, B, x, y, (long long)n_pts, xy_batched, cot, grad_params, (float*)workspace, n_blocks,
+             (hipStream_t)hip_stream);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -540,7 +512,8 @@ int gl_shear_loglike(const gl_model* m, const float* params, int B, const float*
   hipLaunchKernelGGL(gl_shear_fwd_kernel, dim3((unsigned)((long long)B * lay.n_blocks)), dim3(VJP_WG), 0, stream, point_args(m, params, B), s);
   hipLaunchKernelGGL(gl_shear_sum_kernel, dim3((unsigned)B), dim3(VJP_WG), 0, stream, (const float*)s.part, s.n_blocks, ll, chi2);
   if (want_grad)
-    launch_hessian_vjp(m, params, B, x, y, (long long)n_gal, 0, s.cot, grad_params_or_null, (float*)(base + lay.vjp), lay.n_blocks, stream);
+    launch_vjp(gl_hessian_vjp_kernel, m, params, B, x, y, (long long)n_gal, 0, s.cot, grad_params_or_null, (float*)(base + lay.vjp),
+               lay.n_blocks, stream);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -630,13 +603,8 @@ int gl_imgplane_loglike(const gl_model* m, const float* params, int B, const flo
   }
   if (want_grad) {
     hipLaunchKernelGGL(gl_imgp_cot_kernel, dim3((unsigned)((NB + VJP_WG - 1) / VJP_WG)), dim3(VJP_WG), 0, stream, g, B);
-    float* partial = (float*)(base + lay.vjp);
-    if (m->lens_params)
-      hipLaunchKernelGGL(gl_lens_vjp_kernel, dim3((unsigned)((long long)B * m->lens_params * lay.n_blocks)), dim3(VJP_WG), 0, stream, a,
-                         (const float*)g.pts, (const float*)(g.pts + NB), lay.n_pts, 1, (const float*)g.cot, m->lens_params,
-                         (int)lay.n_blocks, partial);
-    hipLaunchKernelGGL(gl_lens_vjp_sum_kernel, dim3((unsigned)((long long)B * m->P)), dim3(VJP_WG), 0, stream, (const float*)partial,
-                       m->P, m->lens_params, (int)lay.n_blocks, grad_params_or_null);
+    launch_vjp(gl_lens_vjp_kernel, m, params, B, g.pts, g.pts + NB, lay.n_pts, 1, g.cot, grad_params_or_null, (float*)(base + lay.vjp),
+               lay.n_blocks, stream);
   }
   GL_HIP(hipGetLastError());
   return GL_OK;
@@ -649,15 +617,7 @@ int gl_lens_potential(const gl_model* m, const float* params, int B, const float
   if (int rp = refuse_planes(m, "gl_lens_potential")) return rp;
   if ((x == nullptr) != (y == nullptr)) return fail(GL_EINVAL, "x and y must both be given or both be null");
   if (B <= 0 || n_pts <= 0) return fail(GL_EINVAL, "B and n_pts must be positive");
-  for (int l = 0; l < m->n_lens; ++l) {
-    const int kind = m->comps[l].kind;
-    if (kind == GL_SERIES)
-      return fail(GL_EUNSUPPORTED, "lens %d is a series expansion: its precomputed field holds the deflection, no potential", l);
-    if (kind == GL_USER_MASS)
-      return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
-                                   "a body defines the deflection only, no potential", l);
-    if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
-  }
+  if (int rc = refuse_potential_lenses(m)) return rc;
   if (int rc = check_ready(m, false, false)) return rc;
   if (!x) {
     if (n_pts != m->N || xy_batched) return fail(GL_EINVAL, "the model grid has %d points and is not batched", m->N);

@@ -275,7 +275,7 @@ class ModellingSequence:
             n += float(torch.count_nonzero(lens_sim.img_region))
         if pm.include_positions:
             # (the flux ratios and the time delays of the families: part of the point-image term)
-            n += pm.n_position + getattr(pm, "n_flux", 0.0) + getattr(pm, "n_delay", 0.0)
+            n += pm.n_position + pm.n_flux + pm.n_delay
         return n
 
     def MAP(self, optimizer: Adam, start=None, n_samples=500, num_steps=350, seed=0, progress=None, graph=None):

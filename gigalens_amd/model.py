@@ -130,62 +130,46 @@ class ProbabilisticModel:
         raise NotImplementedError
 
 
-class _LogLikeFn(torch.autograd.Function):
-    """autograd glue around gl_loglike_fwd_bwd: the gradient w.r.t. the packed parameters is produced
-    by the same fused pass as the value and kept for ``backward``."""
+class _GradFn(torch.autograd.Function):
+    """The autograd glue of every native likelihood whose gradient comes out of the same launches as its value:
+    ``fn(*detached inputs, want_grad)`` returns ``(outputs, grads)`` -- one gradient ``[B, ...]`` of the first output per input, kept
+    for ``backward`` -- and every output but the first is a statistic that carries no gradient.  ``want_grad`` tells ``fn`` whether
+    any input requires one; without, nothing is kept."""
 
     @staticmethod
-    def forward(ctx, packed, model, obs, err, mask, bg_rms, exp_time):
-        want = packed.requires_grad
-        ll, chi2, grad = model.loglike(packed.detach(), obs, err, mask, bg_rms, exp_time, want)
-        ctx.has_grad = want
+    def forward(ctx, fn, *inputs):
+        want = any(t.requires_grad for t in inputs)
+        outputs, grads = fn(*(t.detach() for t in inputs), want)
         if want:
-            ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(chi2)
-        return ll, chi2
+            ctx.save_for_backward(*grads)
+        ctx.mark_non_differentiable(*outputs[1:])
+        return tuple(outputs)
 
     @staticmethod
-    def backward(ctx, g_ll, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_ll[:, None] * grad, None, None, None, None, None, None
+    def backward(ctx, g, *_):
+        return (None,) + tuple(g[:, None] * grad for grad in ctx.saved_tensors)
 
 
-class _LogProbFn(torch.autograd.Function):
-    """autograd glue around ``ForwardProbModel._fused`` (bijector + kernels + prior in one native launch sequence, on one plane or
-    on lens planes)."""
-
-    @staticmethod
-    def forward(ctx, z, prob_model, simulator, terms):
-        want = z.requires_grad
-        lp, ll, chi2, grad = prob_model._fused(simulator, z, want, terms)
-        if want:
-            ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(ll, chi2)
-        return lp, ll, chi2
-
-    @staticmethod
-    def backward(ctx, g_lp, g_ll, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_lp[:, None] * grad, None, None, None
+def _split(result):
+    """``(outputs..., grad)`` of a native entry as the ``(outputs, grads)`` of ``_GradFn``."""
+    return result[:-1], result[-1:]
 
 
-class _PointTermFn(torch.autograd.Function):
-    """autograd glue around a point-image term of the native model: ``entry`` is its bound ``positions`` (gl_positions_fwd_bwd),
-    ``multiplane_positions`` (gl_multiplane_positions_fwd_bwd) or ``position_fluxes`` (gl_position_fluxes_fwd_bwd)."""
+def _from_dict(res, outputs, grads=("grad",)):
+    """The dict of a ``LensSimulator.*_and_grad`` method (float64 statistics as float32) as the ``(outputs, grads)`` of ``_GradFn``."""
+    return tuple(res[k].float() for k in outputs), tuple(res[k] for k in grads)
 
-    @staticmethod
-    def forward(ctx, packed, entry):
-        want = packed.requires_grad
-        ll, chi2, grad = entry(packed.detach(), want)
-        if want:
-            ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(chi2)
-        return ll, chi2
 
-    @staticmethod
-    def backward(ctx, g_ll, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_ll[:, None] * grad, None
+def _log_like(packed, model, *image):
+    """``(log_like, chi2)`` of gl_loglike_fwd_bwd, differentiable in the packed rows; forward only when they need no gradient."""
+    return _GradFn.apply(lambda p, want: _split(model.loglike(p, *image, want)), packed)
+
+
+def _point_term(packed, entry):
+    """``(log_like, chi2)`` of a point-image term of the native model, differentiable in the packed rows: ``entry`` is its bound
+    ``positions`` (gl_positions_fwd_bwd), ``multiplane_positions`` (gl_multiplane_positions_fwd_bwd), ``position_fluxes``
+    (gl_position_fluxes_fwd_bwd) or ``position_delays`` (gl_position_delays_fwd_bwd); forward only when they need no gradient."""
+    return _GradFn.apply(lambda p, want: _split(entry(p, want)), packed)
 
 
 class _GraphEntry:
@@ -346,7 +330,79 @@ class _ChainBijector:
         return self.pack.inverse(self.unconstraining.inverse(x_struct))
 
 
-class ForwardProbModel(ProbabilisticModel):
+class _StreamProbModel(ProbabilisticModel):
+    """What every probabilistic model here shares: the device, the prior's flat form with its bijectors, ``log_prior``, and what
+    ``ModellingSequence.MAP / SVI / HMC`` ask of a model on the stream path -- ``log_prob_and_grad`` by autograd through the
+    subclass's ``log_prob``, ``init_centroids``, and the counts its loss is sized with (``ForwardProbModel`` has a fused
+    ``log_prob_and_grad`` of its own)."""
+
+    include_pixels, include_positions, n_position, n_flux, n_delay = True, False, 0.0, 0.0, 0.0
+
+    def __init__(self, prior):
+        super().__init__(prior)
+        # host logic (prior, bijectors) also runs without a GPU; the likelihood itself never does
+        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
+
+    def _bind_prior_structure(self, prior):
+        """``_flat``, ``pack_bij``, ``unconstraining_bij`` and ``bij`` (tf/model.py:78-87) of ``prior``; returns the example sample
+        the structure is read from.  Called by a constructor after its own argument checks."""
+        self._flat = prior.flat(self.device)
+        example = prior.sample(seed=0)
+        self.pack_bij = _PackBijector(example)
+        self.unconstraining_bij = _prior.JointBijector(self._flat)
+        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+        return example
+
+    def _log_prior_at(self, z, x):
+        return self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+
+    def _x_and_log_prior(self, z):
+        """``z`` as a float32 tensor on the model's device, the constrained ``x`` and ``log_prior(z)``."""
+        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
+        x = self._flat.forward(z)
+        return z, x, self._log_prior_at(z, x)
+
+    def log_prior(self, z):
+        """tf/model.py:182-185."""
+        return self._x_and_log_prior(z)[2]
+
+    def log_prob_and_grad(self, simulator, z, graph=False):
+        """``(log_prob, red_chi2, d log_prob / d z)``, detached, by autograd through ``log_prob``; ``graph`` is accepted and ignored."""
+        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
+        lp, red = self.log_prob(simulator, zz)
+        (g,) = torch.autograd.grad(lp.sum(), zz)
+        return lp.detach(), red.detach(), g
+
+    def init_centroids(self, bs):
+        """tf/model.py:187-194 (no-op without the position branch)."""
+        return None
+
+
+class _JoinsStrong(_StreamProbModel):
+    """A point-like term of its own (``n_own`` data) that a ``ForwardProbModel`` over the same prior may join (``strong=``): the prior
+    is counted once, inside ``strong``'s term, and the reduced chi^2 weighs the two by their data counts."""
+
+    def _bind_strong(self, strong, n_own):
+        """The check of ``strong`` and what ``ModellingSequence`` sizes its loss with: the ``n_own`` data count with the point terms."""
+        if strong is not None and not isinstance(strong, ForwardProbModel):
+            raise TypeError("strong must be a ForwardProbModel over the same prior")
+        self.strong = strong
+        self.include_pixels = bool(strong is not None and strong.include_pixels)
+        self.include_positions = True
+        self.n_position = n_own
+        if strong is not None and strong.include_positions:
+            self.n_position += strong.n_position + strong.n_flux + strong.n_delay
+
+    def _join(self, simulator, z, x, ll, chi2, n_own):
+        """``(log_prob, reduced chi^2)`` of this model's ``(ll, chi2)`` over ``n_own`` data, with ``strong``'s when there is one."""
+        if self.strong is None:
+            return ll + self._log_prior_at(z, x), chi2 / n_own
+        lp_strong, red_strong = self.strong.log_prob(simulator, z)  # (carries the prior)
+        n_strong = float(self.strong._n_eff(simulator))
+        return ll + lp_strong, (chi2 + red_strong * n_strong) / (n_own + n_strong)
+
+
+class ForwardProbModel(_StreamProbModel):
     """Drop-in for ``gigalens.tf.model.ForwardProbModel`` (tf/model.py:12-194): pixel likelihood and
     image-position likelihood.  With the reference's default ``include_positions=True`` and no centroids the
     reference itself fails (it iterates ``None``, tf/model.py:69-70), so that combination raises ``TypeError``."""
@@ -396,8 +452,6 @@ class ForwardProbModel(ProbabilisticModel):
         super().__init__(prior)
         self.include_pixels = include_pixels
         self.include_positions = include_positions
-        # host logic (prior, bijectors) also runs without a GPU; the likelihood itself never does
-        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
         self.observed_image = None
         self.error_map = None
         self.background_rms = None
@@ -441,12 +495,7 @@ class ForwardProbModel(ProbabilisticModel):
                                                                                           self.centroids_x)
         (self.centroids_time_delays, self.centroids_time_delays_errors, self.time_delay_distances,
          self.n_delay) = _family_delays(centroids_time_delays, centroids_time_delays_errors, time_delay_distances, self.centroids_x)
-        self._flat = prior.flat(self.device)
-        example = prior.sample(seed=0)
-        self.pack_bij = _PackBijector(example)
-        self.unconstraining_bij = _prior.JointBijector(self._flat)
-        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
-        self._paths = _prior.nest_paths(example)
+        self._paths = _prior.nest_paths(self._bind_prior_structure(prior))
         self._perm_cache = {}
 
     # ---- z columns -> native packed rows, without materialising the nested structure ----------------
@@ -592,7 +641,7 @@ class ForwardProbModel(ProbabilisticModel):
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         on_planes = self.centroids_x is not None and self._on_planes(simulator)
         model = self._bind_positions(simulator)
-        ll, chi2 = _PointTermFn.apply(packed, model.multiplane_positions if on_planes else model.positions)
+        ll, chi2 = _point_term(packed, model.multiplane_positions if on_planes else model.positions)
         return ll, chi2 / self.n_position
 
     def _need_fluxes(self, what):
@@ -605,7 +654,7 @@ class ForwardProbModel(ProbabilisticModel):
         self._need_fluxes("stats_fluxes")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         self._on_planes(simulator)  # (its refusals; one native entry serves one plane and lens planes)
-        ll, chi2 = _PointTermFn.apply(packed, self._bind_positions(simulator).position_fluxes)
+        ll, chi2 = _point_term(packed, self._bind_positions(simulator).position_fluxes)
         return ll, chi2 / self.n_flux
 
     def predicted_fluxes(self, simulator, params):
@@ -627,7 +676,7 @@ class ForwardProbModel(ProbabilisticModel):
         differentiable in packed ``params``.  One lens plane, lenses with a potential, families with delays on the reference plane."""
         self._need_delays("stats_time_delays")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
-        ll, chi2 = _PointTermFn.apply(packed, self._bind_positions(simulator).position_delays)
+        ll, chi2 = _point_term(packed, self._bind_positions(simulator).position_delays)
         return ll, chi2 / self.n_delay
 
     def fitted_time_delays(self, simulator, params):
@@ -744,7 +793,7 @@ class ForwardProbModel(ProbabilisticModel):
                                           "gradient entries are log_prob / log_prob_and_grad and _model.multiplane_loglike_grad")
             ll, chi2 = simulator._model.multiplane_loglike(packed, *inputs)
         else:
-            ll, chi2 = _LogLikeFn.apply(packed, simulator._model, *inputs)
+            ll, chi2 = _log_like(packed, simulator._model, *inputs)
         return ll, chi2 / self._n_eff(simulator)  # tf/model.py:100
 
     def stats_pixels(self, simulator, params):
@@ -761,7 +810,8 @@ class ForwardProbModel(ProbabilisticModel):
         terms = self._terms()
         if not terms and not self._on_planes(simulator):  # (lens planes refuse a model without a term)
             return self.log_prob_unfused(simulator, z)
-        lp, _, red_chi2 = _LogProbFn.apply(z, self, simulator, terms)
+        # (bijector + kernels + prior in one native launch sequence; forward only when z needs no gradient)
+        lp, _, red_chi2 = _GradFn.apply(lambda zz, want: _split(self._fused(simulator, zz, want, terms)), z)
         return lp, red_chi2
 
     def term_log_prob_and_grad(self, simulator, z, term):
@@ -871,17 +921,8 @@ class ForwardProbModel(ProbabilisticModel):
             ll = ll + self._point_stats(simulator, packed)[0]
         return ll
 
-    def log_prior(self, z):
-        """tf/model.py:182-185."""
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
 
-    def init_centroids(self, bs):
-        """tf/model.py:187-194 (no-op without the position branch)."""
-        return None
-
-
-class BackwardProbModel(ProbabilisticModel):
+class BackwardProbModel(_StreamProbModel):
     """Drop-in for ``gigalens.tf.model.BackwardProbModel`` (tf/model.py:197-273): the noise map comes from the
     OBSERVED image, and the linear light amplitudes are solved by least squares inside the likelihood.
 
@@ -893,69 +934,26 @@ class BackwardProbModel(ProbabilisticModel):
 
     def __init__(self, prior, observed_image, background_rms, exp_time):
         super().__init__(prior)
-        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
         obs = np.asarray(observed_image, dtype=np.float32)
         err = np.sqrt(np.float32(background_rms) ** 2 + np.clip(obs, 0, np.inf) / np.float32(exp_time)).astype(np.float32)
         self.observed_image = torch.as_tensor(obs, device=self.device).contiguous()
         self.err_map = torch.as_tensor(err, device=self.device).contiguous()
-        self._flat = prior.flat(self.device)
-        example = prior.sample(seed=0)
-        self.pack_bij = _PackBijector(example)
-        self.unconstraining_bij = _prior.JointBijector(self._flat)
-        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+        self._bind_prior_structure(prior)
 
     def log_prob(self, simulator, z):
         """tf/model.py:242-273: ``(log_like + log_prior, mean squared normalised residual)``."""
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        x = self._flat.forward(z)
-        log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+        z, x, log_prior = self._x_and_log_prior(z)
         packed = simulator.pack(self.pack_bij.forward(x))
         coeffs = simulator._model.lstsq(packed.detach(), self.observed_image, self.err_map, 7, want="coeffs")[0]
         lin = simulator._linear_cols_dev  # uploaded once per simulator, not per call
         if lin is None or lin.device != packed.device:
             lin = simulator._linear_cols_dev = torch.tensor(simulator._layout.linear, dtype=torch.int64, device=packed.device)
         full = packed.index_copy(1, lin, coeffs / simulator.conversion_factor)  # amplitude = coeff / det(T)
-        ll, chi2 = _LogLikeFn.apply(full, simulator._model, self.observed_image, self.err_map, None, 0.0, 1.0)
+        ll, chi2 = _log_like(full, simulator._model, self.observed_image, self.err_map, None, 0.0, 1.0)
         return ll + log_prior, chi2 / float(self.observed_image.numel())
 
-    # -- what ModellingSequence.MAP / SVI / HMC need from a probabilistic model (shapelets-demo.ipynb runs them on it) --
-    include_pixels, include_positions, n_position = True, False, 0.0
 
-    def log_prob_and_grad(self, simulator, z):
-        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
-        lp, red = self.log_prob(simulator, zz)
-        (g,) = torch.autograd.grad(lp.sum(), zz)
-        return lp.detach(), red.detach(), g
-
-    def log_prior(self, z):
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
-
-    def init_centroids(self, bs):
-        return None
-
-
-class _SourceEvidenceFn(torch.autograd.Function):
-    """log evidence of the pixelated source (``LensSimulator.source_evidence_and_grad``) with its hand-written gradient with
-    respect to the packed rows."""
-
-    @staticmethod
-    def forward(ctx, packed, prob_model, simulator):
-        pm = prob_model
-        res = simulator.source_evidence_and_grad(packed.detach(), pm.observed_image, pm.err_map, n_src=pm.n_src, pitch=pm.pitch,
-                                                 center=pm.center, regularization=pm.regularization, strength=pm.strength,
-                                                 mask=pm.mask)
-        ctx.save_for_backward(res["grad"])
-        ctx.mark_non_differentiable(res["chi2"])
-        return res["log_evidence"].float(), res["chi2"].float()
-
-    @staticmethod
-    def backward(ctx, g_ev, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_ev[:, None] * grad, None, None
-
-
-class SourceEvidenceProbModel(ProbabilisticModel):
+class SourceEvidenceProbModel(_StreamProbModel):
     """The Bayesian evidence of a pixelated source as the target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the reference):
     ``log_prob = log_evidence + log_prior`` of ``LensSimulator.reconstruct_source`` at one regularisation strength, with the
     hand-written gradient of ``LensSimulator.source_evidence_and_grad``.  The prior is over ``lens_mass``, and over ``lens_light``
@@ -963,22 +961,15 @@ class SourceEvidenceProbModel(ProbabilisticModel):
     as in ``reconstruct_source``).  The evidence is continuous but only piecewise smooth in the lens (a kink wherever a ray crosses
     a source-grid line); its gradient is taken with the set of finite rays held fixed.  Runs on the stream path."""
 
-    include_pixels, include_positions, n_position = True, False, 0.0
-
     def __init__(self, prior, observed_image, err_map, *, n_src, pitch, center=(0.0, 0.0), regularization="gradient", strength=1.0,
                  mask=None):
         super().__init__(prior)
-        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
         self.observed_image = torch.as_tensor(np.asarray(observed_image, dtype=np.float32), device=self.device).contiguous()
         self.err_map = torch.as_tensor(np.asarray(err_map, dtype=np.float32), device=self.device).contiguous()
         self.n_src, self.pitch, self.center = (int(n_src[0]), int(n_src[1])), pitch, tuple(center)
         self.regularization, self.strength = regularization, strength
         self.mask = None if mask is None else np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).astype(bool)
-        self._flat = prior.flat(self.device)
-        example = prior.sample(seed=0)
-        self.pack_bij = _PackBijector(example)
-        self.unconstraining_bij = _prior.JointBijector(self._flat)
-        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+        self._bind_prior_structure(prior)
 
     def _n_used(self, simulator):
         used = np.asarray(simulator.img_region.cpu()) != 0
@@ -986,44 +977,13 @@ class SourceEvidenceProbModel(ProbabilisticModel):
 
     def log_prob(self, simulator, z):
         """``(log_evidence + log_prior, chi2 / n_used)``; differentiable with respect to ``z``."""
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        x = self._flat.forward(z)
-        log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+        z, x, log_prior = self._x_and_log_prior(z)
         packed = simulator._pack_partial(self.pack_bij.forward(x))  # missing groups filled; torch.stack keeps the graph
-        ev, chi2 = _SourceEvidenceFn.apply(packed, self, simulator)
+        evidence = lambda p, _: _from_dict(simulator.source_evidence_and_grad(
+            p, self.observed_image, self.err_map, n_src=self.n_src, pitch=self.pitch, center=self.center,
+            regularization=self.regularization, strength=self.strength, mask=self.mask), ("log_evidence", "chi2"))
+        ev, chi2 = _GradFn.apply(evidence, packed)
         return ev + log_prior, chi2 / float(self._n_used(simulator))
-
-    def log_prob_and_grad(self, simulator, z):
-        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
-        lp, red = self.log_prob(simulator, zz)
-        (g,) = torch.autograd.grad(lp.sum(), zz)
-        return lp.detach(), red.detach(), g
-
-    def log_prior(self, z):
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
-
-    def init_centroids(self, bs):
-        return None
-
-
-class _PointImageFn(torch.autograd.Function):
-    """log-likelihood of the extended model plus point images with solved amplitudes
-    (``LensSimulator.point_image_log_like_and_grad``) with its hand-written gradient: packed rows and image positions."""
-
-    @staticmethod
-    def forward(ctx, packed, x, y, prob_model, simulator):
-        pm = prob_model
-        res = simulator.point_image_log_like_and_grad(packed.detach(), x.detach(), y.detach(), pm.observed_image, pm.err_map,
-                                                      mask=pm.mask)
-        ctx.save_for_backward(res["grad"], res["grad_x"], res["grad_y"])
-        ctx.mark_non_differentiable(res["chi2"])
-        return res["log_like"].float(), res["chi2"].float()
-
-    @staticmethod
-    def backward(ctx, g_ll, g_chi2):
-        grad, gx, gy = ctx.saved_tensors
-        return g_ll[:, None] * grad, g_ll[:, None] * gx, g_ll[:, None] * gy, None, None
 
 
 class _SourcePlaneTieFn(torch.autograd.Function):
@@ -1050,7 +1010,7 @@ class _SourcePlaneTieFn(torch.autograd.Function):
         return g[:, None] * g_packed, g[:, None] * gx.t(), g[:, None] * gy.t(), None, None
 
 
-class PointImageProbModel(ProbabilisticModel):
+class PointImageProbModel(_StreamProbModel):
     """The pixel likelihood of an extended model plus the PSF-rendered images of a lensed point source (quasar, supernova) as the
     target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the reference): ``log_prob = log_like + log_prior`` of
     ``LensSimulator.fit_point_images``, where the amplitudes of the images are solved per sample, with the hand-written gradient
@@ -1063,11 +1023,8 @@ class PointImageProbModel(ProbabilisticModel):
     stay refused with their error.  A sample whose fit is singular (``ok == False``) has a NaN ``log_prob``.  Runs on the stream
     path (``MAP(graph=True)`` falls back to it)."""
 
-    include_pixels, include_positions, n_position = True, False, 0.0
-
     def __init__(self, prior, observed_image, err_map, *, mask=None, source_plane_sigma=None):
         super().__init__(prior)
-        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
         self.observed_image = torch.as_tensor(np.asarray(observed_image, dtype=np.float32), device=self.device).contiguous()
         self.err_map = torch.as_tensor(np.asarray(err_map, dtype=np.float32), device=self.device).contiguous()
         self.mask = None if mask is None else torch.as_tensor(np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).astype(bool),
@@ -1078,17 +1035,13 @@ class PointImageProbModel(ProbabilisticModel):
             if not (np.isfinite(source_plane_sigma) and source_plane_sigma > 0):
                 raise ValueError(f"source_plane_sigma must be finite and > 0, got {source_plane_sigma}")
         self.source_plane_sigma = source_plane_sigma
-        self._flat = prior.flat(self.device)
-        example = prior.sample(seed=0)
+        example = self._bind_prior_structure(prior)
         images = example.get("point_images") if isinstance(example, dict) else None
         if not images or any(set(d) != {"x", "y"} for d in images):
             raise ValueError('the prior needs a group "point_images": a list of {"x": ..., "y": ...}, one per image')
         if len(images) > 8:
             raise ValueError(f"{len(images)} point images: at most 8 are served")
         self.n_images = len(images)
-        self.pack_bij = _PackBijector(example)
-        self.unconstraining_bij = _prior.JointBijector(self._flat)
-        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
 
     def _n_used(self, simulator):
         if simulator not in self._n_used_of:
@@ -1098,32 +1051,19 @@ class PointImageProbModel(ProbabilisticModel):
 
     def log_prob(self, simulator, z):
         """``(log_like + source-plane tie + log_prior, chi2 / n_used)``; differentiable with respect to ``z``."""
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        x = self._flat.forward(z)
-        log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
+        z, x, log_prior = self._x_and_log_prior(z)
         struct = self.pack_bij.forward(x)
         packed = simulator._pack_partial(struct)  # groups outside the layout are ignored; torch.stack keeps the graph
         px = torch.stack([d["x"] for d in struct["point_images"]], dim=1)
         py = torch.stack([d["y"] for d in struct["point_images"]], dim=1)
-        ll, chi2 = _PointImageFn.apply(packed, px, py, self, simulator)
+        fit = lambda p, ix, iy, _: _from_dict(simulator.point_image_log_like_and_grad(
+            p, ix, iy, self.observed_image, self.err_map, mask=self.mask), ("log_like", "chi2"), ("grad", "grad_x", "grad_y"))
+        ll, chi2 = _GradFn.apply(fit, packed, px, py)
         lp = ll + log_prior
         if self.source_plane_sigma is not None:
             s = self.source_plane_sigma
             lp = lp + _SourcePlaneTieFn.apply(packed, px, py, simulator, s) - (self.n_images - 1) * math.log(2.0 * math.pi * s * s)
         return lp, chi2 / float(self._n_used(simulator))
-
-    def log_prob_and_grad(self, simulator, z, graph=False):
-        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
-        lp, red = self.log_prob(simulator, zz)
-        (g,) = torch.autograd.grad(lp.sum(), zz)
-        return lp.detach(), red.detach(), g
-
-    def log_prior(self, z):
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
-
-    def init_centroids(self, bs):
-        return None
 
 
 class ShearCatalogue:
@@ -1175,24 +1115,7 @@ class ShearCatalogue:
         return self._dev[key]
 
 
-class _ShearFn(torch.autograd.Function):
-    """log-likelihood of the reduced shear (``LensSimulator.shear_log_like_and_grad``) with its hand-written gradient with respect
-    to the packed rows."""
-
-    @staticmethod
-    def forward(ctx, packed, catalogue, simulator):
-        res = simulator.shear_log_like_and_grad(packed.detach(), catalogue, want_grad=True)
-        ctx.save_for_backward(res["grad"])
-        ctx.mark_non_differentiable(res["chi2"])
-        return res["log_like"], res["chi2"]
-
-    @staticmethod
-    def backward(ctx, g_ll, g_chi2):
-        (grad,) = ctx.saved_tensors
-        return g_ll[:, None] * grad, None, None
-
-
-class WeakLensingProbModel(ProbabilisticModel):
+class WeakLensingProbModel(_JoinsStrong):
     """The weak-lensing shear of a ``ShearCatalogue`` as the target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the reference):
     ``log_prob = log_like + log_prior`` of ``LensSimulator.shear_log_like_and_grad`` with its hand-written gradient.  The prior is
     over ``lens_mass`` (groups the physical model has beside it are packed from the prior when it carries them).
@@ -1207,48 +1130,18 @@ class WeakLensingProbModel(ProbabilisticModel):
         super().__init__(prior)
         if not isinstance(catalogue, ShearCatalogue):
             raise TypeError("catalogue must be a ShearCatalogue")
-        if strong is not None and not isinstance(strong, ForwardProbModel):
-            raise TypeError("strong must be a ForwardProbModel over the same prior")
-        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
-        self.catalogue, self.strong = catalogue, strong
-        # what ModellingSequence sizes its loss with: the 2 N ellipticity components count with the point terms
-        self.include_pixels = bool(strong is not None and strong.include_pixels)
-        self.include_positions = True
-        self.n_position = 2.0 * catalogue.n
-        if strong is not None and strong.include_positions:
-            self.n_position += strong.n_position + getattr(strong, "n_flux", 0.0) + getattr(strong, "n_delay", 0.0)
-        self._flat = prior.flat(self.device)
-        example = prior.sample(seed=0)
-        self.pack_bij = _PackBijector(example)
-        self.unconstraining_bij = _prior.JointBijector(self._flat)
-        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+        self._bind_strong(strong, 2.0 * catalogue.n)  # the 2 N ellipticity components
+        self.catalogue = catalogue
+        self._bind_prior_structure(prior)
 
     def log_prob(self, simulator, z):
         """``(log_like + log_prior [+ strong's log_like], reduced chi^2)``; differentiable with respect to ``z``."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
         x = self._flat.forward(z)
         packed = simulator._pack_partial(self.pack_bij.forward(x))  # missing groups filled; torch.stack keeps the graph
-        ll, chi2 = _ShearFn.apply(packed, self.catalogue, simulator)
-        n_shear = 2.0 * self.catalogue.n
-        if self.strong is None:
-            log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
-            return ll + log_prior, chi2 / n_shear
-        lp_strong, red_strong = self.strong.log_prob(simulator, z)  # (carries the prior)
-        n_strong = float(self.strong._n_eff(simulator))
-        return ll + lp_strong, (chi2 + red_strong * n_strong) / (n_shear + n_strong)
-
-    def log_prob_and_grad(self, simulator, z, graph=False):
-        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
-        lp, red = self.log_prob(simulator, zz)
-        (g,) = torch.autograd.grad(lp.sum(), zz)
-        return lp.detach(), red.detach(), g
-
-    def log_prior(self, z):
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
-
-    def init_centroids(self, bs):
-        return None
+        shear = lambda p, _: _from_dict(simulator.shear_log_like_and_grad(p, self.catalogue, want_grad=True), ("log_like", "chi2"))
+        ll, chi2 = _GradFn.apply(shear, packed)
+        return self._join(simulator, z, x, ll, chi2, 2.0 * self.catalogue.n)
 
 
 class ImageFamilies:
@@ -1355,24 +1248,7 @@ class ImageFamilies:
         return self._dev[key]
 
 
-class _ImagePlaneFn(torch.autograd.Function):
-    """log-likelihood of the image-plane positions (``LensSimulator.image_plane_log_like_and_grad``) with its hand-written gradient
-    with respect to the packed rows."""
-
-    @staticmethod
-    def forward(ctx, packed, families, simulator):
-        res = simulator.image_plane_log_like_and_grad(packed.detach(), families, want_grad=True)
-        ctx.save_for_backward(res["grad"])
-        ctx.mark_non_differentiable(res["chi2"], res["n_lost"])
-        return res["log_like"], res["chi2"], res["n_lost"]
-
-    @staticmethod
-    def backward(ctx, g_ll, g_chi2, g_lost):
-        (grad,) = ctx.saved_tensors
-        return g_ll[:, None] * grad, None, None
-
-
-class ImagePlaneProbModel(ProbabilisticModel):
+class ImagePlaneProbModel(_JoinsStrong):
     """The image-plane position likelihood of ``ImageFamilies`` as the target of ``ModellingSequence.MAP / SVI / HMC`` (beyond the
     reference): ``log_prob = log_like + log_prior`` of ``LensSimulator.image_plane_log_like_and_grad`` with the barycentre source
     of every family and its hand-written gradient -- the stage after a source-plane fit (``ForwardProbModel``'s position term is its
@@ -1392,45 +1268,15 @@ class ImagePlaneProbModel(ProbabilisticModel):
             raise TypeError("families must be an ImageFamilies")
         if families.min_count < 2:
             raise ValueError("ImagePlaneProbModel takes the barycentre source of every family: two or more images per family")
-        if strong is not None and not isinstance(strong, ForwardProbModel):
-            raise TypeError("strong must be a ForwardProbModel over the same prior")
-        self.device = _native.device() if torch.cuda.is_available() else torch.device("cpu")
-        self.families, self.strong = families, strong
-        # what ModellingSequence sizes its loss with: the 2 J image coordinates count with the point terms
-        self.include_pixels = bool(strong is not None and strong.include_pixels)
-        self.include_positions = True
-        self.n_position = 2.0 * families.J
-        if strong is not None and strong.include_positions:
-            self.n_position += strong.n_position + getattr(strong, "n_flux", 0.0) + getattr(strong, "n_delay", 0.0)
-        self._flat = prior.flat(self.device)
-        example = prior.sample(seed=0)
-        self.pack_bij = _PackBijector(example)
-        self.unconstraining_bij = _prior.JointBijector(self._flat)
-        self.bij = _ChainBijector(self.unconstraining_bij, self.pack_bij)
+        self._bind_strong(strong, 2.0 * families.J)  # the 2 J image coordinates
+        self.families = families
+        self._bind_prior_structure(prior)
 
     def log_prob(self, simulator, z):
         """``(log_like + log_prior [+ strong's log_like], reduced chi^2)``; differentiable with respect to ``z``."""
         z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
         x = self._flat.forward(z)
         packed = simulator._pack_partial(self.pack_bij.forward(x))  # missing groups filled; torch.stack keeps the graph
-        ll, chi2, _ = _ImagePlaneFn.apply(packed, self.families, simulator)
-        n_img = 2.0 * self.families.J
-        if self.strong is None:
-            log_prior = self._flat.log_prob(x) + self._flat.fldj_columns(z).sum(-1)
-            return ll + log_prior, chi2 / n_img
-        lp_strong, red_strong = self.strong.log_prob(simulator, z)  # (carries the prior)
-        n_strong = float(self.strong._n_eff(simulator))
-        return ll + lp_strong, (chi2 + red_strong * n_strong) / (n_img + n_strong)
-
-    def log_prob_and_grad(self, simulator, z, graph=False):
-        zz = torch.as_tensor(z, dtype=torch.float32, device=self.device).detach().requires_grad_(True)
-        lp, red = self.log_prob(simulator, zz)
-        (g,) = torch.autograd.grad(lp.sum(), zz)
-        return lp.detach(), red.detach(), g
-
-    def log_prior(self, z):
-        z = torch.as_tensor(z, dtype=torch.float32, device=self.device)
-        return self._flat.log_prob(self._flat.forward(z)) + self._flat.fldj_columns(z).sum(-1)
-
-    def init_centroids(self, bs):
-        return None
+        fit = lambda p, _: _from_dict(simulator.image_plane_log_like_and_grad(p, self.families, want_grad=True), ("log_like", "chi2"))
+        ll, chi2 = _GradFn.apply(fit, packed)
+        return self._join(simulator, z, x, ll, chi2, 2.0 * self.families.J)
