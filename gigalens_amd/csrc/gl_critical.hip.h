@@ -2,8 +2,8 @@
 // (gl_critical_curves; LensSimulator.critical_curves / einstein_radius).  The reference has no such call.  The critical curves are
 // the image-plane locus D = det(I - H) = (1 - f_xx)(1 - f_yy) - f_xy f_yx = 0, contoured by marching squares on a regular
 // n x n grid of cells over a window with the point evaluation of beta and the Hessian the lens-equation solver uses
-// (crit_eval below: the sum of lens_point<Dual<float, 2>> over the lenses that img_lens_eval of gl_images.hip.h forms, restated here
-// because it is built in two forms, see crit_eval_impl; built-in kinds and GL_SCALED catalogues).  Four launches, all
+// (crit_eval below, on lens_jets of gl_positions.hip.h as img_lens_eval of gl_images.hip.h is, and built in two forms, see
+// crit_eval_impl; built-in kinds and GL_SCALED catalogues).  Four launches, all
 // on the caller's stream, no host synchronisation, no allocation:
 //   map    (sample, vertex):   D at the (n+1)^2 vertices, ONE float per vertex, vertex fastest: the parameter row of a wave is
 //                              one broadcast load and the plane of a sample is contiguous for the kernels below; a D that is
@@ -74,38 +74,25 @@ struct CritArgs {
 __device__ inline float crit_vx(const CritArgs& g, int c) { return g.x_lo + (float)c * g.hx; }
 __device__ inline float crit_vy(const CritArgs& g, int r) { return g.y_lo + (float)r * g.hy; }
 
-// D = det(I - H), beta and 1 - kappa of sample b at one point: the sum over the lenses of img_lens_eval (gl_images.hip.h), which must
-// stay in step with it (the dPIS convergence excess included), restated because it needs the CAT switch.  CAT = false is the build for
+// D = det(I - H), beta and 1 - kappa of sample b at one point (H with the dPIS convergence excess).  CAT = false is the build for
 // models without a GL_SCALED catalogue: without the member loop in the switch of lens_point the evaluation fits the 256 VGPRs
 // inline; with it (CAT = true) it is a function call, which keeps the kernels free of register spills.
 template <bool CAT>
 __device__ inline float crit_eval_impl(const PosArgs& a, int b, float px, float py, float c, float& bx, float& by, float& omk) {
-  using R = gld::Dual<float, 2>;
-  R x(px), y(py);
-  x.d[0] = 1.f;
-  y.d[1] = 1.f;
   bx = px;
   by = py;
   float h[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int l = 0; l < a.n_lens; ++l) {
-    const CompDesc cd = a.comps[l];
-    if (!CAT && cd.kind == glp::K_SCALED) continue;  // (the host picks CAT = true for such a model)
-    R p[POS_MAXP];
-    float pf[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
-    R ax, ay;
-    lens_point<R>(a, cd, p, x, y, ax, ay);
-    const float ex = lens_kappa_excess<float>(a, cd, pf, px, py);
-    bx -= ax.v;
-    by -= ay.v;
-    h[0] += ax.d[0] + ex; h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1] + ex;
-    if (lens_singular_at(cd, pf, px, py)) h[0] = __builtin_nanf("");  // exactly on an SIS centre: D is not finite (the vertex is flagged)
-  }
-  if (c != 1.f) {  // (c == 1: every value as the sum formed it)
-    bx = px + c * (bx - px);
-    by = py + c * (by - py);
-    h[0] *= c; h[1] *= c; h[2] *= c; h[3] *= c;
-  }
+  lens_jets<CAT>(
+      a, b, px, py,
+      [&](const CompDesc& cd, const float* pf, const Jet2& ax, const Jet2& ay, float ex) {
+        bx -= ax.v;
+        by -= ay.v;
+        // exactly on an SIS centre D is not finite (the vertex is flagged), as beta is in gl_img_map_kernel
+        h[0] += lens_singular_at(cd, pf, px, py) ? __builtin_nanf("") : ax.d[0] + ex;
+        h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1] + ex;
+      },
+      [](const CompDesc& cd) { return !CAT && cd.kind == glp::K_SCALED; });  // (the host picks CAT = true for such a model)
+  lens_rescale(c, px, py, bx, by, h);
   omk = 1.f - 0.5f * (h[0] + h[3]);
   return (1.f - h[0]) * (1.f - h[3]) - h[1] * h[2];
 }

@@ -32,20 +32,11 @@ __global__ void __launch_bounds__(VJP_WG) gl_hessian_vjp_kernel(PosArgs a, const
                                                                int lens_params, int n_blocks, float* __restrict__ partial) {
   const int blk = blockIdx.x % n_blocks, bc = blockIdx.x / n_blocks;
   const int col = bc % lens_params, b = bc / lens_params;
-  int l = 0;
-  while (l + 1 < a.n_lens && col >= a.comps[l + 1].p_off) ++l;
-  const CompDesc cd = a.comps[l];
-  const int k = col - cd.p_off;
   using R1 = gld::Dual<float, 1>;
   using R = gld::Dual<R1, 2>;
   R p[POS_MAXP];
   R1 p1[POS_MAXP];
-  for (int m = 0; m < POS_MAXP; ++m) {
-    R1 v(m < cd.n_par ? a.params[(size_t)b * a.P + cd.p_off + m] : 0.f);
-    if (m == k) v.d[0] = 1.f;
-    p1[m] = v;
-    p[m] = R(v);
-  }
+  const CompDesc cd = lens_seeded_column(a, b, col, p1, p);
   const long long st = n_pts * a.B, pt = (long long)blk * VJP_PTS + threadIdx.x;
   float acc = 0.f;
   if (pt < n_pts) {
@@ -54,13 +45,13 @@ __global__ void __launch_bounds__(VJP_WG) gl_hessian_vjp_kernel(PosArgs a, const
     const bool zero = cxx == 0.f && cxy == 0.f && cyx == 0.f && cyy == 0.f;
     const bool finite = __builtin_isfinite(cxx) && __builtin_isfinite(cxy) && __builtin_isfinite(cyx) && __builtin_isfinite(cyy);
     if (!zero && finite) {
-      const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-      R xd{R1(px)}, yd{R1(py)};
+      const PointAt at(pt, b, i, xy_batched, x, y);
+      R xd{R1(at.x)}, yd{R1(at.y)};
       xd.d[0] = R1(1.f);
       yd.d[1] = R1(1.f);
       R ax, ay;
       lens_point<R>(a, cd, p, xd, yd, ax, ay);
-      const R1 ex = lens_kappa_excess<R1>(a, cd, p1, px, py);
+      const R1 ex = lens_kappa_excess<R1>(a, cd, p1, at.x, at.y);
       acc = cxx * (ax.d[0].d[0] + ex.d[0]) + cxy * ax.d[1].d[0] + cyx * ay.d[0].d[0] + cyy * (ay.d[1].d[0] + ex.d[0]);
     }
   }
@@ -85,21 +76,10 @@ struct ShearArgs {
 // f_xx, f_xy, f_yy of gl_lens_maps_kernel at one point: the lens loop on Dual<float,2> with the dPIS excess.  Not inlined: the
 // likelihood's own arithmetic and its nine table pointers stay out of the register budget of the largest lens template
 __device__ __noinline__ float3 shear_hessian(const PosArgs& a, int b, float px, float py) {
-  using R = gld::Dual<float, 2>;
-  R xd(px), yd(py);
-  xd.d[0] = 1.f;
-  yd.d[1] = 1.f;
   float fxx = 0.f, fxy = 0.f, fyy = 0.f;
-  for (int l = 0; l < a.n_lens; ++l) {
-    CompDesc cd = a.comps[l];
-    R p[POS_MAXP];
-    float pf[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
-    R ax, ay;
-    lens_point<R>(a, cd, p, xd, yd, ax, ay);
-    const float ex = lens_kappa_excess<float>(a, cd, pf, px, py);
+  lens_jets(a, b, px, py, [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
     fxx += ax.d[0] + ex; fxy += ax.d[1]; fyy += ay.d[1] + ex;
-  }
+  });
   return make_float3(fxx, fxy, fyy);
 }
 

@@ -64,15 +64,10 @@ __global__ void __launch_bounds__(256) gl_img_map_kernel(PosArgs a, ImgArgs g) {
   const int r = v / V1, c = v - r * V1;
   const float x = img_vx(g, c), y = img_vy(g, r);
   float bx = x, by = y;
-  for (int l = 0; l < a.n_lens; ++l) {
-    const CompDesc cd = a.comps[l];
-    float p[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)b * a.P + cd.p_off + k];
-    float ax, ay;
-    lens_point<float>(a, cd, p, x, y, ax, ay);
+  lens_deflections(a, b, x, y, [&](const CompDesc& cd, const float* p, float ax, float ay) {
     bx -= lens_singular_at(cd, p, x, y) ? __builtin_nanf("") : ax;
     by -= ay;
-  }
+  });
   if (!(isfinite(bx) && isfinite(by))) bx = by = __builtin_nanf("");
   g.map[i] = float2{bx, by};
 }
@@ -174,33 +169,18 @@ __global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
   }
 }
 
-// beta and Hessian (f_xx, f_xy, f_yx, f_yy; the dPIS convergence excess included, as P1 and gl_lens_maps have it) at one point
+// beta and Hessian (f_xx, f_xy, f_yx, f_yy; the dPIS convergence excess included) at one point
 // (c: the deflection scale of the source's plane; 1 leaves every value as the sum formed it)
 __device__ inline void img_lens_eval(const PosArgs& a, int b, float px, float py, float& bx, float& by, float* h, float c = 1.f) {
-  using R = gld::Dual<float, 2>;
-  R x(px), y(py);
-  x.d[0] = 1.f;
-  y.d[1] = 1.f;
   bx = px;
   by = py;
   h[0] = h[1] = h[2] = h[3] = 0.f;
-  for (int l = 0; l < a.n_lens; ++l) {
-    const CompDesc cd = a.comps[l];
-    R p[POS_MAXP];
-    float pf[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
-    R ax, ay;
-    lens_point<R>(a, cd, p, x, y, ax, ay);
-    const float ex = lens_kappa_excess<float>(a, cd, pf, px, py);
+  lens_jets(a, b, px, py, [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
     bx -= ax.v;
     by -= ay.v;
     h[0] += ax.d[0] + ex; h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1] + ex;
-  }
-  if (c != 1.f) {
-    bx = px + c * (bx - px);
-    by = py + c * (by - py);
-    h[0] *= c; h[1] *= c; h[2] *= c; h[3] *= c;
-  }
+  });
+  lens_rescale(c, px, py, bx, by, h);
 }
 
 __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g) {

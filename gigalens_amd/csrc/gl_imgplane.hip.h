@@ -47,55 +47,33 @@ struct ImgPlaneArgs {
   long long n_pts;  // J (explicit sources) or 2 J
 };
 
-// beta and the Hessian of one point as img_lens_eval (gl_images.hip.h) forms them, with which it must stay in step, the dPIS
-// convergence excess kept apart: h is the derivative of the deflection, the Hessian of the maps is h + ex on f_xx and f_yy.  Always a
+// beta and the Hessian of one point with the dPIS convergence excess kept apart: h is the derivative of the deflection, the Hessian
+// of the maps is h + ex on f_xx and f_yy.  Always a
 // function call, the device of crit_eval_cat in gl_critical.hip.h: inline, the Newton state beside the largest lens template (and
 // the catalogue member loop in the switch of lens_point) does not fit the 256 VGPRs -- even the build without catalogues spilled 8.
 static __device__ __attribute__((noinline)) void imgp_eval(const PosArgs& a, int b, float px, float py, float c, float& bx, float& by,
                                                            float* h, float& ex) {
-  using R = gld::Dual<float, 2>;
-  R x(px), y(py);
-  x.d[0] = 1.f;
-  y.d[1] = 1.f;
   bx = px;
   by = py;
   h[0] = h[1] = h[2] = h[3] = ex = 0.f;
-  for (int l = 0; l < a.n_lens; ++l) {
-    const CompDesc cd = a.comps[l];
-    R p[POS_MAXP];
-    float pf[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
-    R ax, ay;
-    lens_point<R>(a, cd, p, x, y, ax, ay);
-    ex += lens_kappa_excess<float>(a, cd, pf, px, py);
+  lens_jets(a, b, px, py, [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float e) {
+    ex += e;
     bx -= ax.v;
     by -= ay.v;
     h[0] += ax.d[0]; h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1];
-  }
-  if (c != 1.f) {
-    bx = px + c * (bx - px);
-    by = py + c * (by - py);
-    h[0] *= c; h[1] *= c; h[2] *= c; h[3] *= c;
-    ex *= c;
-  }
+  });
+  lens_rescale(c, px, py, bx, by, h);
+  if (c != 1.f) ex *= c;
 }
 
 // beta alone (the back-traced observed images of the barycentre), always a function call: it stays out of the Newton loop's budget
 static __device__ __attribute__((noinline)) float2 imgp_beta(const PosArgs& a, int b, float px, float py, float c) {
   float bx = px, by = py;
-  for (int l = 0; l < a.n_lens; ++l) {
-    const CompDesc cd = a.comps[l];
-    float p[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)b * a.P + cd.p_off + k];
-    float ax, ay;
-    lens_point<float>(a, cd, p, px, py, ax, ay);
+  lens_deflections(a, b, px, py, [&](const CompDesc&, const float*, float ax, float ay) {
     bx -= ax;
     by -= ay;
-  }
-  if (c != 1.f) {
-    bx = px + c * (bx - px);
-    by = py + c * (by - py);
-  }
+  });
+  lens_rescale(c, px, py, bx, by);
   return float2{bx, by};
 }
 

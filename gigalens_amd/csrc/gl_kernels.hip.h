@@ -54,6 +54,18 @@ struct SeriesDev {
 // image table of one K_INTERPOL light (gl_model_set_light_image): tab[(h + 4)][(w + 4)] with its zero apron; CompDesc::iparam indexes it
 using InterpDev = InterpTab<float>;
 
+// thread i of a (point, sample) launch, sample fastest: its point, its sample and the point's coordinates, which are either one
+// list [n_pts] for all samples or a list per sample [n_pts][B] (xy_batched)
+struct PointAt {
+  long long pt;
+  int b;
+  float x, y;
+  __device__ __forceinline__ PointAt(long long pt_, int b_, long long i, int xy_batched, const float* x_, const float* y_)
+      : pt(pt_), b(b_), x(xy_batched ? x_[i] : x_[pt_]), y(xy_batched ? y_[i] : y_[pt_]) {}
+  __device__ __forceinline__ PointAt(long long i, int B, int xy_batched, const float* x_, const float* y_)
+      : PointAt(i / B, (int)(i - i / B * B), i, xy_batched, x_, y_) {}
+};
+
 // One ZCol per column k of z (the k-th leaf of the prior in tf.nest.flatten order, tf/model.py:76-87); evaluated by z_eval (gl_frontend.hip.h)
 struct ZCol {
   int param_col;  // destination column in the packed [B,P] row

@@ -31,26 +31,18 @@ __global__ void __launch_bounds__(VJP_WG) gl_lens_vjp_kernel(PosArgs a, const fl
                                                             int lens_params, int n_blocks, float* __restrict__ partial) {
   const int blk = blockIdx.x % n_blocks, bc = blockIdx.x / n_blocks;
   const int col = bc % lens_params, b = bc / lens_params;
-  int l = 0;
-  while (l + 1 < a.n_lens && col >= a.comps[l + 1].p_off) ++l;
-  const CompDesc cd = a.comps[l];
-  const int k = col - cd.p_off;
   using R = gld::Dual<float, 1>;
   R p[POS_MAXP];
-  for (int m = 0; m < POS_MAXP; ++m) {
-    R v(m < cd.n_par ? a.params[(size_t)b * a.P + cd.p_off + m] : 0.f);
-    if (m == k) v.d[0] = 1.f;
-    p[m] = v;
-  }
+  const CompDesc cd = lens_seeded_column(a, b, col, p);
   const long long st = n_pts * a.B, pt = (long long)blk * VJP_PTS + threadIdx.x;
   float acc = 0.f;
   if (pt < n_pts) {
     const long long i = pt * a.B + b;
     const float cx = cot[i], cy = cot[st + i];
     if (!((cx == 0.f && cy == 0.f) || !__builtin_isfinite(cx) || !__builtin_isfinite(cy))) {
-      const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
+      const PointAt at(pt, b, i, xy_batched, x, y);
       R ax, ay;
-      lens_point<R>(a, cd, p, R(px), R(py), ax, ay);
+      lens_point<R>(a, cd, p, R(at.x), R(at.y), ax, ay);
       acc = -(cx * ax.d[0] + cy * ay.d[0]);
     }
   }

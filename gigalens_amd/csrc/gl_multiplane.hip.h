@@ -140,16 +140,14 @@ __global__ void __launch_bounds__(MP_MAPS_WG) gl_mp_maps_kernel(PosArgs a, MpArg
   __shared__ float lds[6 * MP_MAXK][MP_MAPS_WG];
   const long long i = (long long)blockIdx.x * MP_MAPS_WG + threadIdx.x;
   if (i >= n_pts * a.B) return;
-  const long long pt = i / a.B;
-  const int b = (int)(i - pt * a.B);
-  const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
+  const PointAt at(i, a.B, xy_batched, x, y);
   using R = gld::Dual<float, 2>;
-  R xd(px), yd(py);
+  R xd(at.x), yd(at.y);
   xd.d[0] = 1.f;
   yd.d[1] = 1.f;
   MpLdsSums sums(&lds[0][threadIdx.x]);
-  mp_trace<R>(a, mp, b, xd, yd, sums);
-  float bx = px, by = py, fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
+  mp_trace<R>(a, mp, at.b, xd, yd, sums);
+  float bx = at.x, by = at.y, fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
 #pragma unroll
   for (int k = 0; k < MP_MAXK; ++k) {
     const float c = tg.c[k];

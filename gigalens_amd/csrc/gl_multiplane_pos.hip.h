@@ -146,8 +146,7 @@ __global__ void __launch_bounds__(MP_POS_WG) gl_mp_pos_p3_kernel(PosArgs a, MpAr
   {
     const int col = i % lens_params, bj = i / lens_params;
     const int b = bj / a.J, j = bj - b * a.J;
-    int own = 0;  // the lens that owns the column
-    while (own + 1 < a.n_lens && col >= a.comps[own + 1].p_off) ++own;
+    const int own = lens_of_column(a, col);
     const int last = mp_pos_last_plane(tg + (size_t)j * MP_MAXK);
     if (mp.plane[own] > last) {  // the column's plane lies at or behind the family: its rays never meet the lens
       a.w_g[((size_t)b * a.J + j) * a.P + col] = 0.f;

@@ -13,33 +13,31 @@ __global__ void __launch_bounds__(256) gl_point_kernel(CompDesc cd, const float*
                                                        const float* __restrict__ shp_tab, int shp_stride, InterpDev itab) {
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_pts * B) return;
-  long long pt = i / B;
-  int b = (int)(i - pt * B);
-  float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  const float* p = params + (size_t)b * cd.n_par;
+  const PointAt at(i, B, xy_batched, x, y);
+  const float* p = params + (size_t)at.b * cd.n_par;
   float o0 = 0.f, o1 = 0.f;
   switch (cd.kind) {
-    case K_EPL: epl_point<float>(p, cd.iparam, px, py, o0, o1); break;
-    case K_SIE: { float d[SIE_ND + 1]; sie_prep<float>(p, d); sie_fwd(d, px, py, o0, o1); } break;
-    case K_NFW: { float d[NFW_ND]; nfw_prep<float>(p, d); nfw_fwd(d, px, py, o0, o1); } break;
-    case K_SHEAR: { float d[4]; shear_prep<float>(p, d); shear_fwd(d, px, py, o0, o1); } break;
-    case K_SIS: { float d[4]; sis_prep<float>(p, d); sis_fwd(d, px, py, o0, o1); } break;
-    case K_DPIS: case K_DPIE: case K_DPIEP: { float d[DPX_ND]; dpie_prep<float>(cd.kind, p, d); dpie_fwd<float>(cd.kind, d, px, py, o0, o1); } break;
-    case K_NFW_ELLIPSE: { float d[NFE_ND]; nfw_ell_prep<float>(p, d); nfw_ell_fwd<float>(d, px, py, o0, o1); } break;
-    case K_TNFW: { float d[TNF_ND]; tnfw_prep<float>(p, d); tnfw_fwd<float>(d, px, py, o0, o1); } break;
-    case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(p, d); o0 = core_sersic_fwd<float>(d, px, py); } break;
-    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(p, itab.h, itab.w, d); o0 = interp_fwd<float>(d, itab, cd.flags & 1u, px, py); } break;
-    case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(p, false, d); o0 = sersic_fwd(d, px, py); } break;
-    case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(p, true, d); o0 = sersic_fwd(d, px, py); } break;
+    case K_EPL: epl_point<float>(p, cd.iparam, at.x, at.y, o0, o1); break;
+    case K_SIE: { float d[SIE_ND + 1]; sie_prep<float>(p, d); sie_fwd(d, at.x, at.y, o0, o1); } break;
+    case K_NFW: { float d[NFW_ND]; nfw_prep<float>(p, d); nfw_fwd(d, at.x, at.y, o0, o1); } break;
+    case K_SHEAR: { float d[4]; shear_prep<float>(p, d); shear_fwd(d, at.x, at.y, o0, o1); } break;
+    case K_SIS: { float d[4]; sis_prep<float>(p, d); sis_fwd(d, at.x, at.y, o0, o1); } break;
+    case K_DPIS: case K_DPIE: case K_DPIEP: { float d[DPX_ND]; dpie_prep<float>(cd.kind, p, d); dpie_fwd<float>(cd.kind, d, at.x, at.y, o0, o1); } break;
+    case K_NFW_ELLIPSE: { float d[NFE_ND]; nfw_ell_prep<float>(p, d); nfw_ell_fwd<float>(d, at.x, at.y, o0, o1); } break;
+    case K_TNFW: { float d[TNF_ND]; tnfw_prep<float>(p, d); tnfw_fwd<float>(d, at.x, at.y, o0, o1); } break;
+    case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(p, d); o0 = core_sersic_fwd<float>(d, at.x, at.y); } break;
+    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(p, itab.h, itab.w, d); o0 = interp_fwd<float>(d, itab, cd.flags & 1u, at.x, at.y); } break;
+    case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(p, false, d); o0 = sersic_fwd(d, at.x, at.y); } break;
+    case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(p, true, d); o0 = sersic_fwd(d, at.x, at.y); } break;
     case K_SHAPELETS: {
       if (cd.iparam > SH_CAP) {  // runtime-order path; amplitudes straight from the parameter row (same triangle order)
         float d[SHP_AMP];
         d[SHP_CX] = p[1]; d[SHP_CY] = p[2]; d[SHP_IB] = 1.f / p[0]; d[SHP_NMAX] = (float)cd.iparam;
-        o0 = shapelets_fwd_amp<float, SH_CAPB>(d, p + 3, shp_tab, shp_stride, cd.flags & 1u, px, py);
+        o0 = shapelets_fwd_amp<float, SH_CAPB>(d, p + 3, shp_tab, shp_stride, cd.flags & 1u, at.x, at.y);
       } else {
         float d[SHP_SQ + SH_SQ * SH_SQ];
         shapelets_prep<float>(p, cd.iparam, d);
-        o0 = shapelets_fwd<float, SH_CAP>(d, shp_tab, shp_stride, cd.flags & 1u, px, py);
+        o0 = shapelets_fwd<float, SH_CAP>(d, shp_tab, shp_stride, cd.flags & 1u, at.x, at.y);
       }
     } break;
   }
@@ -57,10 +55,8 @@ __global__ void __launch_bounds__(256) gl_basis_point_kernel(CompDesc cd, const 
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = n_pts * B;
   if (i >= total) return;
-  long long pt = i / B;
-  int b = (int)(i - pt * B);
-  float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  const float* p = params + (size_t)b * cd.n_par;
+  const PointAt at(i, B, xy_batched, x, y);
+  const float* p = params + (size_t)at.b * cd.n_par;
   if (cd.kind == K_SHAPELETS) {
     float d[SHP_AMP];
     d[SHP_CX] = p[1];
@@ -68,10 +64,10 @@ __global__ void __launch_bounds__(256) gl_basis_point_kernel(CompDesc cd, const 
     d[SHP_IB] = 1.f / p[0];
     d[SHP_NMAX] = (float)cd.iparam;
     if (cd.iparam > SH_CAP)
-      shapelets_basis<float, SH_CAPB>(d, shp_tab, shp_stride, cd.flags & 1u, px, py,
+      shapelets_basis<float, SH_CAPB>(d, shp_tab, shp_stride, cd.flags & 1u, at.x, at.y,
                                       [&](int k, float v) { out[(size_t)k * total + i] = v; });
     else
-      shapelets_basis<float, SH_CAP>(d, shp_tab, shp_stride, cd.flags & 1u, px, py,
+      shapelets_basis<float, SH_CAP>(d, shp_tab, shp_stride, cd.flags & 1u, at.x, at.y,
                                      [&](int k, float v) { out[(size_t)k * total + i] = v; });
     return;
   }
@@ -80,10 +76,10 @@ __global__ void __launch_bounds__(256) gl_basis_point_kernel(CompDesc cd, const 
   q[kind_linear_col(cd.kind, cd.iparam)] = 1.f;
   float v = 0.f;
   switch (cd.kind) {
-    case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(q, d); v = core_sersic_fwd<float>(d, px, py); } break;
-    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(q, itab.h, itab.w, d); v = interp_fwd_unit<float>(d, itab, cd.flags & 1u, px, py); } break;
-    case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(q, false, d); v = sersic_fwd(d, px, py); } break;
-    case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(q, true, d); v = sersic_fwd(d, px, py); } break;
+    case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(q, d); v = core_sersic_fwd<float>(d, at.x, at.y); } break;
+    case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(q, itab.h, itab.w, d); v = interp_fwd_unit<float>(d, itab, cd.flags & 1u, at.x, at.y); } break;
+    case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(q, false, d); v = sersic_fwd(d, at.x, at.y); } break;
+    case K_SERSIC_ELLIPSE: { float d[SER_NDX]; sersic_prep<float>(q, true, d); v = sersic_fwd(d, at.x, at.y); } break;
   }
   out[i] = v;
 }
@@ -96,17 +92,15 @@ __global__ void __launch_bounds__(256) gl_scaled_point_kernel(ScaledDesc sd, con
                                                               float* __restrict__ out0, float* __restrict__ out1) {
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_pts * B) return;
-  long long pt = i / B;
-  int b = (int)(i - pt * B);
-  float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  const float* sc = scales + (size_t)b * n_scales;
+  const PointAt at(i, B, xy_batched, x, y);
+  const float* sc = scales + (size_t)at.b * n_scales;
   float sx = 0.f, sy = 0.f;
   for (int g = 0; g < sd.n_gal; ++g) {
     float ds[DP_NS], dd[DP_ND], ax, ay;
     scaled_static<float>(sd.base_kind, table + (size_t)7 * g, ds);
     scaled_dyn<float>(sd, table + (size_t)7 * g, sc, dd);
-    if (sd.base_kind == K_DPIE) piemd_fwd<float>(ds, dd, px, py, ax, ay);
-    else piep_fwd<float>(ds, dd, px, py, ax, ay);
+    if (sd.base_kind == K_DPIE) piemd_fwd<float>(ds, dd, at.x, at.y, ax, ay);
+    else piep_fwd<float>(ds, dd, at.x, at.y, ax, ay);
     sx += ax;
     sy += ay;
   }

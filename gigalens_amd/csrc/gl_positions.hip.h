@@ -118,26 +118,89 @@ template <class R1> __device__ R1 lens_kappa_excess(const PosArgs& a, const Comp
   return R1(0.f);
 }
 
+// The lens sum of the point kernels, in one place.  lens_jet evaluates ONE lens of sample b at (px, py) on Dual<float, 2> seeded with
+// d (x, y) / d (x, y) = I and hands f(cd, pf, ax, ay, ex): the raw parameters, the deflection (value = alpha, d[] = d alpha / d (x, y))
+// and the dPIS convergence excess.  lens_jets walks the lenses of the sample with it; pre(cd) == true leaves a lens out before its
+// parameters are loaded (or deals with it in its own way).  The caller keeps its own sums: the order of its additions is its own.
+// lens_deflections is the same walk on float, f(cd, p, ax, ay), for the kernels that want beta alone.
+using Jet2 = gld::Dual<float, 2>;
+template <bool CATS = true, class F>
+__device__ __forceinline__ void lens_jet(const PosArgs& a, const CompDesc& cd, int b, float px, float py, F&& f) {
+  using R = Jet2;
+  R x(px), y(py);
+  x.d[0] = 1.f;
+  y.d[1] = 1.f;
+  R p[POS_MAXP];
+  float pf[POS_MAXP];
+  for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
+  R ax, ay;
+  lens_point<R, CATS>(a, cd, p, x, y, ax, ay);
+  const float ex = lens_kappa_excess<float>(a, cd, pf, px, py);
+  f(cd, pf, ax, ay, ex);
+}
+template <bool CATS = true, class F, class Pre>
+__device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f, Pre&& pre) {
+  for (int l = 0; l < a.n_lens; ++l) {
+    const CompDesc cd = a.comps[l];
+    if (pre(cd)) continue;
+    lens_jet<CATS>(a, cd, b, px, py, f);
+  }
+}
+template <class F> __device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f) {
+  lens_jets(a, b, px, py, f, [](const CompDesc&) { return false; });
+}
+template <class F> __device__ __forceinline__ void lens_deflections(const PosArgs& a, int b, float px, float py, F&& f) {
+  for (int l = 0; l < a.n_lens; ++l) {
+    const CompDesc cd = a.comps[l];
+    float p[POS_MAXP];
+    for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)b * a.P + cd.p_off + k];
+    float ax, ay;
+    lens_point<float>(a, cd, p, px, py, ax, ay);
+    f(cd, p, ax, ay);
+  }
+}
+
+// beta and the Hessian h[4] (null: beta alone) of the reference plane on a source plane of deflection scale c: beta = theta - c sum
+// alpha, H -> c H.  c == 1 leaves every value as the sum formed it
+__device__ __forceinline__ void lens_rescale(float c, float px, float py, float& bx, float& by, float* h = nullptr) {
+  if (c != 1.f) {
+    bx = px + c * (bx - px);
+    by = py + c * (by - py);
+    if (h) { h[0] *= c; h[1] *= c; h[2] *= c; h[3] *= c; }
+  }
+}
+
+// the lens that owns column col of the packed parameter row
+__device__ __forceinline__ int lens_of_column(const PosArgs& a, int col) {
+  int l = 0;
+  while (l + 1 < a.n_lens && col >= a.comps[l + 1].p_off) ++l;
+  return l;
+}
+// Column col of the lens parameters as ONE seeded direction: returns the lens that owns it and fills p1[] with that lens's
+// parameters of sample b on Dual<float, 1>, zero-padded, the derivative 1 at the column; p[], where wanted, holds the same on the
+// caller's nested dual
+template <class R = gld::Dual<float, 1>>
+__device__ __forceinline__ CompDesc lens_seeded_column(const PosArgs& a, int b, int col, gld::Dual<float, 1>* p1, R* p = nullptr) {
+  const CompDesc cd = a.comps[lens_of_column(a, col)];
+  const int k = col - cd.p_off;
+  for (int m = 0; m < POS_MAXP; ++m) {
+    gld::Dual<float, 1> v(m < cd.n_par ? a.params[(size_t)b * a.P + cd.p_off + m] : 0.f);
+    if (m == k) v.d[0] = 1.f;
+    p1[m] = v;
+    if (p) p[m] = R(v);
+  }
+  return cd;
+}
+
 __global__ void __launch_bounds__(64) gl_pos_p1_kernel(PosArgs a) {
   int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= a.B * a.J) return;
   int b = i / a.J, j = i - b * a.J;
-  using R = gld::Dual<float, 2>;
-  R x(a.px[j]), y(a.py[j]);
-  x.d[0] = 1.f;
-  y.d[1] = 1.f;
   float bx = a.px[j], by = a.py[j], fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
-  for (int l = 0; l < a.n_lens; ++l) {
-    CompDesc cd = a.comps[l];
-    R p[POS_MAXP];
-    float pf[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
-    R ax, ay;
-    lens_point<R>(a, cd, p, x, y, ax, ay);
-    const float ex = lens_kappa_excess<float>(a, cd, pf, a.px[j], a.py[j]);
+  lens_jets(a, b, a.px[j], a.py[j], [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
     bx -= ax.v; by -= ay.v;
     fxx += ax.d[0] + ex; fxy += ax.d[1]; fyx += ay.d[0]; fyy += ay.d[1] + ex;
-  }
+  });
   if (a.fam_scale) {  // deflection, Hessian and the dPIS excess times the family's scale before P2 forms mean beta and det A
     const float c = a.fam_scale[j];
     bx = a.px[j] + c * (bx - a.px[j]); by = a.py[j] + c * (by - a.py[j]);
@@ -155,40 +218,32 @@ __global__ void __launch_bounds__(64) gl_lens_maps_kernel(PosArgs a, const float
                                                          float* __restrict__ out) {
   long long i = (long long)blockIdx.x * 64 + threadIdx.x;
   if (i >= n_pts * a.B) return;
-  const long long pt = i / a.B;
-  const int b = (int)(i - pt * a.B);
-  const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  using R = gld::Dual<float, 2>;
-  R xd(px), yd(py);
-  xd.d[0] = 1.f;
-  yd.d[1] = 1.f;
-  float bx = px, by = py, fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
-  for (int l = 0; l < a.n_lens; ++l) {
-    CompDesc cd = a.comps[l];
-    R p[POS_MAXP];
-    float pf[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
-    if (cd.kind == glp::K_SERIES) {  // host guarantees: points = the model grid, both fields attached
-      const SeriesDev sv = a.series[cd.flags];
-      const float dl = pf[1] - sv.r0;
-      float acc[5];
-      for (int f = 0; f < 5; ++f) {
-        const float* c = (f < 2 ? sv.coef + (size_t)f * (sv.order + 1) * n_pts
-                                : sv.hcoef + (size_t)(f - 2) * (sv.order + 1) * n_pts) + pt;
-        float v = c[(size_t)sv.order * n_pts];
-        for (int n = sv.order - 1; n >= 0; --n) v = v * dl + c[(size_t)n * n_pts];
-        acc[f] = pf[0] * v;
-      }
-      bx -= acc[0]; by -= acc[1];
-      fxx += acc[2]; fxy += acc[3]; fyx += acc[3]; fyy += acc[4];
-      continue;
-    }
-    R ax, ay;
-    lens_point<R>(a, cd, p, xd, yd, ax, ay);
-    const float ex = lens_kappa_excess<float>(a, cd, pf, px, py);
-    bx -= ax.v; by -= ay.v;
-    fxx += ax.d[0] + ex; fxy += ax.d[1]; fyx += ay.d[0]; fyy += ay.d[1] + ex;
-  }
+  const PointAt at(i, a.B, xy_batched, x, y);
+  float bx = at.x, by = at.y, fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
+  lens_jets(
+      a, at.b, at.x, at.y,
+      [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
+        bx -= ax.v; by -= ay.v;
+        fxx += ax.d[0] + ex; fxy += ax.d[1]; fyx += ay.d[0]; fyy += ay.d[1] + ex;
+      },
+      [&](const CompDesc& cd) {
+        if (cd.kind != glp::K_SERIES) return false;
+        // a series lens is its own sum (host guarantees: points = the model grid, both fields attached)
+        const float* pf = a.params + (size_t)at.b * a.P + cd.p_off;
+        const SeriesDev sv = a.series[cd.flags];
+        const float dl = pf[1] - sv.r0;
+        float acc[5];
+        for (int f = 0; f < 5; ++f) {
+          const float* c = (f < 2 ? sv.coef + (size_t)f * (sv.order + 1) * n_pts
+                                  : sv.hcoef + (size_t)(f - 2) * (sv.order + 1) * n_pts) + at.pt;
+          float v = c[(size_t)sv.order * n_pts];
+          for (int n = sv.order - 1; n >= 0; --n) v = v * dl + c[(size_t)n * n_pts];
+          acc[f] = pf[0] * v;
+        }
+        bx -= acc[0]; by -= acc[1];
+        fxx += acc[2]; fxy += acc[3]; fyx += acc[3]; fyy += acc[4];
+        return true;
+      });
   const long long st = n_pts * a.B;
   out[i] = bx; out[st + i] = by; out[2 * st + i] = fxx; out[3 * st + i] = fxy; out[4 * st + i] = fyx; out[5 * st + i] = fyy;
 }
@@ -200,22 +255,14 @@ __global__ void __launch_bounds__(64) gl_profile_hessian_kernel(CompDesc cd, con
                                                                float* __restrict__ out) {
   long long i = (long long)blockIdx.x * 64 + threadIdx.x;
   if (i >= n_pts * B) return;
-  const long long pt = i / B;
-  const int b = (int)(i - pt * B);
-  const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
-  using R = gld::Dual<float, 2>;
-  R xd(px), yd(py);
-  xd.d[0] = 1.f;
-  yd.d[1] = 1.f;
-  R p[7];
-  float pf[7];
-  for (int k = 0; k < cd.n_par; ++k) { pf[k] = params[(size_t)b * cd.n_par + k]; p[k] = R(pf[k]); }
-  PosArgs none{};
-  R ax, ay;
-  lens_point<R>(none, cd, p, xd, yd, ax, ay);
-  const float ex = lens_kappa_excess<float>(none, cd, pf, px, py);
+  const PointAt at(i, B, xy_batched, x, y);
+  PosArgs one{};  // the one free-standing lens (point_comp: p_off = 0) with its own parameter rows
+  one.params = params;
+  one.P = cd.n_par;
   const long long st = n_pts * B;
-  out[i] = ax.d[0] + ex; out[st + i] = ax.d[1]; out[2 * st + i] = ay.d[0]; out[3 * st + i] = ay.d[1] + ex;
+  lens_jet(one, cd, at.b, at.x, at.y, [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
+    out[i] = ax.d[0] + ex; out[st + i] = ax.d[1]; out[2 * st + i] = ay.d[0]; out[3 * st + i] = ay.d[1] + ex;
+  });
 }
 
 // ScalingRelation.hessian at plugin level (scaling_relation.py:72-83): sum of the member Hessians, out[4][n_pts][B]
@@ -226,16 +273,14 @@ __global__ void __launch_bounds__(64) gl_scaled_hessian_kernel(ScaledDesc sd, co
                                                               float* __restrict__ out) {
   long long i = (long long)blockIdx.x * 64 + threadIdx.x;
   if (i >= n_pts * B) return;
-  const long long pt = i / B;
-  const int b = (int)(i - pt * B);
-  const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
+  const PointAt at(i, B, xy_batched, x, y);
   using R = gld::Dual<float, 2>;
-  R xd(px), yd(py);
+  R xd(at.x), yd(at.y);
   xd.d[0] = 1.f;
   yd.d[1] = 1.f;
   R sc[3];
   float scf[3] = {1.f, 1.f, 1.f};
-  for (int k = 0; k < n_scales; ++k) scf[k] = scales[(size_t)b * n_scales + k];
+  for (int k = 0; k < n_scales; ++k) scf[k] = scales[(size_t)at.b * n_scales + k];
   for (int k = 0; k < 3; ++k) sc[k] = R(scf[k]);
   float fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
   for (int g = 0; g < sd.n_gal; ++g) {
@@ -250,7 +295,7 @@ __global__ void __launch_bounds__(64) gl_scaled_hessian_kernel(ScaledDesc sd, co
     float ex = 0.f;
     if (sd.base_kind == K_DPIS) {  // the analytic dPIS override (piemd.py:62-83)
       scaled_dyn<float>(sd, row, scf, ddf);
-      ex = dpis_kappa_excess<float>(dsf, ddf, px, py);
+      ex = dpis_kappa_excess<float>(dsf, ddf, at.x, at.y);
     }
     fxx += ax.d[0] + ex; fxy += ax.d[1]; fyx += ay.d[0]; fyy += ay.d[1] + ex;
   }
@@ -307,7 +352,7 @@ __global__ void __launch_bounds__(64) gl_pos_p3_kernel(PosArgs a, int lens_param
   if (i >= a.B * a.J * lens_params) return;
   const int col = i % lens_params, bj = i / lens_params;
   const int b = bj / a.J, j = bj - b * a.J;
-  int l = 0;
+  int l = 0;  // (lens_seeded_column, spelled out: through the helper this kernel runs the fused position call 0.7 % slower)
   while (l + 1 < a.n_lens && col >= a.comps[l + 1].p_off) ++l;
   const CompDesc cd = a.comps[l];
   const int k = col - cd.p_off;

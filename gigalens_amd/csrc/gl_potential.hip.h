@@ -51,15 +51,13 @@ __global__ void __launch_bounds__(POT_WG) gl_lens_potential_kernel(PosArgs a, co
                                                                   int xy_batched, float* __restrict__ out) {
   const long long i = (long long)blockIdx.x * POT_WG + threadIdx.x;
   if (i >= n_pts * a.B) return;
-  const long long pt = i / a.B;
-  const int b = (int)(i - pt * a.B);
-  const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
+  const PointAt at(i, a.B, xy_batched, x, y);
   float psi = 0.f;
   for (int l = 0; l < a.n_lens; ++l) {
     const CompDesc cd = a.comps[l];
     float p[POS_MAXP];
-    for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)b * a.P + cd.p_off + k];
-    psi += lens_potential_point<float>(a, cd, p, px, py);
+    for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)at.b * a.P + cd.p_off + k];
+    psi += lens_potential_point<float>(a, cd, p, at.x, at.y);
   }
   out[i] = psi;
 }
@@ -71,13 +69,11 @@ __global__ void __launch_bounds__(POT_WG) gl_profile_potential_kernel(CompDesc c
                                                                      float* __restrict__ out) {
   const long long i = (long long)blockIdx.x * POT_WG + threadIdx.x;
   if (i >= n_pts * B) return;
-  const long long pt = i / B;
-  const int b = (int)(i - pt * B);
-  const float px = xy_batched ? x[i] : x[pt], py = xy_batched ? y[i] : y[pt];
+  const PointAt at(i, B, xy_batched, x, y);
   float p[7];
-  for (int k = 0; k < cd.n_par; ++k) p[k] = params[(size_t)b * cd.n_par + k];
+  for (int k = 0; k < cd.n_par; ++k) p[k] = params[(size_t)at.b * cd.n_par + k];
   PosArgs none{};
-  out[i] = lens_potential_point<float>(none, cd, p, px, py);
+  out[i] = lens_potential_point<float>(none, cd, p, at.x, at.y);
 }
 
 }  // namespace glk

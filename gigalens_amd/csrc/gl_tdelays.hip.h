@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(64) gl_pos_tdelay_grad_kernel(PosArgs a, const
   const int b = bj / a.J, j = bj - b * a.J;
   const float aw = aj[(size_t)b * a.J + j];
   if (aw == 0.f) return;  // (no measured time: P3's bits stay)
-  int l = 0;
+  int l = 0;  // (lens_seeded_column, spelled out as in gl_pos_p3_kernel, for the same reason)
   while (l + 1 < a.n_lens && col >= a.comps[l + 1].p_off) ++l;
   const CompDesc cd = a.comps[l];
   const int k = col - cd.p_off;
