@@ -6,7 +6,7 @@ or a failed call raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 
 import numpy as np
 import torch
@@ -18,6 +18,7 @@ _lib = None
 GL_FLAG_SHAPELETS_INTERPOLATE = 1
 GL_FLAG_INTERPOL_LINEAR = 1
 GL_INTERPOL = 21
+GL_INTERPOL_MASS = 14
 
 
 class NativeLibraryError(RuntimeError):
@@ -175,6 +176,9 @@ SYMBOLS = {
     "gl_lstsq_last_kernels": (c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_size_t]),
     "gl_model_set_catalogue": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_float)]),
     "gl_model_set_light_image": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float)]),
+    "gl_model_set_lens_maps": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_double]),
+    "gl_interpol_mass_eval": (c_int, [POINTER(gl_component), c_int, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int64,
+                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "gl_interpol_eval": (c_int, [POINTER(gl_component), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
                                  c_void_p, c_int, c_void_p]),
     "gl_scaled_eval": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
@@ -642,6 +646,22 @@ def interpol_eval(profile, x, y, kwargs):
     return out.reshape((1,) + tuple(out_shape)) if basis else out.reshape(out_shape)
 
 
+def interpol_mass_eval(profile, x, y, kwargs, hessian):
+    """``Interpolated.deriv`` / ``.hessian`` of the mass profile on points (gl_interpol_mass_eval).  Forward only."""
+    dev = device()
+    comp = component_of(profile)
+    xb, yb, P, B, out_shape = _broadcast_points(profile, x, y, kwargs, list(profile.params), dev)
+    if profile._dev_table is None or profile._dev_table.device != dev:  # both maps, each with its two-pixel zero apron
+        maps = torch.from_numpy(np.stack([profile.alpha_x, profile.alpha_y]))
+        profile._dev_table = torch.nn.functional.pad(maps, (2, 2, 2, 2)).to(dev).contiguous()
+    h, w = profile.alpha_x.shape
+    out = torch.empty((4 if hessian else 2,) + tuple(xb.shape), dtype=torch.float32, device=dev)
+    _check(lib().gl_interpol_mass_eval(ctypes.byref(comp), h, w, _ptr(profile._dev_table[0]), _ptr(profile._dev_table[1]),
+                                       float(profile.pitch), _ptr(xb), _ptr(yb), xb.shape[0], B, 1, _ptr(P), _ptr(out[0]),
+                                       None if hessian else _ptr(out[1]), int(bool(hessian)), _stream()))
+    return tuple(out[k].reshape(out_shape) for k in range(out.shape[0]))
+
+
 # --------------------------------------------------------------------------------------------------
 # model handle
 # --------------------------------------------------------------------------------------------------
@@ -672,7 +692,7 @@ class Model:
         with torch.cuda.device(self.device):
             if bodies:  # user-written profiles: the interpreter kernel is compiled with them now (seconds, once)
                 barr = (ctypes.c_char_p * len(bodies))(*[b.encode() for b in bodies])
-                # (GL_EUNSUPPORTED -- user-written profiles beside an Interpolated light -- raises UnsupportedLensError)
+                # (GL_EUNSUPPORTED -- user-written profiles beside an Interpolated light or lens -- raises UnsupportedLensError)
                 _check_potential(L.gl_model_create_user(arr, n_lens, n_lens_light, n_src, ctypes.byref(g), barr, len(bodies), ctypes.byref(h)))
             else:
                 _check(L.gl_model_create(arr, n_lens, n_lens_light, n_src, ctypes.byref(g), ctypes.byref(h)))
@@ -717,6 +737,16 @@ class Model:
         with torch.cuda.device(self.device):
             _check(lib().gl_model_set_light_image(self._h, int(component), int(img.shape[0]), int(img.shape[1]),
                                                   img.ctypes.data_as(POINTER(c_float))))
+        self._changed(False)
+
+    def set_lens_maps(self, component, alpha_x, alpha_y, pitch):
+        """Attach the deflection maps of a GL_INTERPOL_MASS lens (gl_model_set_lens_maps): 2-D float32 host arrays of one shape."""
+        ax, ay = np.ascontiguousarray(alpha_x, dtype=np.float32), np.ascontiguousarray(alpha_y, dtype=np.float32)
+        if ax.ndim != 2 or ax.shape != ay.shape:
+            raise NativeLibraryError(f"set_lens_maps: alpha_x {ax.shape} and alpha_y {ay.shape} must be 2-D arrays of one shape")
+        with torch.cuda.device(self.device):
+            _check(lib().gl_model_set_lens_maps(self._h, int(component), int(ax.shape[0]), int(ax.shape[1]),
+                                                ax.ctypes.data_as(POINTER(c_float)), ay.ctypes.data_as(POINTER(c_float)), float(pitch)))
         self._changed(False)
 
     def _points(self, x, y, B):

@@ -258,6 +258,7 @@ MainArgs base_args(const gl_model* m, const Workspace& w, int chunk) {
   a.scaled_first = m->cats.empty() ? -1 : m->cats[0].dev.comp;
   a.series = m->d_series;
   a.interp = m->d_interp;
+  a.interp_mass = m->d_interp_mass;
   a.src_scale = m->src_scaled ? m->d_src_scale.get() : nullptr;
   return a;
 }
@@ -269,6 +270,9 @@ int check_ready(const gl_model* m, bool with_series, bool counted) {
                    : fail(GL_EINVAL, "GL_SCALED component without a catalogue");
   if (m->n_interp != m->n_interp_set)
     return fail(GL_EINVAL, "%d GL_INTERPOL component(s) without an image (gl_model_set_light_image)", m->n_interp - m->n_interp_set);
+  if (m->n_interp_mass != m->n_interp_mass_set)
+    return fail(GL_EINVAL, "%d GL_INTERPOL_MASS component(s) without deflection maps (gl_model_set_lens_maps)",
+                m->n_interp_mass - m->n_interp_mass_set);
   if (with_series && no_field)
     return counted ? fail(GL_EINVAL, "%d GL_SERIES component(s) without a coefficient field (gl_model_set_series)", no_field)
                    : fail(GL_EINVAL, "GL_SERIES component without a coefficient field");
@@ -322,10 +326,11 @@ int run_prep(const gl_model* m, const float* params, const float* z, int B, cons
     const int split_rank = plan.tail_rows ? plan.tail_from : -1;
     hipLaunchKernelGGL(gl_prep_wave_kernel, dim3((B + 3) / 4 + (ord ? 1 : 0)), dim3(256), rows, stream, m->d_comps.get(), n_comp,
                        params, z, d_z, zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp,
-                       ord ? w.order : nullptr, rows ? 1 : 0, split_rank, m->d_interp.get());
+                       ord ? w.order : nullptr, rows ? 1 : 0, split_rank, m->d_interp.get(), m->d_interp_mass.get());
   } else {  // thread per component
     hipLaunchKernelGGL(gl_prep_kernel, dim3((B * n_comp + 127) / 128), dim3(128), 0, stream, m->d_comps.get(), n_comp, params, z,
-                       d_z, zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp, m->d_interp.get());
+                       d_z, zcols, src, const_row, m->P, B, rows_out, w.derived, m->D, cost, m->epl_comp, m->d_interp.get(),
+                       m->d_interp_mass.get());
   }
   if (m->G) {  // per (sample, galaxy) constants of the catalogue members, from the constrained parameter rows
     const long long total = (long long)B * m->G;
@@ -621,7 +626,7 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
   for (int i = 0; i < n_comp; ++i) {
     const gl_component& c = comps[i];
     const bool mass = i < n_lens;
-    const bool is_mass_kind = (c.kind >= GL_EPL && c.kind <= GL_TNFW) || c.kind == GL_USER_MASS;
+    const bool is_mass_kind = (c.kind >= GL_EPL && c.kind <= GL_TNFW) || c.kind == GL_USER_MASS || c.kind == GL_INTERPOL_MASS;
     const bool is_light_kind = (c.kind >= GL_SERSIC && c.kind <= GL_CORE_SERSIC) || c.kind == GL_USER_LIGHT || c.kind == GL_INTERPOL;
     if ((mass && !is_mass_kind) || (!mass && !is_light_kind))
       return fail(GL_EINVAL, "component %d: kind %d is not a %s profile", i, c.kind, mass ? "mass" : "light");
@@ -638,7 +643,8 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
     }
     if (c.kind == GL_EPL) { m->epl_comp = m->has_epl ? -2 : i; m->has_epl = true; }
     if (c.kind >= GL_DPIS && c.kind <= GL_SERIES) m->fam = std::max(m->fam, 1);
-    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC || c.kind == GL_INTERPOL) m->fam = 2;
+    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC || c.kind == GL_INTERPOL || c.kind == GL_INTERPOL_MASS)
+      m->fam = 2;
     if (c.kind == GL_SERIES && (iparam < 0 || iparam > SERIES_MAX_ORDER))
       return fail(GL_EINVAL, "component %d: series order %d outside [0, %d]", i, iparam, SERIES_MAX_ORDER);
     if (c.kind == GL_SCALED) {
@@ -674,6 +680,12 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
       m->interp.push_back(InterpDev{nullptr, 0, 0});
       m->interp_buf.emplace_back();
     }
+    if (c.kind == GL_INTERPOL_MASS) {  // table slot; the maps arrive with gl_model_set_lens_maps
+      cd.iparam = m->n_interp_mass++;
+      cd.flags = 0;
+      m->interp_mass.push_back(InterpMassDev{nullptr, nullptr, 0, 0, 0.f});
+      m->interp_mass_buf.emplace_back();
+    }
     cd.lin_off = (int)m->lin_cols.size();
     for (int k = 0; k < kind_num_linear(c.kind, iparam); ++k) m->lin_cols.push_back(p_off + kind_linear_col(c.kind, iparam) + k);
     // a user-written light whose last parameter is declared the linear amplitude (gl_component::reserved): one basis image
@@ -686,6 +698,9 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
   if (m->has_user && m->n_interp)
     return fail(GL_EUNSUPPORTED, "a model that mixes user-written profiles with GL_INTERPOL lights is not served: the run-time "
                                  "compiled kernels carry no image tables");
+  if (m->has_user && m->n_interp_mass)
+    return fail(GL_EUNSUPPORTED, "a model that mixes user-written profiles with GL_INTERPOL_MASS lenses is not served: the run-time "
+                                 "compiled kernels carry no deflection maps");
   m->P = p_off;
   for (int i = 0; i < n_lens; ++i) m->lens_params += m->comps[i].n_par;
   m->D = std::max(d_off, 4);
@@ -1301,6 +1316,40 @@ int gl_model_set_light_image(gl_model* m, int component, int h, int w, const flo
   if (first) ++m->n_interp_set;
   if (!m->d_interp) GL_HIP(m->d_interp.alloc(m->interp.size()));
   GL_HIP(m->d_interp.write(m->interp.data(), m->interp.size()));
+  return GL_OK;
+}
+
+int gl_model_set_lens_maps(gl_model* m, int component, int h, int w, const float* alpha_x_host, const float* alpha_y_host, double pitch) {
+  if (!m || !alpha_x_host || !alpha_y_host) return fail(GL_EINVAL, "null argument");
+  if (component < 0 || component >= m->n_lens || m->comps[component].kind != K_INTERPOL_MASS)
+    return fail(GL_EINVAL, "component %d is not a GL_INTERPOL_MASS lens", component);
+  if (h < 1 || h > GL_INTERPOL_MAX_SIDE || w < 1 || w > GL_INTERPOL_MAX_SIDE)
+    return fail(GL_EINVAL, "deflection maps of %d x %d pixels: height and width must lie in 1..%d", h, w, GL_INTERPOL_MAX_SIDE);
+  if (!(std::isfinite(pitch) && pitch > 0.0 && std::isfinite((float)(1.0 / pitch)) && (float)(1.0 / pitch) > 0.f))
+    return fail(GL_EINVAL, "pitch %g is not finite and > 0", pitch);
+  for (size_t i = 0; i < (size_t)h * w; ++i)
+    if (!std::isfinite(alpha_x_host[i]) || !std::isfinite(alpha_y_host[i])) return fail(GL_EINVAL, "deflection map pixel %zu is not finite", i);
+  // both maps in one buffer, each with the two-pixel zero apron of gl_model_set_light_image; everything that can refuse the call
+  // has done so by here, and the slot changes only after the upload
+  const int ws = w + 2 * glp::INT_APRON, hs = h + 2 * glp::INT_APRON;
+  const size_t plane = (size_t)hs * ws;
+  std::vector<float> padded(2 * plane, 0.f);
+  for (int j = 0; j < h; ++j) {
+    const size_t to = (size_t)(j + glp::INT_APRON) * ws + glp::INT_APRON;
+    std::copy(alpha_x_host + (size_t)j * w, alpha_x_host + (size_t)(j + 1) * w, padded.begin() + to);
+    std::copy(alpha_y_host + (size_t)j * w, alpha_y_host + (size_t)(j + 1) * w, padded.begin() + plane + to);
+  }
+  const int slot = m->comps[component].iparam;
+  glk::DevBuf<float> fresh;
+  GL_HIP(fresh.upload(padded.data(), padded.size()));
+  if (!m->d_interp_mass) GL_HIP(m->d_interp_mass.alloc(m->interp_mass.size()));
+  std::vector<InterpMassDev> tabs = m->interp_mass;
+  tabs[slot] = InterpMassDev{fresh.get(), fresh.get() + plane, h, w, (float)(1.0 / pitch)};
+  GL_HIP(m->d_interp_mass.write(tabs.data(), tabs.size()));
+  const bool first = !m->interp_mass_buf[slot];
+  m->interp_mass_buf[slot] = std::move(fresh);
+  m->interp_mass = std::move(tabs);
+  if (first) ++m->n_interp_mass_set;
   return GL_OK;
 }
 

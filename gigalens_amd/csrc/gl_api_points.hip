@@ -39,6 +39,7 @@ PosArgs point_args(const gl_model* m, const float* params, int B) {
   a.gal_table = m->d_gal_table;
   a.gal_static = m->d_gal_static;
   a.series = m->d_series;
+  a.interp_mass = m->d_interp_mass;
   return a;
 }
 
@@ -62,6 +63,8 @@ int refuse_potential_lenses(const gl_model* m) {
     if (kind == GL_USER_MASS)
       return fail(GL_EUNSUPPORTED, "lens %d is a user-written body (or a run-time compiled ScalingRelation member loop): "
                                    "a body defines the deflection only, no potential", l);
+    if (kind == GL_INTERPOL_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d is an interpolated lens (INTERPOL_SCALED): its maps hold the deflection, no potential", l);
     if (!potential_kind(kind) && kind != GL_SCALED) return fail(GL_EUNSUPPORTED, "lens %d: kind %d has no potential", l, kind);
   }
   return GL_OK;
@@ -342,6 +345,24 @@ int gl_profile_hessian(const gl_component* comp, const float* x, const float* y,
   const long long total = (long long)n_pts * B;
   hipLaunchKernelGGL(gl_profile_hessian_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream,
                      cd, x, y, (long long)n_pts, B, xy_batched, params, out);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+int gl_interpol_mass_eval(const gl_component* comp, int h, int w, const float* alpha_x_dev, const float* alpha_y_dev, double pitch,
+                          const float* x, const float* y, int64_t n_pts, int B, int xy_batched, const float* params, float* out0,
+                          float* out1, int hessian, void* hip_stream) {
+  if (!comp || !alpha_x_dev || !alpha_y_dev || !x || !y || !params || !out0 || (!hessian && !out1)) return fail(GL_EINVAL, "null argument");
+  if (comp->kind != GL_INTERPOL_MASS) return fail(GL_EINVAL, "kind %d is not GL_INTERPOL_MASS", comp->kind);
+  if (n_pts <= 0 || B <= 0) return fail(GL_EINVAL, "n_pts and B must be positive");
+  if (h < 1 || h > GL_INTERPOL_MAX_SIDE || w < 1 || w > GL_INTERPOL_MAX_SIDE)
+    return fail(GL_EINVAL, "deflection maps of %d x %d pixels: height and width must lie in 1..%d", h, w, GL_INTERPOL_MAX_SIDE);
+  if (!(std::isfinite(pitch) && pitch > 0.0 && std::isfinite((float)(1.0 / pitch)) && (float)(1.0 / pitch) > 0.f))
+    return fail(GL_EINVAL, "pitch %g is not finite and > 0", pitch);
+  const InterpMassDev tb{alpha_x_dev, alpha_y_dev, h, w, (float)(1.0 / pitch)};
+  const long long total = (long long)n_pts * B;
+  hipLaunchKernelGGL(gl_interpol_mass_point_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, tb, x,
+                     y, (long long)n_pts, B, xy_batched, params, out0, out1, hessian);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -718,6 +739,8 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
   if (m->has_user) {
     void* args[] = {&a, &g};
     GL_HIP(hipModuleLaunchKernel(m->user_point_fn[5], (unsigned)map_blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr));
+  } else if (m->n_interp_mass) {  // (the build that carries the interpolated lens: gl_images.hip.h)
+    hipLaunchKernelGGL(gl_img_map_im_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
   } else {
     hipLaunchKernelGGL(gl_img_map_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
   }
@@ -725,6 +748,8 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
   if (m->has_user) {
     void* args[] = {&a, &g};
     GL_HIP(hipModuleLaunchKernel(m->user_point_fn[6], (unsigned)pairs, 1, 1, 64, 1, 1, 0, stream, args, nullptr));
+  } else if (m->n_interp_mass) {
+    hipLaunchKernelGGL(gl_img_newton_im_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, a, g);
   } else {
     hipLaunchKernelGGL(gl_img_newton_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, a, g);
   }
@@ -811,7 +836,8 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
   g.seg = seg; g.cau = cau; g.kind = kind;
   g.n_seg = n_seg; g.n_dropped = n_dropped; g.n_flagged = n_flagged; g.open = open;
   g.area = area;
-  const bool cat = m->n_scaled > 0;  // catalogues take the build whose evaluation is a function call (gl_critical.hip.h, crit_eval)
+  // catalogues and interpolated lenses take the build whose evaluation is a function call (gl_critical.hip.h, crit_eval)
+  const bool cat = m->n_scaled > 0 || m->n_interp_mass > 0;
   if (cat) hipLaunchKernelGGL(gl_crit_map_kernel<true>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
   else hipLaunchKernelGGL(gl_crit_map_kernel<false>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
   hipLaunchKernelGGL(gl_crit_scan_kernel, dim3((unsigned)B), dim3(CRIT_WG), 0, stream, g);
@@ -901,6 +927,9 @@ int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, 
   for (int l = 0; l < m->n_lens; ++l)
     if (m->comps[l].kind == K_SCALED)
       return fail(GL_EUNSUPPORTED, "lens %d: galaxy catalogues (GL_SCALED) are not served on lens planes", l);
+  for (int l = 0; l < m->n_lens; ++l)
+    if (m->comps[l].kind == K_INTERPOL_MASS)
+      return fail(GL_EUNSUPPORTED, "lens %d: an interpolated lens (GL_INTERPOL_MASS) is not served on lens planes", l);
   for (int c = m->n_lens; c < (int)m->comps.size(); ++c) {
     const int kind = m->comps[c].kind;
     if (kind != K_SERSIC && kind != K_SERSIC_ELLIPSE && kind != K_CORE_SERSIC)

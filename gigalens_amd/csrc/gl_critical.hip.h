@@ -75,7 +75,7 @@ __device__ inline float crit_vx(const CritArgs& g, int c) { return g.x_lo + (flo
 __device__ inline float crit_vy(const CritArgs& g, int r) { return g.y_lo + (float)r * g.hy; }
 
 // D = det(I - H), beta and 1 - kappa of sample b at one point (H with the dPIS convergence excess).  CAT = false is the build for
-// models without a GL_SCALED catalogue: without the member loop in the switch of lens_point the evaluation fits the 256 VGPRs
+// models without a GL_SCALED catalogue or a GL_INTERPOL_MASS lens: without their cases in the switch of lens_point the evaluation fits the 256 VGPRs
 // inline; with it (CAT = true) it is a function call, which keeps the kernels free of register spills.
 template <bool CAT>
 __device__ inline float crit_eval_impl(const PosArgs& a, int b, float px, float py, float c, float& bx, float& by, float& omk) {

@@ -67,7 +67,8 @@ __device__ __forceinline__ float z_eval_x(const ZCol& c, float z) {
 
 // ---- per-sample prep: raw parameter rows -> derived constants --------------------------------
 // derived block `d` of one component from its slice `p` of the constrained row: the one per-kind switch of the front end
-__device__ __forceinline__ void prep_component(const CompDesc& cd, const float* p, float* d, const InterpDev* __restrict__ interp) {
+__device__ __forceinline__ void prep_component(const CompDesc& cd, const float* p, float* d, const InterpDev* __restrict__ interp,
+                                               const InterpMassDev* __restrict__ interp_mass) {
   switch (cd.kind) {
     case K_EPL: epl_prep<float>(p, cd.iparam, d); break;
     case K_SIE: sie_prep<float>(p, d); break;
@@ -79,6 +80,7 @@ __device__ __forceinline__ void prep_component(const CompDesc& cd, const float* 
     case K_SERIES: d[0] = p[0]; d[1] = p[1]; d[2] = d[3] = 0.f; break;
     case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, d); break;
     case K_TNFW: tnfw_prep<float>(p, d); break;
+    case K_INTERPOL_MASS: interpmass_prep<float>(p, interp_mass[cd.iparam], d); break;
     case K_CORE_SERSIC: core_sersic_prep<float>(p, d); break;
     case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, d); break;
     case K_SERSIC: sersic_prep<float>(p, false, d); break;
@@ -96,7 +98,8 @@ __global__ void __launch_bounds__(128) gl_prep_kernel(const CompDesc* __restrict
                                                       const ZCol* __restrict__ zcols, const int* __restrict__ src,
                                                       const float* __restrict__ const_row, int P, int B,
                                                       float* __restrict__ params_out, float* __restrict__ derived, int D,
-                                                      int* __restrict__ cost, int cost_comp, const InterpDev* __restrict__ interp) {
+                                                      int* __restrict__ cost, int cost_comp, const InterpDev* __restrict__ interp,
+                                                      const InterpMassDev* __restrict__ interp_mass) {
   int i = blockIdx.x * 128 + threadIdx.x;
   if (i >= B * n_comp) return;
   int b = i / n_comp, c = i - b * n_comp;
@@ -114,7 +117,7 @@ __global__ void __launch_bounds__(128) gl_prep_kernel(const CompDesc* __restrict
     p = po;
   }
   float* d = derived + (size_t)b * D + cd.d_off;
-  prep_component(cd, p, d, interp);
+  prep_component(cd, p, d, interp, interp_mass);
   if (cost && c == cost_comp) cost[b] = reinterpret_cast<const int*>(d)[EPL_KI];
 }
 
@@ -240,7 +243,8 @@ __global__ void __launch_bounds__(256) gl_prep_wave_kernel(const CompDesc* __res
                                                            int P, int B, float* __restrict__ params_out,
                                                            float* __restrict__ derived, int D, int* __restrict__ cost,
                                                            int cost_comp, int* __restrict__ order, int row_lds, int split_rank,
-                                                           const InterpDev* __restrict__ interp) {
+                                                           const InterpDev* __restrict__ interp,
+                                                           const InterpMassDev* __restrict__ interp_mass) {
   // Cost-ordered dispatch without a launch of its own: with `order` the grid carries ONE extra workgroup that sorts the samples
   // by the trip count of their EPL series while the others build the samples' constants.  It needs no result of theirs: the count
   // depends on (e1, e2) alone (epl_cost), which it takes from the parameter rows -- or, on the z path, through the two columns'
@@ -314,7 +318,7 @@ __global__ void __launch_bounds__(256) gl_prep_wave_kernel(const CompDesc* __res
     } else if (cd.kind == K_SHAPELETS) {  // the four constants here; the amplitude blocks below, by the whole wavefront
       d[SHP_CX] = p[1]; d[SHP_CY] = p[2]; d[SHP_IB] = 1.f / p[0]; d[SHP_NMAX] = (float)cd.iparam;
     } else {
-      prep_component(cd, p, d, interp);
+      prep_component(cd, p, d, interp, interp_mass);
     }
     if (cost && lane == cost_comp) cost[b] = K;
   }

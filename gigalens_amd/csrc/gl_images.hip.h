@@ -55,7 +55,9 @@ __device__ inline bool lens_singular_at(const CompDesc& cd, const float* p, floa
 __device__ inline float img_vx(const ImgArgs& g, int c) { return g.x_lo + (float)c * g.hx; }
 __device__ inline float img_vy(const ImgArgs& g, int r) { return g.y_lo + (float)r * g.hy; }
 
-__global__ void __launch_bounds__(256) gl_img_map_kernel(PosArgs a, ImgArgs g) {
+// IM: the build for models that hold an interpolated lens (gl_positions.hip.h lens_point); the kernels of every other model are
+// compiled without it and compute bit for bit what they did before that lens existed
+template <bool IM> __device__ __forceinline__ void img_map_body(const PosArgs& a, const ImgArgs& g) {
   const int V1 = g.n + 1;
   const long long V = (long long)V1 * V1;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -64,13 +66,15 @@ __global__ void __launch_bounds__(256) gl_img_map_kernel(PosArgs a, ImgArgs g) {
   const int r = v / V1, c = v - r * V1;
   const float x = img_vx(g, c), y = img_vy(g, r);
   float bx = x, by = y;
-  lens_deflections(a, b, x, y, [&](const CompDesc& cd, const float* p, float ax, float ay) {
+  lens_deflections<IM>(a, b, x, y, [&](const CompDesc& cd, const float* p, float ax, float ay) {
     bx -= lens_singular_at(cd, p, x, y) ? __builtin_nanf("") : ax;
     by -= ay;
   });
   if (!(isfinite(bx) && isfinite(by))) bx = by = __builtin_nanf("");
   g.map[i] = float2{bx, by};
 }
+__global__ void __launch_bounds__(256) gl_img_map_kernel(PosArgs a, ImgArgs g) { img_map_body<false>(a, g); }
+__global__ void __launch_bounds__(256) gl_img_map_im_kernel(PosArgs a, ImgArgs g) { img_map_body<true>(a, g); }
 
 // edge function of the edge (p, q) at s, always evaluated with p = the vertex of lower index: the two triangles that share an
 // edge then see bitwise the same value (up to an exact negation), which makes the tie rule below exact
@@ -171,11 +175,12 @@ __global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
 
 // beta and Hessian (f_xx, f_xy, f_yx, f_yy; the dPIS convergence excess included) at one point
 // (c: the deflection scale of the source's plane; 1 leaves every value as the sum formed it)
+template <bool IM = true>
 __device__ inline void img_lens_eval(const PosArgs& a, int b, float px, float py, float& bx, float& by, float* h, float c = 1.f) {
   bx = px;
   by = py;
   h[0] = h[1] = h[2] = h[3] = 0.f;
-  lens_jets(a, b, px, py, [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
+  lens_jets<IM>(a, b, px, py, [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
     bx -= ax.v;
     by -= ay.v;
     h[0] += ax.d[0] + ex; h[1] += ax.d[1]; h[2] += ay.d[0]; h[3] += ay.d[1] + ex;
@@ -183,7 +188,16 @@ __device__ inline void img_lens_eval(const PosArgs& a, int b, float px, float py
   lens_rescale(c, px, py, bx, by, h);
 }
 
-__global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g) {
+// ... with the interpolated lens in the switch, always a function call (the device of crit_eval_cat in gl_critical.hip.h): inline,
+// twice, beside the Newton state it does not fit the 256 VGPRs
+static __device__ __attribute__((noinline)) void img_lens_eval_im(const PosArgs& a, int b, float px, float py, float& bx, float& by, float* h, float c) {
+  img_lens_eval<true>(a, b, px, py, bx, by, h, c);
+}
+template <bool IM> __device__ __forceinline__ void img_lens_eval_of(const PosArgs& a, int b, float px, float py, float& bx, float& by, float* h, float c) {
+  if constexpr (IM) img_lens_eval_im(a, b, px, py, bx, by, h, c);
+  else img_lens_eval<false>(a, b, px, py, bx, by, h, c);
+}
+template <bool IM> __device__ __forceinline__ void img_newton_body(const PosArgs& a, const ImgArgs& g) {
   __shared__ float rx[IMG_MAXC], ry[IMG_MAXC], rmu[IMG_MAXC];
   __shared__ int rok[IMG_MAXC], order[IMG_MAXC];
   __shared__ int n_keep_s, n_bad_s;
@@ -199,7 +213,7 @@ __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g)
     x = s0.x;
     y = s0.y;
     float bx, by, h[4];
-    img_lens_eval(a, b, x, y, bx, by, h, c);
+    img_lens_eval_of<IM>(a, b, x, y, bx, by, h, c);
     float r_x = sx - bx, r_y = sy - by, r2 = r_x * r_x + r_y * r_y;
     // the affine preimage misses beta_s by more than a cell side: the triangle straddles a singular or discontinuous point of
     // the deflection (the centre of an SIS / SIE / EPL with gamma >= 2), not a smooth neighbourhood of an image; if such a
@@ -222,7 +236,7 @@ __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g)
       }
       const float nx = x + dx, ny = y + dy;
       float nbx, nby, nh[4];
-      img_lens_eval(a, b, nx, ny, nbx, nby, nh, c);
+      img_lens_eval_of<IM>(a, b, nx, ny, nbx, nby, nh, c);
       const float nr_x = sx - nbx, nr_y = sy - nby, nr2 = nr_x * nr_x + nr_y * nr_y;
       if (conv) {  // the polishing step
         if (nr2 <= r2) { x = nx; y = ny; for (int k = 0; k < 4; ++k) h[k] = nh[k]; }
@@ -278,5 +292,7 @@ __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g)
     o[2] = src >= 0 ? rmu[src] : nan;
   }
 }
+__global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g) { img_newton_body<false>(a, g); }
+__global__ void __launch_bounds__(64) gl_img_newton_im_kernel(PosArgs a, ImgArgs g) { img_newton_body<true>(a, g); }
 
 }  // namespace glk

@@ -15,6 +15,7 @@
 #include "gl_dpie.h"
 #include "gl_extra.h"
 #include "gl_interp.h"
+#include "gl_interp_mass.h"
 #include "gl_vec.hip.h"
 #include "gl_members.hip.h"
 #include "gl_series.h"
@@ -53,6 +54,8 @@ struct SeriesDev {
 
 // image table of one K_INTERPOL light (gl_model_set_light_image): tab[(h + 4)][(w + 4)] with its zero apron; CompDesc::iparam indexes it
 using InterpDev = InterpTab<float>;
+// deflection maps of one K_INTERPOL_MASS lens (gl_model_set_lens_maps): two such tables and 1 / pitch; CompDesc::iparam indexes it
+using InterpMassDev = InterpMassTab<float>;
 
 // thread i of a (point, sample) launch, sample fastest: its point, its sample and the point's coordinates, which are either one
 // list [n_pts] for all samples or a list per sample [n_pts][B] (xy_batched)
@@ -128,6 +131,7 @@ struct MainArgs {
   const float* nfw_tab;  // models with NFW lenses: the shared h(X) table (gl_host_tables.h), [kNfwNodes][2]; else null
   const float* src_scale;  // per-source deflection scales c_s [n_src] (beta_s = x - c_s sum alpha), or null: one source plane
   const InterpDev* interp;  // image tables of the K_INTERPOL lights, or null: the model has none
+  const InterpMassDev* interp_mass;  // deflection maps of the K_INTERPOL_MASS lenses, or null: the model has none
   const float* neutral;  // gl_clusterw_kernel: constant blocks of an unused component slot, [NFW (4) | Sersic (16)]; else null
   float grid_rmax;       // largest |(x, y)| of the pixel grid (gl_shp.hip.h: the bound on the shear's deflection)
   int blk_w;             // table-mode shapelet kernel: image width when a wave-tile is an 8-row x 16-column BLOCK of the image (0: 128 consecutive pixels)
@@ -497,6 +501,13 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
             for (int t = 0; t < T; ++t) { float ax, ay; tnfw_fwd<float>(d, x[t], y[t], ax, ay); bx[t] -= ax; by[t] -= ay; }
           }
           break;
+        case K_INTERPOL_MASS:
+          if constexpr (XF) {
+            const InterpMassDev tb = a.interp_mass[comps[l].iparam];
+#pragma unroll
+            for (int t = 0; t < T; ++t) { float ax, ay; interpmass_fwd<float>(d, tb, x[t], y[t], ax, ay); bx[t] -= ax; by[t] -= ay; }
+          }
+          break;
         case K_SERIES: if constexpr (DP) {  // alpha = theta_E sum_n C_n(pixel) (r_cut - r0)^n   (series_profile.py:76-95)
           const SeriesDev sv = a.series[comps[l].flags];
           const float te = d[0], dl = d[1] - sv.r0;
@@ -862,6 +873,18 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
 #pragma unroll
             for (int t = 0; t < T; ++t) tnfw_vjp<float>(d, x[t], y[t], gbx[t], gby[t], acc);
             wave_acc<TNF_NACC>(acc, ac, cd.a_off);
+          } break;
+          case K_INTERPOL_MASS: if constexpr (XF) {
+            const InterpMassDev tb = a.interp_mass[cd.iparam];
+            float acc[IM_NACC];
+#pragma unroll
+            for (int k = 0; k < IM_NACC; ++k) acc[k] = 0.f;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+              float ux = 0.f, uy = 0.f;  // (the cotangent of a grid point: unused)
+              interpmass_vjp<float>(d, tb, x[t], y[t], gbx[t], gby[t], acc, ux, uy);
+            }
+            wave_acc<IM_NACC>(acc, ac, cd.a_off);
           } break;
           case K_SERIES: if constexpr (DP) {
             const SeriesDev sv = a.series[cd.flags];

@@ -30,6 +30,7 @@ using glk::CompDesc;
 using glk::CatDev;
 using glk::SeriesDev;
 using glk::InterpDev;
+using glk::InterpMassDev;
 using glk::ZCol;
 
 namespace glk {
@@ -221,6 +222,11 @@ struct gl_model {
   std::vector<glk::DevBuf<float>> interp_buf;  // the owner of each slot's table, [(h + 4)][(w + 4)] with its zero apron
   int n_interp = 0, n_interp_set = 0;
   glk::DevBuf<InterpDev> d_interp;
+  // interpolated lenses (gl_model_set_lens_maps): the same per GL_INTERPOL_MASS component; one buffer holds both maps of a slot
+  std::vector<InterpMassDev> interp_mass;
+  std::vector<glk::DevBuf<float>> interp_mass_buf;  // [2][(h + 4)][(w + 4)]: alpha_x, alpha_y, each with its zero apron
+  int n_interp_mass = 0, n_interp_mass_set = 0;
+  glk::DevBuf<InterpMassDev> d_interp_mass;
   // linear amplitudes (lstsq_simulate): channel k of the basis stack <-> packed parameter column
   std::vector<int> lin_cols;
   glk::DevBuf<int> d_lin_cols;

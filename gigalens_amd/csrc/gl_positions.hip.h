@@ -43,6 +43,8 @@ struct PosArgs {
   const float* gal_static;  // [G][DP_NS]
   // series-expansion lenses (gl_lens_maps on the model's own grid only)
   const SeriesDev* series;
+  // deflection maps of the K_INTERPOL_MASS lenses (gl_interp_mass.h), indexed by CompDesc::iparam
+  const InterpMassDev* interp_mass;
 };
 
 // parameters of one lens as the point kernels hold them: 7 for the built-in kinds; a user-written body (the run-time compiled
@@ -53,10 +55,10 @@ constexpr int POS_MAXP = 16;
 constexpr int POS_MAXP = 7;
 #endif
 
-// deflection of one lens at (x, y) with raw parameters p, generic in the real type (catalogues are summed).  CATS = false: for
-// models that hold no catalogue (lens planes refuse them) -- the member loop indexes p at run time, which alone keeps the
+// deflection of one closed-form lens (or catalogue) at (x, y) with raw parameters p, generic in the real type (catalogues are summed).  CATS = false: for
+// models that hold no catalogue and no interpolated lens (lens planes refuse them) -- the member loop indexes p at run time, which alone keeps the
 // parameter array of a caller in private memory
-template <class R, bool CATS = true> __device__ void lens_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y, R& ax, R& ay) {
+template <class R, bool CATS = true> __device__ void lens_point_closed(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y, R& ax, R& ay) {
   using namespace glp;
   switch (cd.kind) {
 #ifdef GL_HAVE_USER_POINT
@@ -92,6 +94,24 @@ template <class R, bool CATS = true> __device__ void lens_point(const PosArgs& a
     default: { R d[4]; sis_prep<R>(p, d); sis_fwd<R>(d, x, y, ax, ay); } break;
   }
 }
+// ... and with the interpolated lens (gl_interp_mass.h) in front of it.  The lens is a case of its own function, not of the switch
+// above: as one more case it changed which multiply-adds the compiler fuses in the OTHER cases (the solver, hessian_vjp and the
+// position likelihood of models without such a lens then differed from before in their last bits); in front of the unchanged
+// function they compute what they did.  CATS = false (lens planes, which refuse the lens) leaves it out
+// IM = false: a build for models that hold no such lens (the lens-equation solver keeps one: its kernels then compute bit for bit
+// what they did before the lens existed, and what is generated from its images stays what it was)
+template <class R, bool CATS = true, bool IM = CATS> __device__ void lens_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y, R& ax, R& ay) {
+  if constexpr (IM) {
+    if (cd.kind == glp::K_INTERPOL_MASS) {
+      R d[glp::IM_ND];
+      const InterpMassDev tb = a.interp_mass[cd.iparam];
+      glp::interpmass_prep<R>(p, tb, d);
+      glp::interpmass_fwd<R>(d, tb, x, y, ax, ay);
+      return;
+    }
+  }
+  lens_point_closed<R, CATS>(a, cd, p, x, y, ax, ay);
+}
 // what the reference's analytic dPIS Hessian adds to f_xx and f_yy on top of the derivative of the deflection
 // (piemd.py:62-83, see dpis_kappa_excess); zero for every other profile
 template <class R1> __device__ R1 lens_kappa_excess(const PosArgs& a, const CompDesc& cd, const R1* p, float x, float y) {
@@ -124,7 +144,7 @@ template <class R1> __device__ R1 lens_kappa_excess(const PosArgs& a, const Comp
 // parameters are loaded (or deals with it in its own way).  The caller keeps its own sums: the order of its additions is its own.
 // lens_deflections is the same walk on float, f(cd, p, ax, ay), for the kernels that want beta alone.
 using Jet2 = gld::Dual<float, 2>;
-template <bool CATS = true, class F>
+template <bool CATS = true, bool IM = CATS, class F>
 __device__ __forceinline__ void lens_jet(const PosArgs& a, const CompDesc& cd, int b, float px, float py, F&& f) {
   using R = Jet2;
   R x(px), y(py);
@@ -134,28 +154,28 @@ __device__ __forceinline__ void lens_jet(const PosArgs& a, const CompDesc& cd, i
   float pf[POS_MAXP];
   for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
   R ax, ay;
-  lens_point<R, CATS>(a, cd, p, x, y, ax, ay);
+  lens_point<R, CATS, IM>(a, cd, p, x, y, ax, ay);
   const float ex = lens_kappa_excess<float>(a, cd, pf, px, py);
   f(cd, pf, ax, ay, ex);
 }
-template <bool CATS = true, class F, class Pre>
+template <bool CATS = true, bool IM = CATS, class F, class Pre>
 __device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f, Pre&& pre) {
   for (int l = 0; l < a.n_lens; ++l) {
     const CompDesc cd = a.comps[l];
     if (pre(cd)) continue;
-    lens_jet<CATS>(a, cd, b, px, py, f);
+    lens_jet<CATS, IM>(a, cd, b, px, py, f);
   }
 }
-template <class F> __device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f) {
-  lens_jets(a, b, px, py, f, [](const CompDesc&) { return false; });
+template <bool IM = true, class F> __device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f) {
+  lens_jets<true, IM>(a, b, px, py, f, [](const CompDesc&) { return false; });
 }
-template <class F> __device__ __forceinline__ void lens_deflections(const PosArgs& a, int b, float px, float py, F&& f) {
+template <bool IM = true, class F> __device__ __forceinline__ void lens_deflections(const PosArgs& a, int b, float px, float py, F&& f) {
   for (int l = 0; l < a.n_lens; ++l) {
     const CompDesc cd = a.comps[l];
     float p[POS_MAXP];
     for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)b * a.P + cd.p_off + k];
     float ax, ay;
-    lens_point<float>(a, cd, p, px, py, ax, ay);
+    lens_point<float, true, IM>(a, cd, p, px, py, ax, ay);
     f(cd, p, ax, ay);
   }
 }
@@ -263,6 +283,34 @@ __global__ void __launch_bounds__(64) gl_profile_hessian_kernel(CompDesc cd, con
   lens_jet(one, cd, at.b, at.x, at.y, [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
     out[i] = ax.d[0] + ex; out[st + i] = ax.d[1]; out[2 * st + i] = ay.d[0]; out[3 * st + i] = ay.d[1] + ex;
   });
+}
+
+// MassProfile.deriv / .hessian of one free-standing interpolated lens at plugin level (tables handed in by value):
+// hessian == 0: out0 = alpha_x, out1 = alpha_y, [n_pts][B]; else out0[4][n_pts][B] = f_xx, f_xy, f_yx, f_yy
+__global__ void __launch_bounds__(64) gl_interpol_mass_point_kernel(InterpMassDev tb, const float* __restrict__ x,
+                                                                   const float* __restrict__ y, long long n_pts, int B,
+                                                                   int xy_batched, const float* __restrict__ params,
+                                                                   float* __restrict__ out0, float* __restrict__ out1, int hessian) {
+  long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n_pts * B) return;
+  const PointAt at(i, B, xy_batched, x, y);
+  const float* pf = params + (size_t)at.b * 3;
+  if (!hessian) {
+    float d[glp::IM_ND], ax, ay;
+    glp::interpmass_prep<float>(pf, tb, d);
+    glp::interpmass_fwd<float>(d, tb, at.x, at.y, ax, ay);
+    out0[i] = ax;
+    out1[i] = ay;
+    return;
+  }
+  using R = Jet2;
+  R xd(at.x), yd(at.y), p[3] = {R(pf[0]), R(pf[1]), R(pf[2])}, d[glp::IM_ND], ax, ay;
+  xd.d[0] = 1.f;
+  yd.d[1] = 1.f;
+  glp::interpmass_prep<R>(p, tb, d);
+  glp::interpmass_fwd<R>(d, tb, xd, yd, ax, ay);
+  const long long st = n_pts * B;
+  out0[i] = ax.d[0]; out0[st + i] = ax.d[1]; out0[2 * st + i] = ay.d[0]; out0[3 * st + i] = ay.d[1];
 }
 
 // ScalingRelation.hessian at plugin level (scaling_relation.py:72-83): sum of the member Hessians, out[4][n_pts][B]

@@ -28,6 +28,7 @@ enum Kind : int {
   K_SERIES = 10,                        // series expansion of a (scaled) dPIE in r_cut (gl_series.h); iparam = order, flags = field slot
   K_NFW_ELLIPSE = 11, K_TNFW = 12,      // gl_extra.h
   K_USER_MASS = 13,                     // a body the user wrote (gl_user.hip): iparam = its parameter count, flags = body slot of the model
+  K_INTERPOL_MASS = 14,                 // two deflection maps on a grid (gl_interp_mass.h): iparam = table slot of the model
   K_SERSIC = 16, K_SERSIC_ELLIPSE = 17, K_SHAPELETS = 18,
   K_CORE_SERSIC = 19,                   // gl_extra.h
   K_USER_LIGHT = 20,                    // same for a light profile (amplitude: whatever the body makes of its parameters)
@@ -94,6 +95,7 @@ GL_HD int kind_num_params(int kind, int iparam) {
     case K_SERIES: return (iparam >= 0 && iparam <= 5) ? 2 : -1;       // theta_E, r_cut
     case K_NFW_ELLIPSE: return 6;
     case K_TNFW: return 5;
+    case K_INTERPOL_MASS: return 3;
     case K_CORE_SERSIC: return 10;
     case K_INTERPOL: return 5;
     case K_SERSIC: return 5;
@@ -118,6 +120,7 @@ GL_HD int kind_num_derived(int kind, int iparam) {
     case K_SERIES: return 4;
     case K_NFW_ELLIPSE:
     case K_TNFW: return 8;
+    case K_INTERPOL_MASS: return 8;  // IM_ND
     case K_CORE_SERSIC: return 16;
     case K_INTERPOL: return 8;  // INT_ND
     case K_SERSIC:
@@ -165,6 +168,7 @@ GL_HD int kind_num_acc(int kind, int iparam) {
     case K_SERIES: return 2;
     case K_NFW_ELLIPSE: return 6;
     case K_TNFW: return 5;
+    case K_INTERPOL_MASS: return 3;  // IM_NACC
     case K_CORE_SERSIC: return 10;
     case K_INTERPOL: return 5;  // INT_NACC
     case K_SERSIC:

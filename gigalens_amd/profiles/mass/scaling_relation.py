@@ -90,6 +90,9 @@ class ScalingRelation(MassProfile):
 
     def __init__(self, profile: MassProfile, scaling_params: List, lum_star: float,
                  scaling_params_power: Dict[str, float], galaxy_catalogue: Dict[str, List], chunk_size=None, **kwargs):
+        if getattr(profile, "_kind", 0) == _native.GL_INTERPOL_MASS:
+            raise _native.UnsupportedLensError(f"ScalingRelation over {profile.name}: an interpolated lens is one fixed pair of "
+                                               "deflection maps, not a population of scaled members")
         self.profile = profile
         self._name = f"Scaled-{profile.name}"
         self._params = list(scaling_params)

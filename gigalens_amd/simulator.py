@@ -193,6 +193,8 @@ class LensSimulator(LensSimulatorInterface):
                 self._model.set_series(i, lens.series_var_0, lens._coefs)
             elif getattr(lens, "_kind", 0) == 9:  # galaxy catalogues of ScalingRelation lenses (fused dPIE-family kernels)
                 self._model.set_catalogue(i, *lens._catalogue())
+            elif getattr(lens, "_kind", 0) == _native.GL_INTERPOL_MASS:  # the deflection maps of an Interpolated lens
+                self._model.set_lens_maps(i, lens.alpha_x, lens.alpha_y, lens.pitch)
         for i, light in enumerate(list(phys_model.lens_light) + list(phys_model.source_light)):
             if getattr(light, "_kind", 0) == _native.GL_INTERPOL:  # the image of an Interpolated light, a constant of the model
                 self._model.set_light_image(len(phys_model.lenses) + i, light.image)
@@ -210,6 +212,8 @@ class LensSimulator(LensSimulatorInterface):
             if getattr(lens, "_kind", 0) == 10:
                 raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): a series expansion stores its field on the image-plane "
                                                    "grid, not at the ray's position on the lens's own plane: not served on lens planes")
+            if getattr(lens, "_kind", 0) == _native.GL_INTERPOL_MASS:
+                raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): an interpolated lens is not served on lens planes")
         for p in list(pm.lenses) + list(pm.lens_light) + list(pm.source_light):
             if not getattr(p, "_kind", 0):
                 raise _native.UnsupportedLensError(f"profile {p.name!r}: user-written bodies (hip_body) and run-time compiled member "
@@ -604,6 +608,8 @@ class LensSimulator(LensSimulatorInterface):
             if kind == 10:
                 raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): a series expansion stores its deflection on the pixel "
                                                    "grid only, no potential")
+            if kind == _native.GL_INTERPOL_MASS:
+                raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): deflection maps carry no potential")
             if not kind and getattr(lens, "profile", None) is not None and getattr(lens, "scaling_params", None) is not None:
                 raise _native.UnsupportedLensError(f"lens {i} ({lens.name}): a ScalingRelation compiled at run time as a member loop "
                                                    "(base profile outside the dPIE family) defines a deflection only, no potential")

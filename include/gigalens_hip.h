@@ -61,6 +61,8 @@ typedef enum gl_kind {
   GL_TNFW = 12,        /* tf/profiles/mass/tnfw.py:12   [Rs,alpha_Rs,r_trunc,center_x,center_y] */
   GL_USER_MASS = 13,   /* profile.py:63-82 as an extension point: a body the user wrote (gl_model_create_user); iparam = parameter
                           count, flags = index of the body */
+  GL_INTERPOL_MASS = 14, /* beyond the reference: a lens given as two deflection maps on a grid, interpolated (lenstronomy's
+                            INTERPOL_SCALED by name) [scale_factor,center_x,center_y]; maps attached with gl_model_set_lens_maps */
   /* light profiles: LightProfile.light (profile.py:24-60) */
   GL_SERSIC = 16,         /* tf/profiles/light/sersic.py:23-24 [R_sersic,n_sersic,center_x,center_y,Ie] */
   GL_SERSIC_ELLIPSE = 17, /* sersic.py:68-69 [R_sersic,n_sersic,e1,e2,center_x,center_y,Ie] */
@@ -366,6 +368,28 @@ int gl_model_set_catalogue(gl_model* m, int component, int base_kind, int n_gala
  * 1..GL_INTERPOL_MAX_SIDE, a pixel that is not finite.  gl_model_create_user answers GL_EUNSUPPORTED for a model that mixes
  * user-written profiles with GL_INTERPOL (the run-time compiled kernels carry no image tables). */
 int gl_model_set_light_image(gl_model* m, int component, int h, int w, const float* image_host);
+/* Deflection maps of a GL_INTERPOL_MASS lens (beyond the reference: every lens there is parametric).  With
+ *   u = (x - center_x) / pitch + (w - 1) / 2   (column coordinate; pitch = arcsec per map pixel, > 0)
+ *   v = (y - center_y) / pitch + (h - 1) / 2   (row coordinate)
+ * the lens deflects by  scale_factor * sum_j sum_i k(v - j) k(u - i) alpha_x[j][i]  (alpha_y likewise), the maps zero-extended over
+ * all integers and k Keys' cubic convolution kernel with a = -1/2 (no bilinear order, no rotation): C1 everywhere, zero once
+ * u < -2, u > w + 1, v < -2 or v > h + 1 -- a coordinate that is not finite included.  The Hessian of the lens is the derivative
+ * of this interpolant entry by entry (f_xy and f_yx are not symmetrised); there is no potential: gl_lens_potential, the Fermat
+ * potential and the time-delay term answer GL_EUNSUPPORTED, as do gl_model_set_lens_planes and gl_model_create_user beside
+ * user-written profiles.  The gradient calls differentiate with respect to the three parameters, not the map pixels.
+ *   alpha_x, alpha_y  HOST [h][w] (arcsec), copied with a two-pixel zero apron into a device buffer the model owns; shared by the
+ *                     whole batch.  A set-up call like gl_model_set_light_image.
+ * Every GL_INTERPOL_MASS lens needs its maps before gl_workspace_bytes / any compute call (GL_EINVAL otherwise).  A model that
+ * holds one runs the interpreter kernel in every mode.  GL_EINVAL: `component` is not a GL_INTERPOL_MASS lens, h or w outside
+ * 1..GL_INTERPOL_MAX_SIDE, a map value that is not finite, a pitch that is not finite and > 0; a refused call leaves the model
+ * as it was. */
+int gl_model_set_lens_maps(gl_model* m, int component, int h, int w, const float* alpha_x_host, const float* alpha_y_host, double pitch);
+/* MassProfile.deriv (hessian == 0: out0 = alpha_x, out1 = alpha_y, [n_pts][B]) or .hessian (hessian != 0: out0 [4][n_pts][B] =
+ * f_xx, f_xy, f_yx, f_yy, out1 unused) of a free-standing GL_INTERPOL_MASS lens on arbitrary points: arguments as gl_profile_eval,
+ * params [B,3]; alpha_x_dev / alpha_y_dev: DEVICE [(h+4)][(w+4)], each map with its two-pixel zero apron. */
+int gl_interpol_mass_eval(const gl_component* comp, int h, int w, const float* alpha_x_dev, const float* alpha_y_dev, double pitch,
+                          const float* x, const float* y, int64_t n_pts, int B, int xy_batched, const float* params, float* out0,
+                          float* out1, int hessian, void* hip_stream);
 /* LightProfile.light of a free-standing GL_INTERPOL component on arbitrary points: arguments as gl_profile_eval (basis == 0;
  * params [B,5]) or gl_profile_basis (basis != 0: amplitude 1, out [1][n_pts][B]); image_dev: DEVICE [(h+4)][(w+4)], the image
  * with its two-pixel zero apron. */
