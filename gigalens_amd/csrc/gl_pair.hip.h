@@ -10,8 +10,9 @@
 // `m ? a : b` selects per lane.  Transcendentals (v_rcp/sqrt/log/exp) have no packed form and are applied
 // per lane.  Supported components: EPL, SIE, SHEAR, SIS lenses; SERSIC / SERSIC_ELLIPSE lights (K_SERSIC in a kind list
 // selects the spherical fast path: only for models whose light profiles are ALL spherical, else K_SERSIC_ELLIPSE serves both).
-// Whole unmasked tiles run the select-free flavour of the bodies behind one wave-uniform guard; a wave whose guard fires leaves
-// that loop and does the tile, and the rest of its chunk, with the careful body of the ragged tiles (same bits either way).
+// Whole unmasked tiles run the select-free flavour of the bodies as straight-line code; each folds its guard predicate into
+// wave-private state, and a wave whose guard fired anywhere in its chunk throws its sums away after the last whole tile and does
+// the chunk again with the careful body of the ragged tiles (same bits either way).
 #pragma once
 #include "gl_static.hip.h"
 #include "gl_vec.hip.h"
@@ -158,17 +159,26 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
   // CHECK=false tiles are also SELECT-FREE (gl_vec.hip.h, FAST): the centre selects and the clamp of the EPL, the floors of the
   // Sersic VJP, the R0 == 0 selects of the SIS and the NaN -> 0 rule on the image are not emitted -- each is an unpacked
   // instruction per lane that every regular pixel passes unchanged.  Instead the forward bodies range-check what those selects
-  // look at into `worst`, and once the image m is known the tile asks whether ANY lane of the wave is out of range or has a NaN
-  // image: if so the tile returns false BEFORE it has added to st0, st1 or an accumulator, and the caller hands the same `base`
-  // to the careful (CHECK=true) body, which produces the same bits for a whole unmasked tile (w = 1).  8 instructions per pixel
-  // pair for the guard of EPL + Shear | Sersic against the 22 it replaces.
+  // look at into `guard_worst`, a per-lane running maximum that lives across the tiles of the chunk, and the lanes whose image
+  // pair holds a NaN are OR-ed into the scalar word `guard_nan`.  The tile itself is straight-line code: no vote, no branch, no
+  // early return.  The ONE wave-uniform test of that state comes after the chunk's last whole tile (below): a wave whose guard
+  // fired anywhere discards its sums and redoes the chunk with the careful (CHECK=true) body, which produces the same bits for a
+  // whole unmasked tile (w = 1).  On a singular tile the select-free pass may carry inf or NaN through its VJP: every address it
+  // forms is an input-independent one, and what it summed is thrown away.
+  // (with the branch gone the observation and error-map loads could be requested at the tile's head, beside the grid loads; written
+  // out that way the C2 step measured 13.001 against 13.005 M samples/s with the loads left where the compiler puts them, behind
+  // the series loop -- no gain, so they stay at their use.)
   // (requesting the NEXT whole tile's planes -- grid, observation, error map -- while a tile is worked on was tried in round 4, after
   // the shapelet kernel's dissection showed bare tile loads costing 1 400 cycles per wave-tile there: 147 VGPRs instead of 141 and
   // 0.0823 against 0.0819 ms per C2 step -- at three waves per SIMD the other waves already cover a tile's opening loads.)
-  auto tile = [&](int base, auto check_tag, auto err_tag) -> bool {
+  unsigned guard_worst = 0;            // FAST: this lane's running maximum of the range checks (guard_range) over the chunk
+  // FAST: the lanes of this wave that saw a NaN image pair in some tile of the chunk, the mask's two halves OR-ed into one word
+  // (only "any" is asked of it, and as a 64-bit mask it cost the EPL gradient kernels two more scalar-register spills)
+  unsigned guard_nan = 0;
+  auto tile = [&](int base, auto check_tag, auto err_tag) {
     constexpr bool CHECK = decltype(check_tag)::value;
     constexpr bool FAST = !CHECK;
-    unsigned worst = 0;  // FAST: the running maximum of the range checks (guard_range)
+    unsigned& worst = guard_worst;
     constexpr int ERR = decltype(err_tag)::value;
     const bool herr = ERR == 2 ? has_err : ERR == 1;
     unsigned jj[W], pidx[W];
@@ -227,8 +237,9 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
       m += sersic_fwd_v<V, ell, FAST>(dC[i], src ? bx : x, src ? by : y, sst[i], GRAD ? &worst : nullptr);  // (the floors are the VJP's)
     }, std::make_integer_sequence<int, NLIGHT>{});
     auto nanp = m != m;
-    if constexpr (FAST) {  // the guard: nothing of this tile has been added anywhere yet
-      if ((__builtin_amdgcn_ballot_w64(worst > kGuardWidth) | __builtin_amdgcn_ballot_w64(any_nan(m))) != 0) return false;
+    if constexpr (FAST) {  // the guard's NaN half: folded, not tested (the range half is already in guard_worst)
+      const unsigned long long nn = __builtin_amdgcn_ballot_w64(any_nan(m));
+      guard_nan |= (unsigned)nn | (unsigned)(nn >> 32);
       m = m * a.out_scale;
     } else {
       m = (nanp ? V(0.f) : m) * a.out_scale;  // NaN -> 0 (tf/simulator.py:140), then x det(T) (:156)
@@ -241,7 +252,7 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
       } else {
         if (valid[0]) row[pidx[0]] = m;
       }
-      return true;
+      return;
     }
     V gm;
     if (MODE == IMG_BWD) {
@@ -315,7 +326,6 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
         else sis_vjp_v<V, FAST>(dL[i], x, y, gbx, gby, accL + off);
       }, std::make_integer_sequence<int, NL>{});
     }
-    return true;
   };
   {
     // the per-sample part of the guard (sersic_fast_ok), and the test knob that sends every whole tile to the careful body
@@ -326,15 +336,27 @@ __global__ void __launch_bounds__(WG, WAVES) gl_pair_kernel(MainArgs a) {
       if constexpr (!is_user_code(lkind)) sample_ok = sample_ok && sersic_fast_ok(gder + comps[NL + i].d_off);
     }, std::make_integer_sequence<int, NLIGHT>{});
     const bool plain = !has_mask && !has_pix && sample_ok;
-    int base = p0;
-    if (GL_DBG(a.dbg, 1)) base = p1;
-    if (plain) {  // a tile whose guard fires is not counted in n_whole: the loop below takes over from that tile on
+    const int first = GL_DBG(a.dbg, 1) ? p1 : p0;
+    int base = first;
+    if (plain) {
       if (has_err) {
-        for (; base + WG * W <= p1; base += WG * W, ++n_whole)
-          if (!tile(base, std::false_type{}, std::integral_constant<int, 1>{})) break;
+        for (; base + WG * W <= p1; base += WG * W) tile(base, std::false_type{}, std::integral_constant<int, 1>{});
       } else {
-        for (; base + WG * W <= p1; base += WG * W, ++n_whole)
-          if (!tile(base, std::false_type{}, std::integral_constant<int, 0>{})) break;
+        for (; base + WG * W <= p1; base += WG * W) tile(base, std::false_type{}, std::integral_constant<int, 0>{});
+      }
+      n_whole = (base - first) / (WG * W);
+      // The guard, once per chunk and per wave: did any lane leave a range or see a NaN image in any whole tile?  (A function of
+      // the inputs alone: both halves are taken from each tile's forward pass, never from a sum.)  If so this wave forgets the
+      // select-free pass -- everything it touched is per lane until the epilogue, so no barrier -- and the careful loop below
+      // starts from the chunk's first pixel; IMG_FWD's pixels are stored again over the ones just written.
+      if (__builtin_amdgcn_ballot_w64(guard_worst > kGuardWidth) != 0 || guard_nan != 0) {
+#pragma unroll
+        for (int k = 0; k < NACC_L; ++k) accL[k] = V(0.f);
+#pragma unroll
+        for (int k = 0; k < NACC_C; ++k) accC[k] = V(0.f);
+        st0 = V(0.f); st1 = V(0.f); wsum = V(0.f);
+        n_whole = 0;
+        base = first;
       }
     }
     for (; base < p1; base += WG * W) tile(base, std::true_type{}, std::integral_constant<int, 2>{});

@@ -56,7 +56,8 @@ __device__ __forceinline__ float hsum(v2f a) { return a.x + a.y; }
 // The bodies below carry selects, clamps and floors that only act on singular inputs: a pixel exactly on a profile's centre,
 // a radius outside [1e-10, 1e10].  On a pixel pair each is an unpacked instruction per lane, and every regular pixel passes
 // through them unchanged.  With FAST they are not emitted; instead the value each of them looks at is range-checked into one
-// running word, and the caller (gl_pair.hip.h) abandons the tile for the careful body when any lane of the wave is out of range.
+// running word per lane, kept across the whole tiles of a chunk; after the last of them the caller (gl_pair.hip.h) asks once
+// whether any lane of the wave went out of range, and if so redoes the wave's chunk with the careful body.
 // The check: positive floats order like their bit patterns, so  lo <= v <= hi  is  bits(v) - bits(lo) <= bits(hi) - bits(lo)
 // in unsigned arithmetic; zero, denormals below lo, negative numbers, inf and NaN all land above the width by themselves.  Every
 // check uses the SAME width (that of [1e-10, 1e10], about 66 octaves), so the checks of a tile fold into one running maximum
@@ -237,9 +238,11 @@ __device__ __forceinline__ void epl_vjp_v(const float* d, V gx, V gy, const EplS
 
 // ---- SIE / SHEAR / SIS (stateless: cheap to re-evaluate) ----------------------------------------------
 // The forward state the VJP needs.  sie_vjp_v recomputes it (stateless: the compiler merges the two evaluations inside one basic
-// block); the select-free tiles of gl_pair.hip.h hand it over instead (`keep` / `kept`), because the branch of their guard sits
-// between the forward and the VJP and the evaluations were no longer merged across it (SIE + Shear | Sersic | Sersic: 650 instead
-// of 410 instructions per pixel pair).
+// block); the select-free tiles of gl_pair.hip.h hand it over instead (`keep` / `kept`).  That began when a guard branch sat
+// between their forward and their VJP (650 instead of 410 instructions per pixel pair without it); the tiles are straight-line
+// code now, and the hand-over still never loses: dropping it leaves SIE | Sersic and SIE | SersicEllipse as they are (356 and
+// 377 vector instructions per pixel pair), and costs SIE + Shear | Sersic | Sersic 407 for 406 and the elliptical two-light
+// kernel 697 for 454, with 254 registers for 232 (its two evaluations are not merged even inside the one block).
 template <class V> struct SieStateV { V xr, yr, ipsi, u, v, fu, fv; };
 template <class V> __device__ __forceinline__ SieStateV<V> sie_state_v(const float* d, V x, V y) {
   const float c = d[SIE_C], s = d[SIE_S], q = d[SIE_Q], sq = d[SIE_SQ];

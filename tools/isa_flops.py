@@ -259,10 +259,10 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
       * the inner loop's preheader runs with probability 1 - `frac_short` (series of fewer than two terms skip the loop),
         the blocks of that bypass with probability `frac_short`,
       * other conditional blocks (optional loads of the mask / error planes: <= 3 VALU, no flops) are counted as executed,
-      * gl_pair_kernel's steady-state tiles are select-free behind a wave-uniform guard (gl_pair.hip.h): a wave whose guard fires
-        LEAVES the loop for the careful ragged-end loop, so the fallback is outside the tile loop and weighs 0 by itself; the
-        blocks of the loop behind the guard's branch -- the rest of the likelihood and the whole VJP -- no longer dominate the
-        latch in the structurised control flow, and run once per trip: weight 1.
+      * gl_pair_kernel's steady-state tiles are select-free and straight-line (gl_pair.hip.h): their guard is folded into
+        wave-private state and tested once BEHIND the loop, where a wave that fired redoes its chunk in the careful ragged-end
+        loop; neither the test nor the redo is part of the tile loop, so both weigh 0, and the tile's own blocks (forward,
+        likelihood, VJP) dominate the latch: weight 1 by the first rule.
     Returns per-lane flops and VALU wave-instructions per PIXEL, and the decomposition."""
     # likelihood modes compile the steady-state tile twice, in source (and address) order: with an error map, without one
     # (gl_pair.hip.h err_tag), and the ragged-end tile once: the loop with the most instructions (validity selects, both variance
@@ -281,7 +281,6 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
         mandatory &= cfg.dom[lt]
     mandatory |= {tile.header} & own
     inner_headers = {c.header for c in inner}
-    guards = [b for b in mandatory if _is_tile_guard(cfg, b)]
     out = {k: float(v) for k, v in cfg.tally(mandatory).items()}
     detail = dict(tile_loop_header=hex(tile.header), n_blocks=len(tile.blocks), pixels_per_lane_per_trip=W,
                   mandatory=cfg.tally(mandatory), inner=[], conditional=[])
@@ -293,9 +292,7 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
     for b in sorted(own - mandatory):
         t = cfg.tally([b])
         after_loop = any(h in cfg.dom[b] for h in inner_headers)  # only reachable through the series loop
-        if any(g in cfg.dom[b] for g in guards):
-            prob, why = 1.0, "select-free tile behind its guard (the fallback leaves the loop: weight 0)"
-        elif after_loop and t["packed"] >= 4:
+        if after_loop and t["packed"] >= 4:
             prob, why = frac_odd, "series tail: the term left over by the two-term loop"
         elif after_loop and t["valu"] > 3:
             prob, why = 1.0 - frac_odd, "series tail: the other parity (register moves)"
@@ -311,23 +308,6 @@ def pair_model(cfg, mean_series_pairs, frac_odd, W=2, frac_short=0.0, error_map=
     per_pixel = {k: v / W for k, v in out.items()}
     detail["per_pixel"] = per_pixel
     return per_pixel, detail
-
-
-GUARD_WIDTH = 0x21391bfa  # csrc/gl_vec.hip.h kGuardWidth: bits(1e10f) - bits(1e-10f)
-
-
-def _is_tile_guard(cfg, b):
-    """The block that ends a select-free tile's forward part: it compares the folded range checks with kGuardWidth and tests the
-    image pair for NaN with ONE unordered compare of its two halves (the careful body compares each half with itself)."""
-    for k in cfg.blocks[b]:
-        addr, mnem, ops, tgt = cfg.ins[k]
-        if mnem.startswith("v_cmp_u_f32"):
-            srcs = [o.strip() for o in ops.split(",")][-2:]
-            if len(srcs) == 2 and srcs[0] != srcs[1]:
-                return True
-        if re.search(r"\b0x%x\b" % GUARD_WIDTH, ops):
-            return True
-    return False
 
 
 def _hot_loops(cfg, min_valu=100):
