@@ -19,6 +19,7 @@ GL_FLAG_SHAPELETS_INTERPOLATE = 1
 GL_FLAG_INTERPOL_LINEAR = 1
 GL_INTERPOL = 21
 GL_INTERPOL_MASS = 14
+GL_MULTIPOLE = 15
 
 
 class NativeLibraryError(RuntimeError):
@@ -565,7 +566,7 @@ def profile_eval(profile, x, y, kwargs):
     xb, yb, P, B, out_shape = _broadcast_points(profile, x, y, kwargs, list(profile.params), dev)
     n_pts = xb.shape[0]
     out0 = torch.empty_like(xb)
-    is_mass = comp.kind <= 12
+    is_mass = comp.kind <= 12 or comp.kind == GL_MULTIPOLE
     out1 = torch.empty_like(xb) if is_mass else None
     _check(lib().gl_profile_eval(ctypes.byref(comp), _ptr(xb), _ptr(yb), n_pts, B, 1, _ptr(P), _ptr(out0),
                                  _ptr(out1), _stream()))

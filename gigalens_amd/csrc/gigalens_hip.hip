@@ -626,7 +626,7 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
   for (int i = 0; i < n_comp; ++i) {
     const gl_component& c = comps[i];
     const bool mass = i < n_lens;
-    const bool is_mass_kind = (c.kind >= GL_EPL && c.kind <= GL_TNFW) || c.kind == GL_USER_MASS || c.kind == GL_INTERPOL_MASS;
+    const bool is_mass_kind = (c.kind >= GL_EPL && c.kind <= GL_TNFW) || c.kind == GL_USER_MASS || c.kind == GL_INTERPOL_MASS || c.kind == GL_MULTIPOLE;
     const bool is_light_kind = (c.kind >= GL_SERSIC && c.kind <= GL_CORE_SERSIC) || c.kind == GL_USER_LIGHT || c.kind == GL_INTERPOL;
     if ((mass && !is_mass_kind) || (!mass && !is_light_kind))
       return fail(GL_EINVAL, "component %d: kind %d is not a %s profile", i, c.kind, mass ? "mass" : "light");
@@ -643,10 +643,16 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
     }
     if (c.kind == GL_EPL) { m->epl_comp = m->has_epl ? -2 : i; m->has_epl = true; }
     if (c.kind >= GL_DPIS && c.kind <= GL_SERIES) m->fam = std::max(m->fam, 1);
-    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC || c.kind == GL_INTERPOL || c.kind == GL_INTERPOL_MASS)
+    if (c.kind == GL_NFW_ELLIPSE || c.kind == GL_TNFW || c.kind == GL_CORE_SERSIC || c.kind == GL_INTERPOL || c.kind == GL_INTERPOL_MASS ||
+        c.kind == GL_MULTIPOLE)
       m->fam = 2;
     if (c.kind == GL_SERIES && (iparam < 0 || iparam > SERIES_MAX_ORDER))
       return fail(GL_EINVAL, "component %d: series order %d outside [0, %d]", i, iparam, SERIES_MAX_ORDER);
+    if (c.kind == GL_MULTIPOLE) {
+      if (iparam < MPL_MMIN || iparam > MPL_MMAX)
+        return fail(GL_EINVAL, "component %d: multipole order m = %d outside [%d, %d]", i, iparam, MPL_MMIN, MPL_MMAX);
+      ++m->n_multipole;
+    }
     if (c.kind == GL_SCALED) {
       if (iparam < 1 || iparam > 3) return fail(GL_EINVAL, "component %d: GL_SCALED takes 1..3 scales, got %d", i, iparam);
       ++m->n_scaled;
@@ -701,6 +707,12 @@ int build_components(gl_model* m, const gl_component* comps, int n_comp, const c
   if (m->has_user && m->n_interp_mass)
     return fail(GL_EUNSUPPORTED, "a model that mixes user-written profiles with GL_INTERPOL_MASS lenses is not served: the run-time "
                                  "compiled kernels carry no deflection maps");
+  if (m->has_user && m->n_multipole)
+    return fail(GL_EUNSUPPORTED, "a model that mixes user-written profiles with GL_MULTIPOLE lenses is not served: the run-time "
+                                 "compiled kernels are built without that case");
+  if (m->n_multipole && m->n_interp_mass)
+    return fail(GL_EUNSUPPORTED, "a model that holds both GL_MULTIPOLE and GL_INTERPOL_MASS lenses is not served: each build of the "
+                                 "position kernel carries one of the two cases");
   m->P = p_off;
   for (int i = 0; i < n_lens; ++i) m->lens_params += m->comps[i].n_par;
   m->D = std::max(d_off, 4);

@@ -164,7 +164,7 @@ int gl_profile_eval(const gl_component* comp, const float* x, const float* y, in
   if (comp->kind == GL_SERIES) return fail(GL_EINVAL, "GL_SERIES needs its coefficient field: use gl_series_eval");
   if (comp->kind == GL_INTERPOL) return fail(GL_EINVAL, "GL_INTERPOL needs its image: use gl_interpol_eval");
   if (comp->kind == GL_INTERPOL_MASS) return fail(GL_EINVAL, "GL_INTERPOL_MASS needs its maps: use gl_interpol_mass_eval");
-  const bool mass = comp->kind <= GL_DPIEP || comp->kind == GL_NFW_ELLIPSE || comp->kind == GL_TNFW;
+  const bool mass = comp->kind <= GL_DPIEP || comp->kind == GL_NFW_ELLIPSE || comp->kind == GL_TNFW || comp->kind == GL_MULTIPOLE;
   if (mass && !out1) return fail(GL_EINVAL, "out1 is required for mass profiles");
   const CompDesc cd = point_comp(comp);
   hipStream_t stream = (hipStream_t)hip_stream;

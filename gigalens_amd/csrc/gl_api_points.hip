@@ -51,7 +51,7 @@ int check_window(bool search, float x_lo, float x_hi, float y_lo, float y_hi) {
 }
 
 bool potential_kind(int kind) {
-  return (kind >= GL_EPL && kind <= GL_DPIEP) || kind == GL_NFW_ELLIPSE || kind == GL_TNFW;
+  return (kind >= GL_EPL && kind <= GL_DPIEP) || kind == GL_NFW_ELLIPSE || kind == GL_TNFW || kind == GL_MULTIPOLE;
 }
 
 // the lenses without a potential: what gl_lens_potential and the time-delay term (gl_model_set_position_delays) refuse
@@ -125,6 +125,12 @@ MpArgs mp_args(const gl_model* m) {
 
 namespace glk {
 
+// P1 of a model that holds a multipole: the build of the kernel that carries the case (gl_positions.hip.h pos_p1_body), on the grid
+// run_positions hands in -- the one it gives gl_pos_p1_kernel
+static void launch_pos_p1_mpl(dim3 grid, hipStream_t stream, const PosArgs& a) {
+  hipLaunchKernelGGL(gl_pos_p1_mpl_kernel, grid, dim3(64), 0, stream, a);
+}
+
 int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream, int what,
                   float* amp, float* model_flux, const DelayOut* delay_out) {
   if (m->n_series) return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image-position likelihood");
@@ -165,6 +171,9 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
     if (!m->pos_targets)
       return fail(GL_EINVAL, "the image positions of a model with lens planes need the couplings of their families: "
                              "gl_model_set_position_targets has not been called");
+    if (want_grad && m->lens_params && m->n_multipole)
+      return fail(GL_EUNSUPPORTED, "the gradient of the point likelihoods of a model with lens planes is not served with a GL_MULTIPOLE "
+                                   "lens: gl_mp_pos_p3_kernel is built without that case (with it the kernel spills)");
     const float* tg = m->d_pos_target;
     hipLaunchKernelGGL(gl_mp_pos_p1_kernel, blocks((long long)B * a.J), dim3(MP_POS_WG), 0, stream, a, mp_args(m), tg);
     if (what & POS_POSITIONS) hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
@@ -191,7 +200,8 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
     if (what & POS_FLUXES) GL_HIP(hipGetLastError());  // (the flux launch between the module's kernels)
     return GL_OK;
   }
-  hipLaunchKernelGGL(gl_pos_p1_kernel, blocks((long long)B * a.J), dim3(64), 0, stream, a);
+  if (m->n_multipole) launch_pos_p1_mpl(blocks((long long)B * a.J), stream, a);
+  else hipLaunchKernelGGL(gl_pos_p1_kernel, blocks((long long)B * a.J), dim3(64), 0, stream, a);
   if (what & POS_POSITIONS) hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
   fluxes();
   // the time delays (gl_tdelays.hip.h): statistics and beta adjoints by the thread that owns the family's elements, the direct
@@ -407,8 +417,12 @@ int gl_lens_maps(const gl_model* m, const float* params, int B, const float* x, 
     GL_HIP(hipModuleLaunchKernel(m->user_point_fn[4], (unsigned)((total + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)hip_stream, args, nullptr));
     return GL_OK;
   }
-  hipLaunchKernelGGL(gl_lens_maps_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, a,
-                     x, y, (long long)n_pts, xy_batched, out);
+  if (m->n_multipole)  // (the build that carries the multipole: gl_positions.hip.h lens_maps_body)
+    hipLaunchKernelGGL(gl_lens_maps_mpl_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, a,
+                       x, y, (long long)n_pts, xy_batched, out);
+  else
+    hipLaunchKernelGGL(gl_lens_maps_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, a,
+                       x, y, (long long)n_pts, xy_batched, out);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }
@@ -739,7 +753,7 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
   if (m->has_user) {
     void* args[] = {&a, &g};
     GL_HIP(hipModuleLaunchKernel(m->user_point_fn[5], (unsigned)map_blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr));
-  } else if (m->n_interp_mass) {  // (the build that carries the interpolated lens: gl_images.hip.h)
+  } else if (m->n_interp_mass || m->n_multipole) {  // (the build that carries the interpolated lens and the multipole: gl_images.hip.h)
     hipLaunchKernelGGL(gl_img_map_im_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
   } else {
     hipLaunchKernelGGL(gl_img_map_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
@@ -748,7 +762,7 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
   if (m->has_user) {
     void* args[] = {&a, &g};
     GL_HIP(hipModuleLaunchKernel(m->user_point_fn[6], (unsigned)pairs, 1, 1, 64, 1, 1, 0, stream, args, nullptr));
-  } else if (m->n_interp_mass) {
+  } else if (m->n_interp_mass || m->n_multipole) {
     hipLaunchKernelGGL(gl_img_newton_im_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, a, g);
   } else {
     hipLaunchKernelGGL(gl_img_newton_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, a, g);
@@ -837,7 +851,7 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
   g.n_seg = n_seg; g.n_dropped = n_dropped; g.n_flagged = n_flagged; g.open = open;
   g.area = area;
   // catalogues and interpolated lenses take the build whose evaluation is a function call (gl_critical.hip.h, crit_eval)
-  const bool cat = m->n_scaled > 0 || m->n_interp_mass > 0;
+  const bool cat = m->n_scaled > 0 || m->n_interp_mass > 0 || m->n_multipole > 0;
   if (cat) hipLaunchKernelGGL(gl_crit_map_kernel<true>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
   else hipLaunchKernelGGL(gl_crit_map_kernel<false>, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, g);
   hipLaunchKernelGGL(gl_crit_scan_kernel, dim3((unsigned)B), dim3(CRIT_WG), 0, stream, g);
@@ -894,7 +908,7 @@ int mp_render_bwd(const gl_model* m, int B, const LaunchPlan& plan, const Worksp
   r.out_scale = out_scale;
   r.partial = w.partial;
   bool xf = false;  // the instantiation that carries the NFW_ELLIPSE / TNFW / CoreSersic VJPs
-  for (const CompDesc& c : m->comps) xf = xf || c.kind == K_NFW_ELLIPSE || c.kind == K_TNFW || c.kind == K_CORE_SERSIC;
+  for (const CompDesc& c : m->comps) xf = xf || c.kind == K_NFW_ELLIPSE || c.kind == K_TNFW || c.kind == K_CORE_SERSIC || c.kind == K_MULTIPOLE;
   const size_t shmem = (size_t)(((m->D + 3) & ~3) + m->ncols * m->Apad) * sizeof(float);
   const dim3 grid((unsigned)plan.n_chunks, (unsigned)B), block(MP_WG);
   if (xf) hipLaunchKernelGGL(gl_mp_bwd_kernel<true>, grid, block, shmem, stream, mp_args(m), r);

@@ -72,6 +72,20 @@ GL_HD double l_cos(double x) { return ::cos(x); }
 GL_HD double l_pow(double x, double y) { return ::pow(x, y); }
 GL_HD double l_atanh(double x) { return ::atanh(x); }
 
+// sin and cos of one angle: the leaf pair is formed once, on the innermost value, however deep the nesting
+#if defined(__HIP_DEVICE_COMPILE__)
+GL_HD void l_sincos(float x, float& s, float& c) { ::sincosf(x, &s, &c); }
+GL_HD void l_sincos(double x, double& s, double& c) { ::sincos(x, &s, &c); }
+#else
+GL_HD void l_sincos(float x, float& s, float& c) { s = ::sinf(x); c = ::cosf(x); }
+GL_HD void l_sincos(double x, double& s, double& c) { s = ::sin(x); c = ::cos(x); }
+#endif
+GLD_T void l_sincos(const Dual<T, N>& a, Dual<T, N>& s, Dual<T, N>& c) {
+  T sv, cv;
+  l_sincos(a.v, sv, cv);
+  s = chain(a, sv, cv);
+  c = chain(a, cv, -sv);
+}
 GLD_T Dual<T, N> l_sqrt(const Dual<T, N>& a) { T s = l_sqrt(a.v); return chain(a, s, T(0.5) / s); }
 GLD_T Dual<T, N> l_log(const Dual<T, N>& a) { return chain(a, l_log(a.v), T(1) / a.v); }
 GLD_T Dual<T, N> l_exp(const Dual<T, N>& a) { T e = l_exp(a.v); return chain(a, e, e); }
@@ -112,6 +126,7 @@ GLD_T Dual<T, N> p_sqrt(const Dual<T, N>& a) { return l_sqrt(a); }
 GLD_T Dual<T, N> p_log(const Dual<T, N>& a) { return l_log(a); }
 GLD_T Dual<T, N> p_sin(const Dual<T, N>& a) { return l_sin(a); }
 GLD_T Dual<T, N> p_cos(const Dual<T, N>& a) { return l_cos(a); }
+GLD_T void p_sincos(const Dual<T, N>& a, Dual<T, N>& s, Dual<T, N>& c) { l_sincos(a, s, c); }
 GLD_T Dual<T, N> p_atan2(const Dual<T, N>& y, const Dual<T, N>& x) { return l_atan2(y, x); }
 GLD_T Dual<T, N> p_pow(const Dual<T, N>& x, const Dual<T, N>& y) { return l_pow(x, y); }
 #undef GLD_T

@@ -77,6 +77,7 @@ __device__ __forceinline__ void finalize_sample(const CompDesc* __restrict__ com
         case K_NFW_ELLIPSE: if constexpr (!BASIC) nfw_ell_finalize<float>(p, acc, g); break;
         case K_TNFW: if constexpr (!BASIC) tnfw_finalize<float>(p, acc, g); break;
         case K_INTERPOL_MASS: if constexpr (!BASIC) interpmass_finalize<float>(p, acc, g); break;
+        case K_MULTIPOLE: if constexpr (!BASIC) multipole_finalize<float>(p, acc, g); break;
         case K_CORE_SERSIC: if constexpr (!BASIC) core_sersic_finalize<float>(p, acc, g); break;
         case K_INTERPOL: if constexpr (!BASIC) interp_finalize<float>(p, acc, g); break;
         case K_SERSIC: sersic_finalize<float>(p, false, acc, g); break;

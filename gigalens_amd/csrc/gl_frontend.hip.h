@@ -81,6 +81,7 @@ __device__ __forceinline__ void prep_component(const CompDesc& cd, const float* 
     case K_NFW_ELLIPSE: nfw_ell_prep<float>(p, d); break;
     case K_TNFW: tnfw_prep<float>(p, d); break;
     case K_INTERPOL_MASS: interpmass_prep<float>(p, interp_mass[cd.iparam], d); break;
+    case K_MULTIPOLE: multipole_prep<float>(p, cd.iparam, d); break;
     case K_CORE_SERSIC: core_sersic_prep<float>(p, d); break;
     case K_INTERPOL: interp_prep<float>(p, interp[cd.iparam].h, interp[cd.iparam].w, d); break;
     case K_SERSIC: sersic_prep<float>(p, false, d); break;

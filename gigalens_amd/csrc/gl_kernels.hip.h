@@ -16,6 +16,7 @@
 #include "gl_extra.h"
 #include "gl_interp.h"
 #include "gl_interp_mass.h"
+#include "gl_multipole.h"
 #include "gl_vec.hip.h"
 #include "gl_members.hip.h"
 #include "gl_series.h"
@@ -508,6 +509,13 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
             for (int t = 0; t < T; ++t) { float ax, ay; interpmass_fwd<float>(d, tb, x[t], y[t], ax, ay); bx[t] -= ax; by[t] -= ay; }
           }
           break;
+        case K_MULTIPOLE:
+          if constexpr (XF) {
+            const int m = comps[l].iparam;
+#pragma unroll
+            for (int t = 0; t < T; ++t) { float ax, ay; multipole_fwd<float>(d, m, x[t], y[t], ax, ay); bx[t] -= ax; by[t] -= ay; }
+          }
+          break;
         case K_SERIES: if constexpr (DP) {  // alpha = theta_E sum_n C_n(pixel) (r_cut - r0)^n   (series_profile.py:76-95)
           const SeriesDev sv = a.series[comps[l].flags];
           const float te = d[0], dl = d[1] - sv.r0;
@@ -885,6 +893,17 @@ __global__ void __launch_bounds__(WG, (SHP || FAM) ? 2 : 4) gl_main_kernel(MainA
               interpmass_vjp<float>(d, tb, x[t], y[t], gbx[t], gby[t], acc, ux, uy);
             }
             wave_acc<IM_NACC>(acc, ac, cd.a_off);
+          } break;
+          case K_MULTIPOLE: if constexpr (XF) {
+            float acc[MPL_NACC];
+#pragma unroll
+            for (int k = 0; k < MPL_NACC; ++k) acc[k] = 0.f;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+              float ux = 0.f, uy = 0.f;  // (the cotangent of a grid point: unused)
+              multipole_vjp<float>(d, cd.iparam, x[t], y[t], gbx[t], gby[t], acc, ux, uy);
+            }
+            wave_acc<MPL_NACC>(acc, ac, cd.a_off);
           } break;
           case K_SERIES: if constexpr (DP) {
             const SeriesDev sv = a.series[cd.flags];

@@ -226,6 +226,7 @@ struct gl_model {
   std::vector<InterpMassDev> interp_mass;
   std::vector<glk::DevBuf<float>> interp_mass_buf;  // [2][(h + 4)][(w + 4)]: alpha_x, alpha_y, each with its zero apron
   int n_interp_mass = 0, n_interp_mass_set = 0;
+  int n_multipole = 0;  // GL_MULTIPOLE lenses: the point kernels take the builds that carry the case (gl_positions.hip.h lens_point)
   glk::DevBuf<InterpMassDev> d_interp_mass;
   // linear amplitudes (lstsq_simulate): channel k of the basis stack <-> packed parameter column
   std::vector<int> lin_cols;

@@ -48,7 +48,7 @@ struct MpBwd {
 
 // deflection of one lens from its derived row (what lens_point computes from the raw row)
 template <bool XF>
-__device__ __forceinline__ void mp_lens_fwd(int kind, const float* d, float x, float y, float& ax, float& ay) {
+__device__ __forceinline__ void mp_lens_fwd(int kind, int iparam, const float* d, float x, float y, float& ax, float& ay) {
   ax = 0.f;
   ay = 0.f;
   switch (kind) {
@@ -62,6 +62,7 @@ __device__ __forceinline__ void mp_lens_fwd(int kind, const float* d, float x, f
     case K_DPIEP: piep_fwd<float>(d, d + DP_NS, x, y, ax, ay); break;
     case K_NFW_ELLIPSE: if constexpr (XF) nfw_ell_fwd<float>(d, x, y, ax, ay); break;
     case K_TNFW: if constexpr (XF) tnfw_fwd<float>(d, x, y, ax, ay); break;
+    case K_MULTIPOLE: if constexpr (XF) multipole_fwd<float>(d, iparam, x, y, ax, ay); break;
   }
 }
 
@@ -138,6 +139,12 @@ __device__ __forceinline__ void mp_lens_vjp(const CompDesc& cd, const float* d, 
     case K_TNFW:
       if constexpr (XF) GL_MP_CENTRED(TNF_NACC, TNFA_CX, TNFA_CY, tnfw_vjp<float>(d, x, y, gx, gy, acc))
       break;
+    case K_MULTIPOLE:
+      if constexpr (XF) {
+        float ux = 0.f, uy = 0.f;  // (the point's cotangent: GL_MP_CENTRED takes it from the centre sums)
+        GL_MP_CENTRED(MPL_NACC, MPLA_CX, MPLA_CY, multipole_vjp<float>(d, cd.iparam, x, y, gx, gy, acc, ux, uy))
+      }
+      break;
     case K_SHEAR: {  // evaluated at the un-shifted coordinates: alpha = Gamma (x, y), Gamma symmetric
       float acc[SHR_NACC];
       mp_zero(acc);
@@ -181,7 +188,7 @@ __global__ void __launch_bounds__(MP_WG) gl_mp_bwd_kernel(MpArgs mp, MpBwd r) {
       const int l = mp.order[t], pl = mp.plane[l];
       float x = tx, y = ty, ax, ay;
       a.to_plane(pl, mp.scale, x, y);
-      mp_lens_fwd<XF>(comps[l].kind, s_d + comps[l].d_off, x, y, ax, ay);
+      mp_lens_fwd<XF>(comps[l].kind, comps[l].iparam, s_d + comps[l].d_off, x, y, ax, ay);
       a.add(pl, ax, ay);
     }
     float v = 0.f;

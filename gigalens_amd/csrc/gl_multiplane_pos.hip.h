@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(MP_POS_WG) gl_mp_pos_p3_kernel(PosArgs a, MpAr
         Q p[POS_MAXP];
 #pragma unroll
         for (int m = 0; m < POS_MAXP; ++m) p[m] = Q(mp_pos_param(a, cd, b, m, k));
-        [[clang::always_inline]] lens_point<Q, false>(a, cd, p, xs, ys, qx, qy);
+        [[clang::always_inline]] lens_point<Q, false, false, false>(a, cd, p, xs, ys, qx, qy);  // (without the multipole: with it P3 spills; the host refuses)
       }
       const int j = geti(MPP_J);
       R x, y;

@@ -25,6 +25,7 @@ __global__ void __launch_bounds__(256) gl_point_kernel(CompDesc cd, const float*
     case K_DPIS: case K_DPIE: case K_DPIEP: { float d[DPX_ND]; dpie_prep<float>(cd.kind, p, d); dpie_fwd<float>(cd.kind, d, at.x, at.y, o0, o1); } break;
     case K_NFW_ELLIPSE: { float d[NFE_ND]; nfw_ell_prep<float>(p, d); nfw_ell_fwd<float>(d, at.x, at.y, o0, o1); } break;
     case K_TNFW: { float d[TNF_ND]; tnfw_prep<float>(p, d); tnfw_fwd<float>(d, at.x, at.y, o0, o1); } break;
+    case K_MULTIPOLE: { float d[MPL_ND]; multipole_prep<float>(p, cd.iparam, d); multipole_fwd<float>(d, cd.iparam, at.x, at.y, o0, o1); } break;
     case K_CORE_SERSIC: { float d[CSR_ND]; core_sersic_prep<float>(p, d); o0 = core_sersic_fwd<float>(d, at.x, at.y); } break;
     case K_INTERPOL: { float d[INT_ND]; interp_prep<float>(p, itab.h, itab.w, d); o0 = interp_fwd<float>(d, itab, cd.flags & 1u, at.x, at.y); } break;
     case K_SERSIC: { float d[SER_NDX]; sersic_prep<float>(p, false, d); o0 = sersic_fwd(d, at.x, at.y); } break;

@@ -91,6 +91,11 @@ template <class R, bool CATS = true> __device__ void lens_point_closed(const Pos
         ay += fy;
       }
     } break;
+    // (K_SIS -- and every kind this switch does not name.  K_INTERPOL_MASS and K_MULTIPOLE are cases of lens_point below, under
+    // its IM / MPL flags: a build without one of them must never meet that kind, or it would be evaluated here as an SIS.  The
+    // host keeps that: build_components refuses the mixtures no build serves, and every launch of a build with a flag off is
+    // chosen from m->n_interp_mass / m->n_multipole -- run_positions (P1, the multi-plane P3 refusal), gl_lens_maps,
+    // gl_image_positions, gl_critical_curves)
     default: { R d[4]; sis_prep<R>(p, d); sis_fwd<R>(d, x, y, ax, ay); } break;
   }
 }
@@ -100,7 +105,20 @@ template <class R, bool CATS = true> __device__ void lens_point_closed(const Pos
 // function they compute what they did.  CATS = false (lens planes, which refuse the lens) leaves it out
 // IM = false: a build for models that hold no such lens (the lens-equation solver keeps one: its kernels then compute bit for bit
 // what they did before the lens existed, and what is generated from its images stays what it was)
-template <class R, bool CATS = true, bool IM = CATS> __device__ void lens_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y, R& ax, R& ay) {
+// MPL: the multipole (gl_multipole.h) stands in front of the switch for the same reason.  It is closed-form and is served on lens
+// planes, so a direct caller has it unless it asks for the IM = false build of a catalogue-free, map-free model: lens_jet and
+// lens_deflections, whose IM = false builds are the solver's and the critical curves' kernels for models without such lenses,
+// pass MPL = IM by default and leave those kernels as they were (gl_pos_p1_mpl_kernel and gl_lens_maps_mpl_kernel ask for MPL without IM)
+template <class R, bool CATS = true, bool IM = CATS, bool MPL = IM || !CATS>
+__device__ void lens_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y, R& ax, R& ay) {
+  if constexpr (MPL) {
+    if (cd.kind == glp::K_MULTIPOLE) {
+      R d[glp::MPL_ND];
+      glp::multipole_prep<R>(p, cd.iparam, d);
+      glp::multipole_fwd<R>(d, cd.iparam, x, y, ax, ay);
+      return;
+    }
+  }
   if constexpr (IM) {
     if (cd.kind == glp::K_INTERPOL_MASS) {
       R d[glp::IM_ND];
@@ -144,7 +162,7 @@ template <class R1> __device__ R1 lens_kappa_excess(const PosArgs& a, const Comp
 // parameters are loaded (or deals with it in its own way).  The caller keeps its own sums: the order of its additions is its own.
 // lens_deflections is the same walk on float, f(cd, p, ax, ay), for the kernels that want beta alone.
 using Jet2 = gld::Dual<float, 2>;
-template <bool CATS = true, bool IM = CATS, class F>
+template <bool CATS = true, bool IM = CATS, bool MPL = IM, class F>
 __device__ __forceinline__ void lens_jet(const PosArgs& a, const CompDesc& cd, int b, float px, float py, F&& f) {
   using R = Jet2;
   R x(px), y(py);
@@ -154,20 +172,20 @@ __device__ __forceinline__ void lens_jet(const PosArgs& a, const CompDesc& cd, i
   float pf[POS_MAXP];
   for (int k = 0; k < cd.n_par; ++k) { pf[k] = a.params[(size_t)b * a.P + cd.p_off + k]; p[k] = R(pf[k]); }
   R ax, ay;
-  lens_point<R, CATS, IM>(a, cd, p, x, y, ax, ay);
+  lens_point<R, CATS, IM, MPL>(a, cd, p, x, y, ax, ay);
   const float ex = lens_kappa_excess<float>(a, cd, pf, px, py);
   f(cd, pf, ax, ay, ex);
 }
-template <bool CATS = true, bool IM = CATS, class F, class Pre>
+template <bool CATS = true, bool IM = CATS, bool MPL = IM, class F, class Pre>
 __device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f, Pre&& pre) {
   for (int l = 0; l < a.n_lens; ++l) {
     const CompDesc cd = a.comps[l];
     if (pre(cd)) continue;
-    lens_jet<CATS, IM>(a, cd, b, px, py, f);
+    lens_jet<CATS, IM, MPL>(a, cd, b, px, py, f);
   }
 }
-template <bool IM = true, class F> __device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f) {
-  lens_jets<true, IM>(a, b, px, py, f, [](const CompDesc&) { return false; });
+template <bool IM = true, bool MPL = IM, class F> __device__ __forceinline__ void lens_jets(const PosArgs& a, int b, float px, float py, F&& f) {
+  lens_jets<true, IM, MPL>(a, b, px, py, f, [](const CompDesc&) { return false; });
 }
 template <bool IM = true, class F> __device__ __forceinline__ void lens_deflections(const PosArgs& a, int b, float px, float py, F&& f) {
   for (int l = 0; l < a.n_lens; ++l) {
@@ -175,7 +193,7 @@ template <bool IM = true, class F> __device__ __forceinline__ void lens_deflecti
     float p[POS_MAXP];
     for (int k = 0; k < cd.n_par; ++k) p[k] = a.params[(size_t)b * a.P + cd.p_off + k];
     float ax, ay;
-    lens_point<float, true, IM>(a, cd, p, px, py, ax, ay);
+    lens_point<float, true, IM, IM>(a, cd, p, px, py, ax, ay);
     f(cd, p, ax, ay);
   }
 }
@@ -212,12 +230,15 @@ __device__ __forceinline__ CompDesc lens_seeded_column(const PosArgs& a, int b, 
   return cd;
 }
 
-__global__ void __launch_bounds__(64) gl_pos_p1_kernel(PosArgs a) {
+// MPL: the build for models that hold a multipole.  With both extra cases in front of the switch the kernel no longer fits its 256
+// VGPRs (8 spilled, whatever the case's body holds), so each build carries one of them: the plain kernel the interpolated lens, as
+// before the multipole existed, the other the multipole; a model that holds both kinds is refused at creation
+template <bool MPL> __device__ __forceinline__ void pos_p1_body(const PosArgs& a) {
   int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= a.B * a.J) return;
   int b = i / a.J, j = i - b * a.J;
   float bx = a.px[j], by = a.py[j], fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
-  lens_jets(a, b, a.px[j], a.py[j], [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
+  lens_jets<!MPL, MPL>(a, b, a.px[j], a.py[j], [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
     bx -= ax.v; by -= ay.v;
     fxx += ax.d[0] + ex; fxy += ax.d[1]; fyx += ay.d[0]; fyy += ay.d[1] + ex;
   });
@@ -229,18 +250,22 @@ __global__ void __launch_bounds__(64) gl_pos_p1_kernel(PosArgs a) {
   float* o = a.w_pos + (size_t)i * 6;
   o[0] = bx; o[1] = by; o[2] = fxx; o[3] = fxy; o[4] = fyx; o[5] = fyy;
 }
+__global__ void __launch_bounds__(64) gl_pos_p1_kernel(PosArgs a) { pos_p1_body<false>(a); }
+__global__ void __launch_bounds__(64) gl_pos_p1_mpl_kernel(PosArgs a) { pos_p1_body<true>(a); }
 
 // LensSimulator.beta / .magnification / .convergence / .shear on arbitrary points (tf/simulator.py:72-107):
 // out[6][n_pts][B] = beta_x, beta_y, f_xx, f_xy, f_yx, f_yy summed over the lenses (Hessians as `lens.hessian`
 // resolves them in the reference: derivative of the deflection, plus the dPIS override's convergence excess)
-__global__ void __launch_bounds__(64) gl_lens_maps_kernel(PosArgs a, const float* __restrict__ x,
-                                                         const float* __restrict__ y, long long n_pts, int xy_batched,
-                                                         float* __restrict__ out) {
+// MPL: the build for models that hold a multipole, as pos_p1_body: with both extra cases the kernel drops from two waves per SIMD
+// to one, so each build carries one of them and a model without a multipole runs the kernel it ran before the multipole existed
+template <bool MPL>
+__device__ __forceinline__ void lens_maps_body(const PosArgs& a, const float* __restrict__ x, const float* __restrict__ y,
+                                               long long n_pts, int xy_batched, float* __restrict__ out) {
   long long i = (long long)blockIdx.x * 64 + threadIdx.x;
   if (i >= n_pts * a.B) return;
   const PointAt at(i, a.B, xy_batched, x, y);
   float bx = at.x, by = at.y, fxx = 0.f, fxy = 0.f, fyx = 0.f, fyy = 0.f;
-  lens_jets(
+  lens_jets<true, !MPL, MPL>(
       a, at.b, at.x, at.y,
       [&](const CompDesc&, const float*, const Jet2& ax, const Jet2& ay, float ex) {
         bx -= ax.v; by -= ay.v;
@@ -266,6 +291,14 @@ __global__ void __launch_bounds__(64) gl_lens_maps_kernel(PosArgs a, const float
       });
   const long long st = n_pts * a.B;
   out[i] = bx; out[st + i] = by; out[2 * st + i] = fxx; out[3 * st + i] = fxy; out[4 * st + i] = fyx; out[5 * st + i] = fyy;
+}
+__global__ void __launch_bounds__(64) gl_lens_maps_kernel(PosArgs a, const float* __restrict__ x, const float* __restrict__ y,
+                                                         long long n_pts, int xy_batched, float* __restrict__ out) {
+  lens_maps_body<false>(a, x, y, n_pts, xy_batched, out);
+}
+__global__ void __launch_bounds__(64) gl_lens_maps_mpl_kernel(PosArgs a, const float* __restrict__ x, const float* __restrict__ y,
+                                                             long long n_pts, int xy_batched, float* __restrict__ out) {
+  lens_maps_body<true>(a, x, y, n_pts, xy_batched, out);
 }
 
 // MassProfile.hessian at plugin level (tf/profile.py:9-27 and the analytic overrides): out[4][n_pts][B]

@@ -26,6 +26,7 @@ template <class R> __device__ R lens_potential_point(const PosArgs& a, const Com
     case K_DPIEP: { R d[DPX_ND]; dpie_prep<R>(cd.kind, p, d); return dpie_pot<R>(cd.kind, d, x, y); }
     case K_NFW_ELLIPSE: { R d[NFE_ND]; nfw_ell_prep<R>(p, d); return nfw_ell_pot<R>(d, x, y); }
     case K_TNFW: { R d[TNF_ND]; tnfw_prep<R>(p, d); return tnfw_pot<R>(d, x, y); }
+    case K_MULTIPOLE: { R d[MPL_ND]; multipole_prep<R>(p, cd.iparam, d); return multipole_pot<R>(d, cd.iparam, x, y); }
     case K_SCALED: {
       const CatDev cat = a.cats[cd.iparam];
       const ScaledDesc sd{cat.base_kind, cat.n_gal, {cat.col[0], cat.col[1], cat.col[2]}};

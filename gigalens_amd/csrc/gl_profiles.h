@@ -29,11 +29,13 @@ enum Kind : int {
   K_NFW_ELLIPSE = 11, K_TNFW = 12,      // gl_extra.h
   K_USER_MASS = 13,                     // a body the user wrote (gl_user.hip): iparam = its parameter count, flags = body slot of the model
   K_INTERPOL_MASS = 14,                 // two deflection maps on a grid (gl_interp_mass.h): iparam = table slot of the model
+  K_MULTIPOLE = 15,                     // m-th order multipole (gl_multipole.h): iparam = m
   K_SERSIC = 16, K_SERSIC_ELLIPSE = 17, K_SHAPELETS = 18,
   K_CORE_SERSIC = 19,                   // gl_extra.h
   K_USER_LIGHT = 20,                    // same for a light profile (amplitude: whatever the body makes of its parameters)
   K_INTERPOL = 21                       // a pixelated source image (gl_interp.h): iparam = table slot of the model, flags bit 0 = bilinear
 };
+constexpr int MPL_MMIN = 2, MPL_MMAX = 8;  // orders a K_MULTIPOLE serves (m = 1 is another potential)
 constexpr int USER_MAXP = 16;  // parameters of a user-written profile inside a model (its gradient sums are register arrays)
 
 constexpr int SH_CAP = 10;                              // largest n_max the register-resident / matrix-pipe shapelet kernels serve
@@ -96,6 +98,7 @@ GL_HD int kind_num_params(int kind, int iparam) {
     case K_NFW_ELLIPSE: return 6;
     case K_TNFW: return 5;
     case K_INTERPOL_MASS: return 3;
+    case K_MULTIPOLE: return (iparam >= MPL_MMIN && iparam <= MPL_MMAX) ? 4 : -1;
     case K_CORE_SERSIC: return 10;
     case K_INTERPOL: return 5;
     case K_SERSIC: return 5;
@@ -121,6 +124,7 @@ GL_HD int kind_num_derived(int kind, int iparam) {
     case K_NFW_ELLIPSE:
     case K_TNFW: return 8;
     case K_INTERPOL_MASS: return 8;  // IM_ND
+    case K_MULTIPOLE: return 8;      // MPL_ND
     case K_CORE_SERSIC: return 16;
     case K_INTERPOL: return 8;  // INT_ND
     case K_SERSIC:
@@ -169,6 +173,7 @@ GL_HD int kind_num_acc(int kind, int iparam) {
     case K_NFW_ELLIPSE: return 6;
     case K_TNFW: return 5;
     case K_INTERPOL_MASS: return 3;  // IM_NACC
+    case K_MULTIPOLE: return 4;      // MPL_NACC
     case K_CORE_SERSIC: return 10;
     case K_INTERPOL: return 5;  // INT_NACC
     case K_SERSIC:
@@ -194,6 +199,14 @@ GL_HD float p_sin(float x) { return ::sinf(x); }
 GL_HD float p_cos(float x) { return ::cosf(x); }
 GL_HD float p_log(float x) { return ::logf(x); }
 GL_HD float p_pow(float x, float y) { return ::powf(x, y); }
+// sin and cos of one angle together: on the device one argument reduction serves both
+#if defined(__HIP_DEVICE_COMPILE__)
+GL_HD void p_sincos(float x, float& s, float& c) { ::sincosf(x, &s, &c); }
+GL_HD void p_sincos(double x, double& s, double& c) { ::sincos(x, &s, &c); }
+#else
+GL_HD void p_sincos(float x, float& s, float& c) { s = ::sinf(x); c = ::cosf(x); }
+GL_HD void p_sincos(double x, double& s, double& c) { s = ::sin(x); c = ::cos(x); }
+#endif
 
 // (e1,e2) -> (phi, c, q) with c = min(|e|, cmax); EPL passes cmax = 1 (epl.py:22), every other
 // elliptical profile 0.9999 (sie.py:17, sersic.py:57).  Arithmetic in R like the reference's fp32.

@@ -63,6 +63,8 @@ typedef enum gl_kind {
                           count, flags = index of the body */
   GL_INTERPOL_MASS = 14, /* beyond the reference: a lens given as two deflection maps on a grid, interpolated (lenstronomy's
                             INTERPOL_SCALED by name) [scale_factor,center_x,center_y]; maps attached with gl_model_set_lens_maps */
+  GL_MULTIPOLE = 15, /* beyond the reference: an m-th order multipole of the potential (lenstronomy's MULTIPOLE by name)
+                        [a_m,phi_m,center_x,center_y]; iparam = m, 2 <= m <= 8 (GL_EINVAL otherwise) */
   /* light profiles: LightProfile.light (profile.py:24-60) */
   GL_SERSIC = 16,         /* tf/profiles/light/sersic.py:23-24 [R_sersic,n_sersic,center_x,center_y,Ie] */
   GL_SERSIC_ELLIPSE = 17, /* sersic.py:68-69 [R_sersic,n_sersic,e1,e2,center_x,center_y,Ie] */
