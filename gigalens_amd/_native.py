@@ -139,6 +139,10 @@ SYMBOLS = {
     "gl_model_set_position_targets": (c_int, [c_void_p, POINTER(c_float), c_int, c_int]),
     "gl_multiplane_positions_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                                 c_void_p]),
+    "gl_multiplane_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "gl_multiplane_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_float), c_int, c_float,
+                                              c_float, c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_size_t, c_void_p]),
     "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "gl_image_positions_stage_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
@@ -1055,6 +1059,32 @@ class Model:
                                                    sc.ctypes.data_as(POINTER(c_float)), x_lo, x_hi, y_lo, y_hi, int(n_cells),
                                                    int(max_images), float(tol), int(max_iter), _ptr(out), _ptr(n_images),
                                                    _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
+        return out, n_images, n_dropped
+
+    def multiplane_image_positions(self, params, src_x, src_y, targets, window, n_cells, max_images, tol, max_iter):
+        """gl_multiplane_image_positions: ``image_positions`` on lens planes, source s on the plane with the couplings ``targets[s]``
+        (``[S, K]`` on the host: ``MultiPlane.target_scales(z_s)``).  Returns ``out`` [B, S, max_images, 3] (x, y, mu on the source's
+        plane; NaN-padded), ``n_images`` and ``n_dropped`` [B, S] (int32)."""
+        params = self._params(params)
+        B = params.shape[0]
+        src_x = src_x.to(device=self.device, dtype=torch.float32).contiguous()
+        src_y = src_y.to(device=self.device, dtype=torch.float32).contiguous()
+        if src_x.shape != src_y.shape or src_x.dim() != 2 or src_x.shape[0] != B:
+            raise NativeLibraryError(f"source positions must be [B={B}, S], got {tuple(src_x.shape)} / {tuple(src_y.shape)}")
+        S = src_x.shape[1]
+        t = np.ascontiguousarray(targets, dtype=np.float32)
+        if t.ndim != 2 or t.shape[0] != S:
+            raise NativeLibraryError(f"targets must be [S={S}, n_planes], got {t.shape}")
+        nbytes = lib().gl_multiplane_image_positions_workspace_bytes(self._h, B, S, int(n_cells), int(max_images))
+        ws = self._scratch("multiplane_image_positions", nbytes)
+        out = torch.empty((B, S, max(int(max_images), 1), 3), dtype=torch.float32, device=self.device)
+        n_images = torch.empty((B, S), dtype=torch.int32, device=self.device)
+        n_dropped = torch.empty_like(n_images)
+        x_lo, x_hi, y_lo, y_hi = (float(v) for v in window)
+        _check_potential(lib().gl_multiplane_image_positions(self._h, _ptr(params), B, _ptr(src_x), _ptr(src_y), S,
+                                                             t.ctypes.data_as(POINTER(c_float)), int(t.shape[1]), x_lo, x_hi, y_lo,
+                                                             y_hi, int(n_cells), int(max_images), float(tol), int(max_iter), _ptr(out),
+                                                             _ptr(n_images), _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
         return out, n_images, n_dropped
 
     def image_positions_stage_counts(self, B, n_src, n_cells):

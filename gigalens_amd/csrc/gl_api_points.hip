@@ -17,6 +17,7 @@
 #include "gl_multiplane.hip.h"
 #include "gl_multiplane_bwd.hip.h"
 #include "gl_multiplane_pos.hip.h"
+#include "gl_multiplane_images.hip.h"
 #include "gl_lens_vjp.hip.h"
 #include "gl_hessian_vjp.hip.h"
 #include "gl_imgplane.hip.h"
@@ -85,11 +86,11 @@ int refuse_vjp_lenses(const gl_model* m, const char* fn, const char* what) {
 }
 
 struct ImgLayout { size_t map, cand, n_cand, n_over, scale, bytes; };
-ImgLayout img_layout(int B, int n_src, int n_cells) {
+ImgLayout img_layout(int B, int n_src, int n_cells, int n_maps = 1) {
   ImgLayout l{};
   const size_t V = (size_t)(n_cells + 1) * (size_t)(n_cells + 1), BS = (size_t)B * (size_t)n_src;
   l.map = 0;
-  l.cand = l.map + align_up((size_t)B * V * sizeof(float2), 256);
+  l.cand = l.map + (size_t)n_maps * align_up((size_t)B * V * sizeof(float2), 256);
   l.n_cand = l.cand + align_up(BS * IMG_MAXC * sizeof(float2), 256);
   l.n_over = l.n_cand + align_up(BS * sizeof(int), 256);
   l.scale = l.n_over + align_up(BS * sizeof(int), 256);  // [n_src] deflection scales of gl_image_positions_scaled
@@ -97,6 +98,16 @@ ImgLayout img_layout(int B, int n_src, int n_cells) {
   return l;
 }
 constexpr int IMG_MAX_CELLS = 8192;
+// ... on K lens planes (gl_multiplane_image_positions): the single-plane layout with K maps -- the plane sums [B][K][(n+1)^2] of
+// gl_multiplane_images.hip.h, contiguous from `map` -- and behind it the coupling rows [n_src][K] of the sources
+struct MpImgLayout { ImgLayout img; size_t tgt, bytes; };
+MpImgLayout mp_img_layout(int B, int n_src, int n_cells, int K) {
+  MpImgLayout l{};
+  l.img = img_layout(B, n_src, n_cells, K);
+  l.tgt = l.img.bytes;
+  l.bytes = l.tgt + align_up((size_t)n_src * (size_t)K * sizeof(float), 256);
+  return l;
+}
 
 struct CritLayout { size_t dmap, edge_id, edge_pt, edge_omk, n_edges, n_edge_over, bytes; };
 CritLayout crit_layout(int B, int n_cells, int max_segments) {
@@ -784,6 +795,74 @@ int gl_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_c
   hipStream_t stream = (hipStream_t)hip_stream;
   GL_HIP(hipMemcpyAsync(n_cand, base + lay.n_cand, bytes, hipMemcpyDeviceToDevice, stream));
   GL_HIP(hipMemcpyAsync(n_over, base + lay.n_over, bytes, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+
+// ---- ... on lens planes (gl_multiplane_images.hip.h) -----------------------------------------------------------
+size_t gl_multiplane_image_positions_workspace_bytes(const gl_model* m, int B, int n_src, int n_cells, int max_images) {
+  if (!m || m->mp_K < 2 || B <= 0 || n_src <= 0 || n_cells <= 0 || n_cells > IMG_MAX_CELLS || max_images < 1) return 0;
+  return mp_img_layout(B, n_src, n_cells, m->mp_K).bytes;
+}
+
+int gl_multiplane_image_positions(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                                  const float* targets, int n_planes, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
+                                  int max_images, float tol, int max_iter, float* out, int* n_images, int* n_dropped, void* workspace,
+                                  size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !src_x || !src_y || !targets || !out || !n_images || !n_dropped) return fail(GL_EINVAL, "null argument");
+  if (int rc = check_planes_set(m)) return rc;
+  if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
+  if (n_planes != m->mp_K) return fail(GL_EINVAL, "%d target couplings per source for %d lens planes", n_planes, m->mp_K);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  if (max_images < 1 || max_images > IMG_MAXC) return fail(GL_EINVAL, "max_images %d outside [1, %d]", max_images, IMG_MAXC);
+  if (int rc = check_window(true, x_lo, x_hi, y_lo, y_hi)) return rc;
+  if (!(tol > 0.f) || max_iter < 1) return fail(GL_EINVAL, "tol must be > 0 and max_iter >= 1 (got %g, %d)", tol, max_iter);
+  const int K = n_planes;
+  for (int s = 0; s < n_src; ++s) {  // the rules of gl_model_set_position_targets
+    const float* T = targets + (size_t)s * K;
+    for (int i = 0; i < K; ++i)
+      if (!(std::isfinite(T[i]) && T[i] >= 0.f) || (i > 0 && T[i] != 0.f && T[i - 1] == 0.f))
+        return fail(GL_EINVAL, "targets[%d][%d] = %g: finite and >= 0, 0 from the first plane at or behind the source on", s, i, T[i]);
+    if (T[0] == 0.f) return fail(GL_EINVAL, "source %d: every coupling is zero (the source lies behind no lens plane)", s);
+  }
+  if (int rc = check_ready(m, false, false)) return rc;
+  const MpImgLayout lay = mp_img_layout(B, n_src, n_cells, K);
+  if (!workspace) return fail(GL_EINVAL, "workspace is null");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  const long long V = (long long)(n_cells + 1) * (n_cells + 1);
+  const long long map_blocks = (V * B + 255) / 256, pairs = (long long)B * n_src;
+  if (map_blocks > 0x7fffffffLL || pairs > 0x7fffffffLL) return fail(GL_EINVAL, "too many samples / vertices / sources for one call");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  char* base = (char*)workspace;
+  // the coupling rows, host -> the call's own workspace on the caller's stream (as the scales of gl_image_positions_scaled)
+  float* d_tgt = (float*)(base + lay.tgt);
+  GL_HIP(hipMemcpyAsync(d_tgt, targets, sizeof(float) * (size_t)n_src * (size_t)K, hipMemcpyHostToDevice, stream));
+  PosArgs a = point_args(m, params, B);
+  const MpArgs mp = mp_args(m);
+  ImgArgs g{};
+  g.src_x = src_x;
+  g.src_y = src_y;
+  g.S = n_src;
+  g.n = n_cells;
+  g.x_lo = x_lo; g.x_hi = x_hi; g.y_lo = y_lo; g.y_hi = y_hi;
+  g.hx = (x_hi - x_lo) / (float)n_cells;
+  g.hy = (y_hi - y_lo) / (float)n_cells;
+  g.max_images = max_images;
+  g.max_iter = max_iter;
+  g.tol = tol;
+  g.cand = (float2*)(base + lay.img.cand);
+  g.n_cand = (int*)(base + lay.img.n_cand);
+  g.n_over = (int*)(base + lay.img.n_over);
+  g.out = out;
+  g.n_images = n_images;
+  g.n_dropped = n_dropped;
+  MpImgArgs q{};
+  q.tgt = d_tgt;
+  q.K = K;
+  q.pmap = (float2*)(base + lay.img.map);
+  hipLaunchKernelGGL(gl_mpimg_map_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, mp, g, q);
+  hipLaunchKernelGGL(gl_mpimg_scan_kernel, dim3((unsigned)pairs), dim3(IMG_SCAN_WG), 0, stream, g, q);
+  hipLaunchKernelGGL(gl_mpimg_newton_kernel, dim3((unsigned)pairs), dim3(MP_MAPS_WG), 0, stream, a, mp, g, q);
+  GL_HIP(hipGetLastError());
   return GL_OK;
 }
 

@@ -83,10 +83,6 @@ __device__ inline float img_edge(float2 p, float2 q, float sx, float sy) {
   return (q.x - p.x) * (sy - p.y) - (q.y - p.y) * (sx - p.x);
 }
 
-// Is beta_s inside the image of triangle t?  Cell (ci, cj) holds triangles k = 0: (v00, v10, v11) and k = 1: (v00, v11, v01).
-// A point is inside when every oriented edge function is > 0; on an edge (== 0) it belongs to the triangle that owns that edge,
-// and of two triangles sharing an edge with the same orientation exactly one owns it: the owner is the one whose oriented
-// direction d along the edge has d.y > 0, or d.y == 0 and d.x > 0.  Triangles with a flagged vertex or zero area are skipped.
 // the stored map (beta of the reference plane at vertex v) on the plane of a source with scale c: theta + c (beta - theta).  A function
 // of the vertex alone, without contraction: every triangle that touches the vertex sees bitwise the same value, so the tie rule of
 // img_tri_hit still counts a source on a shared edge once
@@ -99,14 +95,28 @@ __device__ inline float2 img_vertex_beta(const ImgArgs& g, const float2* mp, int
   return float2{x + c * (b1.x - x), y + c * (b1.y - y)};
 }
 
-__device__ inline bool img_tri_hit(const ImgArgs& g, const float2* mp, int t, float sx, float sy, float c, float& seed_x, float& seed_y) {
+// the stored map of one sample on the plane of a source with scale c, as the scan reads it: vertex -> beta
+struct ImgVertexScaled {
+  const ImgArgs& g;
+  const float2* mp;
+  float c;
+  __device__ __forceinline__ float2 operator()(int v) const { return img_vertex_beta(g, mp, v, c); }
+};
+
+// Is beta_s inside the image of triangle t?  Cell (ci, cj) holds triangles k = 0: (v00, v10, v11) and k = 1: (v00, v11, v01).
+// A point is inside when every oriented edge function is > 0; on an edge (== 0) it belongs to the triangle that owns that edge,
+// and of two triangles sharing an edge with the same orientation exactly one owns it: the owner is the one whose oriented
+// direction d along the edge has d.y > 0, or d.y == 0 and d.x > 0.  Triangles with a flagged vertex or zero area are skipped.
+// VB: vertex -> beta on the plane of the source (ImgVertexScaled; gl_multiplane_images.hip.h: the plane sums with the source's couplings)
+template <class VB>
+__device__ inline bool img_tri_hit(const ImgArgs& g, const VB& vertex_beta, int t, float sx, float sy, float& seed_x, float& seed_y) {
   const int n = g.n, V1 = n + 1;
   const int cell = t >> 1, k = t & 1;
   const int cj = cell / n, ci = cell - cj * n;
   const int v00 = cj * V1 + ci;
   int vi[3] = {v00, k ? v00 + V1 + 1 : v00 + 1, k ? v00 + V1 : v00 + V1 + 1};
   float2 bv[3];
-  for (int e = 0; e < 3; ++e) bv[e] = img_vertex_beta(g, mp, vi[e], c);
+  for (int e = 0; e < 3; ++e) bv[e] = vertex_beta(vi[e]);
   float w[3], dx[3], dy[3];
   for (int e = 0; e < 3; ++e) {  // edge e runs from vertex e to vertex e+1
     const int p = e, q = e == 2 ? 0 : e + 1;
@@ -134,16 +144,13 @@ __device__ inline bool img_tri_hit(const ImgArgs& g, const float2* mp, int t, fl
   return true;
 }
 
-__global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
+// the scan of (sample, source) pair bs = blockIdx.x over the triangles of the grid, their vertices read through vertex_beta
+template <class VB> __device__ __forceinline__ void img_scan_body(const ImgArgs& g, int bs, const VB& vertex_beta) {
   constexpr int NW = IMG_SCAN_WG / 64;
   __shared__ float2 list[NW][IMG_MAXC];
   __shared__ int cnt[NW];
-  const int bs = blockIdx.x, b = bs / g.S;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float sx = g.src_x[bs], sy = g.src_y[bs];
-  const float c = g.src_scale ? g.src_scale[bs - b * g.S] : 1.f;
-  const long long V1 = g.n + 1;
-  const float2* mp = g.map + (size_t)b * (size_t)(V1 * V1);
   // wave w walks the w-th quarter of the triangles, 64 consecutive triangles (32 cells of one row) per round
   const int T = 2 * g.n * g.n, per = (T + NW - 1) / NW;
   const int t0 = wave * per, t1 = min(T, t0 + per);
@@ -151,7 +158,7 @@ __global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
   for (int base = t0; base < t1; base += 64) {
     const int t = base + lane;
     float seed_x = 0.f, seed_y = 0.f;
-    const bool hit = t < t1 && img_tri_hit(g, mp, t, sx, sy, c, seed_x, seed_y);
+    const bool hit = t < t1 && img_tri_hit(g, vertex_beta, t, sx, sy, seed_x, seed_y);
     const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
     const int rank = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
     if (hit && rank < IMG_MAXC) list[wave][rank] = float2{seed_x, seed_y};
@@ -171,6 +178,12 @@ __global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
     g.n_cand[bs] = off;
     g.n_over[bs] = total - off;
   }
+}
+__global__ void __launch_bounds__(IMG_SCAN_WG) gl_img_scan_kernel(ImgArgs g) {
+  const int bs = blockIdx.x, b = bs / g.S;
+  const float c = g.src_scale ? g.src_scale[bs - b * g.S] : 1.f;
+  const long long V1 = g.n + 1;
+  img_scan_body(g, bs, ImgVertexScaled{g, g.map + (size_t)b * (size_t)(V1 * V1), c});
 }
 
 // beta and Hessian (f_xx, f_xy, f_yx, f_yy; the dPIS convergence excess included) at one point
@@ -197,14 +210,25 @@ template <bool IM> __device__ __forceinline__ void img_lens_eval_of(const PosArg
   if constexpr (IM) img_lens_eval_im(a, b, px, py, bx, by, h, c);
   else img_lens_eval<false>(a, b, px, py, bx, by, h, c);
 }
-template <bool IM> __device__ __forceinline__ void img_newton_body(const PosArgs& a, const ImgArgs& g) {
+// the evaluation of the single-plane solver at one point of sample b, on the plane of scale c
+template <bool IM> struct ImgEvalScaled {
+  const PosArgs& a;
+  int b;
+  float c;
+  __device__ __forceinline__ void operator()(float px, float py, float& bx, float& by, float* h) const {
+    img_lens_eval_of<IM>(a, b, px, py, bx, by, h, c);
+  }
+};
+
+// Newton, merge, sort and counters of (sample, source) pair bs = blockIdx.x; eval(px, py, bx, by, h): beta and f = I - A at one point
+// on the plane of the source (ImgEvalScaled; gl_multiplane_images.hip.h: the plane recursion with the source's couplings)
+template <class Eval> __device__ __forceinline__ void img_newton_core(const ImgArgs& g, const Eval& eval) {
   __shared__ float rx[IMG_MAXC], ry[IMG_MAXC], rmu[IMG_MAXC];
   __shared__ int rok[IMG_MAXC], order[IMG_MAXC];
   __shared__ int n_keep_s, n_bad_s;
-  const int bs = blockIdx.x, b = bs / g.S, lane = threadIdx.x;
+  const int bs = blockIdx.x, lane = threadIdx.x;
   const int nc = g.n_cand[bs];
   const float sx = g.src_x[bs], sy = g.src_y[bs], tol2 = g.tol * g.tol;
-  const float c = g.src_scale ? g.src_scale[bs - b * g.S] : 1.f;
   const float max_step = sqrtf(g.hx * g.hx + g.hy * g.hy);  // a step is at most one cell diagonal (folds: near-singular I - H)
   bool ok = false;
   float x = 0.f, y = 0.f, mu = 0.f;
@@ -213,7 +237,7 @@ template <bool IM> __device__ __forceinline__ void img_newton_body(const PosArgs
     x = s0.x;
     y = s0.y;
     float bx, by, h[4];
-    img_lens_eval_of<IM>(a, b, x, y, bx, by, h, c);
+    eval(x, y, bx, by, h);
     float r_x = sx - bx, r_y = sy - by, r2 = r_x * r_x + r_y * r_y;
     // the affine preimage misses beta_s by more than a cell side: the triangle straddles a singular or discontinuous point of
     // the deflection (the centre of an SIS / SIE / EPL with gamma >= 2), not a smooth neighbourhood of an image; if such a
@@ -236,7 +260,7 @@ template <bool IM> __device__ __forceinline__ void img_newton_body(const PosArgs
       }
       const float nx = x + dx, ny = y + dy;
       float nbx, nby, nh[4];
-      img_lens_eval_of<IM>(a, b, nx, ny, nbx, nby, nh, c);
+      eval(nx, ny, nbx, nby, nh);
       const float nr_x = sx - nbx, nr_y = sy - nby, nr2 = nr_x * nr_x + nr_y * nr_y;
       if (conv) {  // the polishing step
         if (nr2 <= r2) { x = nx; y = ny; for (int k = 0; k < 4; ++k) h[k] = nh[k]; }
@@ -291,6 +315,11 @@ template <bool IM> __device__ __forceinline__ void img_newton_body(const PosArgs
     o[1] = src >= 0 ? ry[src] : nan;
     o[2] = src >= 0 ? rmu[src] : nan;
   }
+}
+template <bool IM> __device__ __forceinline__ void img_newton_body(const PosArgs& a, const ImgArgs& g) {
+  const int bs = blockIdx.x, b = bs / g.S;
+  const float c = g.src_scale ? g.src_scale[bs - b * g.S] : 1.f;
+  img_newton_core(g, ImgEvalScaled<IM>{a, b, c});
 }
 __global__ void __launch_bounds__(64) gl_img_newton_kernel(PosArgs a, ImgArgs g) { img_newton_body<false>(a, g); }
 __global__ void __launch_bounds__(64) gl_img_newton_im_kernel(PosArgs a, ImgArgs g) { img_newton_body<true>(a, g); }

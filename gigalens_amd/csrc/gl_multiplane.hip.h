@@ -110,10 +110,18 @@ struct MpLdsSums {
   }
 };
 
+// mp_trace's `skip` of the callers that evaluate every lens wherever the ray meets its plane
+struct MpSkipNone {
+  __device__ __forceinline__ bool operator()(const CompDesc&, const float*, float, float) const { return false; }
+};
+
 // the plane recursion for sample b of a.params from (tx, ty): on return `sums` holds every a_i (zero for the planes the model lacks).
 // CATS: lens_point's (no model with planes holds a catalogue; false leaves the catalogue loop out of the kernel)
-template <class R, bool CATS = true, class Sums>
-__device__ __forceinline__ void mp_trace(const PosArgs& a, const MpArgs& mp, int b, const R& tx, const R& ty, Sums& sums) {
+// skip(cd, raw parameters, x_j, y_j) == true: the lens is not evaluated at the ray's position on its plane and its plane sum becomes
+// NaN (the lens-equation solver on planes, gl_multiplane_images.hip.h: a singular centre, a ray that is not finite)
+template <class R, bool CATS = true, class Sums, class Skip = MpSkipNone>
+__device__ __forceinline__ void mp_trace(const PosArgs& a, const MpArgs& mp, int b, const R& tx, const R& ty, Sums& sums,
+                                         const Skip& skip = Skip()) {
   for (int t = 0; t < a.n_lens; ++t) {
     const int l = mp.order[t], pl = mp.plane[l];
     const CompDesc cd = a.comps[l];
@@ -127,9 +135,13 @@ __device__ __forceinline__ void mp_trace(const PosArgs& a, const MpArgs& mp, int
       p[k] = R(pf[k]);
     }
     R ax, ay;
-    lens_point<R, CATS>(a, cd, p, x, y, ax, ay);
-    if constexpr (!std::is_same<R, float>::value)
-      mp_add_excess(ax, ay, x, y, lens_kappa_excess<float>(a, cd, pf, mp_value(x), mp_value(y)));
+    if (skip(cd, pf, mp_value(x), mp_value(y))) {
+      ax = ay = R(__builtin_nanf(""));
+    } else {
+      lens_point<R, CATS>(a, cd, p, x, y, ax, ay);
+      if constexpr (!std::is_same<R, float>::value)
+        mp_add_excess(ax, ay, x, y, lens_kappa_excess<float>(a, cd, pf, mp_value(x), mp_value(y)));
+    }
     sums.add(pl, ax, ay);
   }
 }

@@ -91,8 +91,9 @@ class PhysicalModel(PhysicalModelBase):
         ``LensSimulator.simulate_vjp``, ``ForwardProbModel.stats_pixels`` and, on a ``ForwardProbModel`` without image positions, the
         fused ``log_prob`` / ``log_prob_and_grad`` / ``term_log_prob_and_grad`` that MAP, SVI, HMC and SMC run on -- with the
         image-position likelihood when the ``ForwardProbModel`` places its families by ``centroids_redshifts``.
-        ``BackwardProbModel`` / ``lstsq_simulate``, the solver, curves, potentials and ``reconstruct_source`` raise
-        ``_native.UnsupportedLensError``."""
+        ``LensSimulator.image_positions(source_redshifts=...)`` solves the lens equation for sources at redshifts of their own.
+        ``BackwardProbModel`` / ``lstsq_simulate``, the solver without ``source_redshifts``, curves, potentials and
+        ``reconstruct_source`` raise ``_native.UnsupportedLensError``."""
         super().__init__(lenses, lens_light, source_light, lenses_constants, lens_light_constants,
                          source_light_constants)
         self.multiplane = None

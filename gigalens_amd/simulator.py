@@ -222,8 +222,8 @@ class LensSimulator(LensSimulatorInterface):
     def _single_plane(self, what):
         if self._mp is not None:
             raise _native.UnsupportedLensError(f"{what} does not serve a model with {self._mp.K} lens planes: multi-plane ray tracing "
-                                               "serves beta, magnification, convergence, shear, rotation, simulate*, simulate_vjp and "
-                                               "the pixel likelihood with its gradient")
+                                               "serves beta, magnification, convergence, shear, rotation, simulate*, simulate_vjp, "
+                                               "the pixel likelihood with its gradient and image_positions(source_redshifts=...)")
 
     def _target_scales(self, deflection_scale):
         """The ``deflection_scale`` keyword of the lens maps on a multi-plane model: a source index, or the ``[K]`` couplings of the
@@ -446,8 +446,27 @@ class LensSimulator(LensSimulatorInterface):
             raise ValueError(f"source_x / source_y must have shape [B] or [B, S] with B = {B}, got {tuple(sx.shape)}")
         return sx, sy
 
+    def _source_targets(self, source_redshifts, S, deflection_scale):
+        """The ``source_redshifts`` keyword of ``image_positions``: ``(mp, [S, K] couplings)`` of the ``MultiPlane`` the model was
+        built with -- row s is ``mp.target_scales(z_s)``."""
+        if not (np.ndim(deflection_scale) == 0 and float(deflection_scale) == 1.0):
+            raise ValueError("source_redshifts and deflection_scale are two ways to place the sources: give one")
+        mp = self._mp if self._mp is not None else getattr(self.phys_model, "_multiplane_single", None)
+        if mp is None:
+            raise ValueError("source_redshifts needs a PhysicalModel built with a cosmology.MultiPlane (its planes turn the redshifts "
+                             "into couplings); on a model without one, place the sources with deflection_scale")
+        z = np.asarray(source_redshifts, dtype=np.float64)
+        if z.ndim == 0:
+            z = np.broadcast_to(z, (S,))
+        if z.ndim != 1 or z.size != S:
+            raise ValueError(f"source_redshifts: a scalar or one redshift per source ({S}), got shape {z.shape}")
+        if not np.all(np.isfinite(z)) or np.any(z <= mp.z_planes[0]):
+            raise ValueError(f"source_redshifts: every redshift must be finite and lie behind the first lens plane "
+                             f"(z = {mp.z_planes[0]}), got {z.tolist()}")
+        return mp, np.stack([mp.target_scales(zs) for zs in z], axis=0)
+
     def image_positions(self, lens_params, source_x, source_y, *, window=None, num_cells=None, max_images=8, tol=None,
-                        max_iter=30, strict=False, deflection_scale=1.0):
+                        max_iter=30, strict=False, deflection_scale=1.0, source_redshifts=None):
         """Solve the lens equation beta(theta) = beta_s for every sample (beyond the reference: it only maps theta -> beta).
 
         ``lens_params``: the ``lens_mass`` list of dicts, a nested dict with a ``lens_mass`` entry, or packed ``[B, P]`` rows.
@@ -459,12 +478,22 @@ class LensSimulator(LensSimulatorInterface):
         ``RuntimeError`` with ``strict=True``.  ``deflection_scale``: a scalar, or one value per source ``[S]`` -- source s is solved
         on its own plane ``beta_s(theta) = theta - c_s sum alpha`` (``mu`` is that plane's magnification).  Forward only (no gradient).
 
+        ``source_redshifts`` (instead of ``deflection_scale``; a model built with a ``cosmology.MultiPlane``): a scalar, or one
+        redshift per source ``[S]``.  On two to four lens planes source s is traced through the planes in front of it,
+        ``beta_s(theta) = theta - sum_i T_si a_i(theta)`` with ``T_s = MultiPlane.target_scales(z_s)`` (``gl_multiplane_image_positions``;
+        ``mu`` is ``1 / det A`` of the full, non-symmetric Jacobian on that source's plane); such a model without
+        ``source_redshifts`` raises ``UnsupportedLensError`` -- a source without a redshift names no plane.  On a one-plane
+        ``MultiPlane`` the redshifts become the per-source ``deflection_scale``.  ``ValueError``: together with a
+        ``deflection_scale``, a wrong count, a redshift that is not finite or not behind the first lens plane, a model without a
+        ``MultiPlane``.
+
         The window is half-open for an image exactly ON its boundary: two of the four sides count, one of ``y_lo`` / ``y_hi`` and
         one of ``x_lo`` / ``x_hi`` -- those whose counter-clockwise direction, mapped by ``sign(det A) A`` (``A = I - H``), points
         upwards or exactly to the right; without a lens ``y = y_lo`` and ``x = x_hi``, the corner ``(x_hi, y_lo)`` included.  An
         image on the other two sides is neither returned nor counted.  Strictly inside, an image on a shared cell edge or
         vertex is found once."""
-        self._single_plane("image_positions")
+        if source_redshifts is None:
+            self._single_plane("image_positions")
         if torch.is_tensor(lens_params):
             packed = lens_params
         elif isinstance(lens_params, dict):
@@ -483,10 +512,19 @@ class LensSimulator(LensSimulatorInterface):
         if tol is None:
             tol = self.IMAGE_TOL_EPS * float(np.finfo(np.float32).eps) * max(abs(v) for v in window)
         S = sx.shape[1]
-        scales = np.asarray(deflection_scale, dtype=np.float32)
-        scales = _native.deflection_scales(np.broadcast_to(scales, (S,)) if scales.ndim == 0 else scales, S, "deflection_scale")
-        out, n, dropped = self._model.image_positions(packed, sx, sy, window, int(num_cells), int(max_images), float(tol),
-                                                      int(max_iter), scales=scales if np.any(scales != 1.0) else None)
+        targets = None
+        if source_redshifts is not None:
+            mp, targets = self._source_targets(source_redshifts, S, deflection_scale)
+            if mp.K == 1:  # one plane: the existing path on the sources' own scales
+                deflection_scale, targets = targets[:, 0], None
+        if targets is not None:
+            out, n, dropped = self._model.multiplane_image_positions(packed, sx, sy, targets, window, int(num_cells), int(max_images),
+                                                                     float(tol), int(max_iter))
+        else:
+            scales = np.asarray(deflection_scale, dtype=np.float32)
+            scales = _native.deflection_scales(np.broadcast_to(scales, (S,)) if scales.ndim == 0 else scales, S, "deflection_scale")
+            out, n, dropped = self._model.image_positions(packed, sx, sy, window, int(num_cells), int(max_images), float(tol),
+                                                          int(max_iter), scales=scales if np.any(scales != 1.0) else None)
         n_drop = int(dropped.sum())
         if n_drop:
             msg = (f"image_positions: {n_drop} image(s) found but not returned over {int((dropped > 0).sum())} "

@@ -612,6 +612,25 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
  * GL_EINVAL: null arguments, sizes out of range; GL_ENOMEM: workspace smaller than gl_image_positions_workspace_bytes. */
 int gl_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_cells, const void* workspace,
                                     size_t workspace_bytes, int32_t* n_cand, int32_t* n_over, void* hip_stream);
+/* The lens-equation solver on lens planes (after gl_model_set_lens_planes; gl_image_positions[_scaled] refuse such a model): source s
+ * sits on a plane of its own with the couplings targets [n_src][n_planes] (HOST; row s = MultiPlane.target_scales(z_s): finite,
+ * >= 0, 0 from the first lens plane at or behind the source on, not all 0 -- the rules of gl_model_set_position_targets) and is
+ * solved for beta_t(theta) = theta - sum_i T_si a_i(theta) = beta_s, the recursion of gl_multiplane_maps.  The plane sums a_i do not
+ * depend on the target, so one map of them per sample -- n_planes maps of the single-plane size -- serves every source of the call,
+ * whatever its plane.  A vertex is flagged for a plane when a GL_SIS lens of that plane is centred bit for bit on the ray's position
+ * ON THAT PLANE, when the ray reaches the plane not finite, or when the plane's sum is not finite; a plane at or behind a source
+ * (coupling 0) never flags that source.  Scan, Newton (on the full, non-symmetric Jacobian A_t; the dPIS convergence excess as in
+ * gl_multiplane_maps), merge, sort, window, outputs and counters are those of gl_image_positions; mu = 1 / det A_t, the signed
+ * magnification on the source's own plane.  The rows are copied on hip_stream into the call's workspace.  Deterministic; no host
+ * synchronisation, no allocation: workspace of gl_multiplane_image_positions_workspace_bytes (0 for invalid sizes and for a model
+ * without planes) = the single-plane workspace + (n_planes - 1) maps + the coupling rows.  GL_EINVAL: the cases of
+ * gl_image_positions, a model without planes ("gl_model_set_lens_planes has not been called"), n_planes that differs from the
+ * model's, a bad coupling row.  No gradient. */
+size_t gl_multiplane_image_positions_workspace_bytes(const gl_model* m, int B, int n_src, int n_cells, int max_images);
+int gl_multiplane_image_positions(const gl_model* m, const float* params, int B, const float* src_x, const float* src_y, int n_src,
+                                  const float* targets, int n_planes, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
+                                  int max_images, float tol, int max_iter, float* out, int32_t* n_images, int32_t* n_dropped,
+                                  void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Critical curves and caustics (beyond the reference): the image-plane locus D = det(I - H) = 0 (the Hessian as gl_lens_maps has
  * it) of every sample, contoured by marching squares on n_cells x n_cells cells over the window [x_lo, x_hi] x [y_lo, y_hi], and
