@@ -143,6 +143,9 @@ SYMBOLS = {
     "gl_multiplane_image_positions": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_float), c_int, c_float,
                                               c_float, c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_size_t, c_void_p]),
+    "gl_multiplane_fermat_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "gl_multiplane_fermat": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double),
+                                     POINTER(c_double), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "gl_image_positions_stage_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
@@ -1086,6 +1089,33 @@ class Model:
                                                              y_hi, int(n_cells), int(max_images), float(tol), int(max_iter), _ptr(out),
                                                              _ptr(n_images), _ptr(n_dropped), _ptr(ws), ws.numel(), _stream()))
         return out, n_images, n_dropped
+
+    def multiplane_fermat(self, params, x, y, src_x, src_y, geom, pot):
+        """gl_multiplane_fermat: the arrival time ``T`` of rays from the points ``x, y`` ``[B, S, M]`` (NaN = no point) to the sources
+        ``src_x, src_y`` ``[B, S]`` behind lens planes, float64 ``[B, S, M]``.  ``geom`` ``[S, K]`` and ``pot`` ``[K]`` on the host
+        (``MultiPlane.delay_weights(z_s)``); ``T`` is in arcsec^2 times their unit.  ``UnsupportedLensError``: a lens without a
+        potential."""
+        params = self._params(params)
+        B = params.shape[0]
+        x = torch.as_tensor(x).to(device=self.device, dtype=torch.float32).contiguous()
+        y = torch.as_tensor(y).to(device=self.device, dtype=torch.float32).contiguous()
+        src_x = torch.as_tensor(src_x).to(device=self.device, dtype=torch.float32).contiguous()
+        src_y = torch.as_tensor(src_y).to(device=self.device, dtype=torch.float32).contiguous()
+        if x.shape != y.shape or x.dim() != 3 or x.shape[0] != B or x.numel() == 0:
+            raise NativeLibraryError(f"points must be [B={B}, S, M], got {tuple(x.shape)} / {tuple(y.shape)}")
+        S, M = int(x.shape[1]), int(x.shape[2])
+        if src_x.shape != (B, S) or src_y.shape != (B, S):
+            raise NativeLibraryError(f"source positions must be [B={B}, S={S}], got {tuple(src_x.shape)} / {tuple(src_y.shape)}")
+        g = np.ascontiguousarray(geom, dtype=np.float64)
+        v = np.ascontiguousarray(pot, dtype=np.float64).reshape(-1)
+        if g.ndim != 2 or g.shape[0] != S or g.shape[1] != v.size:
+            raise NativeLibraryError(f"geom must be [S={S}, n_planes] and pot [n_planes], got {g.shape} and {v.shape}")
+        ws = self._scratch("multiplane_fermat", lib().gl_multiplane_fermat_workspace_bytes(self._h, S))
+        out = torch.empty((B, S, M), dtype=torch.float64, device=self.device)
+        _check_potential(lib().gl_multiplane_fermat(self._h, _ptr(params), B, _ptr(x), _ptr(y), _ptr(src_x), _ptr(src_y), S, M,
+                                                    g.ctypes.data_as(POINTER(c_double)), v.ctypes.data_as(POINTER(c_double)),
+                                                    int(v.size), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+        return out
 
     def image_positions_stage_counts(self, B, n_src, n_cells):
         """gl_image_positions_stage_counts: ``n_cand``, ``n_over`` [B, n_src] (int32) of the scan stage, out of the workspace the

@@ -99,3 +99,38 @@ class MultiPlane:
             if zi < z:
                 out[i] = deflection_scale(zi, z, self.z_ref, self.omega_m)
         return out
+
+    def delay_weights(self, z):
+        """``(geom [K], pot [K])`` (float64): the weights of the arrival time of a ray to a source at redshift ``z``,
+
+            T = sum_{i <= K_s} [ geom_i |theta_i - theta_next(i)|^2 / 2 - pot_i psi_i(theta_i) ],
+
+        over the planes in front of the source (``next(i)`` = plane i + 1, or the source behind the last of them), in arcsec^2 times
+        ``c / H0``.  With ``chi = comoving_distance``: ``geom_i = chi_i chi_next / (chi_next - chi_i)`` and
+        ``pot_i = chi_i chi_ref / (chi_ref - chi_i)`` -- the potential of a lens is that of its reduced deflection for ``z_ref``, so its
+        weight is a constant of the plane, and ``geom_i C_i,next(i) = pot_i``.  Planes at or behind ``z`` get 0 in both arrays.  One
+        plane: ``geom_0 = D_dt H0 / c``.  ``ValueError`` under the rules of ``target_scales``."""
+        z = float(z)
+        if not (np.isfinite(z) and z > self.z_planes[0]):
+            raise ValueError(f"a target must be finite and lie behind the first lens plane (z = {self.z_planes[0]}), got {z}")
+        front = self.z_planes < z
+        chi = comoving_distance(self.z_planes, self.omega_m)
+        chi_ref, chi_s = (float(comoving_distance(v, self.omega_m)) for v in (self.z_ref, z))
+        ks = int(front.sum())
+        nxt = np.append(chi[1:ks], chi_s)  # chi of next(i) for the ks planes in front of the source
+        geom, pot = np.zeros(self.K), np.zeros(self.K)
+        geom[:ks] = chi[:ks] * nxt / (nxt - chi[:ks])
+        pot[:ks] = chi[:ks] * chi_ref / (chi_ref - chi[:ks])
+        return geom, pot
+
+
+C_KM_S = 299792.458
+
+
+def hubble_distance_mpc(h0):
+    """``c / H0`` in Mpc for ``h0`` in km/s/Mpc (a scalar or an array).  ``ValueError`` unless every ``h0`` is finite and > 0."""
+    h = np.asarray(h0, dtype=np.float64)
+    if not (np.all(np.isfinite(h)) and np.all(h > 0.0)):
+        raise ValueError(f"h0 must be finite and > 0 (km/s/Mpc), got {h0}")
+    d = C_KM_S / h
+    return float(d) if h.ndim == 0 else d

@@ -1,7 +1,7 @@
 // gl_api_points.hip -- the entry points of the point family: everything that evaluates the lenses of a model (or one free-standing
 // profile) at points through gl_positions.hip.h -- image-position likelihood, lens maps, Hessians, potential, the lens-equation
 // solver, critical curves, the Hessian VJP with the weak-lensing shear likelihood, the image-plane position likelihood, and the lens
-// planes (maps, render and its VJP).
+// planes (maps, render and its VJP, solver, arrival times).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -18,6 +18,7 @@
 #include "gl_multiplane_bwd.hip.h"
 #include "gl_multiplane_pos.hip.h"
 #include "gl_multiplane_images.hip.h"
+#include "gl_multiplane_fermat.hip.h"
 #include "gl_lens_vjp.hip.h"
 #include "gl_hessian_vjp.hip.h"
 #include "gl_imgplane.hip.h"
@@ -106,6 +107,16 @@ MpImgLayout mp_img_layout(int B, int n_src, int n_cells, int K) {
   l.img = img_layout(B, n_src, n_cells, K);
   l.tgt = l.img.bytes;
   l.bytes = l.tgt + align_up((size_t)n_src * (size_t)K * sizeof(float), 256);
+  return l;
+}
+
+// ... and of the arrival times on K lens planes (gl_multiplane_fermat): the weight rows [n_src][K] and [K], as doubles
+struct MpFermatLayout { size_t geom, pot, bytes; };
+MpFermatLayout mp_fermat_layout(int n_src, int K) {
+  MpFermatLayout l{};
+  l.geom = 0;
+  l.pot = l.geom + align_up((size_t)n_src * (size_t)K * sizeof(double), 256);
+  l.bytes = l.pot + align_up((size_t)K * sizeof(double), 256);
   return l;
 }
 
@@ -862,6 +873,60 @@ int gl_multiplane_image_positions(const gl_model* m, const float* params, int B,
   hipLaunchKernelGGL(gl_mpimg_map_kernel, dim3((unsigned)map_blocks), dim3(256), 0, stream, a, mp, g, q);
   hipLaunchKernelGGL(gl_mpimg_scan_kernel, dim3((unsigned)pairs), dim3(IMG_SCAN_WG), 0, stream, g, q);
   hipLaunchKernelGGL(gl_mpimg_newton_kernel, dim3((unsigned)pairs), dim3(MP_MAPS_WG), 0, stream, a, mp, g, q);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- arrival times on lens planes (gl_multiplane_fermat.hip.h) ----------------------------------------------------
+size_t gl_multiplane_fermat_workspace_bytes(const gl_model* m, int n_src) {
+  if (!m || m->mp_K < 2 || n_src <= 0) return 0;
+  return mp_fermat_layout(n_src, m->mp_K).bytes;
+}
+
+int gl_multiplane_fermat(const gl_model* m, const float* params, int B, const float* x, const float* y, const float* src_x,
+                         const float* src_y, int n_src, int n_points, const double* geom, const double* pot, int n_planes,
+                         double* out, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !x || !y || !src_x || !src_y || !geom || !pot || !out) return fail(GL_EINVAL, "null argument");
+  if (int rc = check_planes_set(m)) return rc;
+  if (B <= 0 || n_src <= 0 || n_points <= 0)
+    return fail(GL_EINVAL, "B (%d), n_src (%d) and n_points (%d) must be positive", B, n_src, n_points);
+  if (n_planes != m->mp_K) return fail(GL_EINVAL, "%d delay weights per source for %d lens planes", n_planes, m->mp_K);
+  const int K = n_planes;
+  for (int i = 0; i < K; ++i)
+    if (!(std::isfinite(pot[i]) && pot[i] >= 0.)) return fail(GL_EINVAL, "pot[%d] = %g: finite and >= 0", i, pot[i]);
+  for (int s = 0; s < n_src; ++s) {  // a row of MultiPlane.delay_weights: the zeros are those of the source's coupling row
+    const double* g = geom + (size_t)s * K;
+    for (int i = 0; i < K; ++i)
+      if (!(std::isfinite(g[i]) && g[i] >= 0.) || (i > 0 && g[i] != 0. && g[i - 1] == 0.))
+        return fail(GL_EINVAL, "geom[%d][%d] = %g: finite and >= 0, 0 from the first plane at or behind the source on", s, i, g[i]);
+    if (g[0] == 0.) return fail(GL_EINVAL, "source %d: every geometric weight is zero (the source lies behind no lens plane)", s);
+  }
+  if (int rc = refuse_potential_lenses(m)) return rc;
+  if (int rc = check_ready(m, false, false)) return rc;
+  const MpFermatLayout lay = mp_fermat_layout(n_src, K);
+  if (!workspace) return fail(GL_EINVAL, "workspace is null");
+  if (workspace_bytes < lay.bytes) return fail(GL_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  const long long total = (long long)B * n_src * n_points, blocks = (total + MP_FERMAT_WG - 1) / MP_FERMAT_WG;
+  if (blocks > 0x7fffffffLL) return fail(GL_EINVAL, "too many samples x sources x points for one call");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  char* base = (char*)workspace;
+  // the weight rows, host -> the call's own workspace on the caller's stream (as the coupling rows of the solver)
+  double* d_geom = (double*)(base + lay.geom);
+  double* d_pot = (double*)(base + lay.pot);
+  GL_HIP(hipMemcpyAsync(d_geom, geom, sizeof(double) * (size_t)n_src * (size_t)K, hipMemcpyHostToDevice, stream));
+  GL_HIP(hipMemcpyAsync(d_pot, pot, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, stream));
+  MpFermatArgs q{};
+  q.x = x;
+  q.y = y;
+  q.src_x = src_x;
+  q.src_y = src_y;
+  q.geom = d_geom;
+  q.pot = d_pot;
+  q.n_src = n_src;
+  q.M = n_points;
+  q.K = K;
+  q.out = out;
+  hipLaunchKernelGGL(gl_mp_fermat_kernel, dim3((unsigned)blocks), dim3(MP_FERMAT_WG), 0, stream, point_args(m, params, B), mp_args(m), q);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

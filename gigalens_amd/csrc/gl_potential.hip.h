@@ -13,8 +13,9 @@
 
 namespace glk {
 
-// psi of one lens at (x, y) with raw parameters p (K_SCALED: the member sum with the scaled parameters of scaled_dyn)
-template <class R> __device__ R lens_potential_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y) {
+// psi of one lens at (x, y) with raw parameters p (K_SCALED: the member sum with the scaled parameters of scaled_dyn).  CATS = false:
+// for models that hold no catalogue (lens planes refuse them), as lens_point_closed -- the member loop indexes p at run time
+template <class R, bool CATS = true> __device__ R lens_potential_point(const PosArgs& a, const CompDesc& cd, const R* p, R x, R y) {
   using namespace glp;
   switch (cd.kind) {
     case K_EPL: return epl_pot<R>(p, cd.iparam, x, y);
@@ -27,7 +28,9 @@ template <class R> __device__ R lens_potential_point(const PosArgs& a, const Com
     case K_NFW_ELLIPSE: { R d[NFE_ND]; nfw_ell_prep<R>(p, d); return nfw_ell_pot<R>(d, x, y); }
     case K_TNFW: { R d[TNF_ND]; tnfw_prep<R>(p, d); return tnfw_pot<R>(d, x, y); }
     case K_MULTIPOLE: { R d[MPL_ND]; multipole_prep<R>(p, cd.iparam, d); return multipole_pot<R>(d, cd.iparam, x, y); }
-    case K_SCALED: {
+    case K_SCALED: if constexpr (!CATS) {
+      return R(__builtin_nanf(""));  // (not reached)
+    } else {
       const CatDev cat = a.cats[cd.iparam];
       const ScaledDesc sd{cat.base_kind, cat.n_gal, {cat.col[0], cat.col[1], cat.col[2]}};
       R psi = R(0.f);

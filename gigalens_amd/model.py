@@ -738,21 +738,34 @@ class ForwardProbModel(_StreamProbModel):
             sy.append(by.mean(dim=0))
         return torch.stack(sx, dim=1), torch.stack(sy, dim=1)
 
-    def predicted_time_delays(self, simulator, params, time_delay_distance=None, **solver_kwargs):
+    def predicted_time_delays(self, simulator, params, time_delay_distance=None, h0=None, **solver_kwargs):
         """Images and arrival-time delays the model predicts for every family (beyond the reference), for the same barycentre
         source as ``predicted_positions``.  Returns one ``(x, y, mu, n, dt)`` tuple per family, ``dt`` ``[B, max_images]`` relative
         to the family's first-arriving image, in arcsec^2 of Fermat potential or, with ``time_delay_distance`` (D_dt in Mpc, a
-        scalar or ``[B]``), in days (``LensSimulator.time_delays``, which ``solver_kwargs`` go to).  Forward only."""
+        scalar or ``[B]``), in days (``LensSimulator.time_delays``, which ``solver_kwargs`` go to).  Forward only.
+
+        A model built with ``centroids_redshifts`` on a one-plane ``MultiPlane`` goes through ``time_delays(source_redshifts=...)``,
+        every family on its own scaled plane: ``dt`` in arcsec^2 times ``c / H0``, or in days with ``h0`` (km/s/Mpc); it takes no
+        ``time_delay_distance``.  On several lens planes the call stays refused, as ``predicted_positions``."""
         if self.centroids_x is None:
             raise ValueError("predicted_time_delays needs a model built with centroids_x/centroids_y")
-        if np.any(self._family_scales(simulator)[0] != 1.0):
-            raise NotImplementedError("predicted_time_delays: the Fermat potential of a scaled source plane (centroids_scales != 1) "
-                                      "is not served; time delays stay single-plane")
+        scales = self._family_scales(simulator)[0]  # (lens planes: its UnsupportedLensError)
+        by_redshift = self.centroids_redshifts is not None
+        if not by_redshift:
+            if h0 is not None:
+                raise ValueError("predicted_time_delays: h0 serves families placed by centroids_redshifts; give time_delay_distance")
+            if np.any(scales != 1.0):
+                raise NotImplementedError("predicted_time_delays: the Fermat potential of a scaled source plane (centroids_scales != 1) "
+                                          "is not served without redshifts (centroids_redshifts)")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         if packed.requires_grad:
             raise NotImplementedError("predicted_time_delays is a forward-only diagnostic (no gradient)")
         sx, sy = self._family_sources(simulator, packed)
-        x, y, mu, n, dt = simulator.time_delays(packed, sx, sy, time_delay_distance=time_delay_distance, **solver_kwargs)
+        if by_redshift:
+            x, y, mu, n, dt = simulator.time_delays(packed, sx, sy, source_redshifts=self.centroids_redshifts, h0=h0,
+                                                    time_delay_distance=time_delay_distance, **solver_kwargs)
+        else:
+            x, y, mu, n, dt = simulator.time_delays(packed, sx, sy, time_delay_distance=time_delay_distance, **solver_kwargs)
         return [(x[:, f], y[:, f], mu[:, f], n[:, f], dt[:, f]) for f in range(len(self.centroids_x))]
 
     def image_plane_rms(self, simulator, params, **solver_kwargs):

@@ -223,7 +223,8 @@ class LensSimulator(LensSimulatorInterface):
         if self._mp is not None:
             raise _native.UnsupportedLensError(f"{what} does not serve a model with {self._mp.K} lens planes: multi-plane ray tracing "
                                                "serves beta, magnification, convergence, shear, rotation, simulate*, simulate_vjp, "
-                                               "the pixel likelihood with its gradient and image_positions(source_redshifts=...)")
+                                               "the pixel likelihood with its gradient, image_positions(source_redshifts=...), "
+                                               "time_delays(source_redshifts=...) and fermat_potential(source_redshift=...)")
 
     def _target_scales(self, deflection_scale):
         """The ``deflection_scale`` keyword of the lens maps on a multi-plane model: a source index, or the ``[K]`` couplings of the
@@ -678,40 +679,107 @@ class LensSimulator(LensSimulatorInterface):
         self._potential_lenses()
         return self._model.lens_potential(packed, x, y)
 
-    def fermat_potential(self, x, y, source_x, source_y, lens_params):
+    def _delay_weights(self, source_redshifts, S):
+        """``(mp, targets [S, K], geom [S, K], pot [K])`` of sources at ``source_redshifts`` (a scalar or ``[S]``): the couplings of
+        ``_source_targets`` and the arrival-time weights ``MultiPlane.delay_weights`` (float64).  ``pot`` is a constant of the plane:
+        every source's row holds it for the planes in front of that source, so the largest over the rows is the plane's."""
+        mp, targets = self._source_targets(source_redshifts, S, 1.0)
+        z = np.broadcast_to(np.asarray(source_redshifts, dtype=np.float64), (S,))
+        weights = [mp.delay_weights(zs) for zs in z]
+        return mp, targets, np.stack([w[0] for w in weights], axis=0), np.max(np.stack([w[1] for w in weights], axis=0), axis=0)
+
+    def fermat_potential(self, x, y, source_x, source_y, lens_params, *, source_redshift=None):
         """Fermat potential ``phi = |theta - beta_s|^2 / 2 - psi(theta)`` at ``theta = (x, y)`` for the source ``beta_s`` (beyond the
-        reference; arcsec^2).  ``source_x`` / ``source_y`` broadcast against ``x``, ``y`` (trailing axis = batch).  Forward only."""
+        reference; arcsec^2).  ``source_x`` / ``source_y`` broadcast against ``x``, ``y`` (trailing axis = batch).  Forward only.
+
+        ``source_redshift`` (a model built with a ``cosmology.MultiPlane``): the arrival time ``T`` of the ray from ``theta`` to a source
+        at that redshift, through the lens planes in front of it (``gl_multiplane_fermat``, the formula of
+        ``MultiPlane.delay_weights``), in arcsec^2 times ``c / H0`` and in float64.  On one plane ``T = geom_0 (|theta - beta_s|^2 / 2 -
+        c psi)`` with the source's ``deflection_scale`` c.  A model with lens planes serves this form alone: without a redshift
+        it raises ``UnsupportedLensError``."""
         self._forward_only("fermat_potential", source_x, source_y)
-        psi = self.potential(x, y, lens_params)
-        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
-        y = torch.as_tensor(y, dtype=torch.float32, device=self.device)
-        sx = torch.as_tensor(source_x, dtype=torch.float32, device=self.device)
-        sy = torch.as_tensor(source_y, dtype=torch.float32, device=self.device)
-        return 0.5 * ((x - sx) ** 2 + (y - sy) ** 2) - psi
+        if source_redshift is None:
+            psi = self.potential(x, y, lens_params)
+            x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+            y = torch.as_tensor(y, dtype=torch.float32, device=self.device)
+            sx = torch.as_tensor(source_x, dtype=torch.float32, device=self.device)
+            sy = torch.as_tensor(source_y, dtype=torch.float32, device=self.device)
+            return 0.5 * ((x - sx) ** 2 + (y - sy) ** 2) - psi
+        if np.ndim(source_redshift) != 0:
+            raise ValueError(f"source_redshift: one redshift, got shape {np.shape(source_redshift)}")
+        packed = self._lens_rows(lens_params)
+        self._forward_only("fermat_potential", packed, x, y)
+        self._potential_lenses()
+        mp, targets, geom, pot = self._delay_weights(source_redshift, 1)
+        B = packed.shape[0]
+        x, y, sx, sy = torch.broadcast_tensors(*(torch.as_tensor(v, dtype=torch.float32, device=self.device)
+                                                 for v in (x, y, source_x, source_y)))
+        if x.dim() == 0 or x.shape[-1] not in (1, B):
+            raise ValueError(f"x, y and the source must broadcast to (..., B = {B}), got {tuple(x.shape)}")
+        shape = tuple(x.shape[:-1]) + (B,)
+        x, y, sx, sy = (v.expand(shape).reshape(-1, B).t().contiguous() for v in (x, y, sx, sy))  # [B, N]
+        if mp.K == 1:  # one plane: the source's own scale on the single-plane potential
+            psi = self._model.lens_potential(packed, x.t(), y.t()).t()
+            phi = 0.5 * ((x.double() - sx.double()) ** 2 + (y.double() - sy.double()) ** 2) - float(targets[0, 0]) * psi.double()
+            T = phi * float(geom[0, 0])
+        else:  # every point is the one image of a source of its own
+            N = x.shape[1]
+            T = self._model.multiplane_fermat(packed, x[..., None], y[..., None], sx, sy, np.repeat(geom, N, axis=0), pot)[..., 0]
+        return T.t().reshape(shape)
 
     # D_dt / c * (1 arcsec)^2 in days per Mpc: the time-delay distance turns a Fermat-potential difference in arcsec^2 into a delay
     # (IAU 2012 astronomical unit -> parsec -> Mpc, c exact, 1 day = 86400 s)
     MPC_M = 648000.0 / np.pi * 149597870700.0 * 1e6
     DAYS_PER_MPC_ARCSEC2 = MPC_M / 299792458.0 * (np.pi / 648000.0) ** 2 / 86400.0
 
-    def time_delays(self, lens_params, source_x, source_y, *, time_delay_distance=None, **solver_kwargs):
+    def time_delays(self, lens_params, source_x, source_y, *, source_redshifts=None, h0=None, time_delay_distance=None,
+                    **solver_kwargs):
         """Images of the sources and their arrival times for every sample (beyond the reference).
 
         Calls ``image_positions`` (``solver_kwargs`` go there) and returns its ``x, y, mu, n`` plus ``dt`` ``[B, S, max_images]``:
         the arrival time of every image relative to the first-arriving image of its (sample, source), i.e. its Fermat-potential
         excess ``phi - min phi`` (``dt >= 0``; NaN where ``x`` is NaN).  Units: arcsec^2, or days when ``time_delay_distance``
-        (D_dt in Mpc, a scalar or ``[B]``) is given: ``dt * D_dt * DAYS_PER_MPC_ARCSEC2``.  Forward only."""
-        self._single_plane("time_delays")
+        (D_dt in Mpc, a scalar or ``[B]``) is given: ``dt * D_dt * DAYS_PER_MPC_ARCSEC2``.  Forward only.
+
+        ``source_redshifts`` (a model built with a ``cosmology.MultiPlane``; a scalar or one redshift per source): the images come
+        from ``image_positions(source_redshifts=...)`` and ``dt = T - min T`` with the arrival time ``T`` of the ray through the lens
+        planes in front of each source (``gl_multiplane_fermat``; float64 on the device, cast to float32 last).  Units: arcsec^2
+        times ``c / H0`` -- the weights are comoving distances in that unit --, or days with ``h0`` (km/s/Mpc, a scalar or ``[B]``):
+        ``dt * cosmology.hubble_distance_mpc(h0) * DAYS_PER_MPC_ARCSEC2``.  On a one-plane ``MultiPlane`` source s is solved with its
+        ``deflection_scale`` c_s and ``T = geom_s0 (|theta - beta_s|^2 / 2 - c_s psi)``.  A model with lens planes needs the
+        redshifts (``UnsupportedLensError`` without).  ``ValueError``: ``time_delay_distance`` together with ``source_redshifts`` (on
+        planes there is no single distance), ``h0`` without ``source_redshifts``."""
+        if source_redshifts is not None and time_delay_distance is not None:
+            raise ValueError("time_delay_distance and source_redshifts: with redshifts every plane brings a distance of its own; give "
+                             "h0 for days")
+        if source_redshifts is None and h0 is not None:
+            raise ValueError("h0 turns the arrival times of sources with redshifts into days: give source_redshifts (or, without "
+                             "redshifts, time_delay_distance)")
+        if source_redshifts is None:
+            self._single_plane("time_delays")
         packed = self._lens_rows(lens_params)
         self._forward_only("time_delays", packed, source_x, source_y)
         self._potential_lenses()
         B = packed.shape[0]
-        x, y, mu, n = self.image_positions(packed, source_x, source_y, **solver_kwargs)
         sx, sy = self._source_rows(source_x, source_y, B)                   # [B, S]
+        if source_redshifts is not None:
+            if h0 is not None:
+                from gigalens_amd.cosmology import hubble_distance_mpc
+                time_delay_distance = hubble_distance_mpc(h0.detach().cpu().numpy() if torch.is_tensor(h0) else h0)
+            mp, targets, geom, pot = self._delay_weights(source_redshifts, sx.shape[1])
+            solver_kwargs = dict(solver_kwargs, source_redshifts=source_redshifts)
+        x, y, mu, n = self.image_positions(packed, source_x, source_y, **solver_kwargs)
         ok = ~torch.isnan(x)
-        xs, ys = torch.where(ok, x, torch.zeros_like(x)), torch.where(ok, y, torch.zeros_like(y))
-        psi = self._model.lens_potential(packed, xs.permute(1, 2, 0), ys.permute(1, 2, 0)).permute(2, 0, 1)  # [B, S, M]
-        phi = 0.5 * ((xs.double() - sx[..., None].double()) ** 2 + (ys.double() - sy[..., None].double()) ** 2) - psi.double()
+        if source_redshifts is not None and mp.K >= 2:
+            phi = self._model.multiplane_fermat(packed, x, y, sx, sy, geom, pot)  # [B, S, M] float64; NaN where x is
+        else:
+            xs, ys = torch.where(ok, x, torch.zeros_like(x)), torch.where(ok, y, torch.zeros_like(y))
+            psi = self._model.lens_potential(packed, xs.permute(1, 2, 0), ys.permute(1, 2, 0)).permute(2, 0, 1).double()  # [B, S, M]
+            if source_redshifts is not None:  # one plane: the sources' own scales, and the weight in place of D_dt
+                psi = psi * torch.as_tensor(targets[:, 0], dtype=torch.float64, device=self.device)[None, :, None]
+            phi = 0.5 * ((xs.double() - sx[..., None].double()) ** 2 + (ys.double() - sy[..., None].double()) ** 2) - psi
+            if source_redshifts is not None:
+                phi = phi * torch.as_tensor(geom[:, 0], dtype=torch.float64, device=self.device)[None, :, None]
         phi = torch.where(ok, phi, torch.full_like(phi, float("inf")))
         dt = phi - phi.amin(dim=2, keepdim=True)
         if time_delay_distance is not None:

@@ -631,6 +631,25 @@ int gl_multiplane_image_positions(const gl_model* m, const float* params, int B,
                                   const float* targets, int n_planes, float x_lo, float x_hi, float y_lo, float y_hi, int n_cells,
                                   int max_images, float tol, int max_iter, float* out, int32_t* n_images, int32_t* n_dropped,
                                   void* workspace, size_t workspace_bytes, void* hip_stream);
+/* Arrival times on lens planes (after gl_model_set_lens_planes; gl_lens_potential keeps refusing such a model: one psi is not
+ * defined across planes).  x, y [B][n_src][n_points] (DEVICE; NaN = no point, e.g. the padding of gl_multiplane_image_positions) are
+ * image-plane positions theta of rays to the sources src_x, src_y [B][n_src] (DEVICE); out [B][n_src][n_points] (DEVICE, double) is
+ *   T = sum_{i < Ks} [ geom_si |theta_i - theta_next(i)|^2 / 2 - pot_i psi_i(theta_i) ]
+ * with theta_i the ray's position on plane i (the recursion of gl_multiplane_maps), psi_i the potential of the lenses of plane i
+ * there, next(i) the plane behind i or, for the last plane in front of the source, the source itself.  geom [n_src][n_planes] and
+ * pot [n_planes] (HOST, double; MultiPlane.delay_weights(z_s)): finite and >= 0; a geom row is 0 from the first plane at or behind
+ * its source on and not all 0; pot_i is a constant of plane i (the row delay_weights gives for the farthest source of the call),
+ * read for the planes in front of a source alone.  T is in arcsec^2 times the unit of the weights (c / H0 for delay_weights); only differences between
+ * rays to ONE source are physical.  Everything is evaluated on double.  A NaN point gives NaN, and so does whatever is not finite
+ * on the way (no lens is skipped).  One launch, one thread per (sample, source, point); the rows are copied on hip_stream into the
+ * call's workspace of gl_multiplane_fermat_workspace_bytes (0 for n_src <= 0 and for a model without planes).  Deterministic; no
+ * host synchronisation, no allocation.  GL_EINVAL: null arguments, sizes <= 0, a model without planes ("gl_model_set_lens_planes
+ * has not been called"), n_planes that differs from the model's, a bad weight, a workspace that is too small; GL_EUNSUPPORTED: a
+ * lens without a potential (the cases of gl_lens_potential).  No gradient. */
+size_t gl_multiplane_fermat_workspace_bytes(const gl_model* m, int n_src);
+int gl_multiplane_fermat(const gl_model* m, const float* params, int B, const float* x, const float* y, const float* src_x,
+                         const float* src_y, int n_src, int n_points, const double* geom, const double* pot, int n_planes,
+                         double* out, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Critical curves and caustics (beyond the reference): the image-plane locus D = det(I - H) = 0 (the Hessian as gl_lens_maps has
  * it) of every sample, contoured by marching squares on n_cells x n_cells cells over the window [x_lo, x_hi] x [y_lo, y_hi], and
