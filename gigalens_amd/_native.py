@@ -149,6 +149,8 @@ SYMBOLS = {
     "gl_lens_potential": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "gl_image_positions_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "gl_image_positions_stage_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "gl_multiplane_image_positions_stage_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                           c_void_p]),
     "gl_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "gl_critical_curves": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -1125,8 +1127,21 @@ class Model:
             raise NativeLibraryError("image_positions_stage_counts: no image_positions call has filled a workspace yet")
         n_cand = torch.empty((int(B), int(n_src)), dtype=torch.int32, device=self.device)
         n_over = torch.empty_like(n_cand)
-        _check(lib().gl_image_positions_stage_counts(self._h, int(B), int(n_src), int(n_cells), _ptr(ws), ws.numel(), _ptr(n_cand),
-                                                     _ptr(n_over), _stream()))
+        _check_potential(lib().gl_image_positions_stage_counts(self._h, int(B), int(n_src), int(n_cells), _ptr(ws), ws.numel(),
+                                                               _ptr(n_cand), _ptr(n_over), _stream()))
+        return n_cand, n_over
+
+    def multiplane_image_positions_stage_counts(self, B, n_src, n_cells):
+        """gl_multiplane_image_positions_stage_counts: ``n_cand``, ``n_over`` [B, n_src] (int32) of the scan stage, out of the
+        workspace the last ``multiplane_image_positions`` call of these sizes filled (read-only; for tests and diagnostics)."""
+        ws = self._scratch_bufs.get("multiplane_image_positions")
+        if ws is None:
+            raise NativeLibraryError("multiplane_image_positions_stage_counts: no multiplane_image_positions call has filled a "
+                                     "workspace yet")
+        n_cand = torch.empty((int(B), int(n_src)), dtype=torch.int32, device=self.device)
+        n_over = torch.empty_like(n_cand)
+        _check_potential(lib().gl_multiplane_image_positions_stage_counts(self._h, int(B), int(n_src), int(n_cells), _ptr(ws),
+                                                                          ws.numel(), _ptr(n_cand), _ptr(n_over), _stream()))
         return n_cand, n_over
 
     def critical_curves(self, params, window, n_cells, max_segments, scale=None):

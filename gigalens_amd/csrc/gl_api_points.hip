@@ -110,6 +110,24 @@ MpImgLayout mp_img_layout(int B, int n_src, int n_cells, int K) {
   return l;
 }
 
+// the two stage-count entries: the shared size rules, and the copy of the scan's two planes out of a workspace of layout `lay`
+// (`bytes_needed`: the whole workspace of the call that filled it)
+int check_stage_counts_sizes(int B, int n_src, int n_cells) {
+  if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  return GL_OK;
+}
+int copy_stage_counts(const ImgLayout& lay, size_t bytes_needed, const void* workspace, size_t workspace_bytes, int B, int n_src,
+                      int* n_cand, int* n_over, void* hip_stream) {
+  if (workspace_bytes < bytes_needed) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, bytes_needed);
+  const size_t bytes = sizeof(int) * (size_t)B * (size_t)n_src;
+  const char* base = (const char*)workspace;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  GL_HIP(hipMemcpyAsync(n_cand, base + lay.n_cand, bytes, hipMemcpyDeviceToDevice, stream));
+  GL_HIP(hipMemcpyAsync(n_over, base + lay.n_over, bytes, hipMemcpyDeviceToDevice, stream));
+  return GL_OK;
+}
+
 // ... and of the arrival times on K lens planes (gl_multiplane_fermat): the weight rows [n_src][K] and [K], as doubles
 struct MpFermatLayout { size_t geom, pot, bytes; };
 MpFermatLayout mp_fermat_layout(int n_src, int K) {
@@ -797,16 +815,11 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
 int gl_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_cells, const void* workspace, size_t workspace_bytes,
                                     int* n_cand, int* n_over, void* hip_stream) {
   if (!m || !workspace || !n_cand || !n_over) return fail(GL_EINVAL, "null argument");
-  if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
-  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  // (a workspace of the solver on lens planes holds K maps in front of the counts: gl_multiplane_image_positions_stage_counts)
+  if (int rp = refuse_planes(m, "gl_image_positions_stage_counts")) return rp;
+  if (int rc = check_stage_counts_sizes(B, n_src, n_cells)) return rc;
   const ImgLayout lay = img_layout(B, n_src, n_cells);
-  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
-  const size_t bytes = sizeof(int) * (size_t)B * (size_t)n_src;
-  const char* base = (const char*)workspace;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  GL_HIP(hipMemcpyAsync(n_cand, base + lay.n_cand, bytes, hipMemcpyDeviceToDevice, stream));
-  GL_HIP(hipMemcpyAsync(n_over, base + lay.n_over, bytes, hipMemcpyDeviceToDevice, stream));
-  return GL_OK;
+  return copy_stage_counts(lay, lay.bytes, workspace, workspace_bytes, B, n_src, n_cand, n_over, hip_stream);
 }
 
 // ---- ... on lens planes (gl_multiplane_images.hip.h) -----------------------------------------------------------
@@ -875,6 +888,16 @@ int gl_multiplane_image_positions(const gl_model* m, const float* params, int B,
   hipLaunchKernelGGL(gl_mpimg_newton_kernel, dim3((unsigned)pairs), dim3(MP_MAPS_WG), 0, stream, a, mp, g, q);
   GL_HIP(hipGetLastError());
   return GL_OK;
+}
+
+// read-only, as gl_image_positions_stage_counts: the counts lie behind the K maps of the model's planes
+int gl_multiplane_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_cells, const void* workspace,
+                                               size_t workspace_bytes, int* n_cand, int* n_over, void* hip_stream) {
+  if (!m || !workspace || !n_cand || !n_over) return fail(GL_EINVAL, "null argument");
+  if (int rc = check_planes_set(m)) return rc;
+  if (int rc = check_stage_counts_sizes(B, n_src, n_cells)) return rc;
+  const MpImgLayout lay = mp_img_layout(B, n_src, n_cells, m->mp_K);
+  return copy_stage_counts(lay.img, lay.bytes, workspace, workspace_bytes, B, n_src, n_cand, n_over, hip_stream);
 }
 
 // ---- arrival times on lens planes (gl_multiplane_fermat.hip.h) ----------------------------------------------------

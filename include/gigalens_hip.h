@@ -609,9 +609,15 @@ int gl_image_positions_scaled(const gl_model* m, const float* params, int B, con
  * d = sign(det A) A u has d.y > 0, or d.y == 0 and d.x > 0.  So one of bottom / top and one of left / right is claimed, a corner
  * when both of its sides are; for the identity map: y = y_lo and x = x_hi with the corner (x_hi, y_lo).  An image on an unclaimed
  * side is not seeded and not counted in n_dropped.  Newton's own window test x_lo <= x <= x_hi, y_lo <= y <= y_hi is inclusive.
- * GL_EINVAL: null arguments, sizes out of range; GL_ENOMEM: workspace smaller than gl_image_positions_workspace_bytes. */
+ * GL_EINVAL: null arguments, sizes out of range; GL_ENOMEM: workspace smaller than gl_image_positions_workspace_bytes;
+ * GL_EUNSUPPORTED: a model with lens planes (its workspace holds one map per plane in front of the counts: the entry below).
+ * gl_multiplane_image_positions_stage_counts reads the same two planes out of a workspace that gl_multiplane_image_positions has
+ * just filled with the same B, n_src, n_cells (the layout of gl_multiplane_image_positions_workspace_bytes, on the model's number
+ * of planes); GL_EINVAL also for a model without planes ("gl_model_set_lens_planes has not been called"). */
 int gl_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_cells, const void* workspace,
                                     size_t workspace_bytes, int32_t* n_cand, int32_t* n_over, void* hip_stream);
+int gl_multiplane_image_positions_stage_counts(const gl_model* m, int B, int n_src, int n_cells, const void* workspace,
+                                               size_t workspace_bytes, int32_t* n_cand, int32_t* n_over, void* hip_stream);
 /* The lens-equation solver on lens planes (after gl_model_set_lens_planes; gl_image_positions[_scaled] refuse such a model): source s
  * sits on a plane of its own with the couplings targets [n_src][n_planes] (HOST; row s = MultiPlane.target_scales(z_s): finite,
  * >= 0, 0 from the first lens plane at or behind the source on, not all 0 -- the rules of gl_model_set_position_targets) and is

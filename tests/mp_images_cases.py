@@ -36,6 +36,19 @@ def solve64(phys, mp, lens_params, b, target, sx, sy, window, n):
     return IC._solve64(deriv64(phys, mp, lens_params, b, target), float(sx), float(sy), window, n)
 
 
+def hessian_mu(maps, phys, mp, lens_params, b, target, ref):
+    """``ref`` [K, 3] with its magnifications taken from ``maps`` (``multilens_cases.maps_hessian``) at the reference images.  The
+    solver's A_t carries the dPIS convergence excess (as gl_multiplane_maps does), which the derivative of the deflection -- the mu
+    of ``solve64`` -- does not: for a lens set with a dPIS the reference mu is that of ``maps_hessian``; the images are the same.
+    (``maps`` reads its points as float32 values: that moves mu by |d mu / d theta| 1e-7, far below the gate of 1e-3.)"""
+    if maps is None or len(ref) == 0:
+        return ref
+    m = maps(phys, mp, [{k: v[b:b + 1] for k, v in d.items()} for d in lens_params], ref[:, 0], ref[:, 1], target)[:, :, 0]
+    out = ref.copy()
+    out[:, 2] = 1.0 / (m[2] * m[5] - m[3] * m[4])
+    return out
+
+
 def fold_pair(ref, window, n_cells):
     """The fold rule of ``_check_against_f64``: two reference images closer than FOLD_CELLS cells."""
     if len(ref) < 2:
@@ -59,9 +72,10 @@ def compare_images(got, ref, tag):
     return len(ref_m)
 
 
-def check_against_f64(sim, phys, mp, lens_params, z_sources, srcx, srcy, window, n_cells, **solver):
+def check_against_f64(sim, phys, mp, lens_params, z_sources, srcx, srcy, window, n_cells, maps=None, **solver):
     """``sim.image_positions(..., source_redshifts=z_sources)`` against the float64 solver at ``2 n_cells``; returns (pairs compared,
-    images compared in each).  ``lens_params``: list of dicts of [B] float32 arrays; ``srcx, srcy``: [B, S] float32 arrays."""
+    images compared in each).  ``lens_params``: list of dicts of [B] float32 arrays; ``srcx, srcy``: [B, S] float32 arrays;
+    ``maps``: where the reference mu comes from when not from the derivative of the deflection (``hessian_mu``)."""
     lt = [{k: torch.as_tensor(v) for k, v in d.items()} for d in lens_params]
     B, S = srcx.shape
     x, y, mu, n = sim.image_positions(lt, torch.as_tensor(srcx), torch.as_tensor(srcy), window=window, num_cells=n_cells,
@@ -74,7 +88,7 @@ def check_against_f64(sim, phys, mp, lens_params, z_sources, srcx, srcy, window,
             T = mp.target_scales(np.broadcast_to(np.asarray(z_sources, dtype=np.float64), (S,))[s])
             deriv = deriv64(phys, mp, lens_params, b, T)
             sx, sy = float(srcx[b, s]), float(srcy[b, s])
-            ref = IC._solve64(deriv, sx, sy, window, 2 * n_cells)
+            ref = hessian_mu(maps, phys, mp, lens_params, b, T, IC._solve64(deriv, sx, sy, window, 2 * n_cells))
             k = int(n[b, s])
             got = np.stack([x[b, s, :k], y[b, s, :k], mu[b, s, :k]], axis=1).astype(np.float64)
             assert np.all(np.isfinite(got)) and np.all(np.isnan(x[b, s, k:]))
@@ -98,7 +112,17 @@ GENERAL_CELLS = 32
 GENERAL = {
     "epl_shear|sie": ((0.8, 2.0), [[0.05, 0.12], [0.12, 0.1], [0.1, -0.06]], [[0.03, -0.07], [-0.08, 0.02], [-0.04, 0.09]]),
     "nfw|dpie|sis": ((1.1, 2.5), [[0.04, 0.1], [-0.06, 0.05], [0.08, -0.05]], [[-0.05, 0.06], [0.03, -0.08], [0.07, 0.04]]),
+    # the other three lens sets of multilens_cases.MAP_CASES; first redshift between the last two planes, second behind all
+    "shared": ((0.7, 1.8), [[0.14, 0.07], [0.01, -0.07], [-0.1, 0.14]], [[0.0, -0.12], [0.04, 0.08], [0.03, 0.13]]),
+    "dpis|sie": ((0.6, 2.0), [[-0.05, 0.13], [-0.01, 0.06], [-0.12, -0.12]], [[-0.09, 0.12], [0.05, 0.1], [0.04, -0.03]]),
+    "nfw|dpie|sis>": ((1.1, 2.5), [[0.12, 0.03], [-0.01, 0.08], [-0.14, 0.06]], [[-0.04, -0.12], [0.05, 0.13], [-0.09, 0.04]]),
 }
+
+
+def reference_maps(name):
+    """``maps`` of ``check_against_f64`` / ``hessian_mu`` for a lens set: ``maps_hessian`` where ``map_case`` names it, else None."""
+    m = MC.map_case(name)["maps"]
+    return m if m is MC.maps_hessian else None
 
 
 def general_sources(name):
@@ -109,16 +133,20 @@ def general_sources(name):
 SINGULAR = ("EPL", "SIE", "SIS")  # deflections that are not differentiable at the centre
 
 
-def singular_centre_cells(name, b, target, x, y):
-    """Distance, in cells of the general grid, between the ray from ``(x, y)`` and the nearest centre of an EPL / SIE / SIS of sample
+def singular_centre_cells(name, b, target, x, y, window=None, n_cells=None):
+    """Distance, in cells of the grid in use (``window``, ``n_cells``; default: the general grid), between the ray from ``(x, y)`` and the nearest centre of an EPL / SIE / SIS of sample
     b on a plane in front of the target (``target[plane] != 0``), each measured on the lens's own plane.  The solver promises an
     image only where the map is not folded more finely than a cell (include/gigalens_hip.h): the cell that holds such a centre is folded onto itself however fine the grid, so the triangles
     around it are no affine neighbourhood of an image -- the float64 restatement of the scan (``images_cases.scan64``) misses an
     image half a cell from an EPL centre on this grid just as the kernel does.  The general cases therefore keep every compared
     image at least one cell away from those centres; that is a condition on the chosen sources, asserted on the float64 reference."""
     c = MC.map_case(name)
-    phys, mp = c["phys"], c["mp"]
-    lp = [{k: v[b:b + 1] for k, v in d.items()} for d in MC._tensors({"lens_mass": c["lens_params"]}, MC.F64)["lens_mass"]]
+    return singular_centre_cells_of(c["phys"], c["mp"], c["lens_params"], b, target, x, y, window, n_cells)
+
+
+def singular_centre_cells_of(phys, mp, lens_params, b, target, x, y, window=None, n_cells=None):
+    """``singular_centre_cells`` for any lens set (``lens_params``: list of dicts of [B] float32 arrays)."""
+    lp = [{k: v[b:b + 1] for k, v in d.items()} for d in MC._tensors({"lens_mass": lens_params}, MC.F64)["lens_mass"]]
     xt, yt = (torch.as_tensor(np.asarray([[v]], dtype=np.float64)) for v in (x, y))
     sums = MC.plane_sums(phys, mp, lp, xt, yt)
     Cij = np.asarray(mp.lens_scales, dtype=np.float32).astype(np.float64)
@@ -133,7 +161,9 @@ def singular_centre_cells(name, b, target, x, y):
         for i in range(j):
             xj, yj = xj - Cij[i, j] * sums[i][0], yj - Cij[i, j] * sums[i][1]
         best = min(best, float(torch.hypot(xj - lp[l]["center_x"], yj - lp[l]["center_y"]).min()))
-    return best / ((GENERAL_WINDOW[1] - GENERAL_WINDOW[0]) / GENERAL_CELLS)
+    window, n_cells = window or GENERAL_WINDOW, n_cells or GENERAL_CELLS
+    # (the larger side of a rectangular cell: "one cell away" in either direction)
+    return best / (max(window[1] - window[0], window[3] - window[2]) / n_cells)
 
 
 @functools.lru_cache(maxsize=None)
@@ -141,8 +171,10 @@ def general_reference(name):
     """``{(b, s): [K, 3]}`` of the float64 solver at ``2 GENERAL_CELLS`` -- computed once and shared."""
     c = MC.map_case(name)
     z, sx, sy = general_sources(name)
-    return {(b, s): solve64(c["phys"], c["mp"], c["lens_params"], b, c["mp"].target_scales(z[s]), sx[b, s], sy[b, s], GENERAL_WINDOW,
-                            2 * GENERAL_CELLS) for b in range(3) for s in range(2)}
+    T = [c["mp"].target_scales(v) for v in z]
+    return {(b, s): hessian_mu(reference_maps(name), c["phys"], c["mp"], c["lens_params"], b, T[s],
+                               solve64(c["phys"], c["mp"], c["lens_params"], b, T[s], sx[b, s], sy[b, s], GENERAL_WINDOW,
+                                       2 * GENERAL_CELLS)) for b in range(3) for s in range(2)}
 
 
 # ---- closed forms --------------------------------------------------------------------------------------------------------------------

@@ -35,12 +35,13 @@ KERNEL_GATE = 1e-10
 F32_OUT = 1e-6  # float32 rounding of a returned delay (6e-8) with room for the subtraction of the earliest image
 N_LATTICE = 30
 # largest |host_T - reference_T| / terms over the lattice of each lens set, measured (x86-64, g++ -O2, torch CPU float64): 8.2e-16
-# (epl_shear|sie), 1.7e-11 (both nfw|dpie|sis: the NFW templates against the oracle's NFW), 1.5e-16 (shared), 4.2e-16 (dpis|sie).  The
+# (epl_shear|sie), 1.7e-11 (both nfw|dpie|sis: the NFW templates against the oracle's NFW), 1.5e-16 (shared), 4.2e-16 (dpis|sie),
+# 4.8e-16 (four_planes: K = 4, four sources behind 1, 2, 3 and 4 planes).  The
 # ceiling is twice that, and no less than 32 eps: where the two agree to rounding the measured figure is a single draw of a few
 # ulp of the up to eight summands of T, each the end of tens of double operations whose last bits belong to the math library
 ROUNDING_FLOOR = 32 * 2.0 ** -53
 HOST_CEILING = {k: max(2 * v, ROUNDING_FLOOR) for k, v in {"epl_shear|sie": 8.2e-16, "nfw|dpie|sis": 1.7e-11, "nfw|dpie|sis>": 1.7e-11,
-                                                           "shared": 1.5e-16, "dpis|sie": 4.2e-16}.items()}
+                                                           "shared": 1.5e-16, "dpis|sie": 4.2e-16, "four_planes": 4.8e-16}.items()}
 
 _SO = None
 
@@ -185,17 +186,36 @@ def lattice_redshifts(mp):
     return 0.5 * (mp.z_planes[-2] + mp.z_planes[-1]), MC.Z_REF + 0.5
 
 
+# K = 4 = MP_MAXK (mp_images_cases.four_plane_case, one sample): S = 4 sources behind 1, 2, 3 and 4 planes in one call
+FOUR_PLANES = "four_planes"
+FOUR_PLANES_SRC_X = np.asarray([[0.05, -0.04, 0.02, 0.07]], dtype=np.float32)  # [B = 1, S = 4]
+FOUR_PLANES_SRC_Y = np.asarray([[-0.03, 0.07, 0.06, -0.02]], dtype=np.float32)
+
+
+def four_plane_redshifts(mp):
+    """One source behind each plane: between every two planes, and behind all (and behind the reference plane)."""
+    zp = mp.z_planes
+    return tuple(0.5 * (a + b) for a, b in zip(zp[:-1], zp[1:])) + (MC.Z_REF + 0.5,)
+
+
 @functools.lru_cache(maxsize=None)
 def lattice_data(name, B=3):
-    """``dict(case, x, y [B, 2, N_LATTICE], sx, sy [B, 2], geom, pot, host=(T, terms), ref=(T, terms))`` -- computed once and shared."""
-    c = MC.map_case(name)
+    """``dict(case, z [S], x, y [B, S, N_LATTICE], sx, sy [B, S], geom, pot, host=(T, terms), ref=(T, terms))`` -- computed once and
+    shared.  S = 2 for the lens sets of ``multilens_cases.MAP_CASES``; ``FOUR_PLANES``: B = 1, S = 4."""
+    if name == FOUR_PLANES:
+        phys, phys_mp, mp, lp = MI.four_plane_case()
+        c, B = dict(phys=phys, phys_mp=phys_mp, mp=mp, lens_params=lp), 1
+        z, sx, sy = four_plane_redshifts(mp), FOUR_PLANES_SRC_X, FOUR_PLANES_SRC_Y
+    else:
+        c = MC.map_case(name)
+        z, sx, sy = lattice_redshifts(c["mp"]), LATTICE_SRC_X[:B], LATTICE_SRC_Y[:B]
+    S = len(z)
     px, py = MC.points(N_LATTICE)
-    x = np.ascontiguousarray(np.broadcast_to(px, (B, 2, N_LATTICE)))
-    y = np.ascontiguousarray(np.broadcast_to(py, (B, 2, N_LATTICE)))
-    sx, sy = LATTICE_SRC_X[:B], LATTICE_SRC_Y[:B]
-    geom, pot = weights(c["mp"], lattice_redshifts(c["mp"]))
+    x = np.ascontiguousarray(np.broadcast_to(px, (B, S, N_LATTICE)))
+    y = np.ascontiguousarray(np.broadcast_to(py, (B, S, N_LATTICE)))
+    geom, pot = weights(c["mp"], z)
     lp = MC.sample_rows(c["lens_params"], B)
-    return dict(case=c, x=x, y=y, sx=sx, sy=sy, geom=geom, pot=pot, lens_params=lp,
+    return dict(case=c, z=z, x=x, y=y, sx=sx, sy=sy, geom=geom, pot=pot, lens_params=lp,
                 host=host_T(c["phys"], c["mp"], lp, x, y, sx, sy, geom, pot),
                 ref=reference_T(c["phys"], c["mp"], lp, x, y, sx, sy, geom, pot))
 

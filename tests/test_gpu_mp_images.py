@@ -91,7 +91,8 @@ def test_general_lenses_against_float64(gl, name):
     sim = _sim(gl, name, c["phys_mp"], 3)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)
-        compared, counts = C.check_against_f64(sim, c["phys"], c["mp"], c["lens_params"], z, sx, sy, C.GENERAL_WINDOW, C.GENERAL_CELLS)
+        compared, counts = C.check_against_f64(sim, c["phys"], c["mp"], c["lens_params"], z, sx, sy, C.GENERAL_WINDOW, C.GENERAL_CELLS,
+                                               maps=C.reference_maps(name))
     print(name, "pairs compared", compared, "images per pair", counts)
     assert 4 * (6 - compared) <= 6 and max(counts) >= 3
 

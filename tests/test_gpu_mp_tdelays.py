@@ -43,11 +43,13 @@ def _dev(sim, a):
 
 
 # ---- 1. the kernel on a lattice, against the host build of its thread body ---------------------------------------------------------
-@pytest.mark.parametrize("name", MC.MAP_CASES)
+@pytest.mark.parametrize("name", MC.MAP_CASES + (TD.FOUR_PLANES,))  # (the last: K = 4 = MP_MAXK, B = 1, sources behind 1 .. 4 planes)
 def test_multiplane_fermat_on_a_lattice(gl, name):
     d = TD.lattice_data(name)
     c = d["case"]
-    sim = _sim(gl, name, c["phys_mp"], 3)
+    B, S = d["x"].shape[:2]
+    assert (B, S) == ((1, 4) if name == TD.FOUR_PLANES else (3, 2))
+    sim = _sim(gl, name, c["phys_mp"], B)
     packed = _packed(sim, d["lens_params"])
     T = sim._model.multiplane_fermat(packed, _dev(sim, d["x"]), _dev(sim, d["y"]), _dev(sim, d["sx"]), _dev(sim, d["sy"]), d["geom"],
                                      d["pot"])
@@ -58,11 +60,11 @@ def test_multiplane_fermat_on_a_lattice(gl, name):
           f"{TD.relative_to_terms(T.cpu().numpy(), d['ref'][0], terms):.2e}")
     assert err <= TD.KERNEL_GATE
     # fermat_potential(source_redshift=...): every point the one image of a source of its own -- the same threads, the same bits
-    z = TD.lattice_redshifts(c["mp"])
-    for s in (0, 1):
+    z = d["z"]
+    for s in range(S):
         x, y = _dev(sim, d["x"][:, s].T), _dev(sim, d["y"][:, s].T)  # [n, B]: trailing axis = batch
         phi = sim.fermat_potential(x, y, _dev(sim, d["sx"][:, s]), _dev(sim, d["sy"][:, s]), _lens_t(d["lens_params"]), source_redshift=z[s])
-        assert phi.dtype == torch.float64 and tuple(phi.shape) == (TD.N_LATTICE, 3)
+        assert phi.dtype == torch.float64 and tuple(phi.shape) == (TD.N_LATTICE, B)
         assert torch.equal(_bits(phi), _bits(T[:, s].t()))
 
 

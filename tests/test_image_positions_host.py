@@ -29,3 +29,13 @@ def test_stage_counts_refuses_bad_arguments(native):
     null = ctypes.c_void_p(0)
     assert lib.gl_image_positions_stage_counts(None, 4, 2, 64, null, 0, null, null, null) == -1  # GL_EINVAL
     assert b"null" in lib.gl_last_error()
+    # ... and its twin for a workspace of the solver on lens planes: the model, the workspace and either output
+    buf = ctypes.create_string_buffer(4096)  # stands for every non-null pointer; the checks return before reading any
+    p = ctypes.addressof(buf)
+    full = [p, 4, 2, 64, p, 4096, p, p, None]
+    for entry in (lib.gl_image_positions_stage_counts, lib.gl_multiplane_image_positions_stage_counts):
+        for null_at in (0, 4, 6, 7):
+            args = list(full)
+            args[null_at] = None
+            assert entry(*args) == -1, null_at
+            assert b"null argument" in lib.gl_last_error()

@@ -134,6 +134,28 @@ def test_host_build_against_the_composed_reference(name):
     assert np.ptp(Tr, axis=2).min() > 1e6 * TD.KERNEL_GATE * terms.max()
 
 
+def test_host_build_on_four_planes_against_the_composed_reference():
+    """K = 4 = MP_MAXK: four sources behind 1, 2, 3 and 4 planes in one call (the last plane of a source is found by the first zero of
+    its weights, or by the end of the row)."""
+    d = TD.lattice_data(TD.FOUR_PLANES)
+    (T, terms), (Tr, terms_r) = d["host"], d["ref"]
+    assert d["case"]["mp"].K == TD.MAXK == 4 and T.shape == (1, 4, TD.N_LATTICE)
+    assert [int(np.count_nonzero(g)) for g in d["geom"]] == [1, 2, 3, 4] and np.all(d["pot"] > 0)
+    assert np.isfinite(T).all() and np.isfinite(Tr).all() and (terms > 0).all()
+    err = TD.relative_to_terms(T, Tr, terms)
+    print(f"four planes: host build against the composed reference {err:.2e} of the terms (ceiling {TD.HOST_CEILING[TD.FOUR_PLANES]:.2e}); "
+          f"terms agree to {np.abs(terms / terms_r - 1).max():.1e}")
+    assert err <= TD.HOST_CEILING[TD.FOUR_PLANES] < 0.5 * TD.KERNEL_GATE
+    assert np.ptp(Tr, axis=2).min() > 1e6 * TD.KERNEL_GATE * terms.max()
+    # every source's T is that of a call of its own
+    mp = d["case"]["mp"]
+    for s, z in enumerate(d["z"]):
+        g, v = mp.delay_weights(z)
+        alone = TD.host_T(d["case"]["phys"], mp, d["lens_params"], d["x"][:, s:s + 1], d["y"][:, s:s + 1], d["sx"][:, s:s + 1],
+                          d["sy"][:, s:s + 1], g[None], v)[0]
+        assert np.array_equal(alone[:, 0], T[:, s])
+
+
 def test_sources_at_different_redshifts_share_one_call():
     """The joint weights of a call with two sources give each source the T of a call of its own with ``delay_weights(z_s)``: a plane
     behind the nearer source keeps its potential weight for the farther one, and does not enter the nearer one's T."""
