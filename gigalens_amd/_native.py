@@ -154,6 +154,10 @@ SYMBOLS = {
     "gl_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "gl_critical_curves": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gl_multiplane_critical_curves_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "gl_multiplane_critical_curves": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_float), c_int, c_int, c_float, c_float, c_float,
+                                              c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_pixsrc_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "gl_pixsrc_layout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32)]),
     "gl_pixsrc_reconstruct": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
@@ -1168,6 +1172,31 @@ class Model:
                                                              float(scale), _ptr(seg), _ptr(cau), _ptr(kind), _ptr(n_seg),
                                                              _ptr(n_dropped), _ptr(n_flagged), _ptr(opened), _ptr(area), _ptr(ws),
                                                              ws.numel(), _stream()))
+        return seg, cau, kind, n_seg, n_dropped, n_flagged, opened, area
+
+    def multiplane_critical_curves(self, params, targets, window, n_cells, max_segments):
+        """gl_multiplane_critical_curves: ``critical_curves`` on lens planes, once per source plane with the couplings ``targets[s]``
+        (``[S, K]`` on the host: ``MultiPlane.target_scales(z_s)``).  Returns ``seg``, ``cau`` [B, S, max_segments, 2, 2]
+        (NaN-padded), ``kind`` [B, S, max_segments] (int32; -1 padding), ``n_seg``, ``n_dropped``, ``n_flagged``, ``open`` [B, S]
+        (int32) and the signed ``area`` [B, S, 4]."""
+        params = self._params(params)
+        B, M = params.shape[0], int(max_segments)
+        t = np.ascontiguousarray(targets, dtype=np.float32)
+        if t.ndim != 2 or t.shape[0] < 1:
+            raise NativeLibraryError(f"targets must be [S >= 1, n_planes], got {t.shape}")
+        S = int(t.shape[0])
+        nbytes = lib().gl_multiplane_critical_curves_workspace_bytes(self._h, B, S, int(n_cells), M)
+        ws = self._scratch("multiplane_critical_curves", nbytes)
+        seg = torch.empty((B, S, max(M, 1), 2, 2), dtype=torch.float32, device=self.device)
+        cau = torch.empty_like(seg)
+        kind = torch.empty((B, S, max(M, 1)), dtype=torch.int32, device=self.device)
+        n_seg, n_dropped, n_flagged, opened = (torch.empty((B, S), dtype=torch.int32, device=self.device) for _ in range(4))
+        area = torch.empty((B, S, 4), dtype=torch.float32, device=self.device)
+        x_lo, x_hi, y_lo, y_hi = (float(v) for v in window)
+        _check_potential(lib().gl_multiplane_critical_curves(self._h, _ptr(params), B, t.ctypes.data_as(POINTER(c_float)), S,
+                                                             int(t.shape[1]), x_lo, x_hi, y_lo, y_hi, int(n_cells), M, _ptr(seg),
+                                                             _ptr(cau), _ptr(kind), _ptr(n_seg), _ptr(n_dropped), _ptr(n_flagged),
+                                                             _ptr(opened), _ptr(area), _ptr(ws), ws.numel(), _stream()))
         return seg, cau, kind, n_seg, n_dropped, n_flagged, opened, area
 
     def pixsrc_reconstruct(self, beta_x, beta_y, obs, sigma, lens_light, pix, n_src, pose, regularization, strength):

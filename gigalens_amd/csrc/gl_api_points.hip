@@ -19,6 +19,7 @@
 #include "gl_multiplane_pos.hip.h"
 #include "gl_multiplane_images.hip.h"
 #include "gl_multiplane_fermat.hip.h"
+#include "gl_multiplane_critical.hip.h"
 #include "gl_lens_vjp.hip.h"
 #include "gl_hessian_vjp.hip.h"
 #include "gl_imgplane.hip.h"
@@ -152,6 +153,28 @@ CritLayout crit_layout(int B, int n_cells, int max_segments) {
   return l;
 }
 constexpr int CRIT_MAX_SEGMENTS = 1 << 20;
+// ... on K lens planes (gl_multiplane_critical_curves): the single-plane layout with the rows (sample, source) in the place of the
+// samples, and behind it the coupling rows [n_src][K] of the sources
+struct MpCritLayout { CritLayout crit; size_t tgt, bytes; };
+MpCritLayout mp_crit_layout(int B, int n_src, int n_cells, int max_segments, int K) {
+  MpCritLayout l{};
+  l.crit = crit_layout(B * n_src, n_cells, max_segments);
+  l.tgt = l.crit.bytes;
+  l.bytes = l.tgt + align_up((size_t)n_src * (size_t)K * sizeof(float), 256);
+  return l;
+}
+
+// the coupling rows [n_src][K] of the sources of a call on lens planes: the rules of gl_model_set_position_targets
+int check_target_rows(const float* targets, int n_src, int K) {
+  for (int s = 0; s < n_src; ++s) {
+    const float* T = targets + (size_t)s * K;
+    for (int i = 0; i < K; ++i)
+      if (!(std::isfinite(T[i]) && T[i] >= 0.f) || (i > 0 && T[i] != 0.f && T[i - 1] == 0.f))
+        return fail(GL_EINVAL, "targets[%d][%d] = %g: finite and >= 0, 0 from the first plane at or behind the source on", s, i, T[i]);
+    if (T[0] == 0.f) return fail(GL_EINVAL, "source %d: every coupling is zero (the source lies behind no lens plane)", s);
+  }
+  return GL_OK;
+}
 
 // what the kernels of a model with lens planes read of them (gl_multiplane.hip.h MpArgs)
 MpArgs mp_args(const gl_model* m) {
@@ -841,13 +864,7 @@ int gl_multiplane_image_positions(const gl_model* m, const float* params, int B,
   if (int rc = check_window(true, x_lo, x_hi, y_lo, y_hi)) return rc;
   if (!(tol > 0.f) || max_iter < 1) return fail(GL_EINVAL, "tol must be > 0 and max_iter >= 1 (got %g, %d)", tol, max_iter);
   const int K = n_planes;
-  for (int s = 0; s < n_src; ++s) {  // the rules of gl_model_set_position_targets
-    const float* T = targets + (size_t)s * K;
-    for (int i = 0; i < K; ++i)
-      if (!(std::isfinite(T[i]) && T[i] >= 0.f) || (i > 0 && T[i] != 0.f && T[i - 1] == 0.f))
-        return fail(GL_EINVAL, "targets[%d][%d] = %g: finite and >= 0, 0 from the first plane at or behind the source on", s, i, T[i]);
-    if (T[0] == 0.f) return fail(GL_EINVAL, "source %d: every coupling is zero (the source lies behind no lens plane)", s);
-  }
+  if (int rc = check_target_rows(targets, n_src, K)) return rc;
   if (int rc = check_ready(m, false, false)) return rc;
   const MpImgLayout lay = mp_img_layout(B, n_src, n_cells, K);
   if (!workspace) return fail(GL_EINVAL, "workspace is null");
@@ -1025,6 +1042,77 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
   if (cat) hipLaunchKernelGGL(gl_crit_refine_kernel<true>, dim3((unsigned)refine_blocks), dim3(64), 0, stream, a, g);
   else hipLaunchKernelGGL(gl_crit_refine_kernel<false>, dim3((unsigned)refine_blocks), dim3(64), 0, stream, a, g);
   hipLaunchKernelGGL(gl_crit_cells_kernel, dim3((unsigned)B), dim3(CRIT_WG), 0, stream, g);
+  GL_HIP(hipGetLastError());
+  return GL_OK;
+}
+
+// ---- ... on lens planes (gl_multiplane_critical.hip.h) ------------------------------------------------------------
+size_t gl_multiplane_critical_curves_workspace_bytes(const gl_model* m, int B, int n_src, int n_cells, int max_segments) {
+  if (!m || m->mp_K < 2 || B <= 0 || n_src <= 0 || n_cells <= 0 || n_cells > IMG_MAX_CELLS || max_segments < 1 ||
+      max_segments > CRIT_MAX_SEGMENTS || (long long)B * n_src > 0x7fffffffLL)
+    return 0;
+  return mp_crit_layout(B, n_src, n_cells, max_segments, m->mp_K).bytes;
+}
+
+int gl_multiplane_critical_curves(const gl_model* m, const float* params, int B, const float* targets, int n_src, int n_planes,
+                                  float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_segments, float* seg, float* cau,
+                                  int* kind, int* n_seg, int* n_dropped, int* n_flagged, int* open, float* area, void* workspace,
+                                  size_t workspace_bytes, void* hip_stream) {
+  if (!m || !params || !targets || !seg || !cau || !kind || !n_seg || !n_dropped || !n_flagged || !open || !area)
+    return fail(GL_EINVAL, "null argument");
+  if (int rc = check_planes_set(m)) return rc;
+  if (B <= 0 || n_src <= 0) return fail(GL_EINVAL, "B (%d) and n_src (%d) must be positive", B, n_src);
+  if (n_planes != m->mp_K) return fail(GL_EINVAL, "%d target couplings per source for %d lens planes", n_planes, m->mp_K);
+  if (n_cells <= 0 || n_cells > IMG_MAX_CELLS) return fail(GL_EINVAL, "n_cells %d outside [1, %d]", n_cells, IMG_MAX_CELLS);
+  if (max_segments < 1 || max_segments > CRIT_MAX_SEGMENTS)
+    return fail(GL_EINVAL, "max_segments %d outside [1, %d]", max_segments, CRIT_MAX_SEGMENTS);
+  if (int rc = check_window(false, x_lo, x_hi, y_lo, y_hi)) return rc;
+  const int K = n_planes;
+  if (int rc = check_target_rows(targets, n_src, K)) return rc;
+  if (int rc = check_ready(m, false, false)) return rc;
+  const long long V = (long long)(n_cells + 1) * (n_cells + 1), rows = (long long)B * n_src;
+  const long long map_blocks = (V * B + MP_MAPS_WG - 1) / MP_MAPS_WG;
+  const int max_edges = 2 * max_segments;
+  const long long refine_blocks = rows * ((max_edges + 63) / 64);
+  if (map_blocks > 0x7fffffffLL || rows > 0x7fffffffLL || refine_blocks > 0x7fffffffLL)
+    return fail(GL_EINVAL, "too many samples x vertices (or x sources x max_segments) for one call");
+  const MpCritLayout lay = mp_crit_layout(B, n_src, n_cells, max_segments, K);
+  if (!workspace) return fail(GL_EINVAL, "workspace is null");
+  if (workspace_bytes < lay.bytes) return fail(GL_ENOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, lay.bytes);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  char* base = (char*)workspace;
+  // the coupling rows, host -> the call's own workspace on the caller's stream (as in gl_multiplane_image_positions)
+  float* d_tgt = (float*)(base + lay.tgt);
+  GL_HIP(hipMemcpyAsync(d_tgt, targets, sizeof(float) * (size_t)n_src * (size_t)K, hipMemcpyHostToDevice, stream));
+  PosArgs a = point_args(m, params, B);
+  const MpArgs mp = mp_args(m);
+  CritArgs g{};  // every array [B n_src][...]: row b n_src + s is the "sample" of the scan and cells kernels
+  g.n = n_cells;
+  g.scale = 1.f;  // (not read: the couplings carry the scales)
+  g.max_segments = max_segments;
+  g.max_edges = max_edges;
+  g.x_lo = x_lo; g.x_hi = x_hi; g.y_lo = y_lo; g.y_hi = y_hi;
+  g.hx = (x_hi - x_lo) / (float)n_cells;
+  g.hy = (y_hi - y_lo) / (float)n_cells;
+  g.bracket = CRIT_BRACKET_ULP * std::numeric_limits<float>::epsilon() *
+              std::max(std::max(std::fabs(x_lo), std::fabs(x_hi)), std::max(std::fabs(y_lo), std::fabs(y_hi)));
+  g.dmap = (float*)(base + lay.crit.dmap);
+  g.edge_id = (int*)(base + lay.crit.edge_id);
+  g.edge_pt = (float4*)(base + lay.crit.edge_pt);
+  g.edge_omk = (float*)(base + lay.crit.edge_omk);
+  g.n_edges = (int*)(base + lay.crit.n_edges);
+  g.n_edge_over = (int*)(base + lay.crit.n_edge_over);
+  g.seg = seg; g.cau = cau; g.kind = kind;
+  g.n_seg = n_seg; g.n_dropped = n_dropped; g.n_flagged = n_flagged; g.open = open;
+  g.area = area;
+  MpCritArgs q{};
+  q.tgt = d_tgt;
+  q.K = K;
+  q.S = n_src;
+  hipLaunchKernelGGL(gl_mpcrit_map_kernel, dim3((unsigned)map_blocks), dim3(MP_MAPS_WG), 0, stream, a, mp, g, q);
+  hipLaunchKernelGGL(gl_crit_scan_kernel, dim3((unsigned)rows), dim3(CRIT_WG), 0, stream, g);
+  hipLaunchKernelGGL(gl_mpcrit_refine_kernel, dim3((unsigned)refine_blocks), dim3(MP_MAPS_WG), 0, stream, a, mp, g, q);
+  hipLaunchKernelGGL(gl_crit_cells_kernel, dim3((unsigned)rows), dim3(CRIT_WG), 0, stream, g);
   GL_HIP(hipGetLastError());
   return GL_OK;
 }

@@ -224,7 +224,8 @@ class LensSimulator(LensSimulatorInterface):
             raise _native.UnsupportedLensError(f"{what} does not serve a model with {self._mp.K} lens planes: multi-plane ray tracing "
                                                "serves beta, magnification, convergence, shear, rotation, simulate*, simulate_vjp, "
                                                "the pixel likelihood with its gradient, image_positions(source_redshifts=...), "
-                                               "time_delays(source_redshifts=...) and fermat_potential(source_redshift=...)")
+                                               "time_delays(source_redshifts=...), fermat_potential(source_redshift=...), "
+                                               "critical_curves(source_redshifts=...) and einstein_radius(source_redshifts=...)")
 
     def _target_scales(self, deflection_scale):
         """The ``deflection_scale`` keyword of the lens maps on a multi-plane model: a source index, or the ``[K]`` couplings of the
@@ -536,7 +537,8 @@ class LensSimulator(LensSimulatorInterface):
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
         return out[..., 0], out[..., 1], out[..., 2], n
 
-    def critical_curves(self, lens_params, *, window=None, num_cells=None, max_segments=None, strict=False, deflection_scale=1.0):
+    def critical_curves(self, lens_params, *, window=None, num_cells=None, max_segments=None, strict=False, deflection_scale=1.0,
+                        source_redshifts=None):
         """Critical curves (``det(I - H) = 0``) and caustics of every sample (beyond the reference), as line segments.
 
         ``lens_params`` as ``image_positions`` takes them.  ``window`` = ``(x_lo, x_hi, y_lo, y_hi)`` (default: the bounding box of
@@ -551,10 +553,22 @@ class LensSimulator(LensSimulatorInterface):
         Segments beyond ``max_segments`` and cells skipped because a vertex is singular while its neighbours differ in sign warn,
         or raise ``RuntimeError`` with ``strict=True``.  Built-in kinds and dPIE-family catalogues; series expansions, user-written
         bodies and run-time compiled ScalingRelation member loops raise ``_native.UnsupportedLensError``.  ``deflection_scale``: the
-        curves of the source plane with that scale, ``det(I - c H) = 0`` and ``beta = theta - c sum alpha``.  Forward only."""
-        self._single_plane("critical_curves")
+        curves of the source plane with that scale, ``det(I - c H) = 0`` and ``beta = theta - c sum alpha``.  Forward only.
+
+        ``source_redshifts`` (instead of ``deflection_scale``; a model built with a ``cosmology.MultiPlane``): a scalar returns the
+        dict above for the source plane at that redshift; a sequence of S redshifts returns a list of S such dicts, views of one
+        ``[B, S, ...]`` result of one native call.  On two to four lens planes the curves are ``det A_t = 0`` of the full,
+        non-symmetric Jacobian ``A_t = d beta_t / d theta`` with ``beta_t = theta - sum_i T_si a_i(theta)``,
+        ``T_s = MultiPlane.target_scales(z_s)`` (``gl_multiplane_critical_curves``): the caustic is ``beta_t``, a segment is
+        tangential when ``tr A_t > 0``; ``closed``, the NaN areas, the warning and ``strict`` hold per (sample, source).  Such a model
+        without ``source_redshifts`` raises ``UnsupportedLensError``.  On a one-plane ``MultiPlane`` every redshift becomes a
+        ``deflection_scale`` (one single-plane call each).  ``ValueError``: as ``image_positions``."""
+        if source_redshifts is None:
+            self._single_plane("critical_curves")
         packed = self._lens_rows(lens_params)
         self._forward_only("critical_curves", packed)
+        if source_redshifts is not None:
+            return self._critical_curves_at(packed, source_redshifts, deflection_scale, window, num_cells, max_segments, strict)
         cs = self._scale(deflection_scale)
         if window is None:
             window = (float(self.img_X.min()), float(self.img_X.max()), float(self.img_Y.min()), float(self.img_Y.max()))
@@ -566,31 +580,65 @@ class LensSimulator(LensSimulatorInterface):
         seg, cau, kind, n, dropped, flagged, opened, area = self._model.critical_curves(packed, window, int(num_cells),
                                                                                          int(max_segments),
                                                                                          scale=None if cs == 1.0 else cs)
+        return self._curves_result(seg, cau, kind, n, dropped, flagged, opened, area, max_segments, strict, "sample(s)", 3)
+
+    @staticmethod
+    def _curves_result(seg, cau, kind, n, dropped, flagged, opened, area, max_segments, strict, rows, stacklevel):
+        """The dict of ``critical_curves`` from the native outputs, whose leading axes are ``[B]`` or ``[B, S]`` (``rows``: what one
+        entry of them is called in the warning)."""
         n_drop, n_flag = int(dropped.sum()), int(flagged.sum())
         if n_drop or n_flag:
-            msg = (f"critical_curves: {n_drop} segment(s) not returned over {int((dropped > 0).sum())} sample(s) "
-                   f"(max_segments={max_segments} exceeded), {n_flag} cell(s) skipped over {int((flagged > 0).sum())} sample(s) "
+            msg = (f"critical_curves: {n_drop} segment(s) not returned over {int((dropped > 0).sum())} {rows} "
+                   f"(max_segments={max_segments} exceeded), {n_flag} cell(s) skipped over {int((flagged > 0).sum())} {rows} "
                    f"(a singular vertex between vertices of different sign)")
             if strict:
                 raise RuntimeError(msg)
-            warnings.warn(msg, RuntimeWarning, stacklevel=2)
+            warnings.warn(msg, RuntimeWarning, stacklevel=stacklevel)
         closed = (opened == 0) & (dropped == 0) & (flagged == 0)
-        area = torch.where(closed[:, None], area.abs(), torch.full_like(area, float("nan")))
+        area = torch.where(closed[..., None], area.abs(), torch.full_like(area, float("nan")))
         return {"critical": seg, "caustic": cau, "kind": kind, "n": n, "closed": closed,
-                "area_tangential": area[:, 0], "area_radial": area[:, 1],
-                "caustic_area_tangential": area[:, 2], "caustic_area_radial": area[:, 3]}
+                "area_tangential": area[..., 0], "area_radial": area[..., 1],
+                "caustic_area_tangential": area[..., 2], "caustic_area_radial": area[..., 3]}
+
+    def _critical_curves_at(self, packed, source_redshifts, deflection_scale, window, num_cells, max_segments, strict):
+        """``critical_curves(source_redshifts=...)``: one dict for a scalar redshift, a list of dicts for a sequence."""
+        scalar = np.ndim(source_redshifts) == 0
+        S = 1 if scalar else int(np.size(source_redshifts))
+        if S < 1:
+            raise ValueError("source_redshifts: a scalar or a non-empty sequence of redshifts")
+        mp, targets = self._source_targets(source_redshifts, S, deflection_scale)
+        if mp.K == 1:  # one plane: the existing path on every source's own scale
+            out = [self.critical_curves(packed, window=window, num_cells=num_cells, max_segments=max_segments, strict=strict,
+                                        deflection_scale=float(c)) for c in targets[:, 0]]
+            return out[0] if scalar else out
+        if window is None:
+            window = (float(self.img_X.min()), float(self.img_X.max()), float(self.img_Y.min()), float(self.img_Y.max()))
+        window = tuple(float(v) for v in window)
+        if num_cells is None:
+            num_cells = 2 * int(self.numPix)
+        if max_segments is None:
+            max_segments = 8 * int(num_cells)
+        native = self._model.multiplane_critical_curves(packed, targets, window, int(num_cells), int(max_segments))
+        res = self._curves_result(*native, max_segments, strict, "(sample, source) pair(s)", 4)
+        views = [{k: v[:, s] for k, v in res.items()} for s in range(S)]
+        return views[0] if scalar else views
 
     def einstein_radius(self, lens_params, **kwargs):
         """Effective Einstein radius ``sqrt(A / pi)`` ``[B]`` of every sample (beyond the reference), ``A`` the area the tangential
         critical curve encloses (``critical_curves``, which takes ``kwargs``, ``deflection_scale`` among them).  NaN where the tangential curve is not closed inside
-        the window or absent; such samples are counted in a ``RuntimeWarning``."""
+        the window or absent; such samples are counted in a ``RuntimeWarning``.  ``source_redshifts``: ``[B]`` for a scalar
+        redshift, ``[B, S]`` for a sequence of S (one ``critical_curves`` call)."""
         res = self.critical_curves(lens_params, **kwargs)
-        has_tangential = (res["kind"] == 0).any(dim=1)
-        theta = torch.sqrt(res["area_tangential"] / math.pi)
-        theta = torch.where(has_tangential, theta, torch.full_like(theta, float("nan")))
+
+        def radius(r):
+            has_tangential = (r["kind"] == 0).any(dim=1)
+            theta = torch.sqrt(r["area_tangential"] / math.pi)
+            return torch.where(has_tangential, theta, torch.full_like(theta, float("nan")))
+        theta = torch.stack([radius(r) for r in res], dim=1) if isinstance(res, list) else radius(res)
         n_bad = int(torch.isnan(theta).sum())
         if n_bad:
-            warnings.warn(f"einstein_radius: the tangential critical curve is open or absent in {n_bad} of {theta.numel()} sample(s)",
+            rows = "(sample, source) pair(s)" if isinstance(res, list) else "sample(s)"
+            warnings.warn(f"einstein_radius: the tangential critical curve is open or absent in {n_bad} of {theta.numel()} {rows}",
                           RuntimeWarning, stacklevel=2)
         return theta
 

@@ -692,6 +692,26 @@ int gl_critical_curves_scaled(const gl_model* m, const float* params, int B, flo
                               int n_cells, int max_segments, float scale, float* seg, float* cau, int* kind, int* n_seg,
                               int* n_dropped, int* n_flagged, int* open, float* area, void* workspace, size_t workspace_bytes,
                               void* hip_stream);
+/* Critical curves and caustics on lens planes (after gl_model_set_lens_planes; gl_critical_curves[_scaled] keep refusing such a
+ * model): for every sample and every one of n_src source planes with the couplings targets [n_src][n_planes] (HOST; row s =
+ * MultiPlane.target_scales(z_s), the rules of gl_multiplane_image_positions) the locus
+ *   D = det A_t = A_xx A_yy - A_xy A_yx = 0,   A_t = d beta_t / d theta,   beta_t = theta - sum_i T_si a_i(theta)
+ * of the full, non-symmetric Jacobian (the recursion and the dPIS convergence excess of gl_multiplane_maps), contoured, refined and
+ * summed as gl_critical_curves does.  The caustic is beta_t at the refined points; a segment is tangential when the mean of
+ * tr A_t / 2 at its endpoints is > 0 (on D = 0 the eigenvalues of A_t are 0 and tr A_t).  One dual ray trace per vertex serves
+ * every source of the call.  A vertex is flagged for a source when D is not finite there: a GL_SIS lens centred bit for bit on the
+ * ray's position ON ITS PLANE, a ray that reaches a plane not finite, a sum that is not finite -- on the planes in front of that
+ * source alone (coupling != 0).  Outputs (DEVICE) [B][n_src][...] in the shapes of gl_critical_curves, every rule of its counters
+ * per (sample, source).  The rows are copied on hip_stream into the call's workspace.  Deterministic; no host synchronisation, no
+ * allocation: workspace of gl_multiplane_critical_curves_workspace_bytes (0 for invalid sizes and for a model without planes) = the
+ * workspace of gl_critical_curves for B n_src samples + the coupling rows.  GL_EINVAL: the cases of gl_critical_curves, n_src <= 0,
+ * a model without planes ("gl_model_set_lens_planes has not been called"), n_planes that differs from the model's, a bad coupling
+ * row, more than 2^31 - 1 workgroups in a launch; GL_ENOMEM: a workspace that is too small.  No gradient. */
+size_t gl_multiplane_critical_curves_workspace_bytes(const gl_model* m, int B, int n_src, int n_cells, int max_segments);
+int gl_multiplane_critical_curves(const gl_model* m, const float* params, int B, const float* targets, int n_src, int n_planes,
+                                  float x_lo, float x_hi, float y_lo, float y_hi, int n_cells, int max_segments, float* seg, float* cau,
+                                  int* kind, int* n_seg, int* n_dropped, int* n_flagged, int* open, float* area, void* workspace,
+                                  size_t workspace_bytes, void* hip_stream);
 
 /* Pixelated source reconstruction (beyond the reference): semi-linear inversion (Warren & Dye 2003) with the Bayesian evidence
  * terms of Suyu et al. 2006, for every sample and every regularisation strength.  The source lives on a regular grid of
