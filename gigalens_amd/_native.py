@@ -84,6 +84,10 @@ SYMBOLS = {
     "gl_model_set_position_delays": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_int, POINTER(c_float), c_int]),
     "gl_position_delays_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_size_t, c_void_p]),
+    "gl_model_set_position_plane_delays": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_int, POINTER(c_double),
+                                                   POINTER(c_double), POINTER(c_float), c_int, c_int]),
+    "gl_multiplane_position_delays_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "gl_position_family_terms": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     "gl_image_positions_scaled": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_float), c_float, c_float,
                                           c_float, c_float, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -1029,6 +1033,37 @@ class Model:
         """gl_position_delays_fwd_bwd: ``(loglike, chi2, d loglike / d params or None)`` of the time-delay term; with ``want_model``
         also ``(scale [B, F], offset [B, F], model_delay [B, J])`` = ``lambda_f``, ``T_f`` and ``lambda_f phi_j + T_f`` in days."""
         return self._positions(lib().gl_position_delays_fwd_bwd, _check_potential, params, want_grad,
+                               (self.n_families, self.n_families, self.n_images), want_model)
+
+    def set_position_plane_delays(self, delays, errors, geom, pot, scales):
+        """The measured arrival times of the images of a model with lens planes (gl_model_set_position_plane_delays; after
+        ``set_positions``, ``set_lens_planes`` and ``set_position_targets``, each of which clears them): ``delays``, ``errors`` ``[J]``
+        and ``scales`` ``[F]`` as ``set_position_delays`` -- ``lambda_f`` in days per (arcsec^2 c / H0), NaN to profile it out --,
+        ``geom`` ``[F, K]`` and ``pot`` ``[K]`` float64: the weights of ``MultiPlane.delay_weights``.  ``delays`` None: no delays.  The
+        workspace grows while the model holds plane delays: the cached workspaces are dropped.  A lens without a potential raises
+        ``UnsupportedLensError`` and leaves the model as it was."""
+        fp, dp = (lambda a: a.ctypes.data_as(POINTER(c_float))), (lambda a: a.ctypes.data_as(POINTER(c_double)))
+        with torch.cuda.device(self.device):
+            if delays is None:
+                _check(lib().gl_model_set_position_plane_delays(self._h, None, None, 0, None, None, None, 0, 0))
+            else:
+                t = np.ascontiguousarray(delays, dtype=np.float32).reshape(-1)
+                s = np.ascontiguousarray(errors, dtype=np.float32).reshape(-1)
+                lam = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+                g, v = np.ascontiguousarray(geom, dtype=np.float64), np.ascontiguousarray(pot, dtype=np.float64).reshape(-1)
+                if t.size != s.size:
+                    raise NativeLibraryError("arrival times and their errors must have the same length")
+                if g.ndim != 2 or g.shape != (lam.size, v.size):
+                    raise NativeLibraryError(f"geom must be [n_families = {lam.size}, n_planes = {v.size}], got {g.shape}")
+                _check_potential(lib().gl_model_set_position_plane_delays(self._h, fp(t), fp(s), int(t.size), dp(g), dp(v), fp(lam),
+                                                                          int(lam.size), int(v.size)))
+        self._changed(True)  # the workspace grows with the plane delays
+
+    def multiplane_position_delays(self, params, want_grad, want_model=False):
+        """gl_multiplane_position_delays_fwd_bwd: ``position_delays`` on lens planes -- ``(loglike, chi2, d loglike / d params or
+        None)`` of the time-delay term; with ``want_model`` also ``(scale [B, F], offset [B, F], model_delay [B, J])`` = ``lambda_f``
+        in days per (arcsec^2 c / H0), ``T_f`` and ``lambda_f phi_j + T_f`` in days."""
+        return self._positions(lib().gl_multiplane_position_delays_fwd_bwd, _check_potential, params, want_grad,
                                (self.n_families, self.n_families, self.n_images), want_model)
 
     def position_family_terms(self, B):

@@ -206,6 +206,12 @@ Workspace carve(const gl_model* m, int B, void* base, const LaunchPlan& plan) {
     w.pos_chi2 = take(B);
     w.pos_grad = take((size_t)B * std::max(m->P, 1));
     w.pos_dadj = take((size_t)B * m->pos_J);  // (with or without delays: gl_model_set_position_delays leaves the layout alone)
+    if (m->mpd_n_delay) {  // delays on lens planes (gl_model_set_position_plane_delays): every other model keeps its size
+      auto wide = [&](size_t n) { double* q = (double*)(p + off); off += align_up(n * sizeof(double), 256); return q; };
+      w.mpd_trace = wide((size_t)B * m->pos_J * 5);
+      w.mpd_src = wide((size_t)B * m->pos_F * 2);
+      w.mpd_aj = wide((size_t)B * m->pos_J);
+    }
   }
   if (m->has_post) {
     w.img_ss = (float*)(p + off);
@@ -582,11 +588,14 @@ int logprob_grad(const gl_model* m, const float* z, const float* obs, const floa
   // a model that holds fluxes (gl_model_set_position_fluxes): the flux ratios are part of the point-image term, whose reduced chi2
   // then divides by 2 J + n_flux
   // ... and likewise the time delays of a model that holds arrival times (gl_model_set_position_delays): 2 J + n_flux + n_delay
-  const bool flux = pos && m->pos_n_flux > 0, delays = pos && m->pos_n_delay > 0;
-  if (pos && (rc = run_positions(m, w.params, B, w, want_grad, stream, (flux ? POS_BOTH : POS_POSITIONS) | (delays ? POS_DELAYS : 0))))
+  // ... on lens planes those of gl_model_set_position_plane_delays
+  const bool flux = pos && m->pos_n_flux > 0, delays = pos && m->pos_n_delay > 0, plane_delays = pos && planes && m->mpd_n_delay > 0;
+  if (pos && (rc = run_positions(m, w.params, B, w, want_grad, stream,
+                                 (flux ? POS_BOTH : POS_POSITIONS) | (delays ? POS_DELAYS : 0) | (plane_delays ? POS_PLANE_DELAYS : 0))))
     return rc;
   float n_point = flux ? 2.0f * (float)m->pos_J + (float)m->pos_n_flux : 2.0f * (float)m->pos_J;
   if (delays) n_point += (float)m->pos_n_delay;
+  if (plane_delays) n_point += (float)m->mpd_n_delay;
   return run_finalize(m, w.params, B, fin_rows, w, loglike, chi2, nullptr, stream, z, logprob, grad_z,
                       pix ? 1.0f / (chi2_divisor * n_chi) : 0.f, extra, use_partial, pos,
                       pos ? 1.0f / (n_point * n_chi) : 0.f);
@@ -1461,6 +1470,8 @@ int gl_model_set_positions(gl_model* m, int n_families, const int* family_sizes,
   m->d_pos_delay.reset();
   m->pos_fam_delay.clear();
   m->pos_fam_scale.clear();
+  m->clear_plane_delays();  // ... nor, on lens planes, those of gl_model_set_position_plane_delays
+  m->pos_target_rows.clear();
   return GL_OK;
 }
 

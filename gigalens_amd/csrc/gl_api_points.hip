@@ -19,6 +19,7 @@
 #include "gl_multiplane_pos.hip.h"
 #include "gl_multiplane_images.hip.h"
 #include "gl_multiplane_fermat.hip.h"
+#include "gl_multiplane_tdelays.hip.h"
 #include "gl_multiplane_critical.hip.h"
 #include "gl_lens_vjp.hip.h"
 #include "gl_hessian_vjp.hip.h"
@@ -194,6 +195,38 @@ static void launch_pos_p1_mpl(dim3 grid, hipStream_t stream, const PosArgs& a) {
   hipLaunchKernelGGL(gl_pos_p1_mpl_kernel, grid, dim3(64), 0, stream, a);
 }
 
+// The time-delay term on lens planes (gl_multiplane_tdelays.hip.h) in the plane branch of run_positions: the tables the model
+// holds and the scratch of the workspace, then -- after the flux kernel -- the rays and the family statistics, and -- after P3 -- the
+// direct part of the gradient.  One thread per (sample, image), per (sample, family) and per (sample, image, lens-parameter column).
+static MpDelayArgs mp_delay_args(const gl_model* m, const Workspace& w) {
+  MpDelayArgs q{};
+  const float* tab = m->d_mpd_delay.get();
+  q.delay = tab;
+  q.delay_err = tab + m->pos_J;
+  q.lam_given = tab + 2 * m->pos_J;
+  q.geom = m->d_mpd_weight.get();
+  q.pot = q.geom + (size_t)m->pos_J * MP_MAXK;
+  q.trace = w.mpd_trace;
+  q.src = w.mpd_src;
+  q.aj = w.mpd_aj;
+  return q;
+}
+static unsigned mp_delay_blocks(long long n) { return (unsigned)((n + MP_TDELAY_WG - 1) / MP_TDELAY_WG); }
+static void launch_mp_tdelay_stats(const gl_model* m, const PosArgs& a, const Workspace& w, int accumulate, const DelayOut* delay_out,
+                                   hipStream_t stream) {
+  const DelayOut none{nullptr, nullptr, nullptr};
+  const DelayOut& o = delay_out ? *delay_out : none;
+  const MpDelayArgs q = mp_delay_args(m, w);
+  hipLaunchKernelGGL(gl_mp_pos_tdelay_trace_kernel, dim3(mp_delay_blocks((long long)a.B * a.J)), dim3(MP_TDELAY_WG), 0, stream, a,
+                     mp_args(m), (const float*)m->d_pos_target, q);
+  hipLaunchKernelGGL(gl_mp_pos_tdelay_kernel, dim3(mp_delay_blocks((long long)a.B * a.F)), dim3(MP_TDELAY_WG), 0, stream, a, q, accumulate,
+                     o.scale, o.offset, o.model_delay);
+}
+static void launch_mp_tdelay_grad(const gl_model* m, const PosArgs& a, const Workspace& w, hipStream_t stream) {
+  hipLaunchKernelGGL(gl_mp_pos_tdelay_grad_kernel, dim3(mp_delay_blocks((long long)a.B * a.J * m->lens_params)), dim3(MP_TDELAY_WG), 0,
+                     stream, a, mp_args(m), mp_delay_args(m, w), m->lens_params);
+}
+
 int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream, int what,
                   float* amp, float* model_flux, const DelayOut* delay_out) {
   if (m->n_series) return fail(GL_EUNSUPPORTED, "a series-expansion lens lives on the pixel grid only (series_profile.py:76-81): no image-position likelihood");
@@ -203,6 +236,8 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
   // one plane of built-in lenses whose families with delays lie on the reference plane)
   if ((what & POS_DELAYS) && (m->mp_K >= 2 || m->has_user))
     return fail(GL_EUNSUPPORTED, "the time-delay term serves one lens plane of built-in lenses");
+  if ((what & POS_PLANE_DELAYS) && !(m->mp_K >= 2 && m->mpd_n_delay))
+    return fail(GL_EINVAL, "gl_model_set_position_plane_delays has not been called on this model");
   if (m->has_user)  // the four kernels below, compiled at run time with the user's bodies on the nested duals (once per model text)
     if (int rc = compile_user_points(m)) return rc;
   PosArgs a = point_args(m, params, B);  // + the position tables and the likelihood's workspace
@@ -241,9 +276,14 @@ int run_positions(const gl_model* m, const float* params, int B, const Workspace
     hipLaunchKernelGGL(gl_mp_pos_p1_kernel, blocks((long long)B * a.J), dim3(MP_POS_WG), 0, stream, a, mp_args(m), tg);
     if (what & POS_POSITIONS) hipLaunchKernelGGL(gl_pos_p2_kernel, blocks((long long)B * a.F), dim3(64), 0, stream, a);
     fluxes();
-    if (want_grad && m->lens_params)
+    // the time delays on planes (gl_multiplane_tdelays.hip.h): the rays on double, then statistics and beta adjoints by the thread
+    // that owns the family's elements; the direct d T / d params part is added to what P3 wrote, before P4 sums it
+    if (what & POS_PLANE_DELAYS) launch_mp_tdelay_stats(m, a, w, (what & (POS_POSITIONS | POS_FLUXES)) ? 1 : 0, delay_out, stream);
+    if (want_grad && m->lens_params) {
       hipLaunchKernelGGL(gl_mp_pos_p3_kernel, blocks((long long)B * a.J * m->lens_params), dim3(MP_POS_WG), 0, stream, a, mp_args(m),
                          tg, m->lens_params);
+      if (what & POS_PLANE_DELAYS) launch_mp_tdelay_grad(m, a, w, stream);
+    }
     hipLaunchKernelGGL(gl_pos_p4_kernel, blocks((long long)B * (a.P + 1)), dim3(64), 0, stream, a, m->lens_params);
     GL_HIP(hipGetLastError());
     return GL_OK;
@@ -393,6 +433,84 @@ int gl_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, fl
                                size_t workspace_bytes, void* hip_stream) {
   const DelayOut out{scale_or_null, offset_or_null, model_delay_or_null};
   return point_term_call(m, params, B, loglike, chi2, grad_params_or_null, workspace, workspace_bytes, hip_stream, false, POS_DELAYS,
+                         nullptr, nullptr, &out);
+}
+
+// ---- ... on lens planes (gl_multiplane_tdelays.hip.h) ---------------------------------------------------------------------
+int gl_model_set_position_plane_delays(gl_model* m, const float* delay, const float* delay_err, int n_images, const double* geom,
+                                       const double* pot, const float* scale_per_family, int n_families, int n_planes) {
+  if (!m) return fail(GL_EINVAL, "model is null");
+  if (!m->pos_J) return fail(GL_EINVAL, "gl_model_set_positions has not been called on this model");
+  if (!delay) {  // no delays: the model as gl_model_set_position_targets left it
+    m->clear_plane_delays();
+    return GL_OK;
+  }
+  if (!delay_err || !scale_per_family || !geom || !pot) return fail(GL_EINVAL, "delay_err / geom / pot / scale_per_family is null");
+  if (n_images != m->pos_J) return fail(GL_EINVAL, "%d arrival times for %d image(s)", n_images, m->pos_J);
+  if (n_families != m->pos_F) return fail(GL_EINVAL, "%d delay scales for %d image famil(ies)", n_families, m->pos_F);
+  int n_delay = 0;
+  for (int f = 0; f < m->pos_F; ++f) {  // (the rules of gl_model_set_position_delays)
+    int n = 0;
+    for (int j = m->pos_fam_off[f]; j < m->pos_fam_off[f + 1]; ++j) {
+      if (std::isnan(delay[j])) continue;  // not measured
+      if (!std::isfinite(delay[j])) return fail(GL_EINVAL, "arrival time %d (%g) is not finite", j, delay[j]);
+      if (!(std::isfinite(delay_err[j]) && delay_err[j] > 0.f))
+        return fail(GL_EINVAL, "arrival-time error %d (%g) is not finite and > 0", j, delay_err[j]);
+      ++n;
+    }
+    if (n == 1)
+      return fail(GL_EINVAL, "image family %d has one measured arrival time: the term constrains delay differences, a family takes two "
+                             "or more, or none", f);
+    if (n && std::isinf(scale_per_family[f])) return fail(GL_EINVAL, "delay scale %d (%g) is not finite (NaN: profiled out)", f, scale_per_family[f]);
+    if (n == 2 && std::isnan(scale_per_family[f]))
+      return fail(GL_EINVAL, "image family %d has two measured arrival times and a profiled delay scale: the fit is exact and "
+                             "constrains nothing, a profiled scale takes three or more", f);
+    n_delay += n;
+  }
+  if (m->mp_K < 2) return fail(GL_EINVAL, "gl_model_set_lens_planes has not been called on this model (one plane: gl_model_set_position_delays)");
+  if (!m->pos_targets) return fail(GL_EINVAL, "gl_model_set_position_targets has not been called on this model");
+  if (n_planes != m->mp_K) return fail(GL_EINVAL, "delay weights of %d planes for %d lens planes", n_planes, m->mp_K);
+  const int K = n_planes;
+  for (int i = 0; i < K; ++i)
+    if (!(std::isfinite(pot[i]) && pot[i] >= 0.)) return fail(GL_EINVAL, "pot[%d] = %g: finite and >= 0", i, pot[i]);
+  for (int f = 0; f < m->pos_F; ++f) {  // a row of MultiPlane.delay_weights: the zeros are those of the family's coupling row
+    const double* g = geom + (size_t)f * K;
+    const float* T = m->pos_target_rows.data() + (size_t)f * K;
+    for (int i = 0; i < K; ++i) {
+      if (!(std::isfinite(g[i]) && g[i] >= 0.)) return fail(GL_EINVAL, "geom[%d][%d] = %g: finite and >= 0", f, i, g[i]);
+      if ((g[i] != 0.) != (T[i] != 0.f))
+        return fail(GL_EINVAL, "geom[%d][%d] = %g against the coupling %g of gl_model_set_position_targets: the planes in front of a "
+                               "family are the same in both rows", f, i, g[i], T[i]);
+    }
+  }
+  if (int rc = refuse_potential_lenses(m)) return rc;
+  if (!n_delay) {  // every time is NaN: none
+    m->clear_plane_delays();
+    return GL_OK;
+  }
+  std::vector<float> tab((size_t)2 * m->pos_J + m->pos_F);
+  std::copy(delay, delay + m->pos_J, tab.begin());
+  std::copy(delay_err, delay_err + m->pos_J, tab.begin() + m->pos_J);
+  std::copy(scale_per_family, scale_per_family + m->pos_F, tab.begin() + 2 * (size_t)m->pos_J);
+  std::vector<double> wt((size_t)(m->pos_J + 1) * MP_MAXK, 0.);
+  for (int f = 0; f < m->pos_F; ++f)
+    for (int j = m->pos_fam_off[f]; j < m->pos_fam_off[f + 1]; ++j) std::copy(geom + (size_t)f * K, geom + (size_t)(f + 1) * K, wt.begin() + (size_t)j * MP_MAXK);
+  std::copy(pot, pot + K, wt.begin() + (size_t)m->pos_J * MP_MAXK);
+  glk::DevBuf<float> fresh;  // (a failed upload leaves the model as it was)
+  glk::DevBuf<double> fresh_wt;
+  GL_HIP(fresh.upload(tab.data(), tab.size()));
+  GL_HIP(fresh_wt.upload(wt.data(), wt.size()));
+  m->d_mpd_delay = std::move(fresh);
+  m->d_mpd_weight = std::move(fresh_wt);
+  m->mpd_n_delay = n_delay;
+  return GL_OK;
+}
+
+int gl_multiplane_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
+                                          float* grad_params_or_null, float* scale_or_null, float* offset_or_null,
+                                          float* model_delay_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const DelayOut out{scale_or_null, offset_or_null, model_delay_or_null};
+  return point_term_call(m, params, B, loglike, chi2, grad_params_or_null, workspace, workspace_bytes, hip_stream, true, POS_PLANE_DELAYS,
                          nullptr, nullptr, &out);
 }
 
@@ -1238,6 +1356,8 @@ int gl_model_set_lens_planes(gl_model* m, const int* plane_of_lens, int n_lens, 
   m->mp_K = K;
   m->pos_targets = false;  // new planes: the couplings of the image families are given again
   m->d_pos_target.reset();
+  m->pos_target_rows.clear();
+  m->clear_plane_delays();  // ... and with them the arrival times of gl_model_set_position_plane_delays
   return GL_OK;
 }
 
@@ -1259,6 +1379,8 @@ int gl_model_set_position_targets(gl_model* m, const float* targets, int n_famil
   }
   GL_HIP(m->d_pos_target.upload(per_image.data(), per_image.size()));
   m->pos_targets = true;
+  m->pos_target_rows.assign(targets, targets + (size_t)n_families * n_planes);
+  m->clear_plane_delays();  // new couplings: the arrival times of gl_model_set_position_plane_delays are given again
   return GL_OK;
 }
 

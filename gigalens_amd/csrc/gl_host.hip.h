@@ -30,6 +30,9 @@ struct Workspace {
   float* gal_dyn;  // [B][G][DP_ND] catalogue members' per-sample constants
   float *pos_w, *pos_adj, *pos_g, *pos_fam, *pos_ll, *pos_chi2, *pos_grad;  // image-position likelihood
   float* pos_dadj;  // [B][J] d loglike / d Fermat potential of the time-delay term (gl_tdelays.hip.h)
+  // the time-delay term on lens planes (gl_multiplane_tdelays.hip.h), only while the model holds plane delays: the traced rays
+  // [B][J][5], mean beta [B][F][2] and a_j [B][J]
+  double *mpd_trace, *mpd_src, *mpd_aj;
   float* img_ss;   // supersampled / pre-PSF image or its cotangent (PSF path only)
   float* img_tmp;  // final-resolution image / its cotangent (PSF path only)
   float* stats;    // [B][2] chi2, normalisation of the materialised image (PSF path only)
@@ -74,9 +77,10 @@ GL_INTERNAL int post_bwd(const gl_model* m, int B, const float* gP, float* gS, h
 // ---- gl_api_points.hip --------------------------------------------------------------------------------------------------
 // point-image likelihood on the packed parameter rows `params` [B,P] (already on the device): the image positions, the flux ratios
 // of a model that holds fluxes (gl_model_set_position_fluxes), the time delays of one that holds arrival times
-// (gl_model_set_position_delays) or any sum of them, in w.pos_ll / pos_chi2 / pos_grad.  amp [B][F] and model_flux [B][J]: the flux
+// (gl_model_set_position_delays; on lens planes gl_model_set_position_plane_delays, POS_PLANE_DELAYS) or any sum of them, in
+// w.pos_ll / pos_chi2 / pos_grad.  amp [B][F] and model_flux [B][J]: the flux
 // term's optional outputs (S_f, S_f m_j), or null; delay_out: those of the delay term (lambda_f, T_f [B][F], model delays [B][J])
-enum PosTerms { POS_POSITIONS = 1, POS_FLUXES = 2, POS_BOTH = 3, POS_DELAYS = 4 };
+enum PosTerms { POS_POSITIONS = 1, POS_FLUXES = 2, POS_BOTH = 3, POS_DELAYS = 4, POS_PLANE_DELAYS = 8 };
 struct DelayOut { float *scale, *offset, *model_delay; };
 GL_INTERNAL int run_positions(const gl_model* m, const float* params, int B, const Workspace& w, bool want_grad, hipStream_t stream,
                               int what = POS_POSITIONS, float* amp = nullptr, float* model_flux = nullptr,

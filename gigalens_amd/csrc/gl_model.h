@@ -174,6 +174,18 @@ struct gl_model {
   // image families behind lens planes (gl_model_set_position_targets): the couplings T_f of every image's family
   bool pos_targets = false;
   glk::DevBuf<float> d_pos_target;  // [J][4], zero-padded rows; allocated only while pos_targets
+  std::vector<float> pos_target_rows;  // [F][mp_K] on the host: the rows as given (empty without targets)
+  // measured arrival times of the images on lens planes (gl_model_set_position_plane_delays, gl_multiplane_tdelays.hip.h); a state
+  // of its own, apart from the single-plane one below.  Cleared by gl_model_set_positions, gl_model_set_lens_planes and
+  // gl_model_set_position_targets
+  int mpd_n_delay = 0;              // measured times over all families; 0: the model holds none, and its workspace is as without
+  glk::DevBuf<float> d_mpd_delay;   // [2][J] time (NaN = not measured), error, then [F] lambda_f (NaN = profiled); only while mpd_n_delay
+  glk::DevBuf<double> d_mpd_weight;  // [J][4] g_f of every image's family, zero-padded, then [4] v_i; only while mpd_n_delay
+  void clear_plane_delays() {
+    mpd_n_delay = 0;
+    d_mpd_delay.reset();
+    d_mpd_weight.reset();
+  }
   // measured fluxes of the images (gl_model_set_position_fluxes, gl_fluxes.hip.h): the flux-ratio term of the point-image likelihood
   int pos_n_flux = 0;              // measured fluxes over all families; 0: the model holds none and every call runs as without them
   glk::DevBuf<float> d_pos_flux;   // [2][J]: flux (NaN = not measured), flux error; allocated only while pos_n_flux

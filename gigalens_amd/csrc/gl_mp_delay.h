@@ -7,57 +7,86 @@
 // head of its weight row `geom`):
 //   T = sum_{i<Ks} [ geom_i |theta_i - theta_next(i)|^2 / 2 - pot_i psi_i ],    theta_next(Ks-1) = beta
 // in arcsec^2 c / H0 (cosmology.MultiPlane.delay_weights).  Planes at or behind the source do not enter, whatever their sums hold.
+//
+// R: the number type of the ray -- double, or a dual on double that carries one parameter direction through the recursion (the
+// gradient of the time-delay likelihood on planes, gl_multiplane_tdelays.hip.h).  The couplings and the weights stay plain numbers.
 #pragma once
 #include "gl_math.h"
 
 namespace glp {
 
-// 2 MAXK + MAXK doubles that only unrolled loops with constant indices touch (the plane of a lens selects by comparison, as
+// 2 MAXK + MAXK values that only unrolled loops with constant indices touch (the plane of a lens selects by comparison, as
 // MpRegSums of gl_multiplane.hip.h): registers, no private memory
-template <int MAXK> struct MpDelayState {
-  double ax[MAXK], ay[MAXK], psi[MAXK];
+template <int MAXK, class R = double> struct MpDelayState {
+  R ax[MAXK], ay[MAXK], psi[MAXK];
   GL_HD MpDelayState() {
 #pragma unroll
-    for (int i = 0; i < MAXK; ++i) { ax[i] = 0.; ay[i] = 0.; psi[i] = 0.; }
+    for (int i = 0; i < MAXK; ++i) { ax[i] = R(0.); ay[i] = R(0.); psi[i] = R(0.); }
   }
   // theta_pl = theta - sum_{i<pl} C[i][pl] a_i on the float32 couplings the model holds
-  GL_HD void to_plane(int pl, const float* scale, double& px, double& py) const {
+  GL_HD void to_plane(int pl, const float* scale, R& px, R& py) const {
 #pragma unroll
     for (int i = 0; i < MAXK - 1; ++i)
       if (i < pl) {
         const double c = (double)scale[i * MAXK + pl];
-        px -= c * ax[i];
-        py -= c * ay[i];
+        px -= R(c) * ax[i];
+        py -= R(c) * ay[i];
       }
   }
-  GL_HD void add(int pl, double dax, double day, double dpsi) {
+  GL_HD void add(int pl, R dax, R day, R dpsi) {
 #pragma unroll
     for (int i = 0; i < MAXK; ++i)
       if (i == pl) { ax[i] += dax; ay[i] += day; psi[i] += dpsi; }
   }
   // T of the ray from (tx, ty) to the source (bx, by) once every sum is complete.  terms (or null): sum of the magnitudes of the
   // summands, the scale rounding errors of T are measured against
-  GL_HD double arrival(const float* scale, double tx, double ty, double bx, double by, const double* geom, const double* pot,
-                       int K, double* terms) const {
-    double T = 0., mag = 0.;
-    double cx = tx, cy = ty;  // theta_i
+  GL_HD R arrival(const float* scale, R tx, R ty, R bx, R by, const double* geom, const double* pot, int K, R* terms) const {
+    using glm::fabs_;
+    R T = R(0.), mag = R(0.);
+    R cx = tx, cy = ty;  // theta_i
 #pragma unroll
     for (int i = 0; i < MAXK; ++i) {
       const double g = i < K ? geom[i] : 0.;
       if (g != 0.) {
         const bool last = i + 1 >= K || geom[i + 1 < K ? i + 1 : i] == 0.;
-        double nx = tx, ny = ty;  // theta_next(i)
+        R nx = tx, ny = ty;  // theta_next(i)
         if (last) { nx = bx; ny = by; }
         else to_plane(i + 1, scale, nx, ny);
-        const double dx = cx - nx, dy = cy - ny;
-        const double geo = g * (0.5 * (dx * dx + dy * dy)), grav = pot[i] * psi[i];
+        const R dx = cx - nx, dy = cy - ny;
+        const R geo = R(g) * (R(0.5) * (dx * dx + dy * dy)), grav = R(pot[i]) * psi[i];
         T += geo - grav;
-        mag += glm::fabs_(geo) + glm::fabs_(grav);
+        mag += fabs_(geo) + fabs_(grav);
         cx = nx;
         cy = ny;
       }
     }
     if (terms) *terms = mag;
+    return T;
+  }
+  // T without the geometric summand of the last plane in front of the source -- the only part of T that sees the source -- and
+  // (lx, ly) = theta on that plane:  T = head + geom_last |(lx, ly) - beta|^2 / 2  (the time-delay likelihood on planes, whose
+  // source is the barycentre of the family's rays: known only once every image has been traced)
+  GL_HD R arrival_head(const float* scale, R tx, R ty, const double* geom, const double* pot, int K, R& lx, R& ly) const {
+    R T = R(0.);
+    R cx = tx, cy = ty;  // theta_i
+#pragma unroll
+    for (int i = 0; i < MAXK; ++i) {
+      const double g = i < K ? geom[i] : 0.;
+      if (g != 0.) {
+        const bool last = i + 1 >= K || geom[i + 1 < K ? i + 1 : i] == 0.;
+        if (!last) {
+          R nx = tx, ny = ty;  // theta_next(i)
+          to_plane(i + 1, scale, nx, ny);
+          const R dx = cx - nx, dy = cy - ny;
+          T += R(g) * (R(0.5) * (dx * dx + dy * dy));
+          cx = nx;
+          cy = ny;
+        }
+        T -= R(pot[i]) * psi[i];
+      }
+    }
+    lx = cx;
+    ly = cy;
     return T;
   }
 };

@@ -240,11 +240,30 @@ def _family_fluxes(fluxes, errors, centroids_x):
     return out_f, out_s, float(n_flux)
 
 
-def _family_delays(delays, errors, distances, centroids_x):
+def _family_h0(h0, n_fam):
+    """``[F]`` float64 of ``ForwardProbModel(time_delay_h0=...)`` in km/s/Mpc, NaN where the family's H0 is profiled out:
+    ``"profile"``, one float for every family, or a sequence of ``n_fam`` entries, each a float or ``None`` (profiled).  ``ValueError``
+    for a wrong count and a value that is not finite and > 0."""
+    if isinstance(h0, str):
+        if h0 != "profile":
+            raise ValueError(f"time_delay_h0: 'profile', a float in km/s/Mpc or one float / None per image family, got {h0!r}")
+        return np.full(n_fam, np.nan)
+    entries = [h0] * n_fam if np.ndim(h0) == 0 else list(h0)
+    if len(entries) != n_fam:
+        raise ValueError(f"time_delay_h0: one entry per image family ({n_fam}), got {len(entries)}")
+    out = np.asarray([np.nan if v is None else float(v) for v in entries], dtype=np.float64)
+    given = np.asarray([v is not None for v in entries], dtype=bool)
+    if np.any(given & ~(np.isfinite(out) & (out > 0.0))):
+        raise ValueError(f"time_delay_h0: every H0 must be finite and > 0 (km/s/Mpc; None: profiled out), got {entries!r}")
+    return out
+
+
+def _family_delays(delays, errors, distances, centroids_x, scale_name="time_delay_distances"):
     """``(delays, errors, distances [F] float64 with NaN = profiled, n_delay)`` of ``ForwardProbModel(centroids_time_delays=...,
     centroids_time_delays_errors=..., time_delay_distances=...)``: one float32 array per family shaped like its ``centroids_x``, NaN
     where an image has no measured arrival time (its error is not looked at), errors broadcast as the flux errors are.
-    ``ValueError`` as the constructor documents."""
+    ``ValueError`` as the constructor documents.  ``scale_name``: the keyword the scales came from (``time_delay_h0`` hands its
+    entries in here, so that the family-size rules read them)."""
     if (delays is None) != (errors is None):
         raise ValueError("centroids_time_delays and centroids_time_delays_errors come together: give both or neither")
     if delays is None:
@@ -292,10 +311,10 @@ def _family_delays(delays, errors, distances, centroids_x):
             raise ValueError(f"centroids_time_delays[{f}]: one measured arrival time -- the term constrains delay differences, a family "
                              "takes two or more measured times, or none")
         if n and np.isinf(dist[f]):
-            raise ValueError(f"time_delay_distances[{f}] must be finite (None: profiled out), got {dist[f]}")
+            raise ValueError(f"{scale_name}[{f}] must be finite (None: profiled out), got {dist[f]}")
         if n == 2 and np.isnan(dist[f]):
             raise ValueError(f"centroids_time_delays[{f}]: two measured arrival times with a profiled time-delay distance -- the fit is "
-                             "exact and constrains nothing; give time_delay_distances or three or more measured times")
+                             f"exact and constrains nothing; give {scale_name} or three or more measured times")
         n_delay += n
         out_t.append(t)
         out_s.append(s)
@@ -412,7 +431,7 @@ class ForwardProbModel(_StreamProbModel):
                  centroids_x=None, centroids_y=None, centroids_errors_x=None, centroids_errors_y=None,
                  include_pixels=True, include_positions=True, centroids_scales=None, centroids_redshifts=None,
                  centroids_fluxes=None, centroids_fluxes_errors=None, centroids_time_delays=None,
-                 centroids_time_delays_errors=None, time_delay_distances=None):
+                 centroids_time_delays_errors=None, time_delay_distances=None, time_delay_h0=None):
         """``centroids_scales`` (beyond the reference): one deflection scale per image family of ``centroids_x`` -- a family at its
         own redshift is traced with ``beta = theta - c_f alpha`` and ``A = I - c_f H`` in the position likelihood, the predicted
         positions and the image-plane rms.  Default: all 1.
@@ -449,7 +468,18 @@ class ForwardProbModel(_StreamProbModel):
         measured time in a family, two with a profiled distance (the fit is exact), a measured time that is not finite or whose error
         is not finite and > 0, a distance that is not finite.  At bind time: ``UnsupportedLensError`` on lens planes and for lenses
         without a potential (series expansions, user-written bodies), ``NotImplementedError`` for a family with delays whose
-        ``centroids_scales`` differs from 1."""
+        ``centroids_scales`` differs from 1.
+
+        ``time_delay_h0`` (with ``centroids_redshifts`` and the delays; instead of ``time_delay_distances``): the opt-in to the
+        time-delay term on two to four lens planes.  ``"profile"``, one H0 in km/s/Mpc for every family, or one entry per family,
+        each a float or ``None`` (profiled).  Family f is traced through the planes in front of it, its source is ``mean beta``, and
+        ``phi_j = T(theta_j; mean beta)`` is the arrival time of the ray through the planes in arcsec^2 ``c / H0``
+        (``MultiPlane.delay_weights(z_f)``; ``LensSimulator.time_delays(source_redshifts=...)`` evaluates the same sum); the rest
+        of the term is as above with ``lambda_f = cosmology.hubble_distance_mpc(h0_f) DAYS_PER_MPC_ARCSEC2``, so a profiled scale
+        is ``c / H0`` itself: ``fitted_time_delays`` returns it in Mpc and ``fitted_h0`` as H0.  ``ValueError``: together with
+        ``time_delay_distances``, without delays or without ``centroids_redshifts``, a wrong count, a value that is not finite and
+        > 0; two measured times need a given H0.  At bind time: ``ValueError`` for a simulator without several lens planes (give
+        ``time_delay_distances`` there).  A model built without ``time_delay_h0`` is refused on lens planes as before."""
         super().__init__(prior)
         self.include_pixels = include_pixels
         self.include_positions = include_positions
@@ -494,8 +524,24 @@ class ForwardProbModel(_StreamProbModel):
             self.centroids_redshifts = zf
         self.centroids_fluxes, self.centroids_fluxes_errors, self.n_flux = _family_fluxes(centroids_fluxes, centroids_fluxes_errors,
                                                                                           self.centroids_x)
-        (self.centroids_time_delays, self.centroids_time_delays_errors, self.time_delay_distances,
-         self.n_delay) = _family_delays(centroids_time_delays, centroids_time_delays_errors, time_delay_distances, self.centroids_x)
+        self.time_delay_h0 = None
+        if time_delay_h0 is None:
+            (self.centroids_time_delays, self.centroids_time_delays_errors, self.time_delay_distances,
+             self.n_delay) = _family_delays(centroids_time_delays, centroids_time_delays_errors, time_delay_distances, self.centroids_x)
+        else:  # the time-delay term on lens planes: H0 in the place of the distances
+            if time_delay_distances is not None:
+                raise ValueError("time_delay_h0 and time_delay_distances are two ways to scale the delays: give one (lens planes have "
+                                 "no single time-delay distance, one plane takes no h0)")
+            if centroids_time_delays is None or centroids_time_delays_errors is None:
+                raise ValueError("time_delay_h0 needs centroids_time_delays / centroids_time_delays_errors")
+            if self.centroids_redshifts is None:
+                raise ValueError("time_delay_h0 needs centroids_redshifts: the arrival time through the lens planes depends on the "
+                                 "redshift of every family (one plane: time_delay_distances)")
+            h0 = _family_h0(time_delay_h0, n_fam)
+            (self.centroids_time_delays, self.centroids_time_delays_errors, h0,
+             self.n_delay) = _family_delays(centroids_time_delays, centroids_time_delays_errors,
+                                            [None if np.isnan(v) else v for v in h0], self.centroids_x, "time_delay_h0")
+            self.time_delay_h0, self.time_delay_distances = h0, np.full(n_fam, np.nan)
         self._paths = _prior.nest_paths(self._bind_prior_structure(prior))
         self._perm_cache = {}
 
@@ -574,8 +620,14 @@ class ForwardProbModel(_StreamProbModel):
             mp = simulator._mp
             # (validated before anything is handed over: a refusal leaves the native model as it was)
             targets = self.position_targets(mp) if mp is not None and self.centroids_redshifts is not None else None
+            if self.n_delay and self.time_delay_h0 is not None and mp is None:
+                self._plane_delay_tables(simulator, None)  # (its ValueError: time_delay_h0 serves lens planes)
             scales, given = self._family_scales(simulator) if mp is None else (None, False)
-            delay_scales = self._delay_scales(simulator, scales) if self.n_delay else None
+            delay_scales = plane_delays = None
+            if self.n_delay and self.time_delay_h0 is not None:
+                plane_delays = self._plane_delay_tables(simulator, targets)
+            elif self.n_delay:
+                delay_scales = self._delay_scales(simulator, scales)
             model.set_positions(self.centroids_x, self.centroids_y, self.centroids_errors_x, self.centroids_errors_y)
             if targets is not None:
                 model.set_position_targets(targets)
@@ -583,7 +635,10 @@ class ForwardProbModel(_StreamProbModel):
                 model.set_position_scales(scales)
             if self.n_flux:  # (set_positions has cleared the fluxes of an earlier owner)
                 model.set_position_fluxes(np.concatenate(self.centroids_fluxes), np.concatenate(self.centroids_fluxes_errors))
-            if self.n_delay:  # (... and the arrival times)
+            if plane_delays is not None:  # (... and the arrival times: on lens planes, after the targets)
+                model.set_position_plane_delays(np.concatenate(self.centroids_time_delays),
+                                                np.concatenate(self.centroids_time_delays_errors), *plane_delays)
+            elif self.n_delay:
                 model.set_position_delays(np.concatenate(self.centroids_time_delays), np.concatenate(self.centroids_time_delays_errors),
                                           delay_scales)
             model.positions_owner = self
@@ -594,7 +649,8 @@ class ForwardProbModel(_StreamProbModel):
         ``predicted_time_delays`` words them, before anything is handed to the native model."""
         if simulator._mp is not None:
             raise _native.UnsupportedLensError(f"a model with {simulator._mp.K} lens planes: the time-delay term (centroids_time_delays) "
-                                               "stays single-plane")
+                                               "with time_delay_distances stays single-plane; on lens planes build the model with "
+                                               "time_delay_h0")
         from gigalens_amd.simulator import LensSimulator
         LensSimulator._potential_lenses(simulator)
         has = np.asarray([bool(np.any(~np.isnan(t))) for t in self.centroids_time_delays])
@@ -602,6 +658,34 @@ class ForwardProbModel(_StreamProbModel):
             raise NotImplementedError("centroids_time_delays: the Fermat potential of a scaled source plane (centroids_scales != 1) "
                                       "is not served; time delays stay single-plane")
         return (self.time_delay_distances * LensSimulator.DAYS_PER_MPC_ARCSEC2).astype(np.float32)
+
+    def _plane_delay_tables(self, simulator, targets):
+        """``(geom [F, K] float64, pot [K] float64, lambda_f [F] float32)`` of a model built with ``time_delay_h0`` on a simulator
+        with several lens planes: ``MultiPlane.delay_weights`` of every family, the potential weights of the farthest family with
+        delays, and ``c / H0`` in days per arcsec^2 (NaN: profiled out).  Its refusals come before anything is handed to the native
+        model."""
+        mp = simulator._mp
+        if mp is None or targets is None:
+            raise ValueError("time_delay_h0 serves a model with several lens planes (a PhysicalModel built with a cosmology.MultiPlane "
+                             "of two to four planes); on one plane give time_delay_distances")
+        from gigalens_amd.cosmology import hubble_distance_mpc
+        from gigalens_amd.simulator import LensSimulator
+        LensSimulator._potential_lenses(simulator)
+        weights = [mp.delay_weights(z) for z in self.centroids_redshifts]
+        has = np.asarray([bool(np.any(~np.isnan(t))) for t in self.centroids_time_delays])
+        far = int(np.argmax(np.where(has, self.centroids_redshifts, -np.inf)))
+        given = ~np.isnan(self.time_delay_h0)
+        lam = np.full(len(weights), np.nan)
+        lam[given] = hubble_distance_mpc(self.time_delay_h0[given]) * LensSimulator.DAYS_PER_MPC_ARCSEC2
+        return np.stack([g for g, _ in weights], axis=0), np.asarray(weights[far][1], dtype=np.float64), lam.astype(np.float32)
+
+    def _delay_entry(self, simulator):
+        """The native entry of the time-delay term alone, bound: gl_multiplane_position_delays_fwd_bwd for a model built with
+        ``time_delay_h0`` (lens planes), gl_position_delays_fwd_bwd otherwise."""
+        if self.time_delay_h0 is not None:
+            self._on_planes(simulator)  # (its refusals)
+            return self._bind_positions(simulator).multiplane_position_delays
+        return self._bind_positions(simulator).position_delays
 
     def _on_planes(self, simulator):
         """True for a simulator with several lens planes, whose fused log-probability comes from the multi-plane entries.  A model
@@ -674,24 +758,34 @@ class ForwardProbModel(_StreamProbModel):
 
     def stats_time_delays(self, simulator, params):
         """``(log_like, chi2 / n_delay)`` of the time-delay term alone (beyond the reference; see ``centroids_time_delays``),
-        differentiable in packed ``params``.  One lens plane, lenses with a potential, families with delays on the reference plane."""
+        differentiable in packed ``params``.  One lens plane, lenses with a potential, families with delays on the reference plane;
+        or, for a model built with ``time_delay_h0``, two to four lens planes."""
         self._need_delays("stats_time_delays")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
-        ll, chi2 = _point_term(packed, self._bind_positions(simulator).position_delays)
+        ll, chi2 = _point_term(packed, self._delay_entry(simulator))
         return ll, chi2 / self.n_delay
 
     def fitted_time_delays(self, simulator, params):
         """``(D_dt [B, F], offset [B, F], model_delay [B, J])``: the time-delay distance of every family in Mpc -- the one given, or
         the profiled ``lambda_f / DAYS_PER_MPC_ARCSEC2`` --, the fitted zero ``T_f`` of its clock in days and the arrival times
         ``lambda_f phi_j + T_f`` the model gives its images, in the concatenated image order; NaN for a family without delays.
-        Forward only."""
+        Forward only.  A model built with ``time_delay_h0`` (lens planes): the first entry is ``c / H0`` of every family in Mpc, given
+        or fitted -- ``fitted_h0`` turns it into H0."""
         self._need_delays("fitted_time_delays")
         packed = params if torch.is_tensor(params) else simulator.pack(params)
         if packed.requires_grad:
             raise NotImplementedError("fitted_time_delays is a forward-only diagnostic (no gradient)")
-        lam, off, md = self._bind_positions(simulator).position_delays(packed, False, want_model=True)[3:]
+        lam, off, md = self._delay_entry(simulator)(packed, False, want_model=True)[3:]
         from gigalens_amd.simulator import LensSimulator
         return lam / LensSimulator.DAYS_PER_MPC_ARCSEC2, off, md
+
+    def fitted_h0(self, simulator, params):
+        """``H0 [B, F]`` in km/s/Mpc of a model built with ``time_delay_h0``: the one given, or ``c`` over the profiled ``c / H0`` of
+        ``fitted_time_delays``; NaN for a family without delays.  A negative or huge value is data, not an error.  Forward only."""
+        if self.time_delay_h0 is None:
+            raise ValueError("fitted_h0 needs a model built with time_delay_h0 (one plane: fitted_time_delays gives D_dt)")
+        from gigalens_amd.cosmology import C_KM_S
+        return C_KM_S / self.fitted_time_delays(simulator, params)[0]
 
     def _point_stats(self, simulator, packed):
         """``(log_like, red_chi2)`` of the point-image term: the image positions and, when the model has them, the flux ratios and

@@ -260,6 +260,38 @@ int gl_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, fl
                                float* scale_or_null, float* offset_or_null, float* model_delay_or_null, void* workspace,
                                size_t workspace_bytes, void* hip_stream);
 
+/* ... on lens planes (gl_model_set_lens_planes): family f sits behind the planes 0 .. K_f - 1 (the non-zero head of its coupling row,
+ * gl_model_set_position_targets), its images are traced as gl_multiplane_positions_fwd_bwd traces them, its source is mean beta, and
+ * the Fermat potential is the arrival time of the ray through the planes (gl_multiplane_fermat),
+ *   phi_j = sum_{i<K_f} [ geom_f,i |theta_j,i - theta_j,next(i)|^2 / 2 - pot_i psi_i(theta_j,i) ] ,  theta_j,next(K_f - 1) = mean beta ,
+ * in arcsec^2 c / H0 with the weights of MultiPlane.delay_weights(z_f).  Everything after phi_j is the term above; lambda_f is in
+ * days per (arcsec^2 c / H0): c / H0 [Mpc] x 0.0280, so a profiled lambda_f is the Hubble distance, H0 = c / (lambda_f / 0.0280).
+ * The gradient is the partial derivative at fixed (lambda_f, T_f): through mean beta into the beta adjoints of the position
+ * likelihood on planes, and a_j d phi_j / d params at fixed mean beta in forward mode through the plane recursion (the ray
+ * positions behind the owning lens move with the parameter).
+ *   gl_model_set_position_plane_delays  after gl_model_set_positions, gl_model_set_lens_planes and gl_model_set_position_targets,
+ *       each of which clears the plane delays, as delay = NULL (or every time NaN) does.  delay, delay_err [n_images] and
+ *       scale_per_family [n_families] (lambda_f, NaN: profiled) as gl_model_set_position_delays; geom [n_families][n_planes] and pot
+ *       [n_planes] HOST doubles, copied: row f = the geometric weights of MultiPlane.delay_weights(z_f), pot the potential weights of
+ *       the planes (those of the farthest family with delays).  GL_EINVAL, the model left as it was: the count, finiteness and
+ *       family-size rules of gl_model_set_position_delays; a model without planes or without targets; n_planes other than the
+ *       model's; a weight that is not finite or is negative; a geom row whose non-zero head differs from that of the family's
+ *       coupling row.  GL_EUNSUPPORTED, the model left as it was: a lens without a potential (the set gl_multiplane_fermat refuses).
+ *       The state is apart from that of gl_model_set_position_delays, which keeps refusing a model with planes, as
+ *       gl_model_set_lens_planes keeps refusing one that holds single-plane delays.  The workspace GROWS while the model holds plane
+ *       delays (by [B][n_images][5] + [B][n_families][2] + [B][n_images] doubles): size it again with gl_workspace_bytes after this
+ *       call; every other model keeps its size.  While the model holds plane delays, GL_TERM_POSITIONS of
+ *       gl_multiplane_logprob_fwd_bwd includes the term and its reduced chi2 divides by 2 J + n_flux + n_delay;
+ *       gl_multiplane_positions_fwd_bwd and gl_position_fluxes_fwd_bwd keep their bits.
+ *   gl_multiplane_position_delays_fwd_bwd  the twin of gl_position_delays_fwd_bwd: the term alone, with the same optional outputs
+ *       (scale = lambda_f).  GL_EINVAL before gl_model_set_position_plane_delays; GL_EUNSUPPORTED for the gradient with a
+ *       GL_MULTIPOLE lens, as the other point terms on planes (values are served).  No atomics: two calls give identical bits. */
+int gl_model_set_position_plane_delays(gl_model* m, const float* delay, const float* delay_err, int n_images, const double* geom,
+                                       const double* pot, const float* scale_per_family, int n_families, int n_planes);
+int gl_multiplane_position_delays_fwd_bwd(const gl_model* m, const float* params, int B, float* loglike, float* chi2,
+                                          float* grad_params_or_null, float* scale_or_null, float* offset_or_null,
+                                          float* model_delay_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Per-family read-back of the point likelihood (a test and diagnostic aid): copies w_fam [B][n_families][2] = (log_like, chi2) of
  * every (sample, family) -- as the most recent gl_positions_fwd_bwd / gl_multiplane_positions_fwd_bwd / gl_position_fluxes_fwd_bwd /
  * gl_position_delays_fwd_bwd / GL_TERM_POSITIONS call with the same B left it in `workspace` -- to out (DEVICE) on the caller's
